@@ -4,10 +4,17 @@
   python bench.py --gpus N --steps K --warmup W            (N > 1: starts N rank processes itself)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
+A plain run does what the headline figure needs and no more: set up, warm up, time K steps, print the line.  `--full` adds the
+legs that take host time of their own (CPU baseline, the parity check against it, the repeat content of the index); without it
+`cpu_baseline`, `parity` and the hit fractions of `config` are null.  `--dump-outputs DIR` writes the records the last timed step
+returned as .npy files (same arguments -> same inputs -> comparable across builds).
+
 Default workload = the configuration the metric is quoted on (BASELINE.json configs[2], scaled to one step): an hg38-sized
 synthetic genome (24 chromosomes with hg38's lengths, 3.09 Gbp -> three packed contigs, all resident in HBM, three mapping
 rounds), k = 20, batches of 2^22 2x150 bp pairs = two launch tiles of 2^21 (with two tiles the library walks them round by
-round, so a tile's seeding sees the flags its previous pair stage wrote), eight distinct batches taking turns.
+round, so a tile's seeding sees the flags its previous pair stage wrote), eight distinct batches taking turns.  The inputs are
+made by class Workload below (the preset of circminer_amd/synth.py, generated on host threads side by side with the start-up
+of torch and HIP and with the index build): a pure function of --workload, --pairs, --seed, --batches and the rank.
 
 A "step" is one batch through the whole hot path:
   * its reads come from (page-locked) host memory: cm_reads_stage copies batch k+1 over PCIe on a copy stream while batch
@@ -59,6 +66,251 @@ WORKLOAD_NOTE = {
     "hg38like_sparse": "BASELINE.json configs[2] layout, rounds 1-2 genome: hg38-sized, 6 x 100 000-copy repeat families, sparse genes",
     "chr21": "BASELINE.json configs[1]: chr21-like synthetic contig",
 }
+
+
+# --dump-outputs: a back-splice-junction record (lib.RECORD_DTYPE: global pair index + the 72-byte cm_mapped_read) as a row of float64
+# (every field is an integer below 2^53, so the conversion is exact)
+STATE_COLUMNS = ["spos_r1", "spos_r2", "epos_r1", "epos_r2", "qspos_r1", "qspos_r2", "qepos_r1", "qepos_r2", "mlen_r1", "mlen_r2",
+                 "ed_r1", "ed_r2", "type", "tlen", "contig_num", "chr_id", "junc_num", "r1_forward", "r2_forward", "gm_compatible"]
+RECORD_COLUMNS = ["pair"] + STATE_COLUMNS
+DUMP_MAX_ROWS = 1 << 18        # x 21 columns x 8 bytes = 44 MB; the option writes at most 64 MB in all
+
+
+def dump_outputs(out_dir, rec):
+    """What the last timed step returned -- the BSJ records handed to stage 2 (all ranks', as gathered on rank 0) -- as
+    out_dir/bsj_records.npy, rows in ascending pair index, and out_dir/bsj_record_count.npy.  More than DUMP_MAX_ROWS records:
+    the rows of a fixed, seeded choice of positions in that order."""
+    os.makedirs(out_dir, exist_ok=True)
+    rec = np.array(rec)                                                  # off the page-locked buffer the next call overwrites
+    rec = rec[np.argsort(rec["pair"], kind="stable")]
+    n = len(rec)
+    if n > DUMP_MAX_ROWS:
+        rec = rec[np.sort(np.random.default_rng(20).choice(n, DUMP_MAX_ROWS, replace=False))]
+    rows = np.empty((len(rec), len(RECORD_COLUMNS)), dtype=np.float64)
+    rows[:, 0] = rec["pair"]
+    for k, name in enumerate(STATE_COLUMNS):
+        rows[:, 1 + k] = rec["state"][name]
+    np.save(os.path.join(out_dir, "bsj_records.npy"), rows)
+    np.save(os.path.join(out_dir, "bsj_record_count.npy"), np.array([n], dtype=np.float64))
+
+
+def host_threads():
+    """Host threads this process may keep busy: the logical CPUs, or fewer where OMP_NUM_THREADS says so (a share of a bigger box)."""
+    n = os.cpu_count() or 8
+    try:
+        return max(1, min(n, int(os.environ["OMP_NUM_THREADS"])))
+    except (KeyError, ValueError):
+        return n
+
+
+class Workload(threading.Thread):
+    """The benchmark's inputs, made on host threads while the main thread imports torch, brings up HIP and builds the index.
+
+    Same specification as synth.generate() (genome with the preset's planted repeats, spread genes, 2 x 150 bp pairs,
+    70 % transcriptomic / 25 % genomic / 5 % back-spliced, 0.4 % substitutions, rare 1-bp indels, random strand), stated so that
+    it takes seconds instead of minutes at hg38 scale: every chromosome, the genes and every batch have a random stream of their
+    own (seeded with (seed, a number), so the inputs are a pure function of the arguments), the back-splice reads and the
+    mutations are drawn for all reads of a batch at once, and no truth coordinates are kept (nothing here reads them).
+    Stages: `genome_ready` (contigs, chr_table, genes, GTF file) -> `reads[k]` futures; batch k is written into the (seq1, seq2)
+    matrices the main thread hands over with set_buffers() (page-locked memory: no copy afterwards)."""
+
+    def __init__(self, preset, pairs, seed, n_batches, rank, n_threads, chr_lens=None, contig_size=None):
+        super().__init__(daemon=True)
+        self.chr_lens, self.contig_size = chr_lens, contig_size          # tests: a small genome with a preset's make-up
+        from concurrent.futures import ThreadPoolExecutor
+        self.preset, self.pairs, self.seed, self.n_batches, self.rank = preset, pairs, seed, n_batches, rank
+        self.pool = ThreadPoolExecutor(max_workers=max(1, min(16, n_threads)))
+        self.genome_ready, self.reads_ready, self.stop, self.error = threading.Event(), threading.Event(), threading.Event(), None
+        self.have_buffers = threading.Event()
+        self.tmp = tempfile.TemporaryDirectory()
+        self.gtf = os.path.join(self.tmp.name, "ref.gtf")
+        self.seconds = {}
+
+    def run(self):
+        try:
+            self._run()
+        except BaseException as e:          # handed to the main thread by wait()
+            self.error = e
+        self.genome_ready.set()
+        self.reads_ready.set()
+
+    def wait(self, ev):
+        ev.wait()
+        if self.error is not None:
+            raise self.error
+
+    def cancel(self):
+        """the run ends early (no device): the threads stop at their next stage"""
+        self.stop.set()
+        self.join()
+        self.pool.shutdown(wait=True)
+        self.tmp.cleanup()
+
+    def set_buffers(self, buffers):
+        self.buffers = buffers
+        self.have_buffers.set()
+
+    def _check(self):
+        if self.stop.is_set() or not threading.main_thread().is_alive():
+            raise SystemExit("cancelled")
+
+    def _run(self):
+        from circminer_amd import synth
+        t0 = time.time()
+        lens, gpm, cs, fam_copies = synth.PRESETS[self.preset]
+        lens, cs = list(self.chr_lens or lens), self.contig_size or cs
+        names = [f"chr{i + 1}" for i in range(len(lens))]
+        rng = np.random.default_rng(self.seed)
+
+        def annotation():
+            genes = synth.make_genes(np.random.default_rng([self.seed, 2000]), lens, genes_per_mbp=gpm, spread=self.preset in synth.DENSE)
+            text = synth.gtf_text(genes, names)
+            with open(self.gtf, "w") as f:
+                f.write(text)
+            return genes, text
+        annot = self.pool.submit(annotation)
+        if self.preset in synth.DENSE:
+            # the chromosomes are made in place in the packed contigs (the layout of synth.pack_genome: a new contig when the
+            # size cap would be exceeded, MIDNCNT Ns between neighbours)
+            table, sizes, cur = [], [], 0
+            for name, L in zip(names, lens):
+                if cur == 0 or L + synth.MIDNCNT + cur > cs:
+                    sizes.append(0)
+                    cur = 0
+                start = cur + synth.MIDNCNT if cur else 0
+                table.append((name, len(sizes), start, L))
+                cur = sizes[-1] = start + L
+            self.contigs = [np.empty(n, dtype=np.uint8) for n in sizes]
+            seqs = []
+            for name, con, start, L in table:
+                if start:
+                    self.contigs[con - 1][start - synth.MIDNCNT:start] = ord("N")
+                seqs.append(self.contigs[con - 1][start:start + L])
+            self.chr_table = table
+
+            def base(i):
+                self._check()
+                seqs[i][:] = synth._ACGT[np.random.default_rng([self.seed, 1000 + i]).integers(0, 4, lens[i], dtype=np.uint8)]
+            list(self.pool.map(base, range(len(lens))))
+            self._check()
+            synth.make_genome_tiers(rng, lens, synth.scale_tiers(synth.DENSE_TIERS, sum(lens) / sum(synth.HG38_CHR_LENS)), seqs=seqs)
+        else:
+            seqs = synth.make_genome(rng, lens, fam_copies=fam_copies)
+            self.contigs, self.chr_table = synth.pack_genome(names, seqs, cs)
+        self._check()
+        self.chr_seqs = seqs
+        self.genes, self.gtf_text = annot.result()
+        self.seconds["genome"] = time.time() - t0
+        self.genome_ready.set()
+        self._check()
+        tables = read_tables(seqs, self.genes)
+        self.reads = [self.pool.submit(self._batch, tables, k) for k in range(self.n_batches)]
+        self.seconds["read_tables"] = time.time() - t0 - self.seconds["genome"]
+
+    def _batch(self, tables, k):
+        while not self.have_buffers.wait(0.2):
+            self._check()
+        self._check()
+        make_reads_fast(np.random.default_rng([self.seed, 7919 + 64 * self.rank + k]), self.chr_seqs, tables, self.pairs, *self.buffers[k])
+
+
+READ_LEN = 150
+_ACGT = np.frombuffer(b"ACGT", dtype=np.uint8)
+_CODE = np.zeros(256, dtype=np.uint8)
+_CODE[list(b"ACGT")] = [0, 1, 2, 3]
+
+
+def read_tables(chr_seqs, genes):
+    """Spliced transcript sequences, concatenated (exon after exon, transcript after transcript), and the offsets of every exon and
+    transcript in that array; a circle of consecutive exons of one transcript is a slice of it."""
+    trs = [(g, t) for g in genes for t in g.transcripts]
+    n_ex = np.asarray([len(t.exons) for _, t in trs], dtype=np.int64)
+    ex = np.asarray([e for _, t in trs for e in t.exons], dtype=np.int64).reshape(-1, 2)          # 1-based, inclusive
+    ex_chr = np.repeat(np.asarray([g.chrom for g, _ in trs], dtype=np.int64), n_ex)
+    ex_len = ex[:, 1] - ex[:, 0] + 1
+    ex_off = np.concatenate([[0], np.cumsum(ex_len)])
+    tx_first = np.concatenate([[0], np.cumsum(n_ex)])
+    tx_cat = np.empty(int(ex_off[-1]), dtype=np.uint8)
+    for c, a, b, o in zip(ex_chr.tolist(), (ex[:, 0] - 1).tolist(), ex[:, 1].tolist(), ex_off[:-1].tolist()):
+        tx_cat[o:o + b - a] = chr_seqs[c][a:b]
+    return dict(tx_cat=tx_cat, ex_off=ex_off, tx_first=tx_first, n_ex=n_ex, tx_off=ex_off[tx_first], circ=np.nonzero(n_ex >= 3)[0])
+
+
+def mutate_fast(rng, reads, sub_rate, indel_rate):
+    """synth._mutate for all reads at once: substitutions at a binomial number of uniformly drawn positions (to a different base),
+    then 1-bp deletions (shift left, last base repeated) or insertions (shift right, random base) in a few rows."""
+    n, L = reads.shape
+    flat = reads.reshape(-1)
+    pos = rng.integers(0, n * L, int(rng.binomial(n * L, sub_rate)))
+    flat[pos] = _ACGT[(_CODE[flat[pos]] + rng.integers(1, 4, pos.size)) % 4]
+    rows = np.nonzero(rng.random(n) < indel_rate * L)[0]
+    if rows.size:
+        p = rng.integers(10, L - 10, rows.size)[:, None]
+        dele = rng.random(rows.size) < 0.5
+        ar = np.arange(L)
+        idx = np.where(dele[:, None], np.minimum(ar + (ar >= p), L - 1), ar - (ar > p))
+        sub = np.take_along_axis(reads[rows], idx, 1)
+        ins = np.nonzero(~dele)[0]
+        sub[ins, p[ins, 0]] = _ACGT[rng.integers(0, 4, ins.size)]
+        reads[rows] = sub
+    return reads
+
+
+def make_reads_fast(rng, chr_seqs, T, n_pairs, seq1, seq2, frag_lo=260, frag_hi=450, mix=(0.70, 0.25, 0.05), sub_rate=0.004, indel_rate=0.0002):
+    """One batch of read pairs written into the (n_pairs, read_len) uint8 matrices seq1 / seq2: synth.make_reads' three sources and
+    its mutations, every step on whole arrays."""
+    from circminer_amd.synth import revcomp
+    windows = np.lib.stride_tricks.sliding_window_view          # rows of `windows(s, L)[starts]` are copied as runs of L bytes
+    src = rng.choice(3, size=n_pairs, p=np.asarray(mix) / sum(mix))
+    frag = rng.integers(frag_lo, frag_hi + 1, n_pairs)
+    read_len = seq1.shape[1]
+    ar = np.arange(read_len)
+    tx_cat, tx_off = T["tx_cat"], T["tx_off"]
+    tx_len = np.diff(tx_off)
+    cand = np.nonzero(tx_len >= frag_hi + 2)[0]
+    if cand.size == 0:
+        src[src == 0] = 1
+    if T["circ"].size == 0:
+        src[src == 2] = 1
+    # transcriptomic: a fragment of a spliced transcript, transcripts weighted by length
+    idx = np.nonzero(src == 0)[0]
+    if idx.size:
+        w = tx_len[cand].astype(np.float64)
+        ti = cand[rng.choice(cand.size, size=idx.size, p=w / w.sum())]
+        b = tx_off[ti] + (rng.random(idx.size) * (tx_len[ti] - frag[idx])).astype(np.int64)
+        win = windows(tx_cat, read_len)
+        seq1[idx] = win[b]
+        seq2[idx] = revcomp(win[b + frag[idx] - read_len])
+    # genomic: chromosomes weighted by length
+    idx = np.nonzero(src == 1)[0]
+    if idx.size:
+        lens = np.asarray([len(s) for s in chr_seqs], dtype=np.float64)
+        ci = rng.choice(len(chr_seqs), size=idx.size, p=lens / lens.sum())
+        for c in np.unique(ci):
+            sel = idx[ci == c]
+            s = chr_seqs[c]
+            st = rng.integers(300, len(s) - frag_hi - 300, sel.size)
+            win = windows(s, read_len)
+            seq1[sel] = win[st]
+            seq2[sel] = revcomp(win[st + frag[sel] - read_len])
+    # back-spliced: circle = exons i..j (inner exons) of a transcript, the fragment read around it across the junction
+    idx = np.nonzero(src == 2)[0]
+    if idx.size:
+        k = T["circ"][rng.integers(0, T["circ"].size, idx.size)]
+        ne = T["n_ex"][k]
+        i = 1 + (rng.random(idx.size) * (ne - 2)).astype(np.int64)
+        j = i + (rng.random(idx.size) * (ne - 1 - i)).astype(np.int64)
+        a = T["ex_off"][T["tx_first"][k] + i]
+        clen = T["ex_off"][T["tx_first"][k] + j + 1] - a
+        st = (clen - rng.integers(20, frag[idx] - 20)) % clen
+        seq1[idx] = tx_cat[a[:, None] + (st[:, None] + ar) % clen[:, None]]
+        seq2[idx] = revcomp(tx_cat[a[:, None] + ((st + frag[idx] - read_len)[:, None] + ar) % clen[:, None]])
+    mutate_fast(rng, seq1, sub_rate, indel_rate)
+    mutate_fast(rng, seq2, sub_rate, indel_rate)
+    sw = rng.random(n_pairs) < 0.5                     # random strand: R1 <-> R2
+    tmp = seq1[sw].copy()
+    seq1[sw] = seq2[sw]
+    seq2[sw] = tmp
 
 
 def algorithmic_bytes(counters):
@@ -281,7 +533,14 @@ def main():
                     "two for the default (cm_hot.hip tile_for)")
     ap.add_argument("--seed", type=int, default=38)
     ap.add_argument("--batches", type=int, default=8, help="distinct batches of --pairs pairs that take turns in the timed region (>= 2)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also everything beside the headline figure: the CPU baseline (oracle on all host cores), the parity check of "
+                         "batch 0 against it, the repeat content of the index (config.workload); minutes of host time, off by default")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step handed to its caller as DIR/<name>.npy (float64): bsj_records = one row per "
+                         "back-splice-junction record, columns " + ", ".join(RECORD_COLUMNS) + "; bsj_record_count = how many the step "
+                         "produced (rows beyond %d are a fixed, seeded sample)" % DUMP_MAX_ROWS)
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline and the parity check")
     ap.add_argument("--e2e", type=int, default=0, metavar="PAIRS",
                     help="also run the file-to-file flow (index file + GTF + FASTQ text -> circ_report) on this many pairs and add an "
                          "'end_to_end' object to the line (minutes of extra preparation at hg38 scale: off by default)")
@@ -310,6 +569,11 @@ def main():
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if world != args.gpus:
         raise SystemExit(f"bench.py: --gpus {args.gpus} but WORLD_SIZE={world}")
+    # the inputs are made on host threads from here on, while torch and HIP come up
+    t0 = time.time()
+    n_threads = max(1, host_threads() // max(world, 1))
+    d = Workload(args.workload, args.pairs, args.seed, max(2, args.batches), rank, n_threads)
+    d.start()
     import torch
     dist = None
     # CM_BENCH_FORCE_DIST=1: take the N>1 code path (process group, gatherv, barriers) with a single rank -- a rehearsal of
@@ -322,6 +586,7 @@ def main():
         os.environ.setdefault("MASTER_PORT", "29511")
         if args.backend == "nccl":
             if not torch.cuda.is_available():
+                d.cancel()
                 raise SystemExit("bench.py needs a HIP device: the hot path has no CPU fallback")
             torch.cuda.set_device(local_rank)
             dist.init_process_group("nccl", rank=rank, world_size=world, device_id=torch.device("cuda", local_rank),
@@ -329,6 +594,7 @@ def main():
         else:
             dist.init_process_group(args.backend, rank=rank, world_size=world, timeout=datetime.timedelta(minutes=30))
     if not torch.cuda.is_available():
+        d.cancel()
         if multi:
             dist.barrier()
             dist.destroy_process_group()
@@ -342,60 +608,70 @@ def main():
             ge.build()
         dist.barrier()
     ge.build()
-    from circminer_amd import dist as cdist, lib as cl, synth
+    from circminer_amd import dist as cdist, lib as cl
 
-    # ---- synthetic workload (same genome + annotation on every rank, own stream of reads) ----
-    t0 = time.time()
-    n_threads = max(1, (os.cpu_count() or 8) // max(world, 1))
-    # two different batches take turns, so that consecutive steps really move different reads over PCIe
-    d = synth.generate(args.workload, n_pairs=max(2 * args.pairs, min(args.e2e, 1 << 23) if rank == 0 else 0), seed=args.seed, read_seed=rank)
-    gen_s = time.time() - t0
-    tag = f"cm_bench_{args.workload}_{args.seed}_{os.environ.get('MASTER_PORT', '0')}"
-    sdir = share_dir(tag, 8 * sum(len(c) for c in d.contigs)) if world > 1 else None
-    with tempfile.TemporaryDirectory() as td:
-        gtf = os.path.join(td, "ref.gtf")
-        with open(gtf, "w") as f:
-            f.write(d.gtf_text)
-        if world == 1:
-            hi = cl.HostIndex(d.contigs, d.chr_table, gtf, kmer=20, n_threads=n_threads)
-        else:
-            # the k-mer index is built once per node: rank 0 -> memory-mapped files -> the other ranks
-            if rank == 0:
-                shutil.rmtree(sdir, ignore_errors=True)
-                hi = cl.HostIndex(d.contigs, d.chr_table, gtf, kmer=20, n_threads=os.cpu_count() or 8)
-                hi.save_index(sdir)
-            dist.barrier()
-            if rank != 0:
-                hi = cl.HostIndex(d.contigs, d.chr_table, gtf, kmer=20, index_dir=sdir)
+    # ---- synthetic workload (same genome + annotation on every rank, own stream of reads): class Workload ----
     P = cl.default_params(device=dev_index)
-    prep_s = time.time() - t0
-    # repeat content of the workload as a probe sees it (SURVEY 8(d) targets: ~10 % of the 20-mers with > 1 hit, ~1 % beyond seedLim)
-    hit_stats = hi.hit_stats(P.seed_lim, n_threads) if rank == 0 else []
-
     hp = cl.HotPath(P)
+    tag = f"cm_bench_{args.workload}_{args.seed}_{os.environ.get('MASTER_PORT', '0')}"
+    built = {}
+
+    def build_index():
+        try:
+            d.wait(d.genome_ready)
+            built["genome_s"] = time.time() - t0
+            built["hi"] = cl.HostIndex(d.contigs, d.chr_table, d.gtf, kmer=20, n_threads=n_threads)
+            built["index_s"] = time.time() - t0 - built["genome_s"]
+        except BaseException as e:
+            built["error"] = e
+    if world == 1:                      # the builders run outside the interpreter lock: the reads are made meanwhile
+        indexer = threading.Thread(target=build_index)
+        indexer.start()
+    # the distinct batches the timed region streams round-robin (at least two, so that consecutive steps really move different
+    # reads over PCIe) live in page-locked memory; the workload threads write the reads straight into it
+    blank = np.empty((args.pairs, READ_LEN), dtype=np.uint8)
+    batches = [hp.pinned_batch(blank, blank) for _ in range(d.n_batches)]
+    d.set_buffers([(b.seq1.reshape(args.pairs, READ_LEN), b.seq2.reshape(args.pairs, READ_LEN)) for b in batches])
+    d.wait(d.genome_ready)
+    gen_s = time.time() - t0
+    if world > 1:
+        # the k-mer index is built once per node: rank 0 -> memory-mapped files -> the other ranks
+        sdir = share_dir(tag, 8 * sum(len(c) for c in d.contigs))
+        if rank == 0:
+            shutil.rmtree(sdir, ignore_errors=True)
+            hi = cl.HostIndex(d.contigs, d.chr_table, d.gtf, kmer=20, n_threads=os.cpu_count() or 8)
+            hi.save_index(sdir)
+        dist.barrier()
+        if rank != 0:
+            hi = cl.HostIndex(d.contigs, d.chr_table, d.gtf, kmer=20, index_dir=sdir)
+    t_more = time.time()
+    d.wait(d.reads_ready)
+    for fut in d.reads:
+        fut.result()
+    if args.e2e:                        # the file-to-file leg writes its FASTQ files from the first two batches
+        d.seq1 = np.concatenate([b.seq1.reshape(args.pairs, READ_LEN) for b in batches[:2]])
+        d.seq2 = np.concatenate([b.seq2.reshape(args.pairs, READ_LEN) for b in batches[:2]])
+    d.pool.shutdown()
+    more_s = time.time() - t_more
+    if world == 1:
+        indexer.join()
+        if "error" in built:
+            raise built["error"]
+        hi, gen_s, index_s = built["hi"], built["genome_s"], built["index_s"]
+    else:
+        index_s = time.time() - t0 - gen_s
+    # repeat content of the workload as a probe sees it (SURVEY 8(d) targets: ~10 % of the 20-mers with > 1 hit, ~1 % beyond seedLim):
+    # a pass over the whole index on the host, --full only
+    hit_stats = hi.hit_stats(P.seed_lim, n_threads) if rank == 0 and args.full else []
+
+    t_load = time.time()
     for ci in range(hi.n_contigs):
         hp.load_contig(ci, hi.views[ci], hi.annots[ci])
     if world > 1:
         dist.barrier()
         if rank == 0:
             shutil.rmtree(sdir, ignore_errors=True)          # mappings of the other ranks stay valid until they drop them
-    batches = [hp.pinned_batch(d.seq1[i * args.pairs:(i + 1) * args.pairs], d.seq2[i * args.pairs:(i + 1) * args.pairs]) for i in range(2)]
-    load_s = time.time() - t0 - prep_s
-    # more distinct batches (the timed region streams them round-robin): own streams of reads off the same genome, made on host
-    # threads; batches 0 and 1 stay what earlier rounds measured
-    t_more = time.time()
-    n_more = max(0, args.batches - 2)
-    if n_more:
-        from concurrent.futures import ThreadPoolExecutor
-
-        def more(k):
-            rng = np.random.default_rng([args.seed, 7919 + 64 * rank + k])
-            s1, s2 = synth.make_reads(rng, d.chr_seqs, d.genes, args.pairs)[:2]
-            return s1, s2
-        with ThreadPoolExecutor(max_workers=min(n_more, max(1, n_threads // 2))) as ex:
-            for s1, s2 in ex.map(more, range(n_more)):
-                batches.append(hp.pinned_batch(s1, s2))
-    more_s = time.time() - t_more
+    load_s = time.time() - t_load
     base = rank * args.pairs
     gather = cdist.BsjGather(args.pairs, gather_dev) if multi else None
     turn = [0]
@@ -479,6 +755,9 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
 
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, rec)
+
     if rank == 0:
         total_pairs = args.pairs * world * args.steps
         value = total_pairs / dt
@@ -540,9 +819,10 @@ def main():
             "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": "int32/u8 (chain scores f64)", "data": "synthetic",
             "config": {"workload": f"{WORKLOAD_NOTE[args.workload]} ({sum(len(c) for c in d.contigs)} bp in {hi.n_contigs} packed contig(s), "
-                                   f"{len(d.genes)} genes / {sum(len(g.transcripts) for g in d.genes)} transcripts; indexed 20-mers with > 1 hit "
+                                   f"{len(d.genes)} genes / {sum(len(g.transcripts) for g in d.genes)} transcripts" + (f"; indexed 20-mers with > 1 hit "
                                    f"{'/'.join('%.1f%%' % (100.0 * m / max(n, 1)) for n, m, o, _ in hit_stats)}, beyond seedLim "
-                                   f"{'/'.join('%.2f%%' % (100.0 * o / max(n, 1)) for n, m, o, _ in hit_stats)} per contig), k=20, {hi.n_contigs} mapping round(s) per batch, batches of {args.pairs} 2x150 bp pairs "
+                                   f"{'/'.join('%.2f%%' % (100.0 * o / max(n, 1)) for n, m, o, _ in hit_stats)} per contig" if hit_stats else "") +
+                                   f"), k=20, {hi.n_contigs} mapping round(s) per batch, batches of {args.pairs} 2x150 bp pairs "
                                    f"streamed from host memory ({len(batches)} distinct batches round-robin; H2D inside the timed region, overlapped with the rounds), defaults; "
                                    f"{total_pairs} pairs in the timed region",
                        "scope": "stage 1 hot path (process_read over all rounds + BSJ hand-off); reads start in host memory, "
@@ -552,11 +832,12 @@ def main():
                        "h2d_bytes_per_step": read_bytes,
                        "bsj_records_last_step": int(len(rec)),         # all ranks' records, as gathered on rank 0
                        "genes": len(d.genes), "transcripts": sum(len(g.transcripts) for g in d.genes),
-                       "multi_hit_fraction": [m / max(n, 1) for n, m, o, _ in hit_stats],
-                       "beyond_seed_lim_fraction": [o / max(n, 1) for n, m, o, _ in hit_stats],
+                       "multi_hit_fraction": [m / max(n, 1) for n, m, o, _ in hit_stats] if args.full else None,
+                       "beyond_seed_lim_fraction": [o / max(n, 1) for n, m, o, _ in hit_stats] if args.full else None,
                        "world_size": world,
                        "distinct_batches": len(batches),
-                       "prep_seconds": {"generate": round(gen_s, 1), "index+annotation": round(prep_s - gen_s, 1), "load_to_hbm": round(load_s, 1),
+                       # genome made (from the start of the workload threads); index built; side by side with it, wait for the batches
+                       "prep_seconds": {"generate": round(gen_s, 1), "index+annotation": round(index_s, 1), "load_to_hbm": round(load_s, 1),
                                         "more_batches": round(more_s, 1)}},
             "roofline": {"bound": "hbm", "kernel": KERNELS[dom] + ("+k_hp_* (pair stage: light kernel launch to the join with the heavy pairs' pipeline)" if dom == 2 else ""), "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
@@ -570,17 +851,20 @@ def main():
         # The line's own parity evidence (outside the timed region): batch 0 once more through the same calls the steps make --
         # staged, swapped in, all rounds in one call, two tiles -- and its final MatchedRead (72 B) + re-queue flag of every pair
         # kept; the cpu_baseline leg below maps (a prefix of) the same batch with the oracle and the two are compared byte for byte.
-        hp.stage(batches[0])
-        hp.swap()
-        hp.map_rounds(list(range(hi.n_contigs)), True)
-        gpu_st, _, gpu_act = hp.download()
+        # Both legs run with --full only; a plain run reports null for them.
+        with_cpu = args.full and not args.no_cpu_baseline
+        if with_cpu:
+            hp.stage(batches[0])
+            hp.swap()
+            hp.map_rounds(list(range(hi.n_contigs)), True)
+            gpu_st, _, gpu_act = hp.download()
         if args.e2e:
             hp.close()                                          # its HBM goes back before cm_mapping_run makes a context of its own
             # (file to file the batches are 2^21 pairs: parse / device / write of consecutive batches overlap on the host, and twice as many
             # smaller batches fill that pipeline sooner -- 12.8 against 8.5 M pairs/s with 2^22)
             out["end_to_end"] = end_to_end(d, args.workload, args.e2e, os.cpu_count() or 8, min(args.pairs, 1 << 21), dev_index)
         # rank 0's host cores, after the timed region (the other ranks are idle at the final barrier by then)
-        out["cpu_baseline"] = None if args.no_cpu_baseline else cpu_baseline(P, hi, batches[0])
+        out["cpu_baseline"] = cpu_baseline(P, hi, batches[0]) if with_cpu else None
         if out["cpu_baseline"] is not None:
             n_s, o_st, o_act = cpu_baseline.sample
             eq = bool(gpu_st[:n_s].tobytes() == o_st.tobytes() and (gpu_act[:n_s] == o_act).all())

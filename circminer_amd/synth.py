@@ -119,10 +119,12 @@ def scale_tiers(tiers, frac):
     return out
 
 
-def make_genome_tiers(rng, chr_lens, tiers=DENSE_TIERS, n_runs=2):
+def make_genome_tiers(rng, chr_lens, tiers=DENSE_TIERS, n_runs=2, seqs=None):
     """Uniform ACGT chromosomes with repeat families of a spread of copy numbers / lengths / divergences planted at positions
-    drawn over the whole genome (later copies overwrite earlier ones where they overlap), plus a few N runs."""
-    seqs = [_ACGT[rng.integers(0, 4, L)] for L in chr_lens]
+    drawn over the whole genome (later copies overwrite earlier ones where they overlap), plus a few N runs.
+    seqs: uniform ACGT chromosomes made by the caller (bench.py draws them on several threads); planted in place."""
+    if seqs is None:
+        seqs = [_ACGT[rng.integers(0, 4, L)] for L in chr_lens]
     starts = np.concatenate([[0], np.cumsum(chr_lens)]).astype(np.int64)
     total = int(starts[-1])
     for tier in tiers:

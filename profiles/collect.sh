@@ -20,5 +20,5 @@ echo "write done"
 cd $ROOT
 python3 profiles/make_traffic.py $OUT/fetch/pmc_counter_collection.csv $OUT/write/pmc_counter_collection.csv $OUT/traffic.json $OUT/${R}_pmc_fetch_size.csv $OUT/${R}_pmc_write_size.csv
 cp $OUT/traffic.json profiles/traffic.json
-python3 bench.py > $OUT/${R}_bench_1gpu.json 2> $OUT/bench.err
+python3 bench.py --full > $OUT/${R}_bench_1gpu.json 2> $OUT/bench.err
 cat $OUT/${R}_bench_1gpu.json

@@ -14,7 +14,7 @@ rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $OUT/fetch_$R -o pmc --output-forma
 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $OUT/write_$R -o pmc --output-format csv -- python3 $ROOT/bench.py --workload $WL --steps 2 --warmup 1 --no-cpu-baseline > $OUT/write_$R.log 2>&1
 cd $ROOT
 python3 profiles/make_traffic.py $OUT/fetch_$R/pmc_counter_collection.csv $OUT/write_$R/pmc_counter_collection.csv $OUT/${R}_traffic.json $OUT/${R}_pmc_fetch_size.csv $OUT/${R}_pmc_write_size.csv
-python3 bench.py --workload $WL > $OUT/${R}_bench_1gpu.json 2> $OUT/bench_$R.err
+python3 bench.py --full --workload $WL > $OUT/${R}_bench_1gpu.json 2> $OUT/bench_$R.err
 python3 -c "
 import json; d=json.load(open('$OUT/${R}_bench_1gpu.json')); print('$WL', d['value'], d['ms_per_step'], d['roofline']['frac'])
 t=json.load(open('$OUT/${R}_traffic.json')); print(t['bytes_per_launch'])"
