@@ -35,10 +35,17 @@
 #define CM_HOOK_DP(kind, s, n, t, m) ((void)0)
 #endif
 #if defined(CM_STATS) && !defined(__HIPCC__)
-extern "C" unsigned long long cm_stats[16];
-#define CM_STAT(i, n) (cm_stats[i] += (unsigned long long)(n))
+// CM_NSTATS: how many counters the harness defines -- 16, or 24 if it asks for them before including this header: [16], [17] = mate-pair
+// tasks / unpaired-chain extensions of the second orientation attempt alone.  A counter the harness has no room for is not kept.
+#if !defined(CM_NSTATS)
+#define CM_NSTATS 16
+#endif
+extern "C" unsigned long long cm_stats[CM_NSTATS];
+#define CM_STAT(i, n) ((i) < CM_NSTATS ? (void)(cm_stats[(i) < CM_NSTATS ? (i) : 0] += (unsigned long long)(n)) : (void)0)
+#define CM_STAT_GET(i) (cm_stats[i])
 #else
 #define CM_STAT(i, n) ((void)0)
+#define CM_STAT_GET(i) 0ull
 #endif
 // diagnostic builds only (-DCM_DIAG): cut the pair routine short at phase n (cm_params.reserved)
 #if defined(CM_DIAG)
@@ -2536,8 +2543,11 @@ CM_HD inline int process_read(const Core &c, const DpMem &sm, g_u8 s1, int len1,
         // one call site for both orientations (arguments selected, not branched on): the lanes of a wave whose pairs
         // have opposite orientations stay converged inside process_mates
         const bool r1_fwd = (attempt == 0) == first;                   // forward R1 / backward R2, else forward R2 / backward R1
+        [[maybe_unused]] const unsigned long long tasks0 = CM_STAT_GET(0), unp0 = CM_STAT_GET(2);     // (test-only counters, see CM_STAT)
         const int a = process_mates(c, sm, r1_fwd ? sets[0] : sets[2], r1_fwd ? r1f : r2f, r1_fwd ? sets[3] : sets[1], r1_fwd ? r2b : r1b, mr,
                                     r1_fwd, err);
+        CM_STAT(16, attempt ? CM_STAT_GET(0) - tasks0 : 0ull);
+        CM_STAT(17, attempt ? CM_STAT_GET(2) - unp0 : 0ull);
         if (c.P.scan_level == 0 && a == CM_CONCRD) return CM_CONCRD;
     }
     return mr.type;

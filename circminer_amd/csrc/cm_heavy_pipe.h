@@ -100,11 +100,17 @@ __device__ inline void hp_answer_or_queue(const cmc::DpMem &sm, bool in_range, b
     }
 }
 
+// cm_prof_counters [5] = pairs handed to the fall-back list, [6] = those handed over in the second attempt (rare paths: one atomic each)
+__device__ inline void hp_count_fall(unsigned long long *counters, int attempt) {
+    atomicAdd(&counters[5], 1ull);
+    if (attempt) atomicAdd(&counters[6], 1ull);
+}
+
 // ---- plan ------------------------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(BLK_PAIR, 6) k_hp_plan(KCore kc, ReadsDev rd, uint64_t pair0, const uint32_t *hlist, const unsigned int *n_heavy_p,
                                                         const uint32_t *lst, const unsigned int *n_lst_p, int attempt, const cm_chain *chains,
                                                         const int32_t *nchain, const int32_t *high, const cm_mapped_read *state, HPipe P,
-                                                        uint16_t *lists, int str_cap) {
+                                                        uint16_t *lists, int str_cap, unsigned long long *counters) {
     extern __shared__ uint32_t lds_words[];
     const int lane = threadIdx.x;
     CM_L HSlot *S = (CM_L HSlot *)lds_words;
@@ -236,6 +242,7 @@ __global__ void __launch_bounds__(BLK_PAIR, 6) k_hp_plan(KCore kc, ReadsDev rd, 
             if (over) {
                 S[lane].done = 1;                              // (marks the slot: its tasks become holes, no requests)
                 P.fall[atomicAdd(P.fall_ctr, 1u)] = t;
+                hp_count_fall(counters, attempt);
             }
         }
         __syncthreads();
@@ -487,6 +494,7 @@ __global__ void __launch_bounds__(BLK_PAIR, 8) k_hp_fold(KCore kc, uint64_t pair
             if ((unsigned long long)off + (unsigned int)(nfu + nbu) > (unsigned long long)P.unp_cap) {          // does not fit: the whole pair to the fall-back kernel
                 hp.over = 1;
                 P.fall[atomicAdd(P.fall_ctr, 1u)] = hp.t;
+                hp_count_fall(counters, attempt);
                 // (its stretch of U stays unwritten; the entries below the capacity are made holes)
                 for (int k = 0; k < nfu + nbu; ++k)
                     if ((unsigned long long)off + (unsigned int)k < P.unp_cap) P.U[off + k] = HUnp{0xffffffffu, 0u};
@@ -608,8 +616,11 @@ __global__ void __launch_bounds__(BLK_PAIR, 8) k_hp_finish(KCore kc, uint64_t pa
     for (unsigned int y = x; y < n_items; y += gridDim.x * BLK_PAIR) {
         const uint32_t h = attempt == 0 ? y : lst[y];
         HPair &hp = P.hp[h];
-        if (hp.over) {                                     // goes through the fall-back launch, which may come late: active until then
-            if (attempt == 0) active[pair0 + hp.t] = 1;
+        if (hp.over) {
+            // Goes through the fall-back launch, which may come late: active until then.  In either attempt (hp.over is the current
+            // attempt's): nobody else writes this round's flag of a pair that left the pipeline in its second attempt, and the next
+            // round's seeding of the tile may read it before the fall-back launch does.
+            active[pair0 + hp.t] = 1;
             continue;
         }
         cm_mapped_read mr = hp.mr;
@@ -643,6 +654,7 @@ __global__ void __launch_bounds__(BLK_PAIR, 8) k_hp_finish(KCore kc, uint64_t pa
                     st = (c.P.scan_level == 0 && mr.type == CM_CONCRD) ? CM_CONCRD : mr.type;
                 } else if (second_to_fall) {           // the few others: whole, by the fall-back kernel behind the pipeline
                     P.fall[atomicAdd(P.fall_ctr, 1u)] = hp.t;
+                    hp_count_fall(counters, 0);
                     active[pair0 + hp.t] = 1;
                     continue;
                 } else {

@@ -523,7 +523,7 @@ __global__ void __launch_bounds__(64, CM_CHEAVY_WAVES) k_chain_heavy(KCore kc_, 
         const uint64_t p = pair0 + (r >> 2);
         const int mate = (int)((r >> 1) & 1u);
         const int len = (int)(mate ? rd.off2[p + 1] - rd.off2[p] : rd.off1[p + 1] - rd.off1[p]);
-#if defined(CM_CHAIN_DIAG)      // wave time per phase (100 MHz ticks) into counters[5..7]: load + init, DP, back-tracking
+#if defined(CM_CHAIN_DIAG)      // wave time per phase (100 MHz ticks) into counters[13..15]: load + init, DP, back-tracking
         const unsigned long long dg0 = wall_clock64();
 #endif
         uint32_t st[cmc::MAX_SEEDS], cn[cmc::MAX_SEEDS], base[cmc::MAX_SEEDS + 1];
@@ -841,9 +841,9 @@ __global__ void __launch_bounds__(64, CM_CHEAVY_WAVES) k_chain_heavy(KCore kc_, 
             resid[r] = (uint16_t)rs;
 #if defined(CM_CHAIN_DIAG)
             const unsigned long long dg3 = wall_clock64();
-            atomicAdd(&counters[5], dg1 - dg0);
-            atomicAdd(&counters[6], dg2 - dg1);
-            atomicAdd(&counters[7], dg3 - dg2);
+            atomicAdd(&counters[13], dg1 - dg0);
+            atomicAdd(&counters[14], dg2 - dg1);
+            atomicAdd(&counters[15], dg3 - dg2);
 #endif
         }
         __syncthreads();
@@ -3068,7 +3068,7 @@ static int run_pair_tile(cm_ctx *ctx, const KCore &core, uint64_t p0, uint32_t n
                 if (attempt) hipLaunchKernelGGL(k_hp_reset, dim3(1), dim3(64), 0, sp2, ctx->d_hp_ctr);
                 hipLaunchKernelGGL(k_hp_plan, dim3(HP_PLAN_GRID), dim3(BLK_PAIR), lds_slots, sp2, core, rd, p0, (const uint32_t *)hlist, n_heavy,
                                    (const uint32_t *)ctx->d_hp_list2, n_list2, attempt, (const cm_chain *)rb.chains, (const int32_t *)rb.nchain,
-                                   (const int32_t *)rb.high, (const cm_mapped_read *)ctx->d_state, hp, ctx->d_hp_lists, str_cap);
+                                   (const int32_t *)rb.high, (const cm_mapped_read *)ctx->d_state, hp, ctx->d_hp_lists, str_cap, ctx->d_counters);
                 hipLaunchKernelGGL(k_hp_dp, dim3(pipe_grid), dim3(BLK_PAIR), lds_bytes, sp2, core, rd, p0, attempt, hp, 0, str_cap);
                 if (task_order && attempt == 0) {       // (the second attempt's handful: array order) the tasks by work class, heaviest first (16-class counting sort over the tile's task array)
                     const uint32_t nbt = (ctx->hp_tasks_cap + CLS_T - 1) / CLS_T;

@@ -296,7 +296,9 @@ int cm_prof_get(cm_ctx *ctx, double ms[8], uint64_t launches[8]);
 /* Algorithmic byte counters of SURVEY §8(d) accumulated by the kernels since cm_prof_reset():
  * [0]=probes [1]=binary-search touches [2]=hits consumed (cnt<=seedLim) [3]=pair-rounds; [4]=pair-rounds that needed the re-run
  * launch (a device capacity the reference does not have, e.g. more than 8 memoised exon pieces in one extension: mapped again
- * with room for 2048, results identical); [5..7] reserved (0). */
+ * with room for 2048, results identical); [5]=pair-rounds the heavy-pair pipeline handed whole to its fall-back kernel (their
+ * mate-pair tasks or unpaired chains did not fit the pipeline's arrays, or CM_HP_ATTEMPTS=1), [6]=those of [5] handed over in
+ * the second orientation attempt; [7] reserved (0). */
 int cm_prof_counters(cm_ctx *ctx, uint64_t c[8]);
 
 /* ---------------- host-side builders (stay on host; north_star "index build ... on host") ---- */

@@ -1,5 +1,5 @@
 """Where a heavy chaining problem's wave time goes (load + init / DP / back-tracking): a -DCM_CHAIN_DIAG build of the library
-accumulates 100 MHz ticks per phase into cm_prof_counters[5..7].  python tests/diag/chain_phases.py [pairs]"""
+accumulates 100 MHz ticks per phase into words [13..15] of cm_debug_counters.  python tests/diag/chain_phases.py [pairs]"""
 import os, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
@@ -22,13 +22,13 @@ hp.prof(True); hp.prof_reset()
 hp.map_rounds([0, 1, 2], True); hp.sync()
 ms, nl, cnt = hp.prof_get()
 print("stage ms:", [round(x, 2) for x in ms], "launches", nl)
-t = [c / 1e5 for c in cnt[5:8]]          # ms of wave time
-print(f"k_chain_heavy wave-ms: load+init {t[0]:.0f}, DP {t[1]:.0f}, back-tracking {t[2]:.0f}  (sum {sum(t):.0f}; "
-      f"3072 resident waves -> {sum(t) / 3072:.2f} ms if perfectly packed)")
 import ctypes as C
 raw = (C.c_ulonglong * 32)()
 hp.L.cm_debug_counters.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong)]
 hp.L.cm_debug_counters(hp.h, raw)
+t = [raw[k] / 1e5 for k in (13, 14, 15)]          # ms of wave time
+print(f"k_chain_heavy wave-ms: load+init {t[0]:.0f}, DP {t[1]:.0f}, back-tracking {t[2]:.0f}  (sum {sum(t):.0f}; "
+      f"3072 resident waves -> {sum(t) / 3072:.2f} ms if perfectly packed)")
 tk = [raw[8 + k] for k in range(5)]
 wv = [raw[16 + k] / 1e5 for k in range(4)]
 print(f"DP, lane time (ms, summed over lanes): binary searches {tk[0] / 1e5:.0f}, upper_bound {tk[1] / 1e5:.0f}, window loops {tk[2] / 1e5:.0f}; "

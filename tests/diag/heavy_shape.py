@@ -16,7 +16,7 @@ b = cl.ReadBatch(d.seq1, d.seq2)
 E = conftest.load_emu()
 E.emu_set_stats_out.argtypes = [C.c_void_p]
 E.emu_set_dp_out.argtypes = [C.c_void_p]
-stats = np.zeros((b.n, 16), np.uint64); E.emu_set_stats_out(stats.ctypes.data)
+stats = np.zeros((b.n, E.emu_stats_width()), np.uint64); E.emu_set_stats_out(stats.ctypes.data)
 nchain = np.zeros(b.n * 4, np.int32)
 op.build()
 st, act = op.default_state(P, b.n); cat = np.full(b.n, -1, np.int32)

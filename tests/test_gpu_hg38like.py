@@ -78,15 +78,19 @@ def _stage2(tmp, d, hi, P, st, act, min_pairs):
     return rows, n_planted, n_pass
 
 
-def _compare_all_rounds(d, gtf, P, n_pairs, streamed, stage2=None):
+def _build_index(d, gtf, P):
     t = time.time()
     hi = cl.HostIndex(d.contigs, d.chr_table, gtf, kmer=P.kmer, n_threads=os.cpu_count() or 8)
     print(f"k={P.kmer} index built in {time.time() - t:.0f}s", flush=True)
     assert hi.n_contigs == 3
+    return hi
+
+
+def _device_walk(d, hi, P, n_pairs, streamed):
+    """the three rounds in one cm_map_rounds call on a fresh context: (state, category, active, records of the active pairs, seconds)"""
     hp = cl.HotPath(P)
     for ci in range(3):
         hp.load_contig(ci, hi.views[ci], hi.annots[ci])
-    batch = cl.ReadBatch(d.seq1[:n_pairs], d.seq2[:n_pairs])
     if streamed:                  # the bench's way in: staged from page-locked memory while another batch is resident
         pb = hp.pinned_batch(d.seq1[:n_pairs], d.seq2[:n_pairs])
         hp.upload(cl.ReadBatch(d.seq1[:1000], d.seq2[:1000]))
@@ -94,23 +98,40 @@ def _compare_all_rounds(d, gtf, P, n_pairs, streamed, stage2=None):
         hp.map_round(0, False)
         hp.swap()
     else:
-        hp.upload(batch)
+        hp.upload(cl.ReadBatch(d.seq1[:n_pairs], d.seq2[:n_pairs]))
     t = time.time()
     hp.map_rounds([0, 1, 2], True)
     st1, cat1, act1 = hp.download()
     t_gpu = time.time() - t
     rec = hp.collect_records(0).copy()
     hp.close()
-    t = time.time()
-    st0, act0, cat0 = op.map_all_rounds_mt(P, hi, batch)
-    print(f"{n_pairs} pairs x 3 rounds: GPU {t_gpu * 1e3:.0f} ms, oracle {time.time() - t:.1f}s on {os.cpu_count()} threads; "
-          f"types {np.bincount(st1['type'], minlength=14).tolist()}", flush=True)
+    return st1, cat1, act1, rec, t_gpu
+
+
+def _oracle_walk(d, hi, P, n_pairs, n_threads=None):
+    return op.map_all_rounds_mt(P, hi, cl.ReadBatch(d.seq1[:n_pairs], d.seq2[:n_pairs]), n_threads=n_threads)
+
+
+def _assert_walk_equals_oracle(dev, orc):
+    st1, cat1, act1, rec, _ = dev
+    st0, act0, cat0 = orc
     assert (act0 == act1).all()
     assert st0.tobytes() == st1.tobytes(), first_diff(st0, st1)
     assert (cat0 == cat1).all()                        # -1 for the pairs retired before the last round
     keep = np.nonzero(act1)[0]
     assert (rec["pair"] == keep).all() and rec["state"].tobytes() == st1[keep].tobytes()
     assert set(np.unique(st1["type"][keep])) <= {3, 4}
+
+
+def _compare_all_rounds(d, gtf, P, n_pairs, streamed, stage2=None):
+    hi = _build_index(d, gtf, P)
+    dev = _device_walk(d, hi, P, n_pairs, streamed)
+    t = time.time()
+    orc = _oracle_walk(d, hi, P, n_pairs)
+    print(f"{n_pairs} pairs x 3 rounds: GPU {dev[4] * 1e3:.0f} ms, oracle {time.time() - t:.1f}s on {os.cpu_count()} threads; "
+          f"types {np.bincount(dev[0]['type'], minlength=14).tolist()}", flush=True)
+    _assert_walk_equals_oracle(dev, orc)
+    st1, act1 = dev[0], dev[2]
     res = stage2(hi, st1, act1) if stage2 else None
     hi.close()
     return st1, res
@@ -139,12 +160,27 @@ def test_hg38like_three_rounds(hg38, monkeypatch, tmp_path, tile):
     assert len(np.unique(st["contig_num"][st["type"] == 0])) == 3          # concordant pairs found in every round
 
 
-def test_hg38like_stress_flags(hg38, tmp_path):
-    """configs[4]: k = 22 --seed-lim 1000 --max-ed 8 --scan-lev 2 on the same genome, stage 1 states and stage 2 files."""
+def test_hg38like_stress_flags(hg38, tmp_path, monkeypatch):
+    """configs[4]: k = 22 --seed-lim 1000 --max-ed 8 --scan-lev 2 on the same genome, stage 1 states and stage 2 files.  Under
+    scan level 2 nothing retires before the last round.  The same 100 000 pairs then the bench's way in (staged, swapped in) in
+    four tiles and in exactly two: the walks of the round scheduler that seed a tile's next round early (one k = 22 index, one
+    oracle run and one stage 2 for the three walks)."""
     d, gtf = hg38
     P = cl.default_params(kmer=22, seed_lim=1000, max_ed=8, scan_level=2)
-    _compare_all_rounds(d, gtf, P, N_STRESS, streamed=False,
-                        stage2=lambda hi, st, act: _stage2(tmp_path, d, hi, P, st, act, min_pairs=int(0.02 * N_STRESS)))
+    hi = _build_index(d, gtf, P)
+    dev = _device_walk(d, hi, P, N_STRESS, streamed=False)
+    t = time.time()
+    orc = _oracle_walk(d, hi, P, N_STRESS)
+    print(f"{N_STRESS} pairs x 3 rounds: GPU {dev[4] * 1e3:.0f} ms, oracle {time.time() - t:.1f}s on {os.cpu_count()} threads; "
+          f"types {np.bincount(dev[0]['type'], minlength=14).tolist()}", flush=True)
+    _assert_walk_equals_oracle(dev, orc)
+    _stage2(tmp_path, d, hi, P, dev[0], dev[2], min_pairs=int(0.02 * N_STRESS))
+    for tile in ("32768", "65536"):
+        monkeypatch.setenv("CM_TILE_PAIRS", tile)
+        dev = _device_walk(d, hi, P, N_STRESS, streamed=True)
+        print(f"streamed, CM_TILE_PAIRS={tile} ({-(-N_STRESS // int(tile))} tiles): GPU {dev[4] * 1e3:.0f} ms", flush=True)
+        _assert_walk_equals_oracle(dev, orc)
+    hi.close()
 
 
 def test_hg38like_preset_is_the_surveys(hg38):

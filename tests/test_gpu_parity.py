@@ -9,6 +9,7 @@ import torch
 from circminer_amd import lib as cl
 from oracle import oracle_py as op
 from conftest import first_diff
+from datasets_util import SCHED_IDS, SCHED_PARAMS
 
 pytestmark = pytest.mark.gpu
 
@@ -16,6 +17,26 @@ pytestmark = pytest.mark.gpu
 # torch bring up its bundled HIP runtime first: initialised second, it reports "No HIP GPUs are available".
 if torch.cuda.is_available():
     torch.cuda.init()
+
+
+@pytest.fixture(scope="module")
+def ds_invdup(tmp_path_factory, built):
+    """`tiny2r` with an inverted duplication: the one small data set on which process_read's second orientation attempt has
+    mate-pair tasks (datasets_util.inverted_dup_dataset; test_hostemu_parity.py asserts that it does)"""
+    from datasets_util import inverted_dup_dataset
+    return inverted_dup_dataset(tmp_path_factory.mktemp("invdup"))
+
+
+@pytest.fixture(scope="module")
+def ds_k22(tmp_path_factory, built):
+    """two packed contigs under a k = 22 index (BASELINE.json configs[4]'s k)"""
+    from conftest import DataSet
+    return DataSet(tmp_path_factory.mktemp("k22r"), "tiny2r", 1200, 37, kmer=22)
+
+
+def _sched_cases(tiles):
+    """SCHED_PARAMS x tiles as one parameter list; the default parameter set keeps the ids it had before (the tile alone)"""
+    return [pytest.param(kw, t, id=(str(t) if not kw else f"{kid}-{t}")) for kw, kid in zip(SCHED_PARAMS, SCHED_IDS) for t in tiles]
 
 
 def _chains_equal(c0, n0, c1, n1):
@@ -92,18 +113,25 @@ def test_chain_parity(name, request):
     hp.close()
 
 
-@pytest.mark.parametrize("name", ["ds_tiny", "ds_tiny2r", "ds_small", "ds_variety"])
+@pytest.mark.parametrize("name", ["ds_tiny", "ds_tiny2r", "ds_small", "ds_variety", "ds_invdup"])
 def test_map_parity_all_rounds(name, request):
     ds = request.getfixturevalue(name)
     st = _run_all_rounds(ds, cl.default_params(kmer=ds.kmer))
     # planted truth: most transcriptomic pairs come back concordant at the planted coordinates
     m = (ds.d.src == 0)
+    if name == "ds_invdup":            # (pairs planted in the overwritten 40 kb of chr1 have nowhere to map: left out, with a read length of margin)
+        m &= ~((ds.d.truth_chr == 0) & (ds.d.truth_hi > 70000 - 150) & (ds.d.truth_lo <= 110000 + 150))
     assert (st["type"][m] == cl.CAT["CONCRD"]).mean() > (0.9 if name != "ds_variety" else 0.8)
 
 
-@pytest.mark.parametrize("kw", [dict(scan_level=1), dict(scan_level=2, max_ed=8, seed_lim=1000), dict(max_chain_len=5, max_tlen=300)])
-def test_map_parity_param_variants(ds_tiny2r, kw):
-    _run_all_rounds(ds_tiny2r, cl.default_params(kmer=ds_tiny2r.kmer, **kw))
+_VARIANTS = [dict(scan_level=1), dict(scan_level=2, max_ed=8, seed_lim=1000), dict(max_chain_len=5, max_tlen=300)]
+
+
+@pytest.mark.parametrize("name,kw", [pytest.param(nm, kw, id=(f"kw{i}" if nm == "ds_tiny2r" else f"{nm}-kw{i}"))
+                                     for nm in ("ds_tiny2r", "ds_invdup") for i, kw in enumerate(_VARIANTS)])
+def test_map_parity_param_variants(name, kw, request):
+    ds = request.getfixturevalue(name)
+    _run_all_rounds(ds, cl.default_params(kmer=ds.kmer, **kw))
 
 
 def test_map_batch_wrapper_and_errors(ds_tiny):
@@ -172,7 +200,8 @@ def test_full_size_parity_chr21(tmp_path_factory, n_pairs, seed, kw):
     hp.close()
 
 
-def test_batches_beyond_two_tiles_worth_of_pairs(tmp_path_factory, monkeypatch):
+@pytest.mark.parametrize("kw", [{}, dict(scan_level=1)], ids=["default", "scan1"])
+def test_batches_beyond_two_tiles_worth_of_pairs(tmp_path_factory, monkeypatch, kw):
     """A batch of more than 2^21 pairs is walked in two tiles of half the batch (up to 2^21 pairs each; cm_hot.hip tile_for); with
     CM_TILE_PAIRS=2^20 the same batch takes three tiles, whose seeds are computed a chain stage early (the flags they read are two
     items old).  Both walks must give the same bytes, equal the oracle on ranges around every tile boundary, and keep the
@@ -183,7 +212,7 @@ def test_batches_beyond_two_tiles_worth_of_pairs(tmp_path_factory, monkeypatch):
     from conftest import DataSet
     n = (1 << 21) + 200_000
     ds = DataSet(tmp_path_factory.mktemp("chr21big"), "chr21", n, 91)
-    P = cl.default_params()
+    P = cl.default_params(**kw)
 
     def run():
         hp = cl.HotPath(P)
@@ -231,6 +260,30 @@ def test_config5_stress_params(tmp_path_factory):
     from conftest import DataSet
     ds = DataSet(tmp_path_factory.mktemp("k22s"), "small", 8000, 37, kmer=22)
     _run_all_rounds(ds, cl.default_params(kmer=22, seed_lim=1000, max_ed=8, scan_level=2))
+
+
+@pytest.mark.parametrize("tile", [None, "600", "256"])
+def test_config5_stress_params_rounds_in_one_call(ds_k22, monkeypatch, tile):
+    """configs[4]'s flags and its k through cm_map_rounds: under scan level 2 nothing retires before the last round, so every
+    round seeds and chains the whole batch; one tile, exactly two, five; an even and an odd number of rounds."""
+    if tile:
+        monkeypatch.setenv("CM_TILE_PAIRS", tile)
+    ds = ds_k22
+    P = cl.default_params(kmer=22, seed_lim=1000, max_ed=8, scan_level=2)
+    hp = cl.HotPath(P)
+    for ci in range(ds.hi.n_contigs):
+        hp.load_contig(ci, ds.hi.views[ci], ds.hi.annots[ci])
+    for order in ([0, 1], [1, 0, 1]):
+        st0, act0 = op.default_state(P, ds.batch.n)
+        for k, ci in enumerate(order):
+            cat0 = op.map_round(P, ds.ohi.views[ci], ds.ohi.annots[ci], ds.batch, k == len(order) - 1, st0, act0)
+        hp.upload(ds.batch)
+        hp.map_rounds(order, True)
+        st1, cat1, act1 = hp.download()
+        assert st0.tobytes() == st1.tobytes(), (order, first_diff(st0, st1))
+        assert (act0 == act1).all() and (cat0 == cat1).all(), order
+        assert act1.sum() > 0 and (st1["type"] == cl.CAT["CONCRD"]).sum() > 300      # (not an empty comparison)
+    hp.close()
 
 
 def test_mapping_from_index_files_matches_in_memory_index(ds_tiny2r, tmp_path):
@@ -381,12 +434,15 @@ def test_two_rounds_through_remain_fastq_files(ds_tiny2r, tmp_path):
     assert len(rows) == n and sorted(r.split("\t")[0] for r in rows) == sorted(f"pair{i}" for i in range(n))
 
 
-def test_multi_tile_batches_match_the_oracle(ds_small, monkeypatch):
+@pytest.mark.parametrize("name,tile", [("ds_small", "4096"), ("ds_invdup", "600"), ("ds_invdup", "256")])
+@pytest.mark.parametrize("kw", SCHED_PARAMS, ids=SCHED_IDS)
+def test_multi_tile_batches_match_the_oracle(name, tile, kw, request, monkeypatch):
     """Several launch groups per round (CM_TILE_PAIRS): the per-tile workspaces, the task pipeline of the mid
-    pairs and the second stream are reused tile after tile; results must not depend on the tiling."""
-    monkeypatch.setenv("CM_TILE_PAIRS", "4096")
-    P = cl.default_params(kmer=ds_small.kmer)
-    _run_all_rounds(ds_small, P)
+    pairs and the second stream are reused tile after tile; results must not depend on the tiling.  Five tiles of the 20 000-pair
+    set; exactly two and five of the data set whose pairs reach the second orientation attempt; under every retirement rule."""
+    monkeypatch.setenv("CM_TILE_PAIRS", tile)
+    ds = request.getfixturevalue(name)
+    _run_all_rounds(ds, cl.default_params(kmer=ds.kmer, **kw))
 
 
 def test_ragged_and_dirty_reads(ds_dirty):
@@ -599,12 +655,13 @@ def test_genes_with_more_than_64_isoforms(ds_tiny, tmp_path):
     _run_all_rounds(sh, cl.default_params())
 
 
-def test_staged_batches_overlap_and_match(ds_tiny2r, ds_dirty):
+@pytest.mark.parametrize("kw", SCHED_PARAMS, ids=SCHED_IDS)
+def test_staged_batches_overlap_and_match(ds_tiny2r, ds_dirty, kw):
     """cm_reads_stage / cm_reads_swap: the next batch is copied on the copy stream while the resident one maps; every
     batch's results equal the oracle's, whatever was resident or staged before (ragged batch, carried prior states,
     a staged batch that is replaced before it is swapped in)."""
     ds = ds_tiny2r
-    P = cl.default_params(kmer=ds.kmer)
+    P = cl.default_params(kmer=ds.kmer, **kw)
     hp = cl.HotPath(P)
     for ci in range(ds.hi.n_contigs):
         hp.load_contig(ci, ds.hi.views[ci], ds.hi.annots[ci])
@@ -665,16 +722,22 @@ def test_improvement_log_pool_recovers(ds_small, monkeypatch, pool_max):
     _run_all_rounds(ds_small, cl.default_params(kmer=ds_small.kmer))
 
 
-@pytest.mark.parametrize("tile", [None, "512"])
-def test_rounds_in_one_call_match_round_by_round(ds_tiny2r, ds_small, ds_dirty, ds_variety, monkeypatch, tile):
+@pytest.mark.parametrize("kw,tile", _sched_cases([None, "512", "600"]))
+def test_rounds_in_one_call_match_round_by_round(ds_tiny2r, ds_small, ds_dirty, ds_variety, ds_invdup, monkeypatch, kw, tile):
     """cm_map_rounds: round r + 1 is seeded and chained (other streams, second set of chain buffers, flags of the round before)
     while the pair stage of round r runs.  Same final state, flags, categories and BSJ records as round-by-round calls and as
     the oracle; repeated on one context, with several tiles per batch, with a contig used twice and with an even / odd number
-    of rounds (the active-flag arrays swap roles every round)."""
+    of rounds (the active-flag arrays swap roles every round).  Under every retirement rule (SCHED_PARAMS); tile = 600: exactly
+    two tiles for the 1 200-pair sets, the one count whose early seeding waits for the pair kernels alone.  The sets other than
+    the default leave out the 20 000-pair data set and the four-round order (time)."""
     if tile:
         monkeypatch.setenv("CM_TILE_PAIRS", tile)
-    for ds, order in ((ds_tiny2r, [0, 1]), (ds_dirty, [0, 1]), (ds_tiny2r, [1, 0, 1]), (ds_small, [0]), (ds_tiny2r, [0, 1, 0, 1]), (ds_variety, [0, 1])):
-        P = cl.default_params(kmer=ds.kmer)
+    cases = [(ds_tiny2r, [0, 1]), (ds_dirty, [0, 1]), (ds_tiny2r, [1, 0, 1]), (ds_small, [0]), (ds_tiny2r, [0, 1, 0, 1]), (ds_variety, [0, 1]),
+             (ds_invdup, [0, 1]), (ds_invdup, [0, 0])]
+    if kw:
+        cases = [c for c in cases if c[0] is not ds_small and len(c[1]) < 4]
+    for ds, order in cases:
+        P = cl.default_params(kmer=ds.kmer, **kw)
         hp = cl.HotPath(P)
         for ci in range(ds.hi.n_contigs):
             hp.load_contig(ci, ds.hi.views[ci], ds.hi.annots[ci])
@@ -776,8 +839,9 @@ def test_rerun_launch_under_a_two_entry_memo(tmp_path):
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
     import re
     m = re.search(r"(\d+) passed", r.stdout)
-    # 4 + 3 + 1 + 2 + 1 + 1 + 1 + 1 + 1: the selection must not silently shrink when tests are renamed
-    assert m and int(m.group(1)) >= 15, r.stdout[-1500:]
+    # 5 + 6 + 1 + 9 + 9 + 3 + (1 + 3) + 1 + 1, in the order of the -k expression (test_config5_stress_params selects both tests of that
+    # name): the selection must not silently shrink when tests are renamed
+    assert m and int(m.group(1)) >= 39, r.stdout[-1500:]
 
 
 def test_heavy_pipeline_fall_back_and_variants():
@@ -795,11 +859,166 @@ def test_heavy_pipeline_fall_back_and_variants():
     for knobs in ({"CM_HP_TASKS_CAP": "40", "CM_HP_UNP_CAP": "24", "CM_HEAVY_COST": "2"}, {"CM_HP_TASKS_CAP": "100000", "CM_HP_UNP_CAP": "3", "CM_HEAVY_COST": "2"}, {"CM_HP_ATTEMPTS": "1"}, {"CM_HEAVY_PIPELINE": "0"}):
         env = dict(os.environ, **knobs)
         r = subprocess.run([sys.executable, "-m", "pytest", "-x", "-q", "-m", "gpu", os.path.join(root, "tests", "test_gpu_parity.py"), "-k",
-                            "test_map_parity_all_rounds or test_rounds_in_one_call or test_multi_tile_batches or test_ragged_and_dirty_reads"],
+                            "test_map_parity_all_rounds or test_multi_tile_batches or test_ragged_and_dirty_reads or (test_rounds_in_one_call and not "
+                            "(scan1-None or scan1-512 or scan2-None or scan2-512))"],
                            env=env, capture_output=True, text=True, cwd=root)
         assert r.returncode == 0, str(knobs) + r.stdout[-3000:] + r.stderr[-2000:]
         m = re.search(r"(\d+) passed", r.stdout)
-        assert m and int(m.group(1)) >= 7, str(knobs) + r.stdout[-1500:]
+        # 5 + 9 + 1 + (3 + 1 + 1): all rounds of five data sets; multi-tile x SCHED_PARAMS; dirty reads; rounds in one call with the default
+        # set at every tile and the other two sets at the two-tile size (time) -- every knob set maps the inverted-duplication data
+        # set, whose pairs reach the second attempt, at the two-tile size under every SCHED_PARAMS entry
+        assert m and int(m.group(1)) >= 20, str(knobs) + r.stdout[-1500:]
+
+
+_OVERFLOW_KNOBS = {"CM_HEAVY_COST": "2", "CM_HP_UNP_CAP": "100000", "CM_HP_TASKS_CAP": "200"}
+_overflow_child = {}
+
+
+def _overflow_child_report():
+    """All parametrisations of the two tests below in ONE child process under _OVERFLOW_KNOBS (CM_HEAVY_COST is read once per process),
+    run once per session; every parametrisation then looks up its own line."""
+    if not _overflow_child:
+        import subprocess
+        import sys
+        root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+        env = dict(os.environ, CM_OVERFLOW_CHILD="1", **_OVERFLOW_KNOBS)
+        env.pop("CM_TILE_PAIRS", None)
+        r = subprocess.run([sys.executable, "-m", "pytest", "-q", "-rA", "-m", "gpu", "-p", "no:cacheprovider", os.path.join(root, "tests", "test_gpu_parity.py"), "-k",
+                            "test_overflow_in_the_second_attempt"], env=env, capture_output=True, text=True, cwd=root)
+        _overflow_child["out"] = r.stdout + r.stderr
+        print(_overflow_child["out"][-6000:])
+    return _overflow_child["out"]
+
+
+def _overflow_in_child(request):
+    """parent side of the two tests below: this parametrisation's line of the child run"""
+    out = _overflow_child_report()
+    line = [ln for ln in out.splitlines() if ln.startswith(("PASSED ", "FAILED ", "ERROR ")) and ln.rstrip().endswith("::" + request.node.name)]      # (-rA: one per test)
+    assert line and all(ln.startswith("PASSED ") for ln in line), (request.node.name, line, out[-3000:])
+
+
+_overflow_picks = {}
+
+
+def _overflow_case(request, kw, tiles, kind):
+    """child side.  kind "tasks": pairs of the data set with t1 > t0 >= 1, capacity 200 tasks; kind "unp": pairs of
+    datasets_util.block_and_unique_pairs with unpaired-chain extensions in the second attempt only, capacity 100 chains."""
+    from conftest import _Shim
+    from datasets_util import attempt_counts, block_and_unique_pairs
+    assert os.environ.get("CM_HEAVY_COST") == "2"
+    ds = request.getfixturevalue("ds_invdup")
+    emu = request.getfixturevalue("emu")
+    monkeypatch = request.getfixturevalue("monkeypatch")
+    P = cl.default_params(kmer=ds.kmer, **kw)
+    n = 1200
+    tile = n // tiles
+    assert tile * tiles == n
+    key = (kind, tuple(sorted(kw.items())))
+    if key not in _overflow_picks:                                       # (the same for every tile count)
+        src = ds if kind == "tasks" else _Shim(ds, block_and_unique_pairs(ds))
+        t0, t1, u0, u1, _ = attempt_counts(emu, src, P)                  # round 0, not the final round
+        st_o, act_o = op.default_state(P, src.batch.n)
+        op.map_round(P, ds.ohi.views[0], ds.ohi.annots[0], src.batch, False, st_o, act_o)
+        _overflow_picks[key] = (src, t0, t1, u0, u1, act_o)
+    src, t0, t1, u0, u1, act_o = _overflow_picks[key]
+    rng = np.random.default_rng(7)
+    if kind == "tasks":
+        cap = int(_OVERFLOW_KNOBS["CM_HP_TASKS_CAP"])
+        S = np.nonzero((t1 > t0) & (t0 >= 1) & (act_o != 0))[0]
+        assert len(S) >= 8, len(S)
+        pick = rng.choice(S, n)
+        mx = int(t0[S].max())
+        assert (cap - mx) / mx >= mx, (cap, mx)
+        for k in range(tiles):
+            assert t0[pick[k * tile:(k + 1) * tile]].sum() > cap
+    else:
+        cap = 100
+        monkeypatch.setenv("CM_HP_TASKS_CAP", "100000")
+        monkeypatch.setenv("CM_HP_UNP_CAP", str(cap))
+        S = np.nonzero((u0 == 0) & (u1 >= 1) & (act_o != 0))[0]
+        assert len(S) >= 8, len(S)
+        pick = rng.choice(S, n)
+        for k in range(tiles):
+            assert u1[pick[k * tile:(k + 1) * tile]].sum() > cap
+    s1, s2 = src.batch.seq1.reshape(src.batch.n, -1), src.batch.seq2.reshape(src.batch.n, -1)
+    test_batch = cl.ReadBatch(s1[pick], s2[pick])
+    # the poison: planted transcriptomic pairs that a final round 0 retires
+    st_f, act_f = op.default_state(P, ds.batch.n)
+    op.map_round(P, ds.ohi.views[0], ds.ohi.annots[0], ds.batch, True, st_f, act_f)
+    Z = np.nonzero((ds.d.src == 0) & (act_f == 0))[0]
+    assert len(Z) >= 100
+    zpick = rng.choice(Z, n)
+    poison_batch = cl.ReadBatch(ds.d.seq1[zpick], ds.d.seq2[zpick])
+    if tiles > 1:
+        monkeypatch.setenv("CM_TILE_PAIRS", str(tile))
+    else:
+        monkeypatch.delenv("CM_TILE_PAIRS", raising=False)
+    hp = cl.HotPath(P)
+    for ci in range(ds.hi.n_contigs):
+        hp.load_contig(ci, ds.hi.views[ci], ds.hi.annots[ci])
+    for order in ([0, 0], [0, 1, 0]):
+        hp.upload(poison_batch)
+        for _ in range(2):                                       # both flag arrays: the rounds swap them
+            hp.map_round(0, True)
+            assert not hp.download()[2].any()
+        before = hp.prof_get()[2]
+        hp.upload(test_batch)                                     # same n: same buffers; only the current flags are initialised
+        hp.map_rounds(order, True)
+        st1, cat1, act1 = hp.download()
+        after = hp.prof_get()[2]
+        st0, act0 = op.default_state(P, n)
+        for k, ci in enumerate(order):
+            cat0 = op.map_round(P, ds.ohi.views[ci], ds.ohi.annots[ci], test_batch, k == len(order) - 1, st0, act0)
+        print(f"overflow ({kind}) {kw} tiles={tiles} order={order}: fall-back hand-overs {after[5] - before[5]}, in the second attempt {after[6] - before[6]}; "
+              f"cat differs at {int((cat0 != cat1).sum())} pairs, active at {int((act0 != act1).sum())}, state at "
+              f"{sum(st0[i].tobytes() != st1[i].tobytes() for i in range(n))} of {n}", flush=True)
+        assert after[6] - before[6] >= 1 and after[5] - before[5] >= after[6] - before[6]
+        assert (cat0 == cat1).all(), (order, np.nonzero(cat0 != cat1)[0][:10], cat0[cat0 != cat1][:10], cat1[cat0 != cat1][:10])
+        assert (act0 == act1).all(), order
+        assert st0.tobytes() == st1.tobytes(), (order, first_diff(st0, st1))
+    hp.close()
+
+
+@pytest.mark.parametrize("tiles", [2, 3, 1])
+@pytest.mark.parametrize("kw", SCHED_PARAMS, ids=SCHED_IDS)
+def test_overflow_in_the_second_attempt_keeps_its_flag(kw, tiles, request):
+    """A pair that leaves the heavy-pair pipeline for the fall-back list in its SECOND orientation attempt (k_hp_plan: its tasks do
+    not fit CM_HP_TASKS_CAP) gets this round's active flag from the fall-back kernel, which with several tiles is launched late --
+    after the next round's seeding of that tile has been queued behind the pair kernels alone (two tiles).  Until then the flag
+    must read 1.  k_hp_finish wrote that 1 for the first attempt only; for the second the byte kept whatever the array held: the
+    pair's own earlier 1 wherever a test maps a batch twice, so the test POISONS both flag arrays with zeros first (a batch of
+    pairs that retire, mapped through a final round twice, checked) and uploads the batch under test into the same buffers.
+    A stale 0 makes the next round seed nothing for a pair that is still active: it ends NOPROC_NOMATCH, which the final round's
+    category shows even where the carried state happens to agree.
+
+    The batch: n = 1 200 pairs drawn with repetition from the pairs of the inverted-duplication data set that have more mate-pair
+    tasks in the second attempt than in the first (t1 > t0 >= 1, host emulation's per-attempt counters) and stay active after a
+    non-final round 0.  Capacity C = 200 tasks per tile: the pairs of a tile that fit in attempt 0 have sum(t0) > C - max t0, so
+    there are at least (C - max t0) / max t0 of them, each with t1 >= t0 + 1, hence sum(t1) > C whenever
+    (C - max t0) / max t0 >= max t0 -- asserted from the emulation's numbers together with sum(t0) > C per tile.
+    Not vacuous: cm_prof_counters [6] (pairs handed to the fall-back list in the second attempt) moves.
+    tiles = 2: CM_TILE_PAIRS = n / 2, the case described; 3 tiles and 1 tile order the seeding behind the late launches and are
+    pinned here.  Runs in a child process (CM_HEAVY_COST is read once per process); every parametrisation reads its line of that
+    one run.  On the kernels before the fix: the three two-tile cases fail (158 - 188 categories of 1 200 differ, states and flags
+    equal), the other six pass; [6] = 334 - 1 126 per walk."""
+    if not os.environ.get("CM_OVERFLOW_CHILD"):
+        return _overflow_in_child(request)
+    _overflow_case(request, kw, tiles, "tasks")
+
+
+@pytest.mark.parametrize("tiles", [2, 3, 1])
+@pytest.mark.parametrize("kw", SCHED_PARAMS, ids=SCHED_IDS)
+def test_overflow_in_the_second_attempt_of_unpaired_chains_keeps_its_flag(kw, tiles, request):
+    """The other way out of the pipeline in the second attempt: k_hp_fold, when a pair's unpaired chains do not fit CM_HP_UNP_CAP.
+    Same poison, walks and comparisons as the test above.  The batch: pairs of datasets_util.block_and_unique_pairs whose
+    unpaired chains are extended in the second attempt only (u0 = 0, u1 >= 1 by the emulation's counters; active after a non-final
+    round 0).  With u0 = 0 a pair reserves nothing in attempt 0 (the emulation extends at least one chain whenever the pipeline
+    would reserve any), so every pair of a tile reaches the second attempt and the array, reset in between, has to take what the
+    pipeline reserves for all of them: at least sum(u1), more than the capacity of 100 (asserted per tile) -- some pair goes to the
+    fall-back list in k_hp_fold, attempt 1; cm_prof_counters [6] says so.  Room for 100 000 tasks: k_hp_plan hands nothing over."""
+    if not os.environ.get("CM_OVERFLOW_CHILD"):
+        return _overflow_in_child(request)
+    _overflow_case(request, kw, tiles, "unp")
 
 
 def test_reruns_are_counted(ds_small):
@@ -820,8 +1039,8 @@ def test_reruns_are_counted(ds_small):
         assert reruns == 0
 
 
-@pytest.mark.parametrize("tile", [None, "300"])
-def test_cross_batch_prefetch_is_used_and_discarded_correctly(ds_tiny2r, ds_dirty, monkeypatch, tile):
+@pytest.mark.parametrize("kw,tile", _sched_cases([None, "300"]))
+def test_cross_batch_prefetch_is_used_and_discarded_correctly(ds_tiny2r, ds_dirty, monkeypatch, kw, tile):
     """cm_map_rounds seeds / chains the staged batch's first item (first tile, first round) under the resident batch's last pair
     stage.  Every batch equals the oracle whether that work is taken over (same first slot, same contig: launches[7] counts it)
     or has to be discarded (slot reloaded in between, another first slot, a call that is not the batch's last, a staged batch
@@ -830,7 +1049,7 @@ def test_cross_batch_prefetch_is_used_and_discarded_correctly(ds_tiny2r, ds_dirt
     if tile:
         monkeypatch.setenv("CM_TILE_PAIRS", tile)
     ds = ds_tiny2r
-    P = cl.default_params(kmer=ds.kmer)
+    P = cl.default_params(kmer=ds.kmer, **kw)
     hp = cl.HotPath(P)
     for ci in range(ds.hi.n_contigs):
         hp.load_contig(ci, ds.hi.views[ci], ds.hi.annots[ci])

@@ -9,6 +9,7 @@ import pytest
 from circminer_amd import lib as cl, synth
 from oracle import oracle_py as op
 from conftest import first_diff
+from datasets_util import SCHED_IDS, SCHED_PARAMS
 
 
 def _emu_rounds(E, ds, P):
@@ -24,6 +25,52 @@ def _emu_rounds(E, ds, P):
         assert rc == 0
         assert (cat0 == cat1).all() and (act0 == act1).all()
         assert st0.tobytes() == st1.tobytes(), first_diff(st0, st1)
+
+
+@pytest.fixture(scope="module")
+def ds_invdup(tmp_path_factory, built):
+    from datasets_util import inverted_dup_dataset
+    return inverted_dup_dataset(tmp_path_factory.mktemp("invdup"))
+
+
+@pytest.mark.parametrize("kw", SCHED_PARAMS, ids=SCHED_IDS)
+def test_second_attempt_has_work_on_the_inverted_duplication(emu, ds_invdup, ds_tiny2r, kw):
+    """process_read's second orientation attempt (R2 forward, R1 reverse) on datasets_util.inverted_dup_dataset: the kernel
+    bodies equal the oracle through all rounds, and -- the reason the data set exists -- the second attempt has mate-pair tasks
+    to run, often more than the first.  Counted by the emulation's per-attempt counters (cm_stats [16], [17]), round 0.
+    Measured when the data set was made: 114 - 120 pairs with second-attempt tasks, 13 - 16 of them with t1 > t0 >= 1; the floors
+    below leave room for noise, not for the property to vanish.  If they fail the data set has to be repaired, not the floors.
+    The stock `tiny2r` of the same seed has no second-attempt task at all (why no small test exercised that pass before)."""
+    from datasets_util import attempt_counts
+    P = cl.default_params(**kw)
+    _emu_rounds(emu, ds_invdup, P)
+    t0, t1, _, u1, act = attempt_counts(emu, ds_invdup, P)
+    more = (t1 > t0) & (t0 >= 1)
+    print(f"invdup {kw}: pairs with attempt-1 tasks {int((t1 > 0).sum())} ({int(((t1 > 0) & (act != 0)).sum())} stay active), tasks "
+          f"{int(t0.sum())} / {int(t1.sum())}, max t0 {int(t0.max())} t1 {int(t1.max())}, t1 > t0 >= 1: {int(more.sum())} "
+          f"({int((more & (act != 0)).sum())} stay active), unpaired extensions in attempt 1: {int(u1.sum())}")
+    assert (t1 > 0).sum() >= 50
+    assert more.sum() >= 8
+    s0, s1, _, v1, _ = attempt_counts(emu, ds_tiny2r, P)
+    print(f"tiny2r {kw}: tasks {int(s0.sum())} / {int(s1.sum())}, unpaired extensions in attempt 1: {int(v1.sum())}")
+    assert s0.sum() > 500 and s1.sum() == 0
+
+
+@pytest.mark.parametrize("kw", SCHED_PARAMS, ids=SCHED_IDS)
+def test_second_attempt_unpaired_extensions_exist(emu, ds_invdup, kw):
+    """datasets_util.block_and_unique_pairs: pairs whose unpaired chains are extended in the second attempt ONLY exist (the data sets
+    above have none in the second attempt at all), and the kernel bodies equal the oracle on them.  Measured: 30 of 3 200 under every
+    parameter set; the GPU test that overflows the pipeline's unpaired-chain array in the second attempt draws from them."""
+    from conftest import _Shim
+    from datasets_util import attempt_counts, block_and_unique_pairs
+    P = cl.default_params(**kw)
+    sh = _Shim(ds_invdup, block_and_unique_pairs(ds_invdup))
+    _emu_rounds(emu, sh, P)
+    t0, t1, u0, u1, act = attempt_counts(emu, sh, P)
+    only2 = (u0 == 0) & (u1 >= 1)
+    print(f"block + unique pairs {kw}: {int(only2.sum())} of {sh.batch.n} with unpaired extensions in the second attempt only ({int((only2 & (act != 0)).sum())} "
+          f"stay active), {int((u1 > 0).sum())} with any there; sum u0 {int(u0.sum())}, u1 {int(u1.sum())}")
+    assert (only2 & (act != 0)).sum() >= 8
 
 
 def test_seeds_and_chains(emu, ds_tiny):
