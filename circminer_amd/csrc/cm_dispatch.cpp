@@ -34,6 +34,8 @@ CM_VARIANTS(int, cm_collect_records_device, (void *, uint64_t, uint64_t, void *,
 CM_VARIANTS(int, cm_host_alloc, (void *, uint64_t, void **))
 CM_VARIANTS(int, cm_host_free, (void *, void *))
 CM_VARIANTS(int, cm_load_contig_raw, (void *, int, const cm_index_raw *))
+CM_VARIANTS(int, cm_build_contig, (void *, int, int32_t, const uint8_t *, uint32_t, cm_build_stats *))
+CM_VARIANTS(int, cm_index_download, (void *, int, uint32_t *, uint16_t *, uint32_t *, uint64_t, uint64_t *))
 CM_VARIANTS(int, cm_host_register, (void *, void *, uint64_t))
 CM_VARIANTS(int, cm_host_unregister, (void *, void *))
 CM_VARIANTS(int, cm_type_histogram, (void *, uint64_t *))
@@ -91,6 +93,12 @@ int cm_collect_records_device(cm_ctx *ctx, uint64_t base, uint64_t cap, void *d_
 int cm_host_alloc(cm_ctx *ctx, uint64_t bytes, void **out) { return ctx ? GO(cm_host_alloc, bytes, out) : CM_EINVAL; }
 int cm_host_free(cm_ctx *ctx, void *p) { return ctx ? GO(cm_host_free, p) : CM_EINVAL; }
 int cm_load_contig_raw(cm_ctx *ctx, int slot, const cm_index_raw *raw) { return ctx ? GO(cm_load_contig_raw, slot, raw) : CM_EINVAL; }
+int cm_build_contig(cm_ctx *ctx, int slot, int32_t contig_num, const uint8_t *genome, uint32_t ref_len, cm_build_stats *stats) {
+    return ctx ? GO(cm_build_contig, slot, contig_num, genome, ref_len, stats) : CM_EINVAL;
+}
+int cm_index_download(cm_ctx *ctx, int slot, uint32_t *bucket_off, uint16_t *checksum, uint32_t *pos, uint64_t cap, uint64_t *n) {
+    return ctx ? GO(cm_index_download, slot, bucket_off, checksum, pos, cap, n) : CM_EINVAL;
+}
 int cm_host_register(cm_ctx *ctx, void *p, uint64_t bytes) { return ctx ? GO(cm_host_register, p, bytes) : CM_EINVAL; }
 int cm_host_unregister(cm_ctx *ctx, void *p) { return ctx ? GO(cm_host_unregister, p) : CM_EINVAL; }
 int cm_type_histogram(cm_ctx *ctx, uint64_t out[14]) { return ctx ? GO(cm_type_histogram, out) : CM_EINVAL; }

@@ -10,6 +10,7 @@
 // There is no CPU path in this file: without a HIP device cm_create fails with CM_ENODEV.
 #include <chrono>
 #include <hip/hip_runtime.h>
+#include <rocprim/device/device_radix_sort.hpp>      // the oversize buckets of cm_build_contig only
 
 #include <algorithm>
 #include <atomic>
@@ -26,6 +27,7 @@
 #include "circminer_hot.h"
 #include "cm_core.h"
 #include "cm_aos.h"
+#include "cm_index_build.h"
 
 using cmc::Core;
 using cmc::KCore;
@@ -1644,6 +1646,117 @@ __global__ void __launch_bounds__(BLK) k_raw_scatter(const RawEntry *tab, const 
     }
 }
 
+// ---- cm_build_contig: the k-mer table built on the device from the sequence (bodies: cm_index_build.h) --------------
+// A counting sort.  k_ib_positions<false> adds 1 to the counter of every indexable k-mer's bucket; an inclusive scan turns the
+// counters into the END of every bucket; k_ib_positions<true> takes a slot from the end downwards (returning atomic) and stores
+// (checksum, position) there, so that the cursors finish as the bucket STARTS: the array is bucket_off and no second 1-GiB
+// cursor array exists.  The order inside a bucket is arbitrary at that point; k_ib_order_* make it (checksum, position).
+constexpr int IB_PER = 8, IB_TILE = BLK * IB_PER;           // k-mer starts per lane / per workgroup
+constexpr int IB_HALO = CM_WINDOW_SIZE + 8 - 1;             // k - 1 bases of the next tile, k <= 22
+static_assert(cmc::CM_STAGE_PAD >= 4, "k_ib_positions reads whole words up to 3 bytes past the contig");
+// genome: the slot's copy (4-byte aligned, readable for CM_STAGE_PAD bytes past ref_len).  n_pos = ref_len - k + 1 starts.
+template <bool SCATTER>
+__global__ void __launch_bounds__(BLK) k_ib_positions(const uint8_t *genome, uint32_t ref_len, uint32_t n_pos, int k, int c, uint32_t *cursor,
+                                                      uint16_t *checksum, uint32_t *pos) {
+    __shared__ uint8_t codes[IB_TILE + IB_HALO + 3];
+    const uint64_t t0 = (uint64_t)blockIdx.x * IB_TILE;                     // first start of the tile (a multiple of 4)
+    if (t0 >= n_pos) return;
+    const uint32_t tile_pos = (uint32_t)(n_pos - t0 < (uint64_t)IB_TILE ? n_pos - t0 : (uint64_t)IB_TILE);
+    const uint32_t n_codes = tile_pos + (uint32_t)k - 1;                  // t0 + n_codes <= ref_len
+    const uint32_t *gw = (const uint32_t *)(genome + t0);
+    for (uint32_t w = threadIdx.x; w * 4 < n_codes; w += BLK) {
+        const uint32_t x = gw[w];
+#pragma unroll
+        for (int b = 0; b < 4; ++b) codes[w * 4 + b] = (uint8_t)cmib::base_code((uint8_t)(x >> (8 * b)));
+    }
+    __syncthreads();
+    const uint32_t first = threadIdx.x * IB_PER;
+    if (first >= tile_pos) return;
+    const uint32_t mine = tile_pos - first < (uint32_t)IB_PER ? tile_pos - first : (uint32_t)IB_PER;
+    cmib::scan_positions(codes + first, n_codes - first, mine, k, c, [&](uint32_t j, uint32_t hv, uint32_t ck) {
+        if (SCATTER) {
+            const uint32_t at = atomicSub(&cursor[hv], 1u) - 1u;
+            checksum[at] = (uint16_t)ck;
+            pos[at] = (uint32_t)(t0 + first + j) + 1u;
+        } else {
+            atomicAdd(&cursor[hv], 1u);                                    // result unused: a no-return atomic
+        }
+    });
+}
+// what the ordering passes leave for the host: [0..2] non-empty buckets per path, [3] entries of the fullest bucket,
+// [4] / [5] length of the workgroup list / the oversize list
+enum { IB_ST_PATH = 0, IB_ST_MAX = 3, IB_ST_NMED = 4, IB_ST_NOVER = 5, IB_ST_WORDS = 6 };
+// one lane per bucket: few-entry buckets are ordered here, the others go on the list of their path
+__global__ void __launch_bounds__(BLK) k_ib_order_lane(const uint32_t *bucket_off, uint64_t n_buckets, uint16_t *checksum, uint32_t *pos, uint32_t lane_max,
+                                                       uint32_t wg_max, uint32_t *med_list, uint32_t *over_list, unsigned long long *st) {
+    __shared__ unsigned int cnt[4];
+    if (threadIdx.x < 4) cnt[threadIdx.x] = 0;
+    __syncthreads();
+    const uint64_t hv = (uint64_t)blockIdx.x * BLK + threadIdx.x;
+    if (hv < n_buckets) {
+        const uint32_t b0 = bucket_off[hv], n = bucket_off[hv + 1] - b0;
+        const int path = cmib::bucket_path(n, lane_max, wg_max);
+        if (path >= 0) {
+            atomicAdd(&cnt[path], 1u);
+            atomicMax(&cnt[3], n);
+            if (path == 0) cmib::lane_sort(checksum + b0, pos + b0, n);
+            else if (path == 1) med_list[atomicAdd(&st[IB_ST_NMED], 1ull)] = (uint32_t)hv;
+            else over_list[atomicAdd(&st[IB_ST_NOVER], 1ull)] = (uint32_t)hv;
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < 3 && cnt[threadIdx.x]) atomicAdd(&st[IB_ST_PATH + threadIdx.x], (unsigned long long)cnt[threadIdx.x]);
+    if (threadIdx.x == 3 && cnt[3]) atomicMax(&st[IB_ST_MAX], (unsigned long long)cnt[3]);
+}
+// one workgroup per listed bucket (n <= IB_WG_CAP): the packed keys sorted in LDS
+constexpr uint32_t IB_WG_CAP = cmib::WG_MAX;
+__global__ void __launch_bounds__(BLK) k_ib_order_wg(const uint32_t *bucket_off, const uint32_t *list, uint32_t n_list, uint16_t *checksum, uint32_t *pos) {
+    __shared__ uint64_t keys[IB_WG_CAP];
+    for (uint32_t b = blockIdx.x; b < n_list; b += gridDim.x) {
+        const uint32_t hv = list[b], b0 = bucket_off[hv], n = bucket_off[hv + 1] - b0;
+        if (n > IB_WG_CAP) continue;                                   // (never listed: k_ib_order_lane classifies with wg_max <= IB_WG_CAP)
+        const uint32_t np2 = cmib::pow2_at_least(n);
+        for (uint32_t i = threadIdx.x; i < np2; i += BLK) keys[i] = i < n ? cmib::pack_key(checksum[b0 + i], pos[b0 + i]) : ~0ull;
+        __syncthreads();
+        for (uint32_t size = 2; size <= np2; size <<= 1)
+            for (uint32_t stride = size >> 1; stride > 0; stride >>= 1) {
+                for (uint32_t i = threadIdx.x; i < np2; i += BLK) cmib::bitonic_step(keys, i, size, stride);
+                __syncthreads();
+            }
+        for (uint32_t i = threadIdx.x; i < n; i += BLK) {
+            checksum[b0 + i] = cmib::key_checksum(keys[i]);
+            pos[b0 + i] = cmib::key_pos(keys[i]);
+        }
+        __syncthreads();
+    }
+}
+// oversize list: sizes of the listed buckets (scanned into `start`), their entries packed under the bucket's rank in the chunk,
+// and the sorted keys put back.  Sorted by (rank, checksum, position) a bucket's keys lie where its unsorted ones lay.
+__global__ void __launch_bounds__(BLK) k_ib_over_sizes(const uint32_t *bucket_off, const uint32_t *list, uint32_t n_list, uint32_t *sizes) {
+    const uint32_t i = blockIdx.x * BLK + threadIdx.x;
+    if (i < n_list) sizes[i] = bucket_off[list[i] + 1] - bucket_off[list[i]];
+}
+__global__ void __launch_bounds__(BLK) k_ib_over_pack(const uint32_t *bucket_off, const uint32_t *list, const uint32_t *start, uint32_t r0, uint32_t r1,
+                                                      const uint16_t *checksum, const uint32_t *pos, uint64_t *keys) {
+    const uint32_t base = start[r0];
+    for (uint32_t r = r0 + blockIdx.x; r < r1; r += gridDim.x) {
+        const uint32_t b0 = bucket_off[list[r]], n = start[r + 1] - start[r], at = start[r] - base;
+        for (uint32_t i = threadIdx.x; i < n; i += BLK) keys[at + i] = cmib::over_key(r - r0, checksum[b0 + i], pos[b0 + i]);
+    }
+}
+__global__ void __launch_bounds__(BLK) k_ib_over_unpack(const uint32_t *bucket_off, const uint32_t *list, const uint32_t *start, uint32_t r0, uint32_t r1,
+                                                        const uint64_t *keys, uint16_t *checksum, uint32_t *pos) {
+    const uint32_t base = start[r0];
+    for (uint32_t r = r0 + blockIdx.x; r < r1; r += gridDim.x) {
+        const uint32_t b0 = bucket_off[list[r]], n = start[r + 1] - start[r], at = start[r] - base;
+        for (uint32_t i = threadIdx.x; i < n; i += BLK) {
+            const uint64_t x = keys[at + i];
+            checksum[b0 + i] = cmib::key_checksum(x);
+            pos[b0 + i] = cmib::key_pos(x);
+        }
+    }
+}
+
 __global__ void k_init_state(KCore kc, cm_mapped_read *state, uint8_t *active, int32_t *cat, uint64_t n) {
     const uint64_t i = (uint64_t)blockIdx.x * BLK + threadIdx.x;
     if (i >= n) return;
@@ -2494,6 +2607,202 @@ int cm_load_contig_raw(cm_ctx *ctx, int slot, const cm_index_raw *raw) {
     s.X.pos = d_ps;
     s.X.n_entries = total;
     return finish_contig(ctx, s);       // (synchronises the stream: the temporaries may go)
+}
+
+// The ordering passes of cm_build_contig on ctx->stream; st_host receives the IB_ST_* words.  Temporaries go on `tmp`.
+static int ib_order(cm_ctx *ctx, const uint32_t *d_off, uint16_t *d_cs, uint32_t *d_ps, uint64_t total, uint32_t *d_bs, std::vector<void *> &tmp,
+                    unsigned long long st_host[IB_ST_WORDS], size_t *tmp_bytes) {
+    const uint64_t n_all = (uint64_t)1 << (2 * CM_WINDOW_SIZE);
+    // test / diagnostic knobs: smaller thresholds send small inputs down the workgroup and oversize paths
+    static const uint32_t wg_lim = std::max<uint32_t>(1u, std::min<uint32_t>(getenv("CM_IB_WG_MAX") ? (uint32_t)atoi(getenv("CM_IB_WG_MAX")) : cmib::WG_MAX, IB_WG_CAP));
+    static const uint32_t lane_max = std::max<uint32_t>(1u, std::min<uint32_t>(getenv("CM_IB_LANE_MAX") ? (uint32_t)atoi(getenv("CM_IB_LANE_MAX")) : cmib::LANE_MAX, wg_lim));
+    unsigned long long *d_st = nullptr;
+    uint32_t *d_med = nullptr, *d_over = nullptr;
+    const size_t med_cap = (size_t)(total / ((uint64_t)lane_max + 1)) + 1, over_cap = (size_t)(total / ((uint64_t)wg_lim + 1)) + 1;
+    HIPCHK(ctx, hipMalloc((void **)&d_st, IB_ST_WORDS * sizeof(unsigned long long)));
+    tmp.push_back(d_st);
+    HIPCHK(ctx, hipMalloc((void **)&d_med, med_cap * sizeof(uint32_t)));
+    tmp.push_back(d_med);
+    HIPCHK(ctx, hipMalloc((void **)&d_over, over_cap * sizeof(uint32_t)));
+    tmp.push_back(d_over);
+    *tmp_bytes += (med_cap + over_cap) * sizeof(uint32_t);
+    HIPCHK(ctx, hipMemsetAsync(d_st, 0, IB_ST_WORDS * sizeof(unsigned long long), ctx->stream));
+    hipLaunchKernelGGL(k_ib_order_lane, dim3((unsigned)(n_all / BLK)), dim3(BLK), 0, ctx->stream, d_off, n_all, d_cs, d_ps, lane_max, wg_lim, d_med, d_over, d_st);
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipMemcpyAsync(st_host, d_st, IB_ST_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    const uint32_t n_med = (uint32_t)st_host[IB_ST_NMED], n_over = (uint32_t)st_host[IB_ST_NOVER];
+    if (n_med) {
+        hipLaunchKernelGGL(k_ib_order_wg, dim3(std::min<uint32_t>(n_med, 1u << 16)), dim3(BLK), 0, ctx->stream, d_off, (const uint32_t *)d_med, n_med, d_cs, d_ps);
+        HIPCHK(ctx, hipGetLastError());
+    }
+    if (!n_over) return CM_OK;
+    // oversize buckets: all entries of a chunk of the list (up to 2^16 buckets) in one radix sort of 64-bit keys
+    uint32_t *d_start = nullptr;
+    HIPCHK(ctx, hipMalloc((void **)&d_start, ((size_t)n_over + 1) * sizeof(uint32_t)));
+    tmp.push_back(d_start);
+    HIPCHK(ctx, hipMemsetAsync(d_start + n_over, 0, sizeof(uint32_t), ctx->stream));
+    hipLaunchKernelGGL(k_ib_over_sizes, dim3((n_over + BLK - 1) / BLK), dim3(BLK), 0, ctx->stream, d_off, (const uint32_t *)d_over, n_over, d_start);
+    int rc;
+    if ((rc = scan32(ctx, d_start, (uint64_t)n_over + 1, d_start, d_bs, 0u, 0))) return rc;          // exclusive, in place: start[n_over] = all oversize entries
+    std::vector<uint32_t> start((size_t)n_over + 1);
+    HIPCHK(ctx, hipMemcpyAsync(start.data(), d_start, start.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    auto rank_bits_of = [](uint32_t n_ranks) {
+        unsigned b = 1;
+        while ((1u << b) < n_ranks) ++b;
+        return b;
+    };
+    uint64_t *d_k0 = nullptr, *d_k1 = nullptr;
+    void *d_sort = nullptr;
+    uint32_t largest = 0;
+    size_t sort_bytes = 0;
+    for (uint32_t r0 = 0; r0 < n_over; r0 += cmib::OVER_CHUNK) {           // the largest chunk and the most sort workspace any chunk asks for
+        const uint32_t r1 = std::min(n_over, r0 + cmib::OVER_CHUNK), m = start[r1] - start[r0];
+        size_t need = 0;
+        HIPCHK(ctx, rocprim::radix_sort_keys(nullptr, need, d_k0, d_k1, (size_t)m, 0u, 48u + rank_bits_of(r1 - r0), ctx->stream));
+        largest = std::max(largest, m);
+        sort_bytes = std::max(sort_bytes, need);
+    }
+    HIPCHK(ctx, hipMalloc((void **)&d_k0, (size_t)largest * sizeof(uint64_t)));
+    tmp.push_back(d_k0);
+    HIPCHK(ctx, hipMalloc((void **)&d_k1, (size_t)largest * sizeof(uint64_t)));
+    tmp.push_back(d_k1);
+    HIPCHK(ctx, hipMalloc(&d_sort, sort_bytes ? sort_bytes : 1));
+    tmp.push_back(d_sort);
+    *tmp_bytes += 2 * (size_t)largest * sizeof(uint64_t) + sort_bytes + ((size_t)n_over + 1) * sizeof(uint32_t);
+    for (uint32_t r0 = 0; r0 < n_over; r0 += cmib::OVER_CHUNK) {
+        const uint32_t r1 = std::min(n_over, r0 + cmib::OVER_CHUNK), m = start[r1] - start[r0];
+        const unsigned rank_bits = rank_bits_of(r1 - r0);
+        size_t have = sort_bytes;
+        const dim3 grid(std::min<uint32_t>(r1 - r0, 1u << 16));
+        hipLaunchKernelGGL(k_ib_over_pack, grid, dim3(BLK), 0, ctx->stream, d_off, (const uint32_t *)d_over, (const uint32_t *)d_start, r0, r1, (const uint16_t *)d_cs,
+                           (const uint32_t *)d_ps, d_k0);
+        HIPCHK(ctx, hipGetLastError());
+        HIPCHK(ctx, rocprim::radix_sort_keys(d_sort, have, d_k0, d_k1, (size_t)m, 0u, 48u + rank_bits, ctx->stream));
+        hipLaunchKernelGGL(k_ib_over_unpack, grid, dim3(BLK), 0, ctx->stream, d_off, (const uint32_t *)d_over, (const uint32_t *)d_start, r0, r1, (const uint64_t *)d_k1,
+                           d_cs, d_ps);
+        HIPCHK(ctx, hipGetLastError());
+    }
+    return CM_OK;
+}
+
+static int build_contig_arrays(cm_ctx *ctx, Slot &s, const uint8_t *genome, uint32_t ref_len, cm_build_stats *stats, hipEvent_t ev_a, hipEvent_t ev_b) {
+    const uint64_t n_all = (uint64_t)1 << (2 * CM_WINDOW_SIZE);
+    const int k = ctx->P.kmer, c = k - CM_WINDOW_SIZE;
+    {
+        uint8_t *g = nullptr;
+        const size_t pad = cmc::CM_STAGE_PAD;
+        HIPCHK(ctx, hipMalloc((void **)&g, (size_t)ref_len + 2 * pad));
+        s.idx_allocs.push_back(g);
+        HIPCHK(ctx, hipMemsetAsync(g, 0, (size_t)ref_len + 2 * pad, ctx->stream));
+        if (ref_len) HIPCHK(ctx, hipMemcpyAsync(g + pad, genome, (size_t)ref_len, hipMemcpyHostToDevice, ctx->stream));
+        s.X.genome = g + pad;
+    }
+    std::vector<void *> tmp;
+    struct FreeTmp {
+        cm_ctx *c;
+        std::vector<void *> &v;
+        ~FreeTmp() { free_all(c, v); }
+    } free_tmp{ctx, tmp};
+    size_t tmp_bytes = ((size_t)(n_all / S32_B) + 4) * sizeof(uint32_t);
+    uint32_t *d_bs = nullptr, *d_off = nullptr;
+    HIPCHK(ctx, hipMalloc((void **)&d_bs, tmp_bytes));
+    tmp.push_back(d_bs);
+    HIPCHK(ctx, hipMalloc((void **)&d_off, (n_all + 1) * sizeof(uint32_t)));
+    s.idx_allocs.push_back(d_off);
+    HIPCHK(ctx, hipEventRecord(ev_a, ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(d_off, 0, (n_all + 1) * sizeof(uint32_t), ctx->stream));
+    // the number of entries is at most ref_len - k + 1 < 2^32: the 32-bit counters and scans cannot overflow
+    const uint32_t n_pos = ref_len >= (uint32_t)k ? ref_len - (uint32_t)k + 1u : 0u;
+    const dim3 pgrid((unsigned)(((uint64_t)n_pos + IB_TILE - 1) / IB_TILE));
+    if (n_pos) {
+        hipLaunchKernelGGL(k_ib_positions<false>, pgrid, dim3(BLK), 0, ctx->stream, s.X.genome, ref_len, n_pos, k, c, d_off, (uint16_t *)nullptr, (uint32_t *)nullptr);
+        HIPCHK(ctx, hipGetLastError());
+    }
+    int rc;
+    if ((rc = scan32(ctx, d_off, n_all + 1, d_off, d_bs, 0u, 1))) return rc;             // counts -> bucket ends, in place
+    uint32_t total32 = 0;
+    HIPCHK(ctx, hipMemcpyAsync(&total32, d_off + n_all, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    const uint64_t total = total32;
+    if (total > (uint64_t)n_pos) return fail(ctx, CM_ELIMIT, "%llu entries from %u k-mer starts", (unsigned long long)total, n_pos);
+    uint16_t *d_cs = nullptr;
+    uint32_t *d_ps = nullptr;
+    HIPCHK(ctx, hipMalloc((void **)&d_cs, (total ? total : 1) * sizeof(uint16_t)));
+    s.idx_allocs.push_back(d_cs);
+    HIPCHK(ctx, hipMalloc((void **)&d_ps, (total ? total : 1) * sizeof(uint32_t)));
+    s.idx_allocs.push_back(d_ps);
+    unsigned long long st[IB_ST_WORDS] = {0, 0, 0, 0, 0, 0};
+    if (total) {
+        hipLaunchKernelGGL(k_ib_positions<true>, pgrid, dim3(BLK), 0, ctx->stream, s.X.genome, ref_len, n_pos, k, c, d_off, d_cs, d_ps);   // ends -> starts
+        HIPCHK(ctx, hipGetLastError());
+        if ((rc = ib_order(ctx, d_off, d_cs, d_ps, total, d_bs, tmp, st, &tmp_bytes))) return rc;
+    }
+    HIPCHK(ctx, hipEventRecord(ev_b, ctx->stream));
+    s.X.bucket_off = d_off;
+    s.X.checksum = d_cs;
+    s.X.pos = d_ps;
+    s.X.n_entries = total;
+    if ((rc = finish_contig(ctx, s))) return rc;       // (synchronises the stream: the temporaries may go)
+    if (stats) {
+        float ms = 0.f;
+        HIPCHK(ctx, hipEventElapsedTime(&ms, ev_a, ev_b));
+        memset(stats, 0, sizeof *stats);
+        stats->n_entries = total;
+        stats->max_bucket = (uint32_t)st[IB_ST_MAX];
+        stats->reserved = (uint32_t)std::min<size_t>(tmp_bytes >> 20, 0xffffffffu);      // peak temporary HBM of the build, MiB
+        for (int i = 0; i < 3; ++i) stats->buckets_by_path[i] = st[IB_ST_PATH + i];
+        stats->ms_device = ms;
+    }
+    return CM_OK;
+}
+
+int cm_build_contig(cm_ctx *ctx, int slot, int32_t contig_num, const uint8_t *genome, uint32_t ref_len, cm_build_stats *stats) {
+    if (!ctx) return CM_EINVAL;
+    if (slot < 0 || slot >= MAX_SLOTS) return fail(ctx, CM_EINVAL, "slot %d out of range", slot);
+    if (!genome && ref_len) return fail(ctx, CM_EINVAL, "null genome");
+    HIPCHK(ctx, hipSetDevice(ctx->P.device));
+    Slot &s = ctx->slots[slot];
+    free_all(ctx, s.idx_allocs);
+    s.d_desc = nullptr;
+    s.loaded = false;
+    ++s.gen;
+    s.X = cm_index_view{};
+    s.X.contig_num = contig_num;
+    s.X.ref_len = ref_len;
+    hipEvent_t ev_a = take_event(ctx), ev_b = take_event(ctx);
+    if (!ev_a || !ev_b) return fail(ctx, CM_EHIP, "hipEventCreate failed");
+    const int rc = build_contig_arrays(ctx, s, genome, ref_len, stats, ev_a, ev_b);
+    if (rc != CM_OK) {                                   // the slot stays unloaded and owns nothing
+        (void)hipStreamSynchronize(ctx->stream);
+        (void)hipGetLastError();
+        free_all(ctx, s.idx_allocs);
+        s.d_desc = nullptr;
+        s.loaded = false;
+        s.X = cm_index_view{};
+    }
+    ctx->ev_free.push_back(ev_a);
+    ctx->ev_free.push_back(ev_b);
+    return rc;
+}
+
+int cm_index_download(cm_ctx *ctx, int slot, uint32_t *bucket_off, uint16_t *checksum, uint32_t *pos, uint64_t cap_entries, uint64_t *n_entries) {
+    if (!ctx) return CM_EINVAL;
+    int rc;
+    if ((rc = check_slot(ctx, slot, false))) return rc;
+    const Slot &s = ctx->slots[slot];
+    const uint64_t n = s.X.n_entries;
+    if (n_entries) *n_entries = n;
+    if (!bucket_off && !checksum && !pos) return CM_OK;
+    if ((checksum || pos) && cap_entries < n) return fail(ctx, CM_ELIMIT, "slot %d holds %llu entries, the buffers %llu", slot, (unsigned long long)n, (unsigned long long)cap_entries);
+    HIPCHK(ctx, hipSetDevice(ctx->P.device));
+    const size_t nb = ((size_t)1 << (2 * CM_WINDOW_SIZE)) + 1;
+    if (bucket_off) HIPCHK(ctx, hipMemcpyAsync(bucket_off, s.X.bucket_off, nb * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (checksum && n) HIPCHK(ctx, hipMemcpyAsync(checksum, s.X.checksum, (size_t)n * sizeof(uint16_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (pos && n) HIPCHK(ctx, hipMemcpyAsync(pos, s.X.pos, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return CM_OK;
 }
 
 int cm_load_annotation(cm_ctx *ctx, int slot, const cm_annot_view *av) {

@@ -182,7 +182,13 @@ struct cm_index_file {
         size_t genome_cap = 0, hdr_cap = 0, tab_cap = 0;
     } raw[2];
     int raw_turn = 0;
+    // a packed FASTA opened as a table-less source (cm_host_next_contig_genome only): records are read one at a time
+    bool fasta = false;
+    char *line = nullptr;                // getline buffer; holds the header line of the next record between calls
+    size_t line_cap = 0;
+    ssize_t line_len = -1;               // -1: no header line pending (end of file)
     ~cm_index_file() {
+        free(line);
         free(tab);
         for (auto &r : raw) {
             free(r.genome);
@@ -440,6 +446,34 @@ int cm_host_open_index(const char *index_path, cm_index_file **out, int32_t *kme
     if (!f) return CM_EINVAL;
     cm_index_file *x = new cm_index_file();
     x->f = f;
+    {
+        const int first = fgetc(f);
+        if (first == '>') {              // a packed FASTA: no table, no k.  Its records are counted in one pass ('>' at a line start)
+            uint32_t nrec = 0;
+            std::vector<char> buf(4u << 20);
+            bool at_start = false;       // (the first byte is consumed already)
+            nrec = 1;
+            size_t got;
+            while ((got = fread(buf.data(), 1, buf.size(), f)) > 0)
+                for (size_t i = 0; i < got; ++i) {
+                    if (at_start && buf[i] == '>') ++nrec;
+                    at_start = buf[i] == '\n';
+                }
+            if (ferror(f) || fseek(f, 0, SEEK_SET) != 0) {
+                fclose(f);
+                delete x;
+                return CM_EINVAL;
+            }
+            x->fasta = true;
+            x->line_len = getline(&x->line, &x->line_cap, f);
+            if (kmer) *kmer = 0;
+            if (is_full) *is_full = -1;
+            if (n_records) *n_records = nrec;
+            *out = x;
+            return CM_OK;
+        }
+        if (first != EOF) ungetc(first, f);
+    }
     uint8_t magic = 0, W = 0;
     int8_t c = 0;
     int32_t nrec = 0;
@@ -472,12 +506,63 @@ int cm_host_open_index(const char *index_path, cm_index_file **out, int32_t *kme
     return CM_OK;
 }
 
+// The next record of a packed FASTA: id = first token after '>', the sequence = the first whitespace-delimited token of every
+// following line (read_fasta's rules), upper-cased, anything but A/C/G/T -> N (what cm_host_write_index stores).
+static int next_fasta_record(cm_index_file *x, cm_index_view *out, int *loaded) {
+    *loaded = 0;
+    while (x->line_len >= 0 && x->line[0] != '>') x->line_len = getline(&x->line, &x->line_cap, x->f);     // (nothing in front of the first header counts)
+    if (x->line_len < 0) {
+        x->done = true;
+        return ferror(x->f) ? CM_EIO : CM_OK;
+    }
+    size_t b = 1;
+    while (b < (size_t)x->line_len && !isspace((unsigned char)x->line[b])) ++b;
+    const std::string name(x->line + 1, b - 1);
+    size_t cap = 1u << 20, n = 0;
+    uint8_t *g = (uint8_t *)malloc(cap);
+    if (!g) return CM_ENOMEM;
+    uint8_t lut[256];
+    for (int i = 0; i < 256; ++i) {
+        const int u = toupper(i);
+        lut[i] = (u == 'A' || u == 'C' || u == 'G' || u == 'T') ? (uint8_t)u : (uint8_t)'N';
+    }
+    while ((x->line_len = getline(&x->line, &x->line_cap, x->f)) >= 0 && x->line[0] != '>') {
+        const char *p = x->line;
+        size_t a = 0, len = (size_t)x->line_len;
+        while (a < len && isspace((unsigned char)p[a])) ++a;
+        size_t e = a;
+        while (e < len && !isspace((unsigned char)p[e])) ++e;
+        if (n + (e - a) + 1 > cap) {
+            while (n + (e - a) + 1 > cap) cap *= 2;
+            uint8_t *g2 = (uint8_t *)realloc(g, cap);
+            if (!g2) {
+                free(g);
+                return CM_ENOMEM;
+            }
+            g = g2;
+        }
+        for (size_t i = a; i < e; ++i) g[n++] = lut[(uint8_t)p[i]];
+    }
+    if (ferror(x->f) || n > 0xffffffffull) {
+        free(g);
+        return ferror(x->f) ? CM_EIO : CM_ELIMIT;
+    }
+    g[n] = 0;
+    memset(out, 0, sizeof *out);
+    out->contig_num = atoi(name.c_str()) - 1;
+    out->ref_len = (uint32_t)n;
+    out->genome = g;
+    *loaded = 1;
+    return CM_OK;
+}
+
 // Loads the next packed contig (loadHashTable, HashTable.c:971-1098): genome decoded to ASCII
 // (pac2char_whole_contig, src/match_read.cpp:301-332) and the table in the flattened layout of
 // cm_index_view.  Returns CM_OK and *loaded = 1, or *loaded = 0 after the last contig.
 // The view (including its genome) is released with cm_host_free_loaded_contig.
 static int next_contig(cm_index_file *x, int n_threads, cm_index_view *out, int *loaded, bool genome_only, cm_index_raw *raw_out = nullptr) {
     if (!x || (!out && !raw_out) || !loaded) return CM_EINVAL;
+    if (x->fasta) return (genome_only && out && !raw_out) ? next_fasta_record(x, out, loaded) : CM_EINVAL;      // no table to serve
     if (raw_out && !x->full) return CM_EINVAL;
     cm_index_file::RawSet *RS = raw_out ? &x->raw[x->raw_turn] : nullptr;
     if (raw_out) x->raw_turn ^= 1;

@@ -133,8 +133,14 @@ extern "C" int cm_mapping_run(const cm_mapping_args *a, cm_mapping_stats *stats,
     uint32_t n_rec = 0;
     MAP_TRY(cm_host_open_index(a->index_path, &idx, &kmer, &full, &n_rec), "cm_host_open_index");
     cm_params P = a->params;
+    const bool from_sequence = full < 0;          // index_path is the packed FASTA itself: the tables are built on the device
+    if (from_sequence && P.kmer == 0) {
+        rc = fail(CM_EINVAL, "%s is a packed FASTA, not an index file: there is no k to read, params.kmer must be given", a->index_path);
+        cleanup();
+        return rc;
+    }
     if (P.kmer == 0) P.kmer = kmer;
-    if (P.kmer != kmer) {
+    if (!from_sequence && P.kmer != kmer) {
         rc = fail(CM_EINVAL, "index was built for k = %d, params ask for k = %d", kmer, P.kmer);
         cleanup();
         return rc;
@@ -167,7 +173,38 @@ extern "C" int cm_mapping_run(const cm_mapping_args *a, cm_mapping_stats *stats,
             early_rc = cm_host_build_annotation(a->gtf_path, chrs, n_chr, clen_guess.data(), (uint32_t)clen_guess.size(), P.max_read_len, annots_early.data());
             lap("GTF -> annotation tables (under the contig loads)", tg);
         });
-    if (full) {
+    if (from_sequence) {
+        // no index file: contig c + 1 is read from the packed FASTA (one host thread) while the device builds the table of
+        // contig c from its sequence (cm_build_contig)
+        cm_index_view nxt_iv;
+        int nxt_loaded = 0, nxt_rc = CM_OK;
+        double tl = now();
+        nxt_rc = cm_host_next_contig_genome(idx, &nxt_iv, &nxt_loaded);
+        lap("contig sequence read", tl);
+        for (;;) {
+            MAP_TRY(nxt_rc, "cm_host_next_contig_genome");
+            if (!nxt_loaded) break;
+            cm_index_view iv = nxt_iv;
+            views.push_back(iv);
+            if (iv.contig_num != (int32_t)views.size() - 1) {
+                rc = fail(CM_EINVAL, "packed contigs out of order: record %zu is contig %d", views.size(), iv.contig_num + 1);
+                cleanup();
+                return rc;
+            }
+            std::thread ahead([&]() {
+                const double ta = now();
+                nxt_rc = cm_host_next_contig_genome(idx, &nxt_iv, &nxt_loaded);
+                lap("next contig sequence read (under the build)", ta);
+            });
+            tl = now();
+            const int lrc = cm_build_contig(cm, (int)views.size() - 1, iv.contig_num, iv.genome, iv.ref_len, nullptr);
+            lap("contig uploaded, table built on the device + descriptors", tl);
+            cm_host_free_loaded_contig(&views.back());
+            ahead.join();
+            if (nxt_rc == CM_OK && nxt_loaded && lrc != CM_OK) cm_host_free_loaded_contig(&nxt_iv);
+            MAP_TRY(lrc, "cm_build_contig");
+        }
+    } else if (full) {
         // full-format index: the table crosses PCIe as it is in the file and the device flattens it (cm_load_contig_raw); the
         // host only reads and decodes the bucket headers -- of contig c + 1 while contig c uploads
         cm_index_raw nxt_raw;
@@ -467,7 +504,7 @@ extern "C" int cm_abi_sizes(uint32_t *out, uint32_t cap) {
     const uint32_t v[] = {(uint32_t)sizeof(cm_params),       (uint32_t)sizeof(cm_index_view),  (uint32_t)sizeof(cm_annot_view), (uint32_t)sizeof(cm_mapped_read),
                           (uint32_t)sizeof(cm_reads),        (uint32_t)sizeof(cm_record),      (uint32_t)sizeof(cm_chr_info),   (uint32_t)sizeof(cm_fastq_batch),
                           (uint32_t)sizeof(cm_mapping_args), (uint32_t)sizeof(cm_mapping_stats), (uint32_t)sizeof(cm_circ_res), (uint32_t)sizeof(cm_circ_args),
-                          (uint32_t)sizeof(cm_circ_stats), (uint32_t)sizeof(cm_index_raw)};
+                          (uint32_t)sizeof(cm_circ_stats), (uint32_t)sizeof(cm_index_raw), (uint32_t)sizeof(cm_build_stats)};
     const uint32_t n = (uint32_t)(sizeof v / sizeof v[0]);
     if (!out || cap < n) return CM_EINVAL;
     for (uint32_t i = 0; i < n; ++i) out[i] = v[i];

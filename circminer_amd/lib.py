@@ -74,6 +74,11 @@ class IndexRaw(C.Structure):
                 ("count14", u32p), ("table", C.c_void_p), ("table_slots", C.c_uint64)]
 
 
+class BuildStats(C.Structure):
+    _fields_ = [("n_entries", C.c_uint64), ("max_bucket", C.c_uint32), ("reserved", C.c_uint32), ("buckets_by_path", C.c_uint64 * 3),
+                ("ms_device", C.c_double)]
+
+
 class AnnotView(C.Structure):
     _fields_ = [("n_iv", C.c_uint32), ("iv_spos", u32p), ("iv_epos", u32p), ("iv_max_end", u32p), ("iv_min_end", u32p),
                 ("iv_max_next_exon", u32p), ("iv_seg_off", u32p), ("iv_seg", u32p),
@@ -180,6 +185,8 @@ def load(path: str = LIB_PATH) -> C.CDLL:
         "cm_load_annotation": (C.c_int, [vp, C.c_int, pp(AnnotView)]),
         "cm_load_contig_raw": (C.c_int, [vp, C.c_int, pp(IndexRaw)]),
         "cm_host_next_contig_raw": (C.c_int, [vp, C.c_int, pp(IndexRaw), pp(C.c_int)]),
+        "cm_build_contig": (C.c_int, [vp, C.c_int, C.c_int32, u8p, C.c_uint32, pp(BuildStats)]),
+        "cm_index_download": (C.c_int, [vp, C.c_int, vp, vp, vp, C.c_uint64, pp(C.c_uint64)]),
         "cm_unload_contig": (C.c_int, [vp, C.c_int]),
         "cm_reads_upload": (C.c_int, [vp, pp(Reads), vp]),
         "cm_reads_stage": (C.c_int, [vp, pp(Reads), vp]),
@@ -253,7 +260,7 @@ def load(path: str = LIB_PATH) -> C.CDLL:
     got = (C.c_uint32 * 16)()
     n = L.cm_abi_sizes(got, 16)
     mine = [C.sizeof(t) for t in (Params, IndexView, AnnotView, MappedRead, Reads, C.c_uint8 * RECORD_DTYPE.itemsize, ChrInfo, FastqBatch, MappingArgs,
-                                  MappingStats, CircRes, CircArgs, CircStats, IndexRaw)]
+                                  MappingStats, CircRes, CircArgs, CircStats, IndexRaw, BuildStats)]
     if n != len(mine) or list(got[:n]) != mine:
         raise RuntimeError(f"circminer_amd.lib: struct sizes differ from {path}: library {list(got[:max(n, 0)])}, ctypes {mine}")
     _lib = L
@@ -267,7 +274,8 @@ EXPORTED_SYMBOLS = ["cm_create", "cm_destroy", "cm_last_error", "cm_load_contig"
                     "cm_host_free_annotation", "cm_host_pack_genome", "cm_host_read_index_info", "cm_host_free_index_info",
                     "cm_host_write_index", "cm_host_open_index", "cm_host_next_contig", "cm_host_next_contig_genome", "cm_host_free_loaded_contig",
                     "cm_host_close_index", "cm_fastq_open", "cm_fastq_open_shard", "cm_merge_parts", "cm_fastq_next", "cm_fastq_set_release_hook", "cm_fastq_close", "cm_writer_open", "cm_write_remain",
-                    "cm_write_pam", "cm_write_sam_header", "cm_write_sam", "cm_writer_flush", "cm_writer_close", "cm_mapping_run", "cm_sort_remain", "cm_circ_report", "cm_circ_call", "cm_circ_run", "cm_host_gene_overlap", "cm_regional_table_build", "cm_regional_table_free"]
+                    "cm_write_pam", "cm_write_sam_header", "cm_write_sam", "cm_writer_flush", "cm_writer_close", "cm_mapping_run", "cm_sort_remain", "cm_circ_report", "cm_circ_call", "cm_circ_run", "cm_host_gene_overlap", "cm_regional_table_build", "cm_regional_table_free",
+                    "cm_build_contig", "cm_index_download"]
 
 
 class HostIndex:
@@ -378,8 +386,12 @@ class IndexFile:
         rc = self.L.cm_host_open_index(path.encode(), C.byref(self.h), C.byref(kmer), C.byref(full), C.byref(nrec))
         if rc != 0:
             raise RuntimeError(f"cm_host_open_index failed ({rc}): {path}")
-        self.kmer, self.full, self.n_records, self.n_threads = kmer.value, bool(full.value), nrec.value, n_threads
+        self.kmer, self.full, self.n_records, self.n_threads = kmer.value, full.value > 0, nrec.value, n_threads
+        self.table_less = full.value < 0           # a packed FASTA: sequences only (genome_only=True), for HotPath.build_contig
         self._cur = None
+        if self.table_less and not genome_only:
+            self.close()
+            raise RuntimeError(f"{path} is a packed FASTA: it has no k-mer table, open it with genome_only=True")
 
     def __iter__(self):
         return self
@@ -625,6 +637,26 @@ class HotPath:
         self._chk(self.L.cm_load_contig_raw(self.h, slot, C.byref(raw)), "cm_load_contig_raw")
         if av is not None:
             self._chk(self.L.cm_load_annotation(self.h, slot, C.byref(av)), "cm_load_annotation")
+
+    def build_contig(self, slot, contig_num, genome: np.ndarray, av: AnnotView = None) -> BuildStats:
+        """the contig made resident from its sequence alone: the k-mer table is built on the device (cm_build_contig)"""
+        g = np.ascontiguousarray(genome, dtype=np.uint8)
+        st = BuildStats()
+        self._chk(self.L.cm_build_contig(self.h, slot, contig_num, ptr(g, u8p) if g.size else None, g.size, C.byref(st)), "cm_build_contig")
+        if av is not None:
+            self._chk(self.L.cm_load_annotation(self.h, slot, C.byref(av)), "cm_load_annotation")
+        return st
+
+    def index_arrays(self, slot):
+        """(bucket_off, checksum, pos) of a loaded slot as host arrays (cm_index_download)"""
+        n = C.c_uint64(0)
+        self._chk(self.L.cm_index_download(self.h, slot, None, None, None, 0, C.byref(n)), "cm_index_download")
+        off = np.empty((1 << 28) + 1, np.uint32)
+        cks = np.empty(n.value, np.uint16)
+        pos = np.empty(n.value, np.uint32)
+        self._chk(self.L.cm_index_download(self.h, slot, off.ctypes.data, cks.ctypes.data if n.value else None, pos.ctypes.data if n.value else None,
+                                           n.value, C.byref(n)), "cm_index_download")
+        return off, cks, pos
 
     def upload(self, batch: ReadBatch, prior: np.ndarray = None):
         self.n = batch.n

@@ -2,6 +2,8 @@
 // that stage 2 reads, then stage 2 (circ_detect) to <out>.candidates.pam and <out>.circ_report.  Build:  g++ -std=c++17 -I include examples/cm_map.cpp -L circminer_amd/csrc -lcmhot
 //                              -Wl,-rpath,$PWD/circminer_amd/csrc -o cm_map
 // Usage:  cm_map <ref>.packed.fa.index <annotation.gtf> <R1.fastq[.gz]> <R2.fastq[.gz]> <out_prefix> [pam|sam|none] [k]
+//         cm_map <ref>.packed.fa       ...                                                      [pam|sam|none]  k
+//         (no index file: the k-mer tables are built on the device from the packed FASTA; <ref>.packed.fa.index.info is read as before)
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -14,7 +16,9 @@ int main(int argc, char **argv) {
         fprintf(stderr, "usage: %s index gtf r1 r2 out_prefix [pam|sam|none] [k]\n", argv[0]);
         return 2;
     }
-    const std::string info = std::string(argv[1]) + ".info";
+    const std::string src = argv[1];
+    const bool is_index = src.size() >= 6 && src.compare(src.size() - 6, 6, ".index") == 0;
+    const std::string info = is_index ? src + ".info" : src + ".index.info";
     cm_mapping_args a;
     memset(&a, 0, sizeof a);
     a.index_path = argv[1];

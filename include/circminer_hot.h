@@ -185,6 +185,26 @@ struct cm_index_raw;
  * more entries than its bucket has slots) is CM_EINVAL. */
 int cm_load_contig_raw(cm_ctx *ctx, int slot, const struct cm_index_raw *raw);
 int cm_load_annotation(cm_ctx *ctx, int slot, const cm_annot_view *av);
+/* cm_load_contig with the k-mer table BUILT BY THE DEVICE from the sequence alone: no host builder, no index file.  `genome`
+ * is ref_len host bytes in the convention of cm_index_view.genome and is not normalised: a k-mer is indexed iff all k bases
+ * are upper-case A/C/G/T (k = the context's params.kmer).  A counting sort on the device -- count per 14-mer bucket, scan,
+ * scatter, then every bucket ordered by (checksum, position): few-entry buckets by one lane each, medium ones by a workgroup
+ * in LDS, anything larger (homopolymers, satellite families) through a listed radix-sort path, so no bucket size is a limit.
+ * The resident contig is the same as after cm_host_build_index + cm_load_contig.  CM_ENOMEM leaves the slot unloaded. */
+typedef struct cm_build_stats {
+    uint64_t n_entries;          /* indexed k-mer positions */
+    uint32_t max_bucket;         /* entries of the fullest 14-mer bucket */
+    uint32_t reserved;           /* (diagnostic: temporary device memory the build took besides the resident arrays, MiB) */
+    uint64_t buckets_by_path[3]; /* non-empty buckets ordered by: lane / workgroup (LDS) / oversize path */
+    double ms_device;            /* HIP-event time of the build, sequence upload and descriptors excluded */
+} cm_build_stats;
+int cm_build_contig(cm_ctx *ctx, int slot, int32_t contig_num, const uint8_t *genome, uint32_t ref_len,
+                    cm_build_stats *stats /* nullable */);
+/* The resident index arrays of a loaded slot (any of the three loaders) copied to the caller's buffers: bucket_off holds
+ * 4^14 + 1 words, checksum / pos cap_entries items.  A NULL pointer skips that array (all three NULL: only *n_entries);
+ * CM_ELIMIT when cap_entries is smaller than the slot's entry count. */
+int cm_index_download(cm_ctx *ctx, int slot, uint32_t *bucket_off, uint16_t *checksum, uint32_t *pos,
+                      uint64_t cap_entries, uint64_t *n_entries);
 int cm_unload_contig(cm_ctx *ctx, int slot);
 
 /* Upload a batch of read pairs once; they stay resident for all rounds.
@@ -301,7 +321,7 @@ int cm_prof_get(cm_ctx *ctx, double ms[8], uint64_t launches[8]);
  * the second orientation attempt; [7] reserved (0). */
 int cm_prof_counters(cm_ctx *ctx, uint64_t c[8]);
 
-/* ---------------- host-side builders (stay on host; north_star "index build ... on host") ---- */
+/* ---------------- host-side builders (the k-mer index has a device-side builder too: cm_build_contig) ---- */
 /* In-memory equivalent of generateHashTableOnDisk for one contig
  * (src/mrsfast/HashTable.c:257-380,769-839): caller frees with cm_host_free_index. */
 int cm_host_build_index(const uint8_t *genome, uint32_t ref_len, int32_t kmer, int32_t contig_num,
@@ -347,7 +367,11 @@ int cm_host_write_index(const char *packed_fa_path, const char *index_path, int3
 /* Reader (checkHashTable / initLoadingHashTable / loadHashTable, HashTable.c:485-509, 618-700, 971-1098):
  * open parses the header; every cm_host_next_contig call loads the next packed contig -- genome decoded to
  * ASCII and the table flattened into a cm_index_view ready for cm_load_contig -- and sets *loaded = 0
- * after the last one.  Views are released with cm_host_free_loaded_contig. */
+ * after the last one.  Views are released with cm_host_free_loaded_contig.
+ * A packed FASTA (<ref>.packed.fa, first byte '>') is accepted as a table-less source: *is_full = -1, *kmer = 0, and only
+ * cm_host_next_contig_genome serves its records (one FASTA record = one contig, contig_num = name - 1, bases upper-cased,
+ * anything but A/C/G/T -> N: the bytes the index file written from it holds); cm_host_next_contig and
+ * cm_host_next_contig_raw return CM_EINVAL.  Such contigs are made resident with cm_build_contig. */
 typedef struct cm_index_file cm_index_file;
 int cm_host_open_index(const char *index_path, cm_index_file **out, int32_t *kmer, int32_t *is_full,
                        uint32_t *n_records);
@@ -439,7 +463,9 @@ void cm_writer_close(cm_writer *w);
  *   <out>.mapping.pam (report 1) or <out>.mapping.sam (report 2): the rows map_reads prints (skip || last round);
  *   <out>_<R>_remain_R1.fastq / _R2.fastq, R = number of packed contigs: the CHIBSJ / CHI2BSJ pairs (:395-397).
  * The per-round remain files of the reference (its way of carrying pairs from one contig to the next) are not
- * written: the carried state stays in HBM.  params.kmer == 0 takes the index file's k. */
+ * written: the carried state stays in HBM.  params.kmer == 0 takes the index file's k.
+ * index_path may name the packed FASTA itself (no index file on disk): every contig's table is built on the device
+ * (cm_build_contig) while the next contig's sequence is read; params.kmer must be given then (0 is CM_EINVAL). */
 typedef struct cm_mapping_args {
     const char *index_path;        /* <ref>.packed.fa.index        */
     const char *index_info_path;   /* <ref>.packed.fa.index.info   */
@@ -507,7 +533,7 @@ int cm_circ_call(const cm_params *p, int32_t window_size, uint32_t n_contigs, co
                  const char *report_path, cm_circ_stats *stats);
 /* circ_detect() of the reference (src/circminer.cpp:347-352) from files to files: sorts <out>_<last_round>_remain_R{1,2}.fastq
  * (-> .srt), loads the packed genome from the index file and the GTF, calls the junctions, writes <out>.candidates.pam and
- * <out>.circ_report.  params.kmer == 0 takes the index file's k. */
+ * <out>.circ_report.  params.kmer == 0 takes the index file's k.  index_path may be the packed FASTA (stage 2 needs the sequence only). */
 typedef struct cm_circ_args {
     const char *index_path, *index_info_path, *gtf_path, *out_prefix;
     cm_params params;
@@ -518,7 +544,7 @@ typedef struct cm_circ_args {
 int cm_circ_run(const cm_circ_args *args, cm_circ_stats *stats, char *err, uint64_t err_cap);
 
 /* sizeof of the structs above, in this order: cm_params, cm_index_view, cm_annot_view, cm_mapped_read, cm_reads, cm_record,
- * cm_chr_info, cm_fastq_batch, cm_mapping_args, cm_mapping_stats, cm_circ_res, cm_circ_args, cm_circ_stats, cm_index_raw -- for a binding to
+ * cm_chr_info, cm_fastq_batch, cm_mapping_args, cm_mapping_stats, cm_circ_res, cm_circ_args, cm_circ_stats, cm_index_raw, cm_build_stats -- for a binding to
  * check its mirrors of them against the library it loaded.  Returns the number of entries written (cap must hold them). */
 int cm_abi_sizes(uint32_t *out, uint32_t cap);
 
