@@ -19,7 +19,6 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
-#include <unordered_map>
 #include <functional>
 #include <thread>
 #include <vector>
@@ -1780,21 +1779,179 @@ struct Slot {
 
 struct ProfRec { hipEvent_t a, b; int cls; };
 
+// A device buffer that knows its size and who frees it.  Grow-only (ensure()); `Life` says when the memory goes: with the batch
+// (an empty cm_reads_upload, cm_destroy -- release(ctx, BATCH)) or with the context (cm_destroy only).  A buffer is declared once,
+// in cm_ctx (which is heap-allocated and never moves): the first time it allocates it enters the context's list of its lifetime
+// class, and releasing a class walks that list.
+enum Life { BATCH = 0, CONTEXT = 1 };
+struct DevMem {
+    void *p = nullptr;
+    size_t cap = 0;                            // bytes behind p
+    std::vector<DevMem *> *listed = nullptr;   // the lifetime list this buffer has entered
+    DevMem() = default;
+    DevMem(const DevMem &) = delete;
+    DevMem &operator=(const DevMem &) = delete;
+};
+// pointer and capacity change places, the buffers stay where they are declared: one that has never allocated joins the other's list
+inline void swap(DevMem &a, DevMem &b) {
+    std::swap(a.p, b.p);
+    std::swap(a.cap, b.cap);
+    if (!a.listed && b.listed) (a.listed = b.listed)->push_back(&a);
+    if (!b.listed && a.listed) (b.listed = a.listed)->push_back(&b);
+}
+template <class T, Life L>
+struct DevBuf : DevMem {
+    operator T *() const { return (T *)p; }
+};
+template <class T> using BatchBuf = DevBuf<T, BATCH>;
+template <class T> using CtxBuf = DevBuf<T, CONTEXT>;
+
+// The read buffers of one batch; a context has two (resident, staged) and cm_reads_swap exchanges them.
+struct ReadBufs {
+    BatchBuf<uint8_t> seq1_base, seq2_base;      // CM_STAGE_PAD readable bytes in front of and behind the reads
+    BatchBuf<uint64_t> off1, off2;
+};
+inline void swap(ReadBufs &a, ReadBufs &b) {
+    swap(a.seq1_base, b.seq1_base);
+    swap(a.seq2_base, b.seq2_base);
+    swap(a.off1, b.off1);
+    swap(a.off2, b.off2);
+}
+
+// What the seeding of a tile leaves for its chain stage: the seed ranges of every probe, the DP-cell offsets of every chaining
+// problem (+ total and largest problem, also copied to h_pin[8 + 2 s ..]).  Two sets: see map_rounds_issue.
+// The work classes of the tile's chaining problems and their sorted list (k_chain_cls + counting sort), the zeroed cursors of the
+// chain kernels (improvement-log pool: cm_ctx::pool_cursor(s); heavy work list) -- everything the chain kernels need but the chain
+// records themselves.
+struct SeedSet {
+    BatchBuf<uint32_t> sstart, scnt, sraw;
+    BatchBuf<unsigned long long> celloff, bsum;
+    BatchBuf<unsigned int> bmax;
+    BatchBuf<int8_t> cls4;
+    BatchBuf<unsigned int> cblk, cctr;           // class counters / block histograms of the CHAIN stage's sort (own copies: the pair
+                                                 // stage of the previous round uses its own at the same time)
+    BatchBuf<uint32_t> perm4;
+    BatchBuf<int32_t> thigh;                     // high_hits per problem while the chain records are not free yet (k_chain_apply)
+    bool cls_deferred = false;                   // classes made before the chain records were free, k_chain_apply still to run
+};
+// The chain records of a round.  Two sets: the pair stage of round r reads set r & 1 while the chaining of round r + 1 fills the other.
+struct ChainRecs {
+    BatchBuf<cm_chain> chains;
+    BatchBuf<int32_t> nchain, high;
+    BatchBuf<uint16_t> resid;
+};
+// What a pair stage keeps once per set of chain records (item i + 1 leaves item i's alone, item i + 2 starts after ev.pair[b]): the
+// ordered lists of its pairs, the class counters + work cursors, the per-pair capacity flags (zero between launches), the pairs to
+// re-run (RetryArgs) with [count, cursor], the heavy-pair pipeline's fall-back list with its count.  Views: set b is the b-th half of
+// one allocation each (PairSetMem, cut in prepare_resident).
+struct PairSet {
+    uint32_t *perm = nullptr, *hlist = nullptr;
+    unsigned int *cls_ctr = nullptr;
+    uint32_t *pair_err = nullptr, *retry_list = nullptr;
+    unsigned int *retry_ctr = nullptr;
+    uint32_t *hp_fall = nullptr;
+    unsigned int *hp_fallctr = nullptr;
+};
+struct PairSetMem {
+    BatchBuf<uint32_t> perm, hlist;
+    BatchBuf<unsigned int> cls_ctr;
+    BatchBuf<uint32_t> pair_err, retry_list;
+    BatchBuf<unsigned int> retry_ctr;
+    BatchBuf<uint32_t> hp_fall;
+    BatchBuf<unsigned int> hp_fallctr;
+};
+// scratch of a pair stage's three-pass sort (run_pair_tile), used on the ordering stream only
+struct PairSort {
+    BatchBuf<int8_t> cls, sub, sub2;
+    BatchBuf<uint32_t> perm1, perm0;
+    BatchBuf<unsigned int> ctr2, ctr3, blk_cnt;
+};
+// the heavy pairs as a pipeline of kernels (cm_heavy_pipe.h): arrays of one tile
+struct HeavyPipe {
+    BatchBuf<HPair> pairs;
+    BatchBuf<uint32_t> list2, q, q2;
+    BatchBuf<HTask> T;
+    BatchBuf<int8_t> tcls;                       // work class of every task, the order k_hp_tasks walks them in, the counting sort's scratch
+    BatchBuf<uint32_t> tperm;
+    BatchBuf<unsigned int> tblk, tctr;
+    BatchBuf<HUnp> U;
+    BatchBuf<cmc::PreDP> pre, pre2;
+    BatchBuf<HRes> res;
+    BatchBuf<uint16_t> lists;
+    BatchBuf<unsigned int> ctr;
+    uint32_t tasks_cap = 0, unp_cap = 0;
+};
+// DP cells of the chain kernels and the improvement-log pool
+struct ChainWork {
+    BatchBuf<double> score;
+    BatchBuf<int32_t> prev;
+    unsigned long long cells_cap = 0;
+    BatchBuf<uint8_t> pool;
+    unsigned long long pool_bytes = 0;
+};
+// cm_collect_*: compaction scratch sized for the batch, output staging that outlives it
+struct Collect {
+    BatchBuf<int8_t> cls;
+    BatchBuf<uint32_t> perm;
+    BatchBuf<unsigned int> blk, ctr;
+    CtxBuf<unsigned long long> idx;
+    CtxBuf<cm_mapped_read> st;
+    CtxBuf<cm_record> rec;
+};
+
+// The streams of a context, under the letters of DESIGN §4.  STREAMS lists them in creation order, which decides the hardware
+// queue a stream lands on; everything that walks the streams walks that table.
+struct Streams {
+    hipStream_t B = nullptr;       // main: seeding of the first item, chaining, everything outside cm_map_rounds
+    hipStream_t B2 = nullptr;      // heavy work of a chain stage, concurrent with the light kernel on B
+    hipStream_t C = nullptr;       // H2D copies of the staged batch (cm_reads_stage)
+    // The pair stage of round r runs on its own streams while B / B2 already seed and chain round r + 1 (cm_map_rounds): seeds
+    // and chains are functions of (read, contig) only, the carried state enters in the pair stage.
+    hipStream_t P = nullptr, P2 = nullptr;
+    hipStream_t R = nullptr;       // the late launches of a pair stage: fall-back, re-run (RetryArgs)
+    hipStream_t O = nullptr;       // work classes + ordered lists of a pair stage, computed under the pair stage of the item before
+    hipStream_t S = nullptr;       // seeding of the NEXT item, issued while the chain stage of this one runs (map_rounds_issue)
+};
+enum StreamKind { BLOCKING, NON_BLOCKING, NON_BLOCKING_LOWEST };
+struct StreamDef {
+    hipStream_t Streams::*st;
+    const char *name;              // in teardown diagnostics
+    StreamKind kind;
+};
+// P at the lowest priority: the light kernel's persistent waves are the filler of a pair stage, and the short kernels of the heavy
+// pairs' pipeline and of the next item's seeding / chaining get their workgroups placed first (hg38-like step 74.3 -> 70.9 ms; 72.3
+// with the pipeline's stream raised instead, 76.9 with both, 72.9 with the heavy chaining stream lowered).
+constexpr StreamDef STREAMS[] = {
+    {&Streams::B, "main", BLOCKING},           {&Streams::B2, "heavy chains", BLOCKING},     {&Streams::C, "copy", NON_BLOCKING},
+    {&Streams::P, "pairs", NON_BLOCKING_LOWEST}, {&Streams::P2, "heavy pairs", NON_BLOCKING}, {&Streams::R, "re-run", NON_BLOCKING},
+    {&Streams::O, "pair ordering", NON_BLOCKING}, {&Streams::S, "seeding", NON_BLOCKING},
+};
+// The events of a context, all without timing.  Nothing but hipEvent_t in here: creation and destruction walk the struct as an array.
+struct Events {
+    hipEvent_t fork = nullptr, join = nullptr;          // B -> B2 -> B around the heavy chains
+    hipEvent_t join_p = nullptr, tail = nullptr;
+    hipEvent_t flags = nullptr;                         // main stream: the pair stage two items back is complete (its flags may be read: early seeding)
+    hipEvent_t staged = nullptr, retired = nullptr;     // the staged batch's copies are complete / the buffers a swap retired are free
+    hipEvent_t order[2] = {nullptr, nullptr};           // work classes + ordered lists of a pair stage of set b are complete
+    hipEvent_t seed[2] = {nullptr, nullptr};            // seeds + cell offsets of a seed set are complete
+    hipEvent_t first[2] = {nullptr, nullptr};           // an item's two pair kernels are done (set b): its re-run may start
+    hipEvent_t prep[2] = {nullptr, nullptr}, pair[2] = {nullptr, nullptr};
+    hipEvent_t *begin() { return &fork; }
+    hipEvent_t *end() { return begin() + sizeof(Events) / sizeof(hipEvent_t); }
+};
+static_assert(sizeof(Events) == 17 * sizeof(hipEvent_t), "Events holds events only");
+
 }  // namespace
 
 struct cm_ctx {
     cm_params P{};
     unsigned id = 0;                          // serial number of the context in this process: names it in teardown diagnostics
     int teardown_errors = 0;
-    hipStream_t stream = nullptr;
-    hipStream_t stream2 = nullptr;            // heavy work of a stage, concurrent with the light kernel on `stream`
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    // The pair stage of round r runs on its own pair of streams while `stream` / `stream2` already seed and chain round r + 1
-    // (cm_map_rounds): seeds and chains are functions of (read, contig) only, the carried state enters in the pair stage.
-    hipStream_t stream_p = nullptr, stream_p2 = nullptr, stream_p3 = nullptr;      // p3: the re-run launch of the pair stage (RetryArgs)
-    hipStream_t stream_o = nullptr;           // work classes + ordered lists of a pair stage, computed under the pair stage of the item before
-    hipEvent_t ev_order[2] = {nullptr, nullptr};      // ... of set b are complete
-    // The re-run launch of a pair stage (RetryArgs), decided late: see settle_pair.
+    Streams st;
+    Events ev;
+    std::vector<DevMem *> bufs[2];            // [Life]: the buffers of that lifetime which hold memory
+    // The late launches of a pair stage: the re-run (RetryArgs) and the fall-back of the heavy-pair pipeline (k_pair_heavy over the
+    // pairs that did not fit its arrays), decided late: see settle_pair.
     struct Rerun {
         bool deferred = false;
         cmc::KCore core;
@@ -1806,21 +1963,11 @@ struct cm_ctx {
         uint8_t *act_out = nullptr;
         int is_last = 0, cap2 = 0;
         size_t lds2 = 0;
-        uint32_t *pair_err = nullptr, *retry_list = nullptr;
-        unsigned int *retry_ctr = nullptr;
-        // the fall-back launch of the heavy-pair pipeline (k_pair_heavy over the pairs that did not fit its arrays), decided late as well
         bool fall = false;
-        const uint32_t *fall_list = nullptr;
-        unsigned int *fall_ctr = nullptr, *fall_cursor = nullptr;
         size_t lds_heavy = 0;
         int str_cap = 0;
         unsigned fall_grid = 0;
     } rerun[2];
-    hipStream_t stream_s = nullptr;           // seeding of the NEXT item, issued while the chain stage of this one runs (map_rounds_issue)
-    hipEvent_t ev_seed[2] = {nullptr, nullptr};       // seeds + cell offsets of a seed set are complete
-    hipEvent_t ev_first[2] = {nullptr, nullptr};      // an item's two pair kernels are done (set b): its re-run may start
-    hipEvent_t ev_join_p = nullptr, ev_prep[2] = {nullptr, nullptr}, ev_pair[2] = {nullptr, nullptr}, ev_tail = nullptr;
-    hipEvent_t ev_flags = nullptr;            // main stream: the pair stage two items back is complete (its flags may be read: early seeding)
     bool pair_pending[2] = {false, false};
     // cross-batch prefetch (cm_map_rounds): the staged batch's first round seeded and chained under this batch's last pair stage
     int item_base = 0;                        // items (tile x round) mapped so far: item i uses chain-record set (item_base + i) & 1
@@ -1829,7 +1976,7 @@ struct cm_ctx {
     int pre_slot = -1, pre_b = 0;
     uint64_t pre_gen = 0, pre_n = 0;
     uint32_t pre_nt = 0;                      // pairs of the prefetched item (the staged batch's first tile)
-    uint8_t *d_ones = nullptr;                // all-active flags of a fresh batch
+    BatchBuf<uint8_t> d_ones;                 // all-active flags of a fresh batch
     uint64_t ones_cap = 0;
     unsigned long long *h_pin = nullptr;          // page-locked landing zone of the scalar read-backs (cell total, error flags, counts)
     uint32_t h_pin_nt = 0;                        // pairs of the tile whose heavy load was last sent to h_pin[4] (0: none yet)
@@ -1837,90 +1984,38 @@ struct cm_ctx {
     Slot slots[MAX_SLOTS];
     // reads
     uint64_t n_pairs = 0;
-    uint8_t *d_seq1 = nullptr, *d_seq2 = nullptr, *d_seq1_base = nullptr, *d_seq2_base = nullptr;
-    uint64_t *d_off1 = nullptr, *d_off2 = nullptr;
-    cm_mapped_read *d_state = nullptr;
-    uint8_t *d_active = nullptr;              // current flags (valid after the last completed round)
-    uint8_t *d_active_b = nullptr;            // the other parity: a round reads one array and writes the other
-    int32_t *d_cat = nullptr;
+    ReadBufs rd;
+    BatchBuf<cm_mapped_read> d_state;
+    BatchBuf<uint8_t> d_active;               // current flags (valid after the last completed round)
+    BatchBuf<uint8_t> d_active_b;             // the other parity: a round reads one array and writes the other
+    BatchBuf<int32_t> d_cat;
     int n_seeds = 0, max_len = 0;
     // staged batch (cm_reads_stage): a second set of read buffers filled on the copy stream while the resident batch is mapped
-    hipStream_t stream_copy = nullptr;
-    hipEvent_t ev_staged = nullptr, ev_retired = nullptr;
     bool staged = false;
     uint64_t st_n_pairs = 0;
-    uint8_t *st_seq1_base = nullptr, *st_seq2_base = nullptr;
-    uint64_t *st_off1 = nullptr, *st_off2 = nullptr;
-    cm_mapped_read *st_prior = nullptr;
+    ReadBufs st_rd;
+    BatchBuf<cm_mapped_read> st_prior;
     bool st_has_prior = false;
     int st_max_len = 0;
-    // workspace
+    // workspace of one tile
     uint32_t tile = 0;
-    uint32_t *d_sstart = nullptr, *d_scnt = nullptr, *d_sraw = nullptr, *d_cells = nullptr;
-    unsigned long long *d_celloff = nullptr, *d_bsum = nullptr;
-    unsigned int *d_bmax = nullptr;
-    // second seed set (SeedBufs): item i + 1 is seeded into it while the chain stage of item i reads the first, and vice versa
-    uint32_t *d_sstart_b = nullptr, *d_scnt_b = nullptr, *d_sraw_b = nullptr;
-    unsigned long long *d_celloff_b = nullptr, *d_bsum_b = nullptr;
-    unsigned int *d_bmax_b = nullptr;
-    unsigned int *d_cctr_b = nullptr, *d_cblk_b = nullptr;
-    int8_t *d_cls4_b = nullptr;
-    int32_t *d_thigh = nullptr, *d_thigh_b = nullptr;
-    bool cls_deferred[2] = {false, false};      // seed set s: classes made before the chain records were free, k_chain_apply still to run
-    uint32_t *d_perm4_b = nullptr;
-    double *d_dpscore = nullptr;
-    int32_t *d_dpprev = nullptr;
-    unsigned long long cells_cap = 0;
-    cm_chain *d_chains = nullptr;             // chains of a round: two sets, the pair stage of round r reads set r & 1 while
-    int32_t *d_nchain = nullptr, *d_high = nullptr;       // the chaining of round r + 1 fills the other
-    cm_chain *d_chains_b = nullptr;
-    int32_t *d_nchain_b = nullptr, *d_high_b = nullptr;
-    uint16_t *d_resid_b = nullptr;
-    unsigned int *d_cctr = nullptr, *d_cblk = nullptr;    // class counters / block histograms of the CHAIN stage's sort (own copies: the
-                                                          // pair stage of the previous round uses d_cls_ctr / d_blk_cnt at the same time)
-    unsigned long long *d_lane_clk = nullptr;     // diagnostic build of the timing study only
-    int8_t *d_cls = nullptr, *d_cls4 = nullptr, *d_cls_sub = nullptr, *d_cls_sub2 = nullptr;
-    uint32_t *d_perm1 = nullptr, *d_perm0 = nullptr;
-    unsigned int *d_cls_ctr2 = nullptr, *d_cls_ctr3 = nullptr;
-    uint32_t *d_perm4 = nullptr;
-    uint16_t *d_resid = nullptr;
-    uint32_t *d_perm = nullptr;
-    unsigned int *d_cls_ctr = nullptr, *d_blk_cnt = nullptr;
-    unsigned long long *d_collect_idx = nullptr;
-    cm_mapped_read *d_collect_st = nullptr;
-    cm_record *d_collect_rec = nullptr;
-    uint64_t collect_rec_cap = 0;
-    std::unordered_map<const void *, size_t> caps;   // bytes behind each grow-only per-batch buffer, keyed by the pointer field (ensure())
-    uint64_t collect_cap = 0;
-    int8_t *d_col_cls = nullptr;
-    uint32_t *d_col_perm = nullptr;
-    unsigned int *d_col_blk = nullptr, *d_col_ctr = nullptr;
-    uint32_t *d_hlist = nullptr;
-    HRes *d_hres = nullptr;          // task outcomes of k_pair_heavy: 64 per resident block
-    // the heavy pairs as a pipeline of kernels (cm_heavy_pipe.h)
-    HPair *d_hp = nullptr;
-    uint32_t *d_hp_list2 = nullptr, *d_hp_fall = nullptr, *d_hp_q = nullptr, *d_hp_q2 = nullptr;
-    HTask *d_hp_T = nullptr;
-    int8_t *d_hp_tcls = nullptr;               // work class of every task, the order k_hp_tasks walks them in, the counting sort's scratch
-    uint32_t *d_hp_tperm = nullptr;
-    unsigned int *d_hp_tblk = nullptr, *d_hp_tctr = nullptr;
-    HUnp *d_hp_U = nullptr;
-    cmc::PreDP *d_hp_pre = nullptr, *d_hp_pre2 = nullptr;
-    HRes *d_hp_res = nullptr;
-    uint16_t *d_hp_lists = nullptr;
-    unsigned int *d_hp_ctr = nullptr;
-    uint32_t hp_tasks_cap = 0, hp_unp_cap = 0;
-    unsigned int *d_hp_fallctr = nullptr;      // [set]
-    unsigned long long *d_type_hist = nullptr;
-    unsigned int *d_retry_ctr = nullptr;                          // [set][count, cursor]
-    unsigned long long *d_heavy_load = nullptr;                   // cost beyond HEAVY_COST summed over the tile in the pair stage (k_pair_cost)
-    uint32_t *d_pair_err = nullptr, *d_retry_list = nullptr;      // per-pair capacity flags of a tile (zero between launches), pairs to re-run (RetryArgs)
-    cmc::MemoSpill *d_spill = nullptr;                            // RETRY_GRID x 64 lanes x RETRY_SPILL overflow entries of the extension memo
-    uint8_t *d_pool = nullptr;
-    unsigned long long pool_bytes = 0;
-    unsigned long long *d_pool_cursor = nullptr;
-    int *d_err = nullptr;
-    unsigned long long *d_counters = nullptr;
+    SeedSet seed[2];                          // item i + 1 is seeded into one while the chain stage of item i reads the other
+    ChainRecs rec[2];
+    PairSetMem pair_mem;
+    PairSet pset[2];
+    PairSort sort;
+    ChainWork dp;
+    HeavyPipe hp;
+    Collect col;
+    BatchBuf<unsigned long long> d_lane_clk;      // diagnostic build of the timing study only
+    BatchBuf<HRes> d_hres;                        // task outcomes of k_pair_heavy: 64 per resident block
+    BatchBuf<unsigned long long> d_type_hist;
+    BatchBuf<unsigned long long> d_heavy_load;    // cost beyond HEAVY_COST summed over the tile in the pair stage (k_pair_cost)
+    BatchBuf<cmc::MemoSpill> d_spill;             // RETRY_GRID x 64 lanes x RETRY_SPILL overflow entries of the extension memo
+    CtxBuf<unsigned long long> d_pool_cursor;     // [seed set]
+    unsigned long long *pool_cursor(int s) const { return d_pool_cursor + s; }
+    CtxBuf<int> d_err;
+    CtxBuf<unsigned long long> d_counters;
     std::vector<unsigned long long> h_celloff;
     // profiling
     bool prof = false;
@@ -1962,7 +2057,7 @@ int up(cm_ctx *ctx, std::vector<void *> &allocs, const T *host, size_t n, const 
     size_t bytes = (n ? n : 1) * sizeof(T);
     HIPCHK(ctx, hipMalloc(&d, bytes));
     allocs.push_back(d);
-    if (n) HIPCHK(ctx, hipMemcpyAsync(d, host, n * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
+    if (n) HIPCHK(ctx, hipMemcpyAsync(d, host, n * sizeof(T), hipMemcpyHostToDevice, ctx->st.B));
     *dev = (const T *)d;
     return CM_OK;
 }
@@ -1970,41 +2065,38 @@ void free_all(cm_ctx *ctx, std::vector<void *> &v) {
     for (void *p : v) report_hip(ctx, "hipFree", hipFree(p));
     v.clear();
 }
-template <class T>
-void dfree(cm_ctx *ctx, T *&p) {
-    if (p) report_hip(ctx, "hipFree", hipFree((void *)p));
-    p = nullptr;
-}
-
-// Grow-only per-batch buffers: a batch re-uses the previous batch's allocation when it is large enough.  hipFree + hipMalloc
+// Grow-only buffers: a batch re-uses the previous batch's allocation when it is large enough.  hipFree + hipMalloc
 // of the multi-GB workspaces cost ~0.85 s per 1 M-pair batch on MI355X, 85x the mapping itself (tests/diag/upload_rate.py).
-template <class T>
-hipError_t ensure(cm_ctx *c, T *&p, size_t bytes) {
-    size_t &cap = c->caps[(const void *)&p];
-    if (p && cap >= bytes) return hipSuccess;
-    dfree(c, p);
-    cap = 0;
-    const hipError_t e = hipMalloc((void **)&p, bytes ? bytes : 1);
-    if (e == hipSuccess) cap = bytes;
+// On growth the old memory is freed first and the contents are lost; 0 bytes allocate 1.
+void dfree(cm_ctx *c, DevMem &m) {
+    if (m.p) report_hip(c, "hipFree", hipFree(m.p));
+    m.p = nullptr;
+    m.cap = 0;
+}
+template <class T, Life L>
+hipError_t ensure(cm_ctx *c, DevBuf<T, L> &m, size_t bytes) {
+    if (m.p && m.cap >= bytes) return hipSuccess;
+    dfree(c, m);
+    const hipError_t e = hipMalloc(&m.p, bytes ? bytes : 1);
+    if (e != hipSuccess) return e;
+    m.cap = bytes;
+    if (!m.listed) (m.listed = &c->bufs[L])->push_back(&m);
     return e;
+}
+// every buffer of one lifetime class
+void release(cm_ctx *c, Life l) {
+    for (DevMem *m : c->bufs[l]) {
+        dfree(c, *m);
+        m->listed = nullptr;
+    }
+    c->bufs[l].clear();
 }
 
 void free_reads(cm_ctx *c) {
-    dfree(c, c->d_seq1_base); dfree(c, c->d_seq2_base); c->d_seq1 = c->d_seq2 = nullptr; dfree(c, c->d_off1); dfree(c, c->d_off2);
-    dfree(c, c->d_state); dfree(c, c->d_active); dfree(c, c->d_active_b); dfree(c, c->d_cat);
-    dfree(c, c->d_chains_b); dfree(c, c->d_nchain_b); dfree(c, c->d_high_b); dfree(c, c->d_resid_b); dfree(c, c->d_cctr); dfree(c, c->d_cblk);
-    dfree(c, c->d_sstart); dfree(c, c->d_scnt); dfree(c, c->d_sraw); dfree(c, c->d_cells); dfree(c, c->d_celloff); dfree(c, c->d_bsum); dfree(c, c->d_bmax);
-    dfree(c, c->d_sstart_b); dfree(c, c->d_scnt_b); dfree(c, c->d_sraw_b); dfree(c, c->d_celloff_b); dfree(c, c->d_bsum_b); dfree(c, c->d_bmax_b);
-    dfree(c, c->d_cctr_b); dfree(c, c->d_cblk_b); dfree(c, c->d_cls4_b); dfree(c, c->d_perm4_b); dfree(c, c->d_thigh); dfree(c, c->d_thigh_b);
-    dfree(c, c->d_dpscore); dfree(c, c->d_dpprev); dfree(c, c->d_chains); dfree(c, c->d_nchain); dfree(c, c->d_high);
-    dfree(c, c->d_pool); dfree(c, c->d_lane_clk); dfree(c, c->d_cls); dfree(c, c->d_cls4); dfree(c, c->d_perm4); dfree(c, c->d_resid); dfree(c, c->d_perm); dfree(c, c->d_cls_ctr); dfree(c, c->d_cls_ctr2); dfree(c, c->d_cls_sub); dfree(c, c->d_perm1); dfree(c, c->d_cls_ctr3); dfree(c, c->d_cls_sub2); dfree(c, c->d_perm0); dfree(c, c->d_blk_cnt); dfree(c, c->d_hlist); dfree(c, c->d_hres);
-    dfree(c, c->d_hp); dfree(c, c->d_hp_list2); dfree(c, c->d_hp_fall); dfree(c, c->d_hp_fallctr); dfree(c, c->d_hp_q); dfree(c, c->d_hp_q2); dfree(c, c->d_hp_T); dfree(c, c->d_hp_tcls); dfree(c, c->d_hp_tperm); dfree(c, c->d_hp_tblk); dfree(c, c->d_hp_tctr); dfree(c, c->d_hp_U);
-    dfree(c, c->d_hp_pre); dfree(c, c->d_hp_pre2); dfree(c, c->d_hp_res); dfree(c, c->d_hp_lists); dfree(c, c->d_hp_ctr);
-    dfree(c, c->d_pair_err); dfree(c, c->d_retry_list); dfree(c, c->d_spill); dfree(c, c->d_type_hist); dfree(c, c->d_retry_ctr); dfree(c, c->d_heavy_load);
-    dfree(c, c->d_col_cls); dfree(c, c->d_col_perm); dfree(c, c->d_col_blk); dfree(c, c->d_col_ctr);
-    if (c->stream_copy) report_hip(c, "hipStreamSynchronize(copy stream)", hipStreamSynchronize(c->stream_copy));
-    dfree(c, c->st_seq1_base); dfree(c, c->st_seq2_base); dfree(c, c->st_off1); dfree(c, c->st_off2); dfree(c, c->st_prior);
-    dfree(c, c->d_ones);
+    // the staged buffers may still be the target of copies in flight
+    if (c->st.C) report_hip(c, "hipStreamSynchronize(copy stream)", hipStreamSynchronize(c->st.C));
+    release(c, BATCH);
+    c->pset[0] = c->pset[1] = PairSet{};
     c->ones_cap = 0;
     c->pre_launched = c->pre_ready = false;
     c->staged = false;
@@ -2027,7 +2119,7 @@ struct Timer {
     ProfRec r{};
     bool on;
     hipStream_t st;
-    Timer(cm_ctx *ctx, int k, hipStream_t stream = nullptr) : c(ctx), cls(k), on(ctx->prof), st(stream ? stream : ctx->stream) {
+    Timer(cm_ctx *ctx, int k, hipStream_t stream = nullptr) : c(ctx), cls(k), on(ctx->prof), st(stream ? stream : ctx->st.B) {
         if (on) {
             r.a = take_event(c);
             r.b = take_event(c);
@@ -2059,33 +2151,9 @@ int check_slot(cm_ctx *ctx, int slot, bool need_annot) {
     return CM_OK;
 }
 
-// seeds (+ optionally chains) of one tile; leaves results in the workspace
-struct RoundBufs { cm_chain *chains; int32_t *nchain, *high; uint16_t *resid; };
-RoundBufs round_bufs(cm_ctx *c, int b) {
-    return b ? RoundBufs{c->d_chains_b, c->d_nchain_b, c->d_high_b, c->d_resid_b} : RoundBufs{c->d_chains, c->d_nchain, c->d_high, c->d_resid};
-}
+ReadsDev reads_dev(const ReadBufs &r) { return ReadsDev{r.seq1_base + cmc::CM_STAGE_PAD, r.seq2_base + cmc::CM_STAGE_PAD, r.off1, r.off2}; }
+ReadsDev current_reads(const cm_ctx *ctx) { return reads_dev(ctx->rd); }
 
-ReadsDev current_reads(const cm_ctx *ctx) { return ReadsDev{ctx->d_seq1, ctx->d_seq2, ctx->d_off1, ctx->d_off2}; }
-
-// What the seeding of a tile leaves for its chain stage: the seed ranges of every probe, the DP-cell offsets of every chaining
-// problem (+ total and largest problem, also copied to h_pin[8 + 2 s ..]).  Two sets: see map_rounds_issue.
-// The work classes of the tile's chaining problems and their sorted list (k_chain_cls + counting sort), the zeroed cursors of the
-// chain kernels (improvement-log pool, heavy work list) -- everything the chain kernels need but the chain records themselves.
-struct SeedBufs {
-    uint32_t *sstart, *scnt, *sraw;
-    unsigned long long *celloff, *bsum;
-    unsigned int *bmax;
-    int8_t *cls4;
-    unsigned int *cblk, *cctr;
-    uint32_t *perm4;
-    unsigned long long *pool_cursor;
-    int32_t *thigh;              // high_hits per problem while the chain records are not free yet (k_chain_apply)
-};
-SeedBufs seed_bufs(cm_ctx *c, int s) {
-    return s ? SeedBufs{c->d_sstart_b, c->d_scnt_b, c->d_sraw_b, c->d_celloff_b, c->d_bsum_b, c->d_bmax_b, c->d_cls4_b, c->d_cblk_b, c->d_cctr_b, c->d_perm4_b,
-                        c->d_pool_cursor + 1, c->d_thigh_b}
-             : SeedBufs{c->d_sstart, c->d_scnt, c->d_sraw, c->d_celloff, c->d_bsum, c->d_bmax, c->d_cls4, c->d_cblk, c->d_cctr, c->d_perm4, c->d_pool_cursor, c->d_thigh};
-}
 constexpr unsigned HP_PLAN_GRID = 2048;      // workgroups of k_hp_plan (each with its own task-list scratch)
 // CM_HEAVY_PIPELINE=0: the heavy pairs of a tile through k_pair_heavy alone (the round-3 path)
 static bool heavy_pipeline() {
@@ -2103,15 +2171,15 @@ static unsigned int chain_light_cells() {
 
 // seeds of one tile into seed set s, on stream st: k_seed, the scan of the problems' DP cells, the two totals to the host; with
 // rb (the chain records the tile's chain stage will fill: their per-problem counters are initialised here) also the work
-// classes + sorted lists of the chaining problems and the zeroed cursors.  ev_seed[s] is recorded behind them.
+// classes + sorted lists of the chaining problems and the zeroed cursors.  ev.seed[s] is recorded behind them.
 // The second half of run_seed_tile: the work classes + sorted lists of the chaining problems of seed set s, the per-problem counters of
 // the chain records rb and the zeroed cursors.  (On its own when the seeds were computed before the chain records were free: the
 // cross-batch prefetch.)
-static int seed_classes(cm_ctx *ctx, uint64_t pair0, uint32_t n_tile, const uint8_t *act, int s, hipStream_t st, const RoundBufs *rb, bool defer = false) {
+static int seed_classes(cm_ctx *ctx, uint64_t pair0, uint32_t n_tile, const uint8_t *act, int s, hipStream_t st, const ChainRecs *rb, bool defer = false) {
     const int S = ctx->n_seeds;
     const uint32_t n_prob = n_tile * 4u;
     if ((uint64_t)n_prob * (uint64_t)S == 0) return CM_OK;
-    const SeedBufs sb = seed_bufs(ctx, s);
+    const SeedSet &sb = ctx->seed[s];
     // Light problems: one lane each, index order.  Heavy problems (many hits): one wave each (k_chain_heavy), heaviest class
     // first.  (Used by run_chain_tile when it takes the split path; computed here because these five small launches, queued
     // behind the persistent pair kernels of the previous item, took 6 ms of the chain stage's critical path.)
@@ -2121,24 +2189,24 @@ static int seed_classes(cm_ctx *ctx, uint64_t pair0, uint32_t n_tile, const uint
     // (k_chain_apply) when it is ordered behind that stage
     hipLaunchKernelGGL(k_chain_cls, dim3((n_prob + BLK - 1) / BLK), dim3(BLK), 0, st, sb.scnt, sb.sraw, S, n_prob, sb.cls4, defer ? sb.thigh : rb->high,
                        chain_light_w(), chain_light_cells(), defer ? (int32_t *)nullptr : rb->nchain, defer ? (uint16_t *)nullptr : rb->resid, act, pair0);
-    ctx->cls_deferred[s] = defer;
+    ctx->seed[s].cls_deferred = defer;
     hipLaunchKernelGGL(k_cls_hist, dim3(nbk), dim3(CLS_W), 0, st, sb.cls4, n_prob, sb.cblk, nbk, (const uint32_t *)nullptr,
                        (const unsigned int *)nullptr);
     hipLaunchKernelGGL(k_cls_scan, dim3(1), dim3(SCAN_CLS_T), 0, st, sb.cblk, nbk, sb.cctr, -1, N_CLS);
     hipLaunchKernelGGL(k_cls_place, dim3(nbk), dim3(CLS_W), 0, st, sb.cls4, n_prob, sb.cblk, nbk, sb.cctr, sb.perm4,
                        (uint32_t *)nullptr, (const uint32_t *)nullptr, (const unsigned int *)nullptr);
     ctx->launches[5] += 4;
-    HIPCHK(ctx, hipMemsetAsync(sb.pool_cursor, 0, sizeof(unsigned long long), st));
+    HIPCHK(ctx, hipMemsetAsync(ctx->pool_cursor(s), 0, sizeof(unsigned long long), st));
     HIPCHK(ctx, hipMemsetAsync(sb.cctr + 48, 0, sizeof(unsigned int), st));       // spare word of the class counters: work cursor of k_chain_heavy
     HIPCHK(ctx, hipGetLastError());
     return CM_OK;
 }
 int run_seed_tile(cm_ctx *ctx, const KCore &core, const ReadsDev &rd, uint64_t pair0, uint32_t n_tile, const uint8_t *act, int s, hipStream_t st,
-                  const RoundBufs *rb, bool defer_rb = false) {
+                  const ChainRecs *rb, bool defer_rb = false) {
     const int S = ctx->n_seeds;
     const uint64_t total = (uint64_t)n_tile * 4u * (uint64_t)S;
     if (total == 0) return CM_OK;
-    const SeedBufs sb = seed_bufs(ctx, s);
+    const SeedSet &sb = ctx->seed[s];
     {
         Timer t(ctx, 0, st);
         hipLaunchKernelGGL(k_seed, dim3((unsigned)((total + BLK - 1) / BLK)), dim3(BLK), 0, st, core, rd, act, pair0, n_tile, S,
@@ -2159,7 +2227,7 @@ int run_seed_tile(cm_ctx *ctx, const KCore &core, const ReadsDev &rd, uint64_t p
         const int rc = seed_classes(ctx, pair0, n_tile, act, s, st, rb, defer_rb);
         if (rc) return rc;
     }
-    HIPCHK(ctx, hipEventRecord(ctx->ev_seed[s], st));
+    HIPCHK(ctx, hipEventRecord(ctx->ev.seed[s], st));
     HIPCHK(ctx, hipGetLastError());
     return CM_OK;
 }
@@ -2167,41 +2235,39 @@ int run_seed_tile(cm_ctx *ctx, const KCore &core, const ReadsDev &rd, uint64_t p
 // chains of one tile from seed set s (run_seed_tile) into the chain records rb.  `after_launch` (may be empty) is called once, when
 // the chain kernels of the tile have been launched and before the host waits for them.
 int run_chain_tile(cm_ctx *ctx, const KCore &core, const ReadsDev &rd, uint64_t pair0, uint32_t n_tile, bool parallel_ok, const uint8_t *act,
-                   const RoundBufs &rb, int s, const std::function<int()> &after_launch = {}) {
+                   const ChainRecs &rb, int s, const std::function<int()> &after_launch = {}) {
     const int S = ctx->n_seeds;
     const uint32_t n_prob = n_tile * 4u;
     if (n_prob == 0 || S == 0) return after_launch ? after_launch() : CM_OK;
-    const SeedBufs sb = seed_bufs(ctx, s);
-    HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_seed[s], 0));
-    HIPCHK(ctx, hipEventSynchronize(ctx->ev_seed[s]));
-    if (ctx->cls_deferred[s]) {           // classes made while the chain records were in use (the caller has ordered this stream behind that)
-        hipLaunchKernelGGL(k_chain_apply, dim3((n_prob + BLK - 1) / BLK), dim3(BLK), 0, ctx->stream, n_prob, (const int8_t *)sb.cls4, (const int32_t *)sb.thigh,
+    const SeedSet &sb = ctx->seed[s];
+    HIPCHK(ctx, hipStreamWaitEvent(ctx->st.B, ctx->ev.seed[s], 0));
+    HIPCHK(ctx, hipEventSynchronize(ctx->ev.seed[s]));
+    if (ctx->seed[s].cls_deferred) {           // classes made while the chain records were in use (the caller has ordered this stream behind that)
+        hipLaunchKernelGGL(k_chain_apply, dim3((n_prob + BLK - 1) / BLK), dim3(BLK), 0, ctx->st.B, n_prob, (const int8_t *)sb.cls4, (const int32_t *)sb.thigh,
                            rb.high, rb.nchain, rb.resid);
-        ctx->cls_deferred[s] = false;
+        ctx->seed[s].cls_deferred = false;
     }
     const unsigned long long total = ctx->h_pin[8 + 2 * s];
     const unsigned long long max_cells = ctx->h_pin[9 + 2 * s];       // of one problem
     // problem ranges whose DP cells fit the workspace
     std::vector<std::pair<uint32_t, uint32_t>> ranges;
-    if (total <= ctx->cells_cap) {
+    if (total <= ctx->dp.cells_cap) {
         ranges.push_back({0u, n_prob});
     } else {
         ctx->h_celloff.resize((size_t)n_prob + 1);
         HIPCHK(ctx, hipMemcpyAsync(ctx->h_celloff.data(), sb.celloff, ((size_t)n_prob + 1) * sizeof(unsigned long long), hipMemcpyDeviceToHost,
-                                   ctx->stream));
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+                                   ctx->st.B));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->st.B));
         uint32_t a = 0;
         while (a < n_prob) {
             uint32_t b = a;
-            while (b < n_prob && ctx->h_celloff[b + 1] - ctx->h_celloff[a] <= ctx->cells_cap) ++b;
+            while (b < n_prob && ctx->h_celloff[b + 1] - ctx->h_celloff[a] <= ctx->dp.cells_cap) ++b;
             if (b == a) return fail(ctx, CM_ELIMIT, "one chaining problem needs %llu DP cells (> workspace %llu)",
-                                    ctx->h_celloff[a + 1] - ctx->h_celloff[a], ctx->cells_cap);
+                                    ctx->h_celloff[a + 1] - ctx->h_celloff[a], ctx->dp.cells_cap);
             ranges.push_back({a, b});
             a = b;
         }
     }
-    // CM_CHAIN_SPLIT=0 keeps everything on the sequential kernel (the class lists of run_seed_tile go unused).
-    static const char *split_env = getenv("CM_CHAIN_SPLIT");
     // k_chain_heavy keeps a problem's hit positions in LDS: sized for the largest problem of this tile (a multiple of 2 KB, so
     // that launches of similar tiles share a configuration), not for the n_seeds x seed_lim a problem could have in theory --
     // the kernel waits on memory most of the time and the LDS request decides how many waves a CU holds.
@@ -2209,22 +2275,23 @@ int run_chain_tile(cm_ctx *ctx, const KCore &core, const ReadsDev &rd, uint64_t 
     const size_t lds_extra = ((size_t)max_cells / 64 + 2) * 8 + 640;
     const size_t heavy_lds = std::min<size_t>((size_t)S * (size_t)ctx->P.seed_lim * sizeof(uint32_t),
                                               ((size_t)max_cells * sizeof(uint32_t) + 2047) / 2048 * 2048 + 2048) + (lds_extra + 255) / 256 * 256;
-    const bool split = !(split_env && split_env[0] == '0') && ranges.size() == 1 && parallel_ok && heavy_lds <= 152u * 1024u;
+    // (otherwise everything stays on the sequential kernel and the class lists of run_seed_tile go unused)
+    const bool split = ranges.size() == 1 && parallel_ok && heavy_lds <= 152u * 1024u;
     bool fresh = true;            // the cursors are still as run_seed_tile zeroed them
     // one launch group over problems [a, b) whose DP cells start at `base`: the improvement log of every problem comes out of the
     // shared pool, whose cursor starts at 0 for every group
     auto launch_group = [&](uint32_t a, uint32_t b, unsigned long long base, bool use_split) -> int {
         const uint32_t n = b - a;
         if (!fresh) {
-            HIPCHK(ctx, hipMemsetAsync(sb.pool_cursor, 0, sizeof(unsigned long long), ctx->stream));
-            HIPCHK(ctx, hipMemsetAsync(sb.cctr + 48, 0, sizeof(unsigned int), ctx->stream));       // spare word of the class counters: work cursor
+            HIPCHK(ctx, hipMemsetAsync(ctx->pool_cursor(s), 0, sizeof(unsigned long long), ctx->st.B));
+            HIPCHK(ctx, hipMemsetAsync(sb.cctr + 48, 0, sizeof(unsigned int), ctx->st.B));       // spare word of the class counters: work cursor
         }
         fresh = false;
         if (use_split) {          // the few long problems run on the second stream, concurrently with the bulk
-            HIPCHK(ctx, hipEventRecord(ctx->ev_fork, ctx->stream));
-            HIPCHK(ctx, hipStreamWaitEvent(ctx->stream2, ctx->ev_fork, 0));
+            HIPCHK(ctx, hipEventRecord(ctx->ev.fork, ctx->st.B));
+            HIPCHK(ctx, hipStreamWaitEvent(ctx->st.B2, ctx->ev.fork, 0));
             {
-            Timer t(ctx, 6, ctx->stream2);
+            Timer t(ctx, 6, ctx->st.B2);
             // (a property of the function, process-wide: only ever raised, so a launch in flight from another context of this
             // process never sees its limit lowered)
             static std::atomic<size_t> heavy_attr{64u * 1024u};
@@ -2233,34 +2300,32 @@ int run_chain_tile(cm_ctx *ctx, const KCore &core, const ReadsDev &rd, uint64_t 
                 heavy_attr.store(heavy_lds);
             }
             const uint32_t hb = n < 8192u ? n : 8192u;
-            static const size_t heavy_pad = getenv("CM_CHEAVY_LDS_PAD") ? (size_t)atoi(getenv("CM_CHEAVY_LDS_PAD")) : 0;     // occupancy experiment
-            hipLaunchKernelGGL(k_chain_heavy, dim3(hb), dim3(64), heavy_lds + heavy_pad, ctx->stream2, core, rd, pair0, S, sb.sstart, sb.scnt, sb.celloff,
-                               ctx->d_dpscore, ctx->d_dpprev, ctx->d_pool, ctx->pool_bytes, sb.pool_cursor, rb.chains, rb.nchain, ctx->d_err,
+            hipLaunchKernelGGL(k_chain_heavy, dim3(hb), dim3(64), heavy_lds, ctx->st.B2, core, rd, pair0, S, sb.sstart, sb.scnt, sb.celloff,
+                               ctx->dp.score, ctx->dp.prev, ctx->dp.pool, ctx->dp.pool_bytes, ctx->pool_cursor(s), rb.chains, rb.nchain, ctx->d_err,
                                rb.resid, sb.perm4, sb.cctr + CTR_BASE + CHAIN_LIGHT_CLS - 1, sb.cctr + 48, ctx->d_counters);
             ++ctx->launches[6];
             }
-            HIPCHK(ctx, hipEventRecord(ctx->ev_join, ctx->stream2));
+            HIPCHK(ctx, hipEventRecord(ctx->ev.join, ctx->st.B2));
         }
         Timer t(ctx, 1);
-        static const size_t light_pad = getenv("CM_CHAIN_LDS_PAD") ? (size_t)atoi(getenv("CM_CHAIN_LDS_PAD")) : 0;       // occupancy experiment
-        hipLaunchKernelGGL(k_chain, dim3((n + BLK_CHAIN - 1) / BLK_CHAIN), dim3(BLK_CHAIN), light_pad, ctx->stream, core, rd, act, pair0, a, b, S,
-                           sb.sstart, sb.scnt, sb.sraw, sb.celloff, base, ctx->d_dpscore, ctx->d_dpprev, ctx->d_pool,
-                           ctx->pool_bytes, sb.pool_cursor, rb.chains, rb.nchain, rb.high, ctx->d_err, rb.resid,
+        hipLaunchKernelGGL(k_chain, dim3((n + BLK_CHAIN - 1) / BLK_CHAIN), dim3(BLK_CHAIN), 0, ctx->st.B, core, rd, act, pair0, a, b, S,
+                           sb.sstart, sb.scnt, sb.sraw, sb.celloff, base, ctx->dp.score, ctx->dp.prev, ctx->dp.pool,
+                           ctx->dp.pool_bytes, ctx->pool_cursor(s), rb.chains, rb.nchain, rb.high, ctx->d_err, rb.resid,
                            use_split ? sb.perm4 : (const uint32_t *)nullptr, sb.cctr + CTR_BASE + CHAIN_LIGHT_CLS - 1, sb.cctr + CTR_SUM);
-        if (use_split) HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));       // timed with the light kernel: the stage ends here
+        if (use_split) HIPCHK(ctx, hipStreamWaitEvent(ctx->st.B, ctx->ev.join, 0));       // timed with the light kernel: the stage ends here
         ++ctx->launches[1];
         HIPCHK(ctx, hipGetLastError());
         return CM_OK;
     };
     // did the group run out of log space?  (one small read-back per group; the pair stage must not start on truncated logs)
     auto pool_lost = [&](bool *lost) -> int {
-        HIPCHK(ctx, hipMemcpyAsync(ctx->h_pin + 2, ctx->d_err, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(ctx->h_pin + 2, ctx->d_err, sizeof(int), hipMemcpyDeviceToHost, ctx->st.B));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->st.B));
         const int e = *(const int *)(ctx->h_pin + 2);
         *lost = (e & cmc::ERR_POOL) != 0;
         if (*lost) {                                          // the other flags stay for cm_sync to report (the pair stage of the
-            hipLaunchKernelGGL(k_err_clear, dim3(1), dim3(64), 0, ctx->stream, ctx->d_err, (int)cmc::ERR_POOL);   // previous round may be setting some right now)
-            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+            hipLaunchKernelGGL(k_err_clear, dim3(1), dim3(64), 0, ctx->st.B, ctx->d_err, (int)cmc::ERR_POOL);   // previous round may be setting some right now)
+            HIPCHK(ctx, hipStreamSynchronize(ctx->st.B));
         }
         return CM_OK;
     };
@@ -2278,16 +2343,16 @@ int run_chain_tile(cm_ctx *ctx, const KCore &core, const ReadsDev &rd, uint64_t 
         // The reference's score2chain has no capacity limit.  When the log pool ran out: first a larger pool (x4 up to pool_max)
         // and the same group again; then the group in halves on the one-lane-per-problem kernel, every piece with the whole pool
         // to itself.  Every retry recomputes its problems from the seeds, so nothing of the failed attempt survives.
-        while (lost && ctx->pool_bytes < pool_max) {
-            unsigned long long want = ctx->pool_bytes * 4ull;
+        while (lost && ctx->dp.pool_bytes < pool_max) {
+            unsigned long long want = ctx->dp.pool_bytes * 4ull;
             if (want > pool_max) want = pool_max;
-            HIPCHK(ctx, hipStreamSynchronize(ctx->stream2));
-            if (ensure(ctx, ctx->d_pool, want) != hipSuccess) {            // not enough HBM for a larger pool: keep the old size, go to the split path
+            HIPCHK(ctx, hipStreamSynchronize(ctx->st.B2));
+            if (ensure(ctx, ctx->dp.pool, want) != hipSuccess) {            // not enough HBM for a larger pool: keep the old size, go to the split path
                 (void)hipGetLastError();
-                HIPCHK(ctx, ensure(ctx, ctx->d_pool, ctx->pool_bytes));
+                HIPCHK(ctx, ensure(ctx, ctx->dp.pool, ctx->dp.pool_bytes));
                 break;
             }
-            ctx->pool_bytes = want;
+            ctx->dp.pool_bytes = want;
             if ((rc = launch_group(rg.first, rg.second, base, split))) return rc;
             if ((rc = pool_lost(&lost))) return rc;
         }
@@ -2300,7 +2365,7 @@ int run_chain_tile(cm_ctx *ctx, const KCore &core, const ReadsDev &rd, uint64_t 
                 if ((rc = pool_lost(&lost))) return rc;
                 if (!lost) continue;
                 if (pc.second - pc.first <= 1)
-                    return fail(ctx, CM_ELIMIT, "one chaining problem's improvement log does not fit %llu bytes", ctx->pool_bytes);
+                    return fail(ctx, CM_ELIMIT, "one chaining problem's improvement log does not fit %llu bytes", ctx->dp.pool_bytes);
                 const uint32_t mid = pc.first + (pc.second - pc.first) / 2;
                 todo.push_back({mid, pc.second});
                 todo.push_back({pc.first, mid});
@@ -2311,11 +2376,11 @@ int run_chain_tile(cm_ctx *ctx, const KCore &core, const ReadsDev &rd, uint64_t 
 }
 
 int check_dev_err(cm_ctx *ctx) {
-    HIPCHK(ctx, hipMemcpyAsync(ctx->h_pin, ctx->d_err, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->h_pin, ctx->d_err, sizeof(int), hipMemcpyDeviceToHost, ctx->st.B));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->st.B));
     const int e = *(const int *)ctx->h_pin;
     if (e) {
-        (void)hipMemsetAsync(ctx->d_err, 0, sizeof(int), ctx->stream);       // reported once: the next batch starts clean
+        (void)hipMemsetAsync(ctx->d_err, 0, sizeof(int), ctx->st.B);       // reported once: the next batch starts clean
         return fail(ctx, CM_ELIMIT, "device capacity limit hit:%s%s%s", (e & cmc::ERR_POOL) ? " chain improvement-log pool exhausted;" : "",
                     (e & (cmc::ERR_SEEDS | cmc::ERR_BAND)) ? " DP string longer than the staging buffer;" : "",
                     (e & cmc::ERR_MEMO) ? " extension memo overflowed where the reference's memo would have served a colliding key" : "");
@@ -2356,65 +2421,32 @@ int cm_create(const cm_params *p, cm_ctx **out) {
         static std::atomic<unsigned> serial{0};
         ctx->id = ++serial;
     }
-    // CM_STREAM_PRIO (tuning knob): bit 0 = seeding and pair-ordering streams at the highest priority, bit 1 = the heavy-pair stream too
-    static const int prio_mask = getenv("CM_STREAM_PRIO") ? atoi(getenv("CM_STREAM_PRIO")) : 0;
     int prio_lo = 0, prio_hi = 0;
-    if (prio_mask) (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
-    // CM_STREAM_LOW: bit 0 = the light pair kernel's stream at the lowest priority, bit 1 = the heavy chaining stream.  Default 1: the light
-    // kernel's persistent waves are the filler of a pair stage, and the short kernels of the heavy pairs' pipeline and of the next item's
-    // seeding / chaining get their workgroups placed first (hg38-like step 74.3 -> 70.9 ms; 72.3 with the pipeline's stream raised
-    // instead, 76.9 with both, 72.9 with the heavy chaining stream lowered).
-    static const int low_mask = getenv("CM_STREAM_LOW") ? atoi(getenv("CM_STREAM_LOW")) : 1;
-    if (low_mask && !prio_mask) (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
-    auto mk_stream = [&](hipStream_t *st, bool high, bool low = false) {
-        return high ? hipStreamCreateWithPriority(st, hipStreamNonBlocking, prio_hi)
-                    : low ? hipStreamCreateWithPriority(st, hipStreamNonBlocking, prio_lo) : hipStreamCreateWithFlags(st, hipStreamNonBlocking);
-    };
-    // (CM_STREAM_PRIO bit 2 = the heavy chaining stream, bit 3 = the main stream)
-    if (((prio_mask & 8) ? hipStreamCreateWithPriority(&ctx->stream, hipStreamDefault, prio_hi) : hipStreamCreate(&ctx->stream)) != hipSuccess ||
-        ((low_mask & 2)    ? hipStreamCreateWithPriority(&ctx->stream2, hipStreamDefault, prio_lo)
-         : (prio_mask & 4) ? hipStreamCreateWithPriority(&ctx->stream2, hipStreamDefault, prio_hi)
-                           : hipStreamCreate(&ctx->stream2)) != hipSuccess ||
-        hipStreamCreateWithFlags(&ctx->stream_copy, hipStreamNonBlocking) != hipSuccess ||
-        mk_stream(&ctx->stream_p, false, (low_mask & 1) != 0) != hipSuccess ||
-        mk_stream(&ctx->stream_p2, (prio_mask & 2) != 0) != hipSuccess ||
-        hipStreamCreateWithFlags(&ctx->stream_p3, hipStreamNonBlocking) != hipSuccess ||
-        mk_stream(&ctx->stream_o, (prio_mask & 1) != 0) != hipSuccess ||
-        hipEventCreateWithFlags(&ctx->ev_order[0], hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&ctx->ev_order[1], hipEventDisableTiming) != hipSuccess ||
-        mk_stream(&ctx->stream_s, (prio_mask & 1) != 0) != hipSuccess ||
-        hipEventCreateWithFlags(&ctx->ev_seed[0], hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&ctx->ev_seed[1], hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&ctx->ev_first[0], hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&ctx->ev_first[1], hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&ctx->ev_join_p, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&ctx->ev_prep[0], hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&ctx->ev_prep[1], hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&ctx->ev_pair[0], hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&ctx->ev_pair[1], hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&ctx->ev_tail, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&ctx->ev_flags, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&ctx->ev_staged, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&ctx->ev_retired, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming) != hipSuccess) {
-        cm_destroy(ctx);
-        return CM_EHIP;
+    (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
+    for (const StreamDef &d : STREAMS) {
+        hipStream_t *st = &(ctx->st.*d.st);
+        if ((d.kind == BLOCKING              ? hipStreamCreate(st)
+             : d.kind == NON_BLOCKING_LOWEST ? hipStreamCreateWithPriority(st, hipStreamNonBlocking, prio_lo)
+                                             : hipStreamCreateWithFlags(st, hipStreamNonBlocking)) != hipSuccess) {
+            cm_destroy(ctx);
+            return CM_EHIP;
+        }
     }
-    if (hipMalloc((void **)&ctx->d_pool_cursor, 2 * sizeof(unsigned long long)) != hipSuccess ||
-        hipMalloc((void **)&ctx->d_err, sizeof(int)) != hipSuccess ||
-        hipMalloc((void **)&ctx->d_counters, 32 * sizeof(unsigned long long)) != hipSuccess ||
+    for (hipEvent_t &e : ctx->ev)
+        if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) {
+            cm_destroy(ctx);
+            return CM_EHIP;
+        }
+    if (ensure(ctx, ctx->d_pool_cursor, 2 * sizeof(unsigned long long)) != hipSuccess ||
+        ensure(ctx, ctx->d_err, sizeof(int)) != hipSuccess ||
+        ensure(ctx, ctx->d_counters, 32 * sizeof(unsigned long long)) != hipSuccess ||
         hipHostMalloc((void **)&ctx->h_pin, 128, hipHostMallocDefault) != hipSuccess) {
         cm_destroy(ctx);
         return CM_ENOMEM;
     }
     memset(ctx->h_pin, 0, 128);
-    (void)hipMemsetAsync(ctx->d_err, 0, sizeof(int), ctx->stream);
-    (void)hipMemsetAsync(ctx->d_counters, 0, 32 * sizeof(unsigned long long), ctx->stream);
-    if (getenv("CM_ONE_STREAM")) {           // diagnostic: no concurrency between the light and the heavy kernels
-        (void)hipStreamDestroy(ctx->stream2);
-        ctx->stream2 = ctx->stream;
-    }
+    (void)hipMemsetAsync(ctx->d_err, 0, sizeof(int), ctx->st.B);
+    (void)hipMemsetAsync(ctx->d_counters, 0, 32 * sizeof(unsigned long long), ctx->st.B);
     if (hwq_low) {
         ctx->err = "note: GPU_MAX_HW_QUEUES was " + std::string(hwq ? hwq : "unset") +
                    " when this context was created; if HIP was initialised earlier in this process the seven streams of a context share the "
@@ -2432,12 +2464,8 @@ void cm_destroy(cm_ctx *ctx) {
     // Every stream of the context is drained, and its status looked at, before anything it could still touch is released: an
     // asynchronous error of this context's work is reported here, under this context's id, instead of surfacing as an abort in
     // whichever context uses the device next.
-    const std::pair<hipStream_t, const char *> streams[] = {{ctx->stream, "hipStreamSynchronize(main)"},        {ctx->stream2, "hipStreamSynchronize(heavy chains)"},
-                                                            {ctx->stream_s, "hipStreamSynchronize(seeding)"},    {ctx->stream_p, "hipStreamSynchronize(pairs)"},
-                                                            {ctx->stream_p2, "hipStreamSynchronize(heavy pairs)"}, {ctx->stream_p3, "hipStreamSynchronize(re-run)"}, {ctx->stream_o, "hipStreamSynchronize(pair ordering)"},
-                                                            {ctx->stream_copy, "hipStreamSynchronize(copy)"}};
-    for (const auto &st : streams)
-        if (st.first) report_hip(ctx, st.second, hipStreamSynchronize(st.first));
+    for (const StreamDef &d : STREAMS)
+        if (ctx->st.*d.st) report_hip(ctx, (std::string("hipStreamSynchronize(") + d.name + ")").c_str(), hipStreamSynchronize(ctx->st.*d.st));
     report_hip(ctx, "hipGetLastError at teardown", hipGetLastError());
     for (auto e : ctx->ev_free) report_hip(ctx, "hipEventDestroy", hipEventDestroy(e));
     ctx->ev_free.clear();
@@ -2451,20 +2479,12 @@ void cm_destroy(cm_ctx *ctx) {
         free_all(ctx, s.idx_allocs);
         free_all(ctx, s.ann_allocs);
     }
-    dfree(ctx, ctx->d_collect_idx);
-    dfree(ctx, ctx->d_collect_st);
-    dfree(ctx, ctx->d_collect_rec);        // grow-only output staging outlives a batch (collect_cap / collect_rec_cap go with it)
-    dfree(ctx, ctx->d_pool_cursor);
-    dfree(ctx, ctx->d_err);
-    dfree(ctx, ctx->d_counters);
+    release(ctx, CONTEXT);                 // (the grow-only output staging of cm_collect_* outlives a batch)
     if (ctx->h_pin) report_hip(ctx, "hipHostFree", hipHostFree(ctx->h_pin));
-    for (hipEvent_t e : {ctx->ev_fork, ctx->ev_join, ctx->ev_join_p, ctx->ev_prep[0], ctx->ev_prep[1], ctx->ev_pair[0], ctx->ev_pair[1], ctx->ev_tail, ctx->ev_flags,
-                         ctx->ev_first[0], ctx->ev_first[1], ctx->ev_order[0], ctx->ev_order[1], ctx->ev_seed[0], ctx->ev_seed[1], ctx->ev_staged, ctx->ev_retired})
+    for (hipEvent_t e : ctx->ev)
         if (e) report_hip(ctx, "hipEventDestroy", hipEventDestroy(e));
-    for (hipStream_t st : {ctx->stream_p3, ctx->stream_o, ctx->stream_s, ctx->stream_p, ctx->stream_p2, ctx->stream_copy})
-        if (st) report_hip(ctx, "hipStreamDestroy", hipStreamDestroy(st));
-    if (ctx->stream2 && ctx->stream2 != ctx->stream) report_hip(ctx, "hipStreamDestroy", hipStreamDestroy(ctx->stream2));
-    if (ctx->stream) report_hip(ctx, "hipStreamDestroy", hipStreamDestroy(ctx->stream));
+    for (const StreamDef &d : STREAMS)
+        if (ctx->st.*d.st) report_hip(ctx, "hipStreamDestroy", hipStreamDestroy(ctx->st.*d.st));
     delete ctx;
 }
 
@@ -2480,13 +2500,13 @@ static int finish_contig(cm_ctx *ctx, Slot &s) {
         uint32_t *d = nullptr;
         if (hipMalloc((void **)&d, n_buckets * cmc::DESC_WORDS * sizeof(uint32_t)) == hipSuccess) {
             s.idx_allocs.push_back(d);
-            hipLaunchKernelGGL(k_build_desc, dim3((unsigned)((n_buckets + BLK - 1) / BLK)), dim3(BLK), 0, ctx->stream, s.X.bucket_off, s.X.checksum, n_buckets,
+            hipLaunchKernelGGL(k_build_desc, dim3((unsigned)((n_buckets + BLK - 1) / BLK)), dim3(BLK), 0, ctx->st.B, s.X.bucket_off, s.X.checksum, n_buckets,
                                ctx->P.kmer, d);
             HIPCHK(ctx, hipGetLastError());
             s.d_desc = d;
         } else (void)hipGetLastError();      // not enough HBM: probes go through the arrays
     }
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->st.B));
     s.loaded = true;
     return CM_OK;
 }
@@ -2509,8 +2529,8 @@ int cm_load_contig(cm_ctx *ctx, int slot, const cm_index_view *iv) {
         const size_t pad = cmc::CM_STAGE_PAD;
         HIPCHK(ctx, hipMalloc((void **)&g, (size_t)iv->ref_len + 2 * pad));
         s.idx_allocs.push_back(g);
-        HIPCHK(ctx, hipMemsetAsync(g, 0, (size_t)iv->ref_len + 2 * pad, ctx->stream));
-        HIPCHK(ctx, hipMemcpyAsync(g + pad, iv->genome, (size_t)iv->ref_len, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, hipMemsetAsync(g, 0, (size_t)iv->ref_len + 2 * pad, ctx->st.B));
+        HIPCHK(ctx, hipMemcpyAsync(g + pad, iv->genome, (size_t)iv->ref_len, hipMemcpyHostToDevice, ctx->st.B));
         s.X.genome = g + pad;
     }
     if ((rc = up(ctx, s.idx_allocs, iv->bucket_off, nb, &s.X.bucket_off))) return rc;
@@ -2519,13 +2539,13 @@ int cm_load_contig(cm_ctx *ctx, int slot, const cm_index_view *iv) {
     return finish_contig(ctx, s);
 }
 
-// exclusive (or inclusive) scan of n uint32 items on ctx->stream; tmp: (n / S32_B + 2) words
+// exclusive (or inclusive) scan of n uint32 items on ctx->st.B; tmp: (n / S32_B + 2) words
 static int scan32(cm_ctx *ctx, const uint32_t *in, uint64_t n, uint32_t *out, uint32_t *tmp, uint32_t add, int inclusive) {
     const uint32_t nb = (uint32_t)((n + S32_B - 1) / S32_B);
     if (nb == 0) return CM_OK;
-    hipLaunchKernelGGL(k_scan32_a, dim3(nb), dim3(S32_T), 0, ctx->stream, in, n, out, tmp, add, inclusive);
-    hipLaunchKernelGGL(k_scan32_b, dim3(1), dim3(1024), 0, ctx->stream, tmp, nb);
-    hipLaunchKernelGGL(k_scan32_c, dim3(nb), dim3(S32_T), 0, ctx->stream, out, n, (const uint32_t *)tmp);
+    hipLaunchKernelGGL(k_scan32_a, dim3(nb), dim3(S32_T), 0, ctx->st.B, in, n, out, tmp, add, inclusive);
+    hipLaunchKernelGGL(k_scan32_b, dim3(1), dim3(1024), 0, ctx->st.B, tmp, nb);
+    hipLaunchKernelGGL(k_scan32_c, dim3(nb), dim3(S32_T), 0, ctx->st.B, out, n, (const uint32_t *)tmp);
     HIPCHK(ctx, hipGetLastError());
     return CM_OK;
 }
@@ -2552,8 +2572,8 @@ int cm_load_contig_raw(cm_ctx *ctx, int slot, const cm_index_raw *raw) {
         const size_t pad = cmc::CM_STAGE_PAD;
         HIPCHK(ctx, hipMalloc((void **)&g, (size_t)raw->ref_len + 2 * pad));
         s.idx_allocs.push_back(g);
-        HIPCHK(ctx, hipMemsetAsync(g, 0, (size_t)raw->ref_len + 2 * pad, ctx->stream));
-        HIPCHK(ctx, hipMemcpyAsync(g + pad, raw->genome, (size_t)raw->ref_len, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, hipMemsetAsync(g, 0, (size_t)raw->ref_len + 2 * pad, ctx->st.B));
+        HIPCHK(ctx, hipMemcpyAsync(g + pad, raw->genome, (size_t)raw->ref_len, hipMemcpyHostToDevice, ctx->st.B));
         s.X.genome = g + pad;
     }
     // temporaries: the table as in the file, the bucket list, the table offset of every bucket, scan block sums
@@ -2576,20 +2596,20 @@ int cm_load_contig_raw(cm_ctx *ctx, int slot, const cm_index_raw *raw) {
     tmp.push_back(d_bs);
     HIPCHK(ctx, hipMalloc((void **)&d_bad, sizeof(int)));
     tmp.push_back(d_bad);
-    HIPCHK(ctx, hipMemsetAsync(d_bad, 0, sizeof(int), ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(d_bad, 0, sizeof(int), ctx->st.B));
     HIPCHK(ctx, hipMalloc((void **)&d_off, (n_all + 1) * sizeof(uint32_t)));
     s.idx_allocs.push_back(d_off);
-    HIPCHK(ctx, hipMemsetAsync(d_off, 0, (n_all + 1) * sizeof(uint32_t), ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(d_off, 0, (n_all + 1) * sizeof(uint32_t), ctx->st.B));
     if ((rc = scan32(ctx, d_cnt, n_b, d_start, d_bs, 1u, 0))) return rc;                 // slot of every bucket's header
     if (n_b) {
-        hipLaunchKernelGGL(k_raw_counts, dim3((n_b + BLK - 1) / BLK), dim3(BLK), 0, ctx->stream, d_tab, (const uint32_t *)d_start, d_hv, d_cnt, n_b, n_all, d_off, d_bad);
+        hipLaunchKernelGGL(k_raw_counts, dim3((n_b + BLK - 1) / BLK), dim3(BLK), 0, ctx->st.B, d_tab, (const uint32_t *)d_start, d_hv, d_cnt, n_b, n_all, d_off, d_bad);
         HIPCHK(ctx, hipGetLastError());
     }
     if ((rc = scan32(ctx, d_off, n_all + 1, d_off, d_bs, 0u, 1))) return rc;             // counts -> bucket offsets, in place
     unsigned long long landing[2] = {0, 0};
-    HIPCHK(ctx, hipMemcpyAsync(&landing[0], d_off + n_all, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(&landing[1], d_bad, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(&landing[0], d_off + n_all, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->st.B));
+    HIPCHK(ctx, hipMemcpyAsync(&landing[1], d_bad, sizeof(int), hipMemcpyDeviceToHost, ctx->st.B));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->st.B));
     if ((int)landing[1]) return fail(ctx, CM_EINVAL, "malformed index table: a bucket header is out of range");
     const uint64_t total = (uint32_t)landing[0];
     uint16_t *d_cs = nullptr;
@@ -2599,7 +2619,7 @@ int cm_load_contig_raw(cm_ctx *ctx, int slot, const cm_index_raw *raw) {
     HIPCHK(ctx, hipMalloc((void **)&d_ps, (total ? total : 1) * sizeof(uint32_t)));
     s.idx_allocs.push_back(d_ps);
     if (n_b) {
-        hipLaunchKernelGGL(k_raw_scatter, dim3((n_b + BLK - 1) / BLK), dim3(BLK), 0, ctx->stream, d_tab, (const uint32_t *)d_start, d_hv, n_b, (const uint32_t *)d_off, d_cs, d_ps);
+        hipLaunchKernelGGL(k_raw_scatter, dim3((n_b + BLK - 1) / BLK), dim3(BLK), 0, ctx->st.B, d_tab, (const uint32_t *)d_start, d_hv, n_b, (const uint32_t *)d_off, d_cs, d_ps);
         HIPCHK(ctx, hipGetLastError());
     }
     s.X.bucket_off = d_off;
@@ -2609,7 +2629,7 @@ int cm_load_contig_raw(cm_ctx *ctx, int slot, const cm_index_raw *raw) {
     return finish_contig(ctx, s);       // (synchronises the stream: the temporaries may go)
 }
 
-// The ordering passes of cm_build_contig on ctx->stream; st_host receives the IB_ST_* words.  Temporaries go on `tmp`.
+// The ordering passes of cm_build_contig on ctx->st.B; st_host receives the IB_ST_* words.  Temporaries go on `tmp`.
 static int ib_order(cm_ctx *ctx, const uint32_t *d_off, uint16_t *d_cs, uint32_t *d_ps, uint64_t total, uint32_t *d_bs, std::vector<void *> &tmp,
                     unsigned long long st_host[IB_ST_WORDS], size_t *tmp_bytes) {
     const uint64_t n_all = (uint64_t)1 << (2 * CM_WINDOW_SIZE);
@@ -2626,14 +2646,14 @@ static int ib_order(cm_ctx *ctx, const uint32_t *d_off, uint16_t *d_cs, uint32_t
     HIPCHK(ctx, hipMalloc((void **)&d_over, over_cap * sizeof(uint32_t)));
     tmp.push_back(d_over);
     *tmp_bytes += (med_cap + over_cap) * sizeof(uint32_t);
-    HIPCHK(ctx, hipMemsetAsync(d_st, 0, IB_ST_WORDS * sizeof(unsigned long long), ctx->stream));
-    hipLaunchKernelGGL(k_ib_order_lane, dim3((unsigned)(n_all / BLK)), dim3(BLK), 0, ctx->stream, d_off, n_all, d_cs, d_ps, lane_max, wg_lim, d_med, d_over, d_st);
+    HIPCHK(ctx, hipMemsetAsync(d_st, 0, IB_ST_WORDS * sizeof(unsigned long long), ctx->st.B));
+    hipLaunchKernelGGL(k_ib_order_lane, dim3((unsigned)(n_all / BLK)), dim3(BLK), 0, ctx->st.B, d_off, n_all, d_cs, d_ps, lane_max, wg_lim, d_med, d_over, d_st);
     HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipMemcpyAsync(st_host, d_st, IB_ST_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(st_host, d_st, IB_ST_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->st.B));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->st.B));
     const uint32_t n_med = (uint32_t)st_host[IB_ST_NMED], n_over = (uint32_t)st_host[IB_ST_NOVER];
     if (n_med) {
-        hipLaunchKernelGGL(k_ib_order_wg, dim3(std::min<uint32_t>(n_med, 1u << 16)), dim3(BLK), 0, ctx->stream, d_off, (const uint32_t *)d_med, n_med, d_cs, d_ps);
+        hipLaunchKernelGGL(k_ib_order_wg, dim3(std::min<uint32_t>(n_med, 1u << 16)), dim3(BLK), 0, ctx->st.B, d_off, (const uint32_t *)d_med, n_med, d_cs, d_ps);
         HIPCHK(ctx, hipGetLastError());
     }
     if (!n_over) return CM_OK;
@@ -2641,13 +2661,13 @@ static int ib_order(cm_ctx *ctx, const uint32_t *d_off, uint16_t *d_cs, uint32_t
     uint32_t *d_start = nullptr;
     HIPCHK(ctx, hipMalloc((void **)&d_start, ((size_t)n_over + 1) * sizeof(uint32_t)));
     tmp.push_back(d_start);
-    HIPCHK(ctx, hipMemsetAsync(d_start + n_over, 0, sizeof(uint32_t), ctx->stream));
-    hipLaunchKernelGGL(k_ib_over_sizes, dim3((n_over + BLK - 1) / BLK), dim3(BLK), 0, ctx->stream, d_off, (const uint32_t *)d_over, n_over, d_start);
+    HIPCHK(ctx, hipMemsetAsync(d_start + n_over, 0, sizeof(uint32_t), ctx->st.B));
+    hipLaunchKernelGGL(k_ib_over_sizes, dim3((n_over + BLK - 1) / BLK), dim3(BLK), 0, ctx->st.B, d_off, (const uint32_t *)d_over, n_over, d_start);
     int rc;
     if ((rc = scan32(ctx, d_start, (uint64_t)n_over + 1, d_start, d_bs, 0u, 0))) return rc;          // exclusive, in place: start[n_over] = all oversize entries
     std::vector<uint32_t> start((size_t)n_over + 1);
-    HIPCHK(ctx, hipMemcpyAsync(start.data(), d_start, start.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(start.data(), d_start, start.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->st.B));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->st.B));
     auto rank_bits_of = [](uint32_t n_ranks) {
         unsigned b = 1;
         while ((1u << b) < n_ranks) ++b;
@@ -2660,7 +2680,7 @@ static int ib_order(cm_ctx *ctx, const uint32_t *d_off, uint16_t *d_cs, uint32_t
     for (uint32_t r0 = 0; r0 < n_over; r0 += cmib::OVER_CHUNK) {           // the largest chunk and the most sort workspace any chunk asks for
         const uint32_t r1 = std::min(n_over, r0 + cmib::OVER_CHUNK), m = start[r1] - start[r0];
         size_t need = 0;
-        HIPCHK(ctx, rocprim::radix_sort_keys(nullptr, need, d_k0, d_k1, (size_t)m, 0u, 48u + rank_bits_of(r1 - r0), ctx->stream));
+        HIPCHK(ctx, rocprim::radix_sort_keys(nullptr, need, d_k0, d_k1, (size_t)m, 0u, 48u + rank_bits_of(r1 - r0), ctx->st.B));
         largest = std::max(largest, m);
         sort_bytes = std::max(sort_bytes, need);
     }
@@ -2676,11 +2696,11 @@ static int ib_order(cm_ctx *ctx, const uint32_t *d_off, uint16_t *d_cs, uint32_t
         const unsigned rank_bits = rank_bits_of(r1 - r0);
         size_t have = sort_bytes;
         const dim3 grid(std::min<uint32_t>(r1 - r0, 1u << 16));
-        hipLaunchKernelGGL(k_ib_over_pack, grid, dim3(BLK), 0, ctx->stream, d_off, (const uint32_t *)d_over, (const uint32_t *)d_start, r0, r1, (const uint16_t *)d_cs,
+        hipLaunchKernelGGL(k_ib_over_pack, grid, dim3(BLK), 0, ctx->st.B, d_off, (const uint32_t *)d_over, (const uint32_t *)d_start, r0, r1, (const uint16_t *)d_cs,
                            (const uint32_t *)d_ps, d_k0);
         HIPCHK(ctx, hipGetLastError());
-        HIPCHK(ctx, rocprim::radix_sort_keys(d_sort, have, d_k0, d_k1, (size_t)m, 0u, 48u + rank_bits, ctx->stream));
-        hipLaunchKernelGGL(k_ib_over_unpack, grid, dim3(BLK), 0, ctx->stream, d_off, (const uint32_t *)d_over, (const uint32_t *)d_start, r0, r1, (const uint64_t *)d_k1,
+        HIPCHK(ctx, rocprim::radix_sort_keys(d_sort, have, d_k0, d_k1, (size_t)m, 0u, 48u + rank_bits, ctx->st.B));
+        hipLaunchKernelGGL(k_ib_over_unpack, grid, dim3(BLK), 0, ctx->st.B, d_off, (const uint32_t *)d_over, (const uint32_t *)d_start, r0, r1, (const uint64_t *)d_k1,
                            d_cs, d_ps);
         HIPCHK(ctx, hipGetLastError());
     }
@@ -2695,8 +2715,8 @@ static int build_contig_arrays(cm_ctx *ctx, Slot &s, const uint8_t *genome, uint
         const size_t pad = cmc::CM_STAGE_PAD;
         HIPCHK(ctx, hipMalloc((void **)&g, (size_t)ref_len + 2 * pad));
         s.idx_allocs.push_back(g);
-        HIPCHK(ctx, hipMemsetAsync(g, 0, (size_t)ref_len + 2 * pad, ctx->stream));
-        if (ref_len) HIPCHK(ctx, hipMemcpyAsync(g + pad, genome, (size_t)ref_len, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, hipMemsetAsync(g, 0, (size_t)ref_len + 2 * pad, ctx->st.B));
+        if (ref_len) HIPCHK(ctx, hipMemcpyAsync(g + pad, genome, (size_t)ref_len, hipMemcpyHostToDevice, ctx->st.B));
         s.X.genome = g + pad;
     }
     std::vector<void *> tmp;
@@ -2711,20 +2731,20 @@ static int build_contig_arrays(cm_ctx *ctx, Slot &s, const uint8_t *genome, uint
     tmp.push_back(d_bs);
     HIPCHK(ctx, hipMalloc((void **)&d_off, (n_all + 1) * sizeof(uint32_t)));
     s.idx_allocs.push_back(d_off);
-    HIPCHK(ctx, hipEventRecord(ev_a, ctx->stream));
-    HIPCHK(ctx, hipMemsetAsync(d_off, 0, (n_all + 1) * sizeof(uint32_t), ctx->stream));
+    HIPCHK(ctx, hipEventRecord(ev_a, ctx->st.B));
+    HIPCHK(ctx, hipMemsetAsync(d_off, 0, (n_all + 1) * sizeof(uint32_t), ctx->st.B));
     // the number of entries is at most ref_len - k + 1 < 2^32: the 32-bit counters and scans cannot overflow
     const uint32_t n_pos = ref_len >= (uint32_t)k ? ref_len - (uint32_t)k + 1u : 0u;
     const dim3 pgrid((unsigned)(((uint64_t)n_pos + IB_TILE - 1) / IB_TILE));
     if (n_pos) {
-        hipLaunchKernelGGL(k_ib_positions<false>, pgrid, dim3(BLK), 0, ctx->stream, s.X.genome, ref_len, n_pos, k, c, d_off, (uint16_t *)nullptr, (uint32_t *)nullptr);
+        hipLaunchKernelGGL(k_ib_positions<false>, pgrid, dim3(BLK), 0, ctx->st.B, s.X.genome, ref_len, n_pos, k, c, d_off, (uint16_t *)nullptr, (uint32_t *)nullptr);
         HIPCHK(ctx, hipGetLastError());
     }
     int rc;
     if ((rc = scan32(ctx, d_off, n_all + 1, d_off, d_bs, 0u, 1))) return rc;             // counts -> bucket ends, in place
     uint32_t total32 = 0;
-    HIPCHK(ctx, hipMemcpyAsync(&total32, d_off + n_all, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(&total32, d_off + n_all, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->st.B));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->st.B));
     const uint64_t total = total32;
     if (total > (uint64_t)n_pos) return fail(ctx, CM_ELIMIT, "%llu entries from %u k-mer starts", (unsigned long long)total, n_pos);
     uint16_t *d_cs = nullptr;
@@ -2735,11 +2755,11 @@ static int build_contig_arrays(cm_ctx *ctx, Slot &s, const uint8_t *genome, uint
     s.idx_allocs.push_back(d_ps);
     unsigned long long st[IB_ST_WORDS] = {0, 0, 0, 0, 0, 0};
     if (total) {
-        hipLaunchKernelGGL(k_ib_positions<true>, pgrid, dim3(BLK), 0, ctx->stream, s.X.genome, ref_len, n_pos, k, c, d_off, d_cs, d_ps);   // ends -> starts
+        hipLaunchKernelGGL(k_ib_positions<true>, pgrid, dim3(BLK), 0, ctx->st.B, s.X.genome, ref_len, n_pos, k, c, d_off, d_cs, d_ps);   // ends -> starts
         HIPCHK(ctx, hipGetLastError());
         if ((rc = ib_order(ctx, d_off, d_cs, d_ps, total, d_bs, tmp, st, &tmp_bytes))) return rc;
     }
-    HIPCHK(ctx, hipEventRecord(ev_b, ctx->stream));
+    HIPCHK(ctx, hipEventRecord(ev_b, ctx->st.B));
     s.X.bucket_off = d_off;
     s.X.checksum = d_cs;
     s.X.pos = d_ps;
@@ -2775,7 +2795,7 @@ int cm_build_contig(cm_ctx *ctx, int slot, int32_t contig_num, const uint8_t *ge
     if (!ev_a || !ev_b) return fail(ctx, CM_EHIP, "hipEventCreate failed");
     const int rc = build_contig_arrays(ctx, s, genome, ref_len, stats, ev_a, ev_b);
     if (rc != CM_OK) {                                   // the slot stays unloaded and owns nothing
-        (void)hipStreamSynchronize(ctx->stream);
+        (void)hipStreamSynchronize(ctx->st.B);
         (void)hipGetLastError();
         free_all(ctx, s.idx_allocs);
         s.d_desc = nullptr;
@@ -2798,10 +2818,10 @@ int cm_index_download(cm_ctx *ctx, int slot, uint32_t *bucket_off, uint16_t *che
     if ((checksum || pos) && cap_entries < n) return fail(ctx, CM_ELIMIT, "slot %d holds %llu entries, the buffers %llu", slot, (unsigned long long)n, (unsigned long long)cap_entries);
     HIPCHK(ctx, hipSetDevice(ctx->P.device));
     const size_t nb = ((size_t)1 << (2 * CM_WINDOW_SIZE)) + 1;
-    if (bucket_off) HIPCHK(ctx, hipMemcpyAsync(bucket_off, s.X.bucket_off, nb * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    if (checksum && n) HIPCHK(ctx, hipMemcpyAsync(checksum, s.X.checksum, (size_t)n * sizeof(uint16_t), hipMemcpyDeviceToHost, ctx->stream));
-    if (pos && n) HIPCHK(ctx, hipMemcpyAsync(pos, s.X.pos, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    if (bucket_off) HIPCHK(ctx, hipMemcpyAsync(bucket_off, s.X.bucket_off, nb * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->st.B));
+    if (checksum && n) HIPCHK(ctx, hipMemcpyAsync(checksum, s.X.checksum, (size_t)n * sizeof(uint16_t), hipMemcpyDeviceToHost, ctx->st.B));
+    if (pos && n) HIPCHK(ctx, hipMemcpyAsync(pos, s.X.pos, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->st.B));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->st.B));
     return CM_OK;
 }
 
@@ -2839,7 +2859,7 @@ int cm_load_annotation(cm_ctx *ctx, int slot, const cm_annot_view *av) {
         A.n_iv_bucket = av->n_iv_bucket;
     }
     // the staging copies are asynchronous: the host vectors must outlive them
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->st.B));
     {   // every window bound upper_bound() can return lies within maxIntronLen of the queried hit (k_chain_heavy)
         const long long mi = ctx->P.max_intron;
         bool ok = mi >= (long long)ctx->P.max_read_len + ctx->P.max_ed && mi < (1ll << 30);
@@ -2857,7 +2877,7 @@ int cm_load_annotation(cm_ctx *ctx, int slot, const cm_annot_view *av) {
 int cm_unload_contig(cm_ctx *ctx, int slot) {
     if (!ctx || slot < 0 || slot >= MAX_SLOTS) return CM_EINVAL;
     (void)hipSetDevice(ctx->P.device);
-    (void)hipStreamSynchronize(ctx->stream);
+    (void)hipStreamSynchronize(ctx->st.B);
     free_all(ctx, ctx->slots[slot].idx_allocs);
     free_all(ctx, ctx->slots[slot].ann_allocs);
     ctx->slots[slot].loaded = ctx->slots[slot].has_annot = false;
@@ -2947,49 +2967,38 @@ static int prepare_resident(cm_ctx *ctx, uint64_t n, int max_len) {
     const uint32_t tile = tile_for(n);
     ctx->tile = tile;
     const size_t nprob = (size_t)tile * 4, nprobe = nprob * (size_t)(ctx->n_seeds ? ctx->n_seeds : 1);
-    HIPCHK(ctx, ensure(ctx, ctx->d_sstart, nprobe * 4));
-    HIPCHK(ctx, ensure(ctx, ctx->d_scnt, nprobe * 4));
-    HIPCHK(ctx, ensure(ctx, ctx->d_sraw, nprobe * 4));
-    HIPCHK(ctx, ensure(ctx, ctx->d_cells, nprob * 4));
-    HIPCHK(ctx, ensure(ctx, ctx->d_celloff, (nprob + 2) * 8));
-    HIPCHK(ctx, ensure(ctx, ctx->d_bmax, (nprob / SCAN_ELEMS + 2) * 4));
-    HIPCHK(ctx, ensure(ctx, ctx->d_bsum, (nprob / SCAN_ELEMS + 2) * 8));
-    HIPCHK(ctx, ensure(ctx, ctx->d_sstart_b, nprobe * 4));
-    HIPCHK(ctx, ensure(ctx, ctx->d_scnt_b, nprobe * 4));
-    HIPCHK(ctx, ensure(ctx, ctx->d_sraw_b, nprobe * 4));
-    HIPCHK(ctx, ensure(ctx, ctx->d_celloff_b, (nprob + 2) * 8));
-    HIPCHK(ctx, ensure(ctx, ctx->d_bmax_b, (nprob / SCAN_ELEMS + 2) * 4));
-    HIPCHK(ctx, ensure(ctx, ctx->d_bsum_b, (nprob / SCAN_ELEMS + 2) * 8));
+    for (SeedSet &sd : ctx->seed) {
+        HIPCHK(ctx, ensure(ctx, sd.sstart, nprobe * 4));
+        HIPCHK(ctx, ensure(ctx, sd.scnt, nprobe * 4));
+        HIPCHK(ctx, ensure(ctx, sd.sraw, nprobe * 4));
+        HIPCHK(ctx, ensure(ctx, sd.celloff, (nprob + 2) * 8));
+        HIPCHK(ctx, ensure(ctx, sd.bmax, (nprob / SCAN_ELEMS + 2) * 4));
+        HIPCHK(ctx, ensure(ctx, sd.bsum, (nprob / SCAN_ELEMS + 2) * 8));
+        HIPCHK(ctx, ensure(ctx, sd.cctr, CTR_WORDS * sizeof(unsigned int)));
+        HIPCHK(ctx, ensure(ctx, sd.cblk, (size_t)N_CLS * (4 * (size_t)tile / CLS_T + 2) * sizeof(unsigned int)));
+        HIPCHK(ctx, ensure(ctx, sd.cls4, (size_t)tile * 4));
+        HIPCHK(ctx, ensure(ctx, sd.perm4, (size_t)tile * 4 * 4));
+        HIPCHK(ctx, ensure(ctx, sd.thigh, (size_t)tile * 4 * sizeof(int32_t)));
+    }
+    for (ChainRecs &cr : ctx->rec) {
+        HIPCHK(ctx, ensure(ctx, cr.chains, nprob * CM_BESTCHAINLIM * sizeof(cm_chain)));
+        HIPCHK(ctx, ensure(ctx, cr.nchain, nprob * 4));
+        HIPCHK(ctx, ensure(ctx, cr.high, nprob * 4));
+        HIPCHK(ctx, ensure(ctx, cr.resid, (size_t)tile * 4 * sizeof(uint16_t)));
+    }
     // DP cells: room for 64 cells per problem on average, at least 8M (one worst-case problem is
     // n_seeds * seed_lim cells); larger tiles are split into ranges by run_chain_tile.
     unsigned long long cap = (unsigned long long)nprob * 64ull;
     const unsigned long long worst = (unsigned long long)ctx->P.seed_lim * (unsigned long long)(ctx->n_seeds ? ctx->n_seeds : 1);
     if (cap < (8ull << 20)) cap = 8ull << 20;
     if (cap < worst) cap = worst;
-    if (cap > ctx->cells_cap || !ctx->d_dpscore) ctx->cells_cap = cap;        // grow-only, like the buffers behind it
-    HIPCHK(ctx, ensure(ctx, ctx->d_dpscore, ctx->cells_cap * sizeof(double)));
-    HIPCHK(ctx, ensure(ctx, ctx->d_dpprev, ctx->cells_cap * sizeof(int32_t)));
-    HIPCHK(ctx, ensure(ctx, ctx->d_chains, nprob * CM_BESTCHAINLIM * sizeof(cm_chain)));
-    HIPCHK(ctx, ensure(ctx, ctx->d_nchain, nprob * 4));
-    HIPCHK(ctx, ensure(ctx, ctx->d_high, nprob * 4));
-    HIPCHK(ctx, ensure(ctx, ctx->d_chains_b, nprob * CM_BESTCHAINLIM * sizeof(cm_chain)));
-    HIPCHK(ctx, ensure(ctx, ctx->d_nchain_b, nprob * 4));
-    HIPCHK(ctx, ensure(ctx, ctx->d_high_b, nprob * 4));
-    HIPCHK(ctx, ensure(ctx, ctx->d_resid_b, (size_t)tile * 4 * sizeof(uint16_t)));
-    HIPCHK(ctx, ensure(ctx, ctx->d_cctr, CTR_WORDS * sizeof(unsigned int)));
-    HIPCHK(ctx, ensure(ctx, ctx->d_cblk, (size_t)N_CLS * (4 * (size_t)tile / CLS_T + 2) * sizeof(unsigned int)));
-    HIPCHK(ctx, ensure(ctx, ctx->d_cls, (size_t)tile));
-    HIPCHK(ctx, ensure(ctx, ctx->d_cls4, (size_t)tile * 4));
-    HIPCHK(ctx, ensure(ctx, ctx->d_perm4, (size_t)tile * 4 * 4));
-    HIPCHK(ctx, ensure(ctx, ctx->d_cctr_b, CTR_WORDS * sizeof(unsigned int)));
-    HIPCHK(ctx, ensure(ctx, ctx->d_cblk_b, (size_t)N_CLS * (4 * (size_t)tile / CLS_T + 2) * sizeof(unsigned int)));
-    HIPCHK(ctx, ensure(ctx, ctx->d_cls4_b, (size_t)tile * 4));
-    HIPCHK(ctx, ensure(ctx, ctx->d_thigh, (size_t)tile * 4 * sizeof(int32_t)));
-    HIPCHK(ctx, ensure(ctx, ctx->d_thigh_b, (size_t)tile * 4 * sizeof(int32_t)));
-    HIPCHK(ctx, ensure(ctx, ctx->d_perm4_b, (size_t)tile * 4 * 4));
-    HIPCHK(ctx, ensure(ctx, ctx->d_resid, (size_t)tile * 4 * sizeof(uint16_t)));
-    HIPCHK(ctx, ensure(ctx, ctx->d_perm, (size_t)tile * 4 * 2));          // x 2: one per set of chain records, like the re-run list (run_pair_tile)
-    HIPCHK(ctx, ensure(ctx, ctx->d_hlist, (size_t)tile * 4 * 2));
+    if (cap > ctx->dp.cells_cap || !ctx->dp.score) ctx->dp.cells_cap = cap;        // grow-only, like the buffers behind it
+    HIPCHK(ctx, ensure(ctx, ctx->dp.score, ctx->dp.cells_cap * sizeof(double)));
+    HIPCHK(ctx, ensure(ctx, ctx->dp.prev, ctx->dp.cells_cap * sizeof(int32_t)));
+    HIPCHK(ctx, ensure(ctx, ctx->sort.cls, (size_t)tile));
+    PairSetMem &pm = ctx->pair_mem;           // x 2: one half per set of chain records (run_pair_tile)
+    HIPCHK(ctx, ensure(ctx, pm.perm, (size_t)tile * 4 * 2));
+    HIPCHK(ctx, ensure(ctx, pm.hlist, (size_t)tile * 4 * 2));
     HIPCHK(ctx, ensure(ctx, ctx->d_hres, (size_t)HEAVY_GRID_MAX * (64 * sizeof(HRes) + HEAVY_SCRATCH)));
     if (heavy_pipeline()) {
         // the pipeline's arrays: per heavy pair, per mate-pair task (~ 10 per heavy pair on the dense workload, room for 6 per pair of
@@ -2997,43 +3006,43 @@ static int prepare_resident(cm_ctx *ctx, uint64_t n, int max_len) {
         // (CM_HP_TASKS_CAP / CM_HP_UNP_CAP: test knobs, small capacities so that the fall-back path is taken)
         const size_t tc = getenv("CM_HP_TASKS_CAP") ? (size_t)std::max(1, atoi(getenv("CM_HP_TASKS_CAP"))) : std::max<size_t>((size_t)tile * 6, 4096);
         const size_t uc = getenv("CM_HP_UNP_CAP") ? (size_t)std::max(1, atoi(getenv("CM_HP_UNP_CAP"))) : std::max<size_t>((size_t)tile * 4, 4096);
-        ctx->hp_tasks_cap = (uint32_t)tc;
-        ctx->hp_unp_cap = (uint32_t)uc;
-        HIPCHK(ctx, ensure(ctx, ctx->d_hp, (size_t)tile * sizeof(HPair)));
-        HIPCHK(ctx, ensure(ctx, ctx->d_hp_list2, (size_t)tile * 4));
-        HIPCHK(ctx, ensure(ctx, ctx->d_hp_fall, (size_t)tile * 4 * 2));
-        HIPCHK(ctx, ensure(ctx, ctx->d_hp_fallctr, 2 * sizeof(unsigned int)));
-        HIPCHK(ctx, ensure(ctx, ctx->d_hp_T, tc * sizeof(HTask)));
-        HIPCHK(ctx, ensure(ctx, ctx->d_hp_tcls, tc));
-        HIPCHK(ctx, ensure(ctx, ctx->d_hp_tperm, tc * 4));
-        HIPCHK(ctx, ensure(ctx, ctx->d_hp_tblk, (size_t)N_CLS * (tc / CLS_T + 2) * sizeof(unsigned int)));
-        HIPCHK(ctx, ensure(ctx, ctx->d_hp_tctr, CTR_WORDS * sizeof(unsigned int)));
-        HIPCHK(ctx, ensure(ctx, ctx->d_hp_pre, tc * 4 * sizeof(cmc::PreDP)));
-        HIPCHK(ctx, ensure(ctx, ctx->d_hp_q, tc * 4 * 4));
-        HIPCHK(ctx, ensure(ctx, ctx->d_hp_res, tc * sizeof(HRes)));
-        HIPCHK(ctx, ensure(ctx, ctx->d_hp_U, uc * sizeof(HUnp)));
-        HIPCHK(ctx, ensure(ctx, ctx->d_hp_pre2, uc * 2 * sizeof(cmc::PreDP)));
-        HIPCHK(ctx, ensure(ctx, ctx->d_hp_q2, uc * 2 * 4));
-        HIPCHK(ctx, ensure(ctx, ctx->d_hp_lists, (size_t)HP_PLAN_GRID * HEAVY_LIST * 2));
-        HIPCHK(ctx, ensure(ctx, ctx->d_hp_ctr, HC_WORDS * sizeof(unsigned int)));
+        ctx->hp.tasks_cap = (uint32_t)tc;
+        ctx->hp.unp_cap = (uint32_t)uc;
+        HIPCHK(ctx, ensure(ctx, ctx->hp.pairs, (size_t)tile * sizeof(HPair)));
+        HIPCHK(ctx, ensure(ctx, ctx->hp.list2, (size_t)tile * 4));
+        HIPCHK(ctx, ensure(ctx, pm.hp_fall, (size_t)tile * 4 * 2));
+        HIPCHK(ctx, ensure(ctx, pm.hp_fallctr, 2 * sizeof(unsigned int)));
+        HIPCHK(ctx, ensure(ctx, ctx->hp.T, tc * sizeof(HTask)));
+        HIPCHK(ctx, ensure(ctx, ctx->hp.tcls, tc));
+        HIPCHK(ctx, ensure(ctx, ctx->hp.tperm, tc * 4));
+        HIPCHK(ctx, ensure(ctx, ctx->hp.tblk, (size_t)N_CLS * (tc / CLS_T + 2) * sizeof(unsigned int)));
+        HIPCHK(ctx, ensure(ctx, ctx->hp.tctr, CTR_WORDS * sizeof(unsigned int)));
+        HIPCHK(ctx, ensure(ctx, ctx->hp.pre, tc * 4 * sizeof(cmc::PreDP)));
+        HIPCHK(ctx, ensure(ctx, ctx->hp.q, tc * 4 * 4));
+        HIPCHK(ctx, ensure(ctx, ctx->hp.res, tc * sizeof(HRes)));
+        HIPCHK(ctx, ensure(ctx, ctx->hp.U, uc * sizeof(HUnp)));
+        HIPCHK(ctx, ensure(ctx, ctx->hp.pre2, uc * 2 * sizeof(cmc::PreDP)));
+        HIPCHK(ctx, ensure(ctx, ctx->hp.q2, uc * 2 * 4));
+        HIPCHK(ctx, ensure(ctx, ctx->hp.lists, (size_t)HP_PLAN_GRID * HEAVY_LIST * 2));
+        HIPCHK(ctx, ensure(ctx, ctx->hp.ctr, HC_WORDS * sizeof(unsigned int)));
     }
     {
-        const uint32_t *before = ctx->d_pair_err;
-        HIPCHK(ctx, ensure(ctx, ctx->d_pair_err, (size_t)tile * 4 * 2));      // one set per set of chain records (run_pair_tile)
-        if (ctx->d_pair_err != before) HIPCHK(ctx, hipMemsetAsync(ctx->d_pair_err, 0, (size_t)tile * 4 * 2, ctx->stream_p));   // the kernels keep it zero
+        const uint32_t *before = pm.pair_err;
+        HIPCHK(ctx, ensure(ctx, pm.pair_err, (size_t)tile * 4 * 2));      // one set per set of chain records (run_pair_tile)
+        if (pm.pair_err != before) HIPCHK(ctx, hipMemsetAsync(pm.pair_err, 0, (size_t)tile * 4 * 2, ctx->st.P));   // the kernels keep it zero
     }
-    HIPCHK(ctx, ensure(ctx, ctx->d_retry_list, (size_t)tile * 4 * 2));
-    HIPCHK(ctx, ensure(ctx, ctx->d_retry_ctr, 4 * sizeof(unsigned int)));
+    HIPCHK(ctx, ensure(ctx, pm.retry_list, (size_t)tile * 4 * 2));
+    HIPCHK(ctx, ensure(ctx, pm.retry_ctr, 4 * sizeof(unsigned int)));
     HIPCHK(ctx, ensure(ctx, ctx->d_heavy_load, sizeof(unsigned long long)));
     HIPCHK(ctx, ensure(ctx, ctx->d_spill, (size_t)RETRY_GRID * BLK_PAIR * RETRY_SPILL * sizeof(cmc::MemoSpill)));
-    HIPCHK(ctx, ensure(ctx, ctx->d_cls_ctr, 2 * CTR_WORDS * sizeof(unsigned int)));
-    HIPCHK(ctx, ensure(ctx, ctx->d_cls_ctr2, CTR_WORDS * sizeof(unsigned int)));
-    HIPCHK(ctx, ensure(ctx, ctx->d_cls_sub, (size_t)tile));
-    HIPCHK(ctx, ensure(ctx, ctx->d_perm1, (size_t)tile * 4));
-    HIPCHK(ctx, ensure(ctx, ctx->d_cls_ctr3, CTR_WORDS * sizeof(unsigned int)));
-    HIPCHK(ctx, ensure(ctx, ctx->d_cls_sub2, (size_t)tile));
-    HIPCHK(ctx, ensure(ctx, ctx->d_perm0, (size_t)tile * 4));
-    HIPCHK(ctx, ensure(ctx, ctx->d_blk_cnt, (size_t)N_CLS * (4 * (size_t)tile / CLS_T + 2) * sizeof(unsigned int)));
+    HIPCHK(ctx, ensure(ctx, pm.cls_ctr, 2 * CTR_WORDS * sizeof(unsigned int)));
+    HIPCHK(ctx, ensure(ctx, ctx->sort.ctr2, CTR_WORDS * sizeof(unsigned int)));
+    HIPCHK(ctx, ensure(ctx, ctx->sort.sub, (size_t)tile));
+    HIPCHK(ctx, ensure(ctx, ctx->sort.perm1, (size_t)tile * 4));
+    HIPCHK(ctx, ensure(ctx, ctx->sort.ctr3, CTR_WORDS * sizeof(unsigned int)));
+    HIPCHK(ctx, ensure(ctx, ctx->sort.sub2, (size_t)tile));
+    HIPCHK(ctx, ensure(ctx, ctx->sort.perm0, (size_t)tile * 4));
+    HIPCHK(ctx, ensure(ctx, ctx->sort.blk_cnt, (size_t)N_CLS * (4 * (size_t)tile / CLS_T + 2) * sizeof(unsigned int)));
     if (getenv("CM_LANE_CLK")) {
 #if defined(CM_DIAG)
         const size_t clk_words = 16 * 2 + 1;  // per-pair rows + wave-level rows of k_pair and k_pair_heavy (diag)
@@ -3041,46 +3050,52 @@ static int prepare_resident(cm_ctx *ctx, uint64_t n, int max_len) {
         const size_t clk_words = 1;
 #endif
         HIPCHK(ctx, ensure(ctx, ctx->d_lane_clk, n * 8 * clk_words));
-        HIPCHK(ctx, hipMemsetAsync(ctx->d_lane_clk, 0, n * 8 * clk_words, ctx->stream));
+        HIPCHK(ctx, hipMemsetAsync(ctx->d_lane_clk, 0, n * 8 * clk_words, ctx->st.B));
     }
     unsigned long long pool = (unsigned long long)nprob * 2048ull;       // improvement log
     if (pool < (256ull << 20)) pool = 256ull << 20;
     if (pool > (8ull << 30)) pool = 8ull << 30;
     if (const char *e = getenv("CM_POOL_BYTES")) {       // test knob: start with a small log pool to exercise the recovery path
         const unsigned long long v = strtoull(e, nullptr, 10);
-        if (v >= 4096 && !ctx->d_pool) pool = v;
+        if (v >= 4096 && !ctx->dp.pool) pool = v;
     }
-    if (pool > ctx->pool_bytes || !ctx->d_pool) ctx->pool_bytes = pool;
-    HIPCHK(ctx, ensure(ctx, ctx->d_pool, ctx->pool_bytes));
+    if (pool > ctx->dp.pool_bytes || !ctx->dp.pool) ctx->dp.pool_bytes = pool;
+    HIPCHK(ctx, ensure(ctx, ctx->dp.pool, ctx->dp.pool_bytes));
+    for (int b = 0; b < 2; ++b) {             // set b: the b-th half (the only place that cuts them)
+        const size_t at = (size_t)b * tile;
+        ctx->pset[b] = PairSet{pm.perm + at,       pm.hlist + at,      pm.cls_ctr + (size_t)b * CTR_WORDS,
+                               pm.pair_err + at,   pm.retry_list + at, pm.retry_ctr + 2 * b,       // [count, cursor]
+                               pm.hp_fall ? pm.hp_fall + at : nullptr, pm.hp_fallctr ? pm.hp_fallctr + b : nullptr};
+    }
     return CM_OK;
 }
 
 // Copies of one batch into (grow-only) read buffers on stream `st`: only the CM_STAGE_PAD slack around the reads is
 // cleared (cmc::stage over-reads into it), the reads themselves are overwritten by the copy.
-static int copy_reads(cm_ctx *ctx, const cm_reads *rd, hipStream_t st, uint8_t *&seq1_base, uint8_t *&seq2_base, uint64_t *&off1, uint64_t *&off2) {
+static int copy_reads(cm_ctx *ctx, const cm_reads *rd, hipStream_t st, ReadBufs &to) {
     const uint64_t n = rd->n_pairs;
     const size_t b1 = (size_t)rd->off1[n] - (size_t)rd->off1[0], b2 = (size_t)rd->off2[n] - (size_t)rd->off2[0];
     if (rd->off1[0] != 0 || rd->off2[0] != 0) return fail(ctx, CM_EINVAL, "read offsets must start at 0");
     const size_t pad = cmc::CM_STAGE_PAD;                  // readable slack around the reads (see cmc::stage)
-    HIPCHK(ctx, ensure(ctx, seq1_base, b1 + 2 * pad));
-    HIPCHK(ctx, ensure(ctx, seq2_base, b2 + 2 * pad));
-    HIPCHK(ctx, ensure(ctx, off1, (n + 1) * sizeof(uint64_t)));
-    HIPCHK(ctx, ensure(ctx, off2, (n + 1) * sizeof(uint64_t)));
-    HIPCHK(ctx, hipMemsetAsync(seq1_base, 0, pad, st));
-    HIPCHK(ctx, hipMemsetAsync(seq1_base + pad + b1, 0, pad, st));
-    HIPCHK(ctx, hipMemsetAsync(seq2_base, 0, pad, st));
-    HIPCHK(ctx, hipMemsetAsync(seq2_base + pad + b2, 0, pad, st));
-    if (b1) HIPCHK(ctx, hipMemcpyAsync(seq1_base + pad, rd->seq1, b1, hipMemcpyHostToDevice, st));
-    if (b2) HIPCHK(ctx, hipMemcpyAsync(seq2_base + pad, rd->seq2, b2, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemcpyAsync(off1, rd->off1, (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemcpyAsync(off2, rd->off2, (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, ensure(ctx, to.seq1_base, b1 + 2 * pad));
+    HIPCHK(ctx, ensure(ctx, to.seq2_base, b2 + 2 * pad));
+    HIPCHK(ctx, ensure(ctx, to.off1, (n + 1) * sizeof(uint64_t)));
+    HIPCHK(ctx, ensure(ctx, to.off2, (n + 1) * sizeof(uint64_t)));
+    HIPCHK(ctx, hipMemsetAsync(to.seq1_base, 0, pad, st));
+    HIPCHK(ctx, hipMemsetAsync(to.seq1_base + pad + b1, 0, pad, st));
+    HIPCHK(ctx, hipMemsetAsync(to.seq2_base, 0, pad, st));
+    HIPCHK(ctx, hipMemsetAsync(to.seq2_base + pad + b2, 0, pad, st));
+    if (b1) HIPCHK(ctx, hipMemcpyAsync(to.seq1_base + pad, rd->seq1, b1, hipMemcpyHostToDevice, st));
+    if (b2) HIPCHK(ctx, hipMemcpyAsync(to.seq2_base + pad, rd->seq2, b2, hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, hipMemcpyAsync(to.off1, rd->off1, (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, hipMemcpyAsync(to.off2, rd->off2, (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
     return CM_OK;
 }
 
 int cm_reads_upload(cm_ctx *ctx, const cm_reads *rd, const cm_mapped_read *prior) {
     if (!ctx || !rd) return CM_EINVAL;
     HIPCHK(ctx, hipSetDevice(ctx->P.device));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->st.B));
     const uint64_t n = rd->n_pairs;
     ctx->pre_ready = false;                        // a prefetched first round belonged to a batch that came in through cm_reads_swap
     ctx->n_pairs = 0;
@@ -3092,20 +3107,18 @@ int cm_reads_upload(cm_ctx *ctx, const cm_reads *rd, const cm_mapped_read *prior
     int max_len = 0;
     int rc = check_reads(ctx, rd, &max_len);
     if (rc) return rc;
-    if ((rc = copy_reads(ctx, rd, ctx->stream, ctx->d_seq1_base, ctx->d_seq2_base, ctx->d_off1, ctx->d_off2))) return rc;
-    ctx->d_seq1 = ctx->d_seq1_base + cmc::CM_STAGE_PAD;
-    ctx->d_seq2 = ctx->d_seq2_base + cmc::CM_STAGE_PAD;
+    if ((rc = copy_reads(ctx, rd, ctx->st.B, ctx->rd))) return rc;
     if ((rc = prepare_resident(ctx, n, max_len))) return rc;
     ctx->n_pairs = n;
     KCore k{};
     k.P = ctx->P;
-    hipLaunchKernelGGL(k_init_state, dim3((unsigned)((n + BLK - 1) / BLK)), dim3(BLK), 0, ctx->stream, k, ctx->d_state, ctx->d_active, ctx->d_cat, n);
+    hipLaunchKernelGGL(k_init_state, dim3((unsigned)((n + BLK - 1) / BLK)), dim3(BLK), 0, ctx->st.B, k, ctx->d_state, ctx->d_active, ctx->d_cat, n);
     if (prior) {
         // carried state of an earlier round: a pair is active unless the caller marks it retired
         // by type < 0 (never produced by this library); active flags are otherwise all 1.
-        HIPCHK(ctx, hipMemcpyAsync(ctx->d_state, prior, n * sizeof(cm_mapped_read), hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(ctx->d_state, prior, n * sizeof(cm_mapped_read), hipMemcpyHostToDevice, ctx->st.B));
     }
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->st.B));
     return CM_OK;
 }
 
@@ -3114,27 +3127,18 @@ int cm_reads_stage(cm_ctx *ctx, const cm_reads *rd, const cm_mapped_read *prior)
     HIPCHK(ctx, hipSetDevice(ctx->P.device));
     if (rd->n_pairs == 0) return fail(ctx, CM_EINVAL, "cm_reads_stage: empty batch");
     int max_len = 0;
-    static const bool trace = getenv("CM_STAGE_TRACE") != nullptr;          // diagnostic: host time of the three parts
-    const auto t0 = std::chrono::steady_clock::now();
     int rc = check_reads(ctx, rd, &max_len);
     if (rc) return rc;
-    const auto t1 = std::chrono::steady_clock::now();
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream_copy));          // an earlier staged batch that was never swapped in is dropped
-    const auto t2 = std::chrono::steady_clock::now();
+    HIPCHK(ctx, hipStreamSynchronize(ctx->st.C));          // an earlier staged batch that was never swapped in is dropped
     ctx->staged = false;
     ctx->pre_launched = false;
-    if ((rc = copy_reads(ctx, rd, ctx->stream_copy, ctx->st_seq1_base, ctx->st_seq2_base, ctx->st_off1, ctx->st_off2))) return rc;
-    if (trace) {
-        const auto t3 = std::chrono::steady_clock::now();
-        auto ms = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
-        fprintf(stderr, "cm_reads_stage: check %.3f ms, wait for the copy stream %.3f ms, copies issued %.3f ms\n", ms(t0, t1), ms(t1, t2), ms(t2, t3));
-    }
+    if ((rc = copy_reads(ctx, rd, ctx->st.C, ctx->st_rd))) return rc;
     ctx->st_has_prior = prior != nullptr;
     if (prior) {
         HIPCHK(ctx, ensure(ctx, ctx->st_prior, rd->n_pairs * sizeof(cm_mapped_read)));
-        HIPCHK(ctx, hipMemcpyAsync(ctx->st_prior, prior, rd->n_pairs * sizeof(cm_mapped_read), hipMemcpyHostToDevice, ctx->stream_copy));
+        HIPCHK(ctx, hipMemcpyAsync(ctx->st_prior, prior, rd->n_pairs * sizeof(cm_mapped_read), hipMemcpyHostToDevice, ctx->st.C));
     }
-    HIPCHK(ctx, hipEventRecord(ctx->ev_staged, ctx->stream_copy));
+    HIPCHK(ctx, hipEventRecord(ctx->ev.staged, ctx->st.C));
     ctx->st_n_pairs = rd->n_pairs;
     ctx->st_max_len = max_len;
     ctx->staged = true;
@@ -3147,16 +3151,7 @@ int cm_reads_swap(cm_ctx *ctx) {
     if (!ctx->staged) return fail(ctx, CM_ESTATE, "cm_reads_swap: no staged batch");
     // work already queued on the mapping stream still reads the old buffers: order the swap behind it on the device
     // (no host wait), and the new batch's first kernel behind the staged copies
-    std::swap(ctx->d_seq1_base, ctx->st_seq1_base);
-    std::swap(ctx->d_seq2_base, ctx->st_seq2_base);
-    std::swap(ctx->d_off1, ctx->st_off1);
-    std::swap(ctx->d_off2, ctx->st_off2);
-    std::swap(ctx->caps[(const void *)&ctx->d_seq1_base], ctx->caps[(const void *)&ctx->st_seq1_base]);
-    std::swap(ctx->caps[(const void *)&ctx->d_seq2_base], ctx->caps[(const void *)&ctx->st_seq2_base]);
-    std::swap(ctx->caps[(const void *)&ctx->d_off1], ctx->caps[(const void *)&ctx->st_off1]);
-    std::swap(ctx->caps[(const void *)&ctx->d_off2], ctx->caps[(const void *)&ctx->st_off2]);
-    ctx->d_seq1 = ctx->d_seq1_base + cmc::CM_STAGE_PAD;
-    ctx->d_seq2 = ctx->d_seq2_base + cmc::CM_STAGE_PAD;
+    swap(ctx->rd, ctx->st_rd);
     ctx->staged = false;
     const uint64_t n = ctx->st_n_pairs;
     ctx->pre_ready = ctx->pre_launched;                            // cm_map_rounds prepared this batch's first round already
@@ -3166,33 +3161,32 @@ int cm_reads_swap(cm_ctx *ctx) {
     int rc = prepare_resident(ctx, n, ctx->st_max_len);
     if (rc) return rc;
     ctx->n_pairs = n;
-    HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_staged, 0));
+    HIPCHK(ctx, hipStreamWaitEvent(ctx->st.B, ctx->ev.staged, 0));
     KCore k{};
     k.P = ctx->P;
-    hipLaunchKernelGGL(k_init_state, dim3((unsigned)((n + BLK - 1) / BLK)), dim3(BLK), 0, ctx->stream, k, ctx->d_state, ctx->d_active, ctx->d_cat, n);
+    hipLaunchKernelGGL(k_init_state, dim3((unsigned)((n + BLK - 1) / BLK)), dim3(BLK), 0, ctx->st.B, k, ctx->d_state, ctx->d_active, ctx->d_cat, n);
     if (ctx->st_has_prior)
-        HIPCHK(ctx, hipMemcpyAsync(ctx->d_state, ctx->st_prior, n * sizeof(cm_mapped_read), hipMemcpyDeviceToDevice, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(ctx->d_state, ctx->st_prior, n * sizeof(cm_mapped_read), hipMemcpyDeviceToDevice, ctx->st.B));
     // the next cm_reads_stage overwrites the buffers this swap retired: it must wait for the mapping stream's work on them
-    HIPCHK(ctx, hipEventRecord(ctx->ev_retired, ctx->stream));
-    HIPCHK(ctx, hipStreamWaitEvent(ctx->stream_copy, ctx->ev_retired, 0));
+    HIPCHK(ctx, hipEventRecord(ctx->ev.retired, ctx->st.B));
+    HIPCHK(ctx, hipStreamWaitEvent(ctx->st.C, ctx->ev.retired, 0));
     HIPCHK(ctx, hipGetLastError());
     return CM_OK;
 }
 
-// The re-run launch of a pair stage and ev_pair[b] behind it.  Eight blocks that each ask for 47 - 64 KB of LDS behind kernels that
+// The re-run launch of a pair stage and ev.pair[b] behind it.  Eight blocks that each ask for 47 - 64 KB of LDS behind kernels that
 // fill the chip wait milliseconds for their turn -- on the hg38-like bench until the heavy chaining kernel of the NEXT item had
 // drained, and the item after that (its seeding reads the flags, its chaining rewrites the chain records) behind them -- to find,
 // nearly always, an empty list.  So with several tiles the decision is made late (`defer`): the pair stage copies the length of
 // its re-run list to the host, and whoever first needs the stage to be complete calls settle_pair, which waits for the two pair
-// kernels (ev_first[b]), launches the re-run only if something is queued, and records ev_pair[b].
+// kernels (ev.first[b]), launches the re-run only if something is queued, and records ev.pair[b].
 static int launch_rerun(cm_ctx *ctx, int b) {
     const cm_ctx::Rerun &q = ctx->rerun[b];
-    static const bool no_rerun = getenv("CM_NO_RERUN") != nullptr;      // diagnostic: what the launch costs (a queued pair would stay unmapped)
-    if (no_rerun) return CM_OK;
-    const RetryArgs ra2{q.pair_err, q.retry_list, q.retry_ctr, ctx->d_spill, RETRY_SPILL, 0};
-    hipLaunchKernelGGL(k_pair_rerun, dim3(RETRY_GRID), dim3(BLK_PAIR), q.lds2, ctx->stream_p3, q.core, q.rd, q.p0, q.nt, q.chains, q.nchain, q.high,
+    const PairSet &ps = ctx->pset[b];
+    const RetryArgs ra2{ps.pair_err, ps.retry_list, ps.retry_ctr, ctx->d_spill, RETRY_SPILL, 0};
+    hipLaunchKernelGGL(k_pair_rerun, dim3(RETRY_GRID), dim3(BLK_PAIR), q.lds2, ctx->st.R, q.core, q.rd, q.p0, q.nt, q.chains, q.nchain, q.high,
                        ctx->d_state, q.act_out, ctx->d_cat, q.is_last, ctx->d_err, ctx->d_counters, q.cap2, (unsigned long long *)nullptr,
-                       (const uint32_t *)q.retry_list, (const unsigned int *)q.retry_ctr, q.retry_ctr + 1, ra2);
+                       (const uint32_t *)ps.retry_list, (const unsigned int *)ps.retry_ctr, ps.retry_ctr + 1, ra2);
     HIPCHK(ctx, hipGetLastError());
     return CM_OK;
 }
@@ -3201,10 +3195,11 @@ static int launch_rerun(cm_ctx *ctx, int b) {
 // of the next item at the end of every pair stage: decided late like the re-run, from the list length the stage copied to the host.
 static int launch_fall_back(cm_ctx *ctx, int b, hipStream_t st) {
     const cm_ctx::Rerun &q = ctx->rerun[b];
-    const RetryArgs ra1{q.pair_err, q.retry_list, q.retry_ctr, nullptr, 0, 1};
-    hipLaunchKernelGGL(k_pair_heavy, dim3(q.fall_grid), dim3(BLK_PAIR), q.lds_heavy, st, q.core, q.rd, q.p0, q.fall_list, (const unsigned int *)q.fall_ctr, q.chains,
+    const PairSet &ps = ctx->pset[b];
+    const RetryArgs ra1{ps.pair_err, ps.retry_list, ps.retry_ctr, nullptr, 0, 1};
+    hipLaunchKernelGGL(k_pair_heavy, dim3(q.fall_grid), dim3(BLK_PAIR), q.lds_heavy, st, q.core, q.rd, q.p0, (const uint32_t *)ps.hp_fall, (const unsigned int *)ps.hp_fallctr, q.chains,
                        q.nchain, q.high, ctx->d_state, q.act_out, ctx->d_cat, q.is_last, ctx->d_err, ctx->d_counters, q.str_cap, (unsigned long long *)nullptr,
-                       ctx->d_hres, q.fall_cursor, ra1);
+                       ctx->d_hres, ps.cls_ctr + CTR_NEXT + 1, ra1);
     HIPCHK(ctx, hipGetLastError());
     ++ctx->launches[4];
     return CM_OK;
@@ -3213,11 +3208,11 @@ static int launch_fall_back(cm_ctx *ctx, int b, hipStream_t st) {
 static int settle_pair(cm_ctx *ctx, int b, bool wait = true) {
     if (!ctx->rerun[b].deferred) return CM_OK;
     ctx->rerun[b].deferred = false;
-    if (wait) HIPCHK(ctx, hipEventSynchronize(ctx->ev_first[b]));
-    HIPCHK(ctx, hipStreamWaitEvent(ctx->stream_p3, ctx->ev_first[b], 0));
+    if (wait) HIPCHK(ctx, hipEventSynchronize(ctx->ev.first[b]));
+    HIPCHK(ctx, hipStreamWaitEvent(ctx->st.R, ctx->ev.first[b], 0));
     bool fell = false;
     if (ctx->rerun[b].fall && (!wait || *(const volatile unsigned int *)(ctx->h_pin + 14 + b) != 0u)) {
-        const int rc = launch_fall_back(ctx, b, ctx->stream_p3);        // (may queue pairs for the re-run: that one unconditionally then)
+        const int rc = launch_fall_back(ctx, b, ctx->st.R);        // (may queue pairs for the re-run: that one unconditionally then)
         if (rc) return rc;
         fell = true;
     }
@@ -3225,18 +3220,18 @@ static int settle_pair(cm_ctx *ctx, int b, bool wait = true) {
         const int rc = launch_rerun(ctx, b);
         if (rc) return rc;
     }
-    HIPCHK(ctx, hipEventRecord(ctx->ev_pair[b], ctx->stream_p3));
+    HIPCHK(ctx, hipEventRecord(ctx->ev.pair[b], ctx->st.R));
     return CM_OK;
 }
 
-// The pair stage of one tile and round on the pair streams: waits for that item's chains (ev_prep[b]), reads the flags
-// act_in, writes act_out for every pair of the tile, signals ev_pair[b] when the chain buffers of set b are free again.
-// same_tile_as_prev: the previous item was this tile's previous round -- its re-run launch (stream p3) wrote states and flags this
-// item's pair kernels read; every other consumer is ordered behind the re-run through ev_pair[].
+// The pair stage of one tile and round on the pair streams: waits for that item's chains (ev.prep[b]), reads the flags
+// act_in, writes act_out for every pair of the tile, signals ev.pair[b] when the chain buffers of set b are free again.
+// same_tile_as_prev: the previous item was this tile's previous round -- its re-run launch (stream R) wrote states and flags this
+// item's pair kernels read; every other consumer is ordered behind the re-run through ev.pair[].
 static int run_pair_tile(cm_ctx *ctx, const KCore &core, uint64_t p0, uint32_t nt, int is_last_round, const uint8_t *act_in, uint8_t *act_out,
-                         const RoundBufs &rb, int b, bool same_tile_as_prev, bool defer) {
-    const ReadsDev rd{ctx->d_seq1, ctx->d_seq2, ctx->d_off1, ctx->d_off2};
-    hipStream_t sp = ctx->stream_p, sp2 = ctx->stream_p2, sp3 = ctx->stream_p3;
+                         const ChainRecs &rb, int b, bool same_tile_as_prev, bool defer) {
+    const ReadsDev rd = current_reads(ctx);
+    hipStream_t sp = ctx->st.P, sp2 = ctx->st.P2, sp3 = ctx->st.R;
     {
         int rc;
         if ((rc = settle_pair(ctx, b))) return rc;                       // this set's previous stage (its re-run list is about to be reused)
@@ -3246,31 +3241,23 @@ static int run_pair_tile(cm_ctx *ctx, const KCore &core, uint64_t p0, uint32_t n
     // kernels read from them existing once per set of chain records -- they are computed while the pair stage of the item before
     // still runs, as soon as this item's chains are complete; behind that stage on the pair stream they were 1.7 ms per item with
     // nothing else on the chip but the next item's seeding (12 % of the hg38-like step).
-    hipStream_t so = ctx->stream_o;
-    HIPCHK(ctx, hipStreamWaitEvent(so, ctx->ev_prep[b], 0));
-    if (same_tile_as_prev && ctx->pair_pending[b ^ 1]) HIPCHK(ctx, hipStreamWaitEvent(so, ctx->ev_pair[b ^ 1], 0));
-    uint32_t *const perm = ctx->d_perm + (size_t)b * ctx->tile, *const hlist = ctx->d_hlist + (size_t)b * ctx->tile;
-    unsigned int *const cls_ctr = ctx->d_cls_ctr + (size_t)b * CTR_WORDS;
-    // (the re-run list, its counters and the per-pair flags exist once per set of chain records, like those: item i + 1 leaves
-    // item i's alone, item i + 2 starts after ev_pair[b])
-    uint32_t *pair_err = ctx->d_pair_err + (size_t)b * ctx->tile, *retry_list = ctx->d_retry_list + (size_t)b * ctx->tile;
-    unsigned int *retry_ctr = ctx->d_retry_ctr + 2 * b;
+    hipStream_t so = ctx->st.O;
+    HIPCHK(ctx, hipStreamWaitEvent(so, ctx->ev.prep[b], 0));
+    if (same_tile_as_prev && ctx->pair_pending[b ^ 1]) HIPCHK(ctx, hipStreamWaitEvent(so, ctx->ev.pair[b ^ 1], 0));
+    const PairSet &ps = ctx->pset[b];
+    uint32_t *const perm = ps.perm, *const hlist = ps.hlist, *const pair_err = ps.pair_err;
+    unsigned int *const cls_ctr = ps.cls_ctr, *const retry_ctr = ps.retry_ctr;
     // str_cap: chars per staged string (multiple of 8); LDS = 2 strings x lbuf_bytes(str_cap) x 64 lanes
     // a DP string is at most a read minus one seed, plus the band (extend_side: len + band; dp_fits() reports anything longer)
-    // (+ 4 characters of slack: 144 characters = 76-byte rows for 2 x 150 bp at k = 20.  CM_PAIR_LDS_SLACK=0 gives 72-byte rows and
-    // takes k_pair_heavy's LDS per wave from 12 to 11 allocation steps of 1 280 bytes: its kernel time -4 %, the step +1 %: NOTES 44)
-    static const int str_slack = getenv("CM_PAIR_LDS_SLACK") ? atoi(getenv("CM_PAIR_LDS_SLACK")) : 4;
+    // (+ 4 characters of slack: 144 characters = 76-byte rows for 2 x 150 bp at k = 20.  No slack gives 72-byte rows and takes
+    // k_pair_heavy's LDS per wave from 12 to 11 allocation steps of 1 280 bytes: its kernel time -4 %, the step +1 %: NOTES 44)
+    constexpr int str_slack = 4;
     const int str_cap = ((ctx->max_len - ctx->P.kmer + ctx->P.band + str_slack + 7) / 8) * 8;
     // The pair kernels' time hardly depends on their occupancy (16.0 / 16.2 / 16.4 ms per step at 4 / 3 / 2 waves per SIMD on the
-    // hg38-like bench; 22 ms at 1).  CM_PAIR_OCC = 1..3 pads their LDS request to hold them at that many waves per SIMD, which
-    // leaves registers and wave slots to the seeding / chaining of the next round; measured best overall: no padding (4).
-    static const int pair_waves = getenv("CM_PAIR_OCC") ? atoi(getenv("CM_PAIR_OCC")) : 4;
-    const size_t lds_need = (size_t)2 * lbuf_bytes(str_cap) * BLK_PAIR;
-    size_t lds_bytes = lds_need;
-    if (pair_waves >= 1 && pair_waves <= 3) {
-        const size_t want = ((size_t)160 * 1024 / (size_t)(4 * pair_waves)) - HG * sizeof(HSlot) - 256;      // heavy adds its slots; keep clear of the next step
-        if (want > lds_bytes && want <= 60 * 1024) lds_bytes = want;
-    }
+    // hg38-like bench; 22 ms at 1).  Padding their LDS request to hold them at 1..3 waves per SIMD would leave registers and wave
+    // slots to the seeding / chaining of the next round; measured best overall: no padding (4 waves per SIMD).
+    constexpr unsigned slots_per_simd = 4;
+    const size_t lds_bytes = (size_t)2 * lbuf_bytes(str_cap) * BLK_PAIR;
     const size_t lds_heavy = lds_bytes + HG * sizeof(HSlot);
     // the re-run launch of k_pair (RetryArgs): staging buffers for strings of any length a read of this batch can produce
     const int cap2 = std::min(((2 * ctx->max_len + 64 + 7) / 8) * 8, 1016);      // 1016: 64 KB of LDS per wave
@@ -3299,117 +3286,109 @@ static int run_pair_tile(cm_ctx *ctx, const KCore &core, uint64_t p0, uint32_t n
             HIPCHK(ctx, hipMemcpyAsync((void *)(ctx->h_pin + 4), load, sizeof(unsigned long long), hipMemcpyDeviceToHost, so));
             ctx->h_pin_nt = nt;
         }
-        hipLaunchKernelGGL(k_pair_cls, dim3((nt + BLK - 1) / BLK), dim3(BLK), 0, so, core, rb.chains, rb.resid, rb.nchain, act_in, p0, nt, ctx->d_cls,
-                           ctx->d_cat, heavy_cost, ctx->d_cls_sub, ctx->d_cls_sub2, act_out, (const unsigned long long *)load);
+        hipLaunchKernelGGL(k_pair_cls, dim3((nt + BLK - 1) / BLK), dim3(BLK), 0, so, core, rb.chains, rb.resid, rb.nchain, act_in, p0, nt, ctx->sort.cls,
+                           ctx->d_cat, heavy_cost, ctx->sort.sub, ctx->sort.sub2, act_out, (const unsigned long long *)load);
         // three-pass LSD radix sort, 16 x 16 x 16 classes: by the longest residual, by the set of extensions a pair needs,
         // then (stable) by its class
         const uint32_t *no_order = nullptr;
         const unsigned int *no_count = nullptr;
-        hipLaunchKernelGGL(k_cls_hist, dim3(nbk), dim3(CLS_W), 0, so, ctx->d_cls_sub2, nt, ctx->d_blk_cnt, nbk, no_order, no_count);
-        hipLaunchKernelGGL(k_cls_scan, dim3(1), dim3(SCAN_CLS_T), 0, so, ctx->d_blk_cnt, nbk, ctx->d_cls_ctr3, -1, N_CLS);
-        hipLaunchKernelGGL(k_cls_place, dim3(nbk), dim3(CLS_W), 0, so, ctx->d_cls_sub2, nt, ctx->d_blk_cnt, nbk, ctx->d_cls_ctr3, ctx->d_perm0,
+        hipLaunchKernelGGL(k_cls_hist, dim3(nbk), dim3(CLS_W), 0, so, ctx->sort.sub2, nt, ctx->sort.blk_cnt, nbk, no_order, no_count);
+        hipLaunchKernelGGL(k_cls_scan, dim3(1), dim3(SCAN_CLS_T), 0, so, ctx->sort.blk_cnt, nbk, ctx->sort.ctr3, -1, N_CLS);
+        hipLaunchKernelGGL(k_cls_place, dim3(nbk), dim3(CLS_W), 0, so, ctx->sort.sub2, nt, ctx->sort.blk_cnt, nbk, ctx->sort.ctr3, ctx->sort.perm0,
                            (uint32_t *)nullptr, no_order, no_count);
-        hipLaunchKernelGGL(k_cls_hist, dim3(nbk), dim3(CLS_W), 0, so, ctx->d_cls_sub, nt, ctx->d_blk_cnt, nbk, (const uint32_t *)ctx->d_perm0,
-                           (const unsigned int *)(ctx->d_cls_ctr3 + CTR_SUM));
-        hipLaunchKernelGGL(k_cls_scan, dim3(1), dim3(SCAN_CLS_T), 0, so, ctx->d_blk_cnt, nbk, ctx->d_cls_ctr2, -1, N_CLS);
-        hipLaunchKernelGGL(k_cls_place, dim3(nbk), dim3(CLS_W), 0, so, ctx->d_cls_sub, nt, ctx->d_blk_cnt, nbk, ctx->d_cls_ctr2, ctx->d_perm1,
-                           (uint32_t *)nullptr, (const uint32_t *)ctx->d_perm0, (const unsigned int *)(ctx->d_cls_ctr3 + CTR_SUM));
-        hipLaunchKernelGGL(k_cls_hist, dim3(nbk), dim3(CLS_W), 0, so, ctx->d_cls, nt, ctx->d_blk_cnt, nbk, (const uint32_t *)ctx->d_perm1,
-                           (const unsigned int *)(ctx->d_cls_ctr2 + CTR_SUM));
-        hipLaunchKernelGGL(k_cls_scan, dim3(1), dim3(SCAN_CLS_T), 0, so, ctx->d_blk_cnt, nbk, cls_ctr, 1 << HEAVY_CLS, N_CLS);
-        hipLaunchKernelGGL(k_cls_place, dim3(nbk), dim3(CLS_W), 0, so, ctx->d_cls, nt, ctx->d_blk_cnt, nbk, cls_ctr, perm,
-                           hlist, (const uint32_t *)ctx->d_perm1, (const unsigned int *)(ctx->d_cls_ctr2 + CTR_SUM));
+        hipLaunchKernelGGL(k_cls_hist, dim3(nbk), dim3(CLS_W), 0, so, ctx->sort.sub, nt, ctx->sort.blk_cnt, nbk, (const uint32_t *)ctx->sort.perm0,
+                           (const unsigned int *)(ctx->sort.ctr3 + CTR_SUM));
+        hipLaunchKernelGGL(k_cls_scan, dim3(1), dim3(SCAN_CLS_T), 0, so, ctx->sort.blk_cnt, nbk, ctx->sort.ctr2, -1, N_CLS);
+        hipLaunchKernelGGL(k_cls_place, dim3(nbk), dim3(CLS_W), 0, so, ctx->sort.sub, nt, ctx->sort.blk_cnt, nbk, ctx->sort.ctr2, ctx->sort.perm1,
+                           (uint32_t *)nullptr, (const uint32_t *)ctx->sort.perm0, (const unsigned int *)(ctx->sort.ctr3 + CTR_SUM));
+        hipLaunchKernelGGL(k_cls_hist, dim3(nbk), dim3(CLS_W), 0, so, ctx->sort.cls, nt, ctx->sort.blk_cnt, nbk, (const uint32_t *)ctx->sort.perm1,
+                           (const unsigned int *)(ctx->sort.ctr2 + CTR_SUM));
+        hipLaunchKernelGGL(k_cls_scan, dim3(1), dim3(SCAN_CLS_T), 0, so, ctx->sort.blk_cnt, nbk, cls_ctr, 1 << HEAVY_CLS, N_CLS);
+        hipLaunchKernelGGL(k_cls_place, dim3(nbk), dim3(CLS_W), 0, so, ctx->sort.cls, nt, ctx->sort.blk_cnt, nbk, cls_ctr, perm,
+                           hlist, (const uint32_t *)ctx->sort.perm1, (const unsigned int *)(ctx->sort.ctr2 + CTR_SUM));
         ctx->launches[5] += 10;
     }
     HIPCHK(ctx, hipMemsetAsync(cls_ctr + CTR_NEXT, 0, 2 * sizeof(unsigned int), so));     // both work cursors
     HIPCHK(ctx, hipMemsetAsync(retry_ctr, 0, 2 * sizeof(unsigned int), so));                     // re-run count + cursor of this set
-    HIPCHK(ctx, hipEventRecord(ctx->ev_order[b], so));
-    HIPCHK(ctx, hipStreamWaitEvent(sp, ctx->ev_prep[b], 0));
-    HIPCHK(ctx, hipStreamWaitEvent(sp, ctx->ev_order[b], 0));
-    const RetryArgs ra1{pair_err, retry_list, retry_ctr, nullptr, 0, 1};
+    HIPCHK(ctx, hipEventRecord(ctx->ev.order[b], so));
+    HIPCHK(ctx, hipStreamWaitEvent(sp, ctx->ev.prep[b], 0));
+    HIPCHK(ctx, hipStreamWaitEvent(sp, ctx->ev.order[b], 0));
+    const RetryArgs ra1{pair_err, ps.retry_list, retry_ctr, nullptr, 0, 1};
     {   // what the late launches of this stage need (settle_pair: the re-run, the pipeline's fall-back)
         cm_ctx::Rerun &q = ctx->rerun[b];
         q.core = core; q.rd = rd; q.p0 = p0; q.nt = nt;
         q.chains = rb.chains; q.nchain = rb.nchain; q.high = rb.high;
         q.act_out = act_out; q.is_last = is_last_round; q.cap2 = cap2; q.lds2 = lds2;
-        q.pair_err = pair_err; q.retry_list = retry_list; q.retry_ctr = retry_ctr;
         q.fall = false;
     }
     // The heavy pairs go to a second stream: their kernels fit into the slots the light kernel leaves instead of queueing behind it.
     // That stream waits for this item's chains and lists itself, not for the light stream (which sits at the lowest priority, behind the
     // light kernel of the item before): what the heavy kernels share with the previous stage's light kernel exists once per set (re-run
-    // list, cursors) or per tile (states, flags: another tile's, or ordered behind ev_pair through the ordering stream).
-    HIPCHK(ctx, hipStreamWaitEvent(sp2, ctx->ev_prep[b], 0));
-    HIPCHK(ctx, hipStreamWaitEvent(sp2, ctx->ev_order[b], 0));
+    // list, cursors) or per tile (states, flags: another tile's, or ordered behind ev.pair through the ordering stream).
+    HIPCHK(ctx, hipStreamWaitEvent(sp2, ctx->ev.prep[b], 0));
+    HIPCHK(ctx, hipStreamWaitEvent(sp2, ctx->ev.order[b], 0));
     {
         Timer t(ctx, 4, sp2);
-        // both pair kernels are persistent: together they fill `pair_waves` wave slots per SIMD (256 CUs x 4 SIMDs), half each
-        static const unsigned slots_per_simd = (pair_waves >= 1 && pair_waves <= 3) ? (unsigned)pair_waves : 4u;
+        // both pair kernels are persistent: together they fill the wave slots of every SIMD (256 CUs x 4 SIMDs), half each
         const unsigned cap = 256u * 4u * slots_per_simd;
         // Heavy grid: half the wave capacity, or all of it when the tiles of this run carry a large heavy load (the value
         // k_pair_cost left for an earlier item, read without waiting): on the dense genome the heavy kernel has work for every
         // slot (19.9 vs 18.9 M pairs/s); with little heavy work the extra waves only sit on registers the next item's chain
         // stage is waiting for (round-2 genome: 43.3 vs 44.4 M pairs/s).
-        static const unsigned heavy_div_env = getenv("CM_HEAVY_DIV") ? (unsigned)atoi(getenv("CM_HEAVY_DIV")) : 0u;      // tuning knob
         const volatile unsigned long long *seen = (const volatile unsigned long long *)(ctx->h_pin + 4);
         const bool loaded_run = ctx->h_pin_nt && *seen > HEAVY_LOAD * (unsigned long long)ctx->h_pin_nt;
-        const unsigned heavy_div = heavy_div_env ? heavy_div_env : (loaded_run ? 1u : 2u);
-        const unsigned heavy_cap = cap / heavy_div;
-        static const unsigned heavy_fix = getenv("CM_HEAVY_GRID") ? (unsigned)atoi(getenv("CM_HEAVY_GRID")) : 0u;    // tuning knob
-        const unsigned heavy_lim = std::min(heavy_fix ? heavy_fix : heavy_cap, HEAVY_GRID_MAX);     // d_hres is sized for HEAVY_GRID_MAX blocks
+        const unsigned heavy_cap = cap / (loaded_run ? 1u : 2u);
+        const unsigned heavy_lim = std::min(heavy_cap, HEAVY_GRID_MAX);     // d_hres is sized for HEAVY_GRID_MAX blocks
         const unsigned heavy_grid = nt < heavy_lim ? (nt ? nt : 1u) : heavy_lim;
         if (heavy_pipeline() && ctx->P.band == 3) {
             // the heavy pairs as a pipeline of full-width kernels (cm_heavy_pipe.h); what does not fit its arrays comes back in a
             // fall-back list and goes through k_pair_heavy behind it
-            const HPipe hp{ctx->d_hp, ctx->d_hp_list2, ctx->d_hp_fall + (size_t)b * ctx->tile, ctx->d_hp_T, ctx->d_hp_pre, ctx->d_hp_q, ctx->d_hp_res, ctx->d_hp_U, ctx->d_hp_pre2,
-                           ctx->d_hp_q2, ctx->d_hp_ctr, ctx->hp_tasks_cap, ctx->hp_unp_cap, ctx->d_hp_fallctr + b, ctx->d_hp_tcls};
-            const unsigned int *n_heavy = cls_ctr + HEAVY_CLS, *n_list2 = ctx->d_hp_ctr + HC_LIST2;
-            static const unsigned pipe_grid = getenv("CM_HP_GRID") ? (unsigned)atoi(getenv("CM_HP_GRID")) : 2048u;        // tuning knob: workgroups of the item kernels
+            const HPipe hp{ctx->hp.pairs, ctx->hp.list2, ps.hp_fall, ctx->hp.T, ctx->hp.pre, ctx->hp.q, ctx->hp.res, ctx->hp.U, ctx->hp.pre2,
+                           ctx->hp.q2, ctx->hp.ctr, ctx->hp.tasks_cap, ctx->hp.unp_cap, ps.hp_fallctr, ctx->hp.tcls};
+            const unsigned int *n_heavy = cls_ctr + HEAVY_CLS, *n_list2 = ctx->hp.ctr + HC_LIST2;
+            constexpr unsigned pipe_grid = 2048u;        // workgroups of the item kernels
             const size_t lds_slots = HG * sizeof(HSlot);
-            HIPCHK(ctx, hipMemsetAsync(ctx->d_hp_ctr, 0, HC_WORDS * sizeof(unsigned int), sp2));
-            HIPCHK(ctx, hipMemsetAsync(ctx->d_hp_fallctr + b, 0, sizeof(unsigned int), sp2));
+            HIPCHK(ctx, hipMemsetAsync(ctx->hp.ctr, 0, HC_WORDS * sizeof(unsigned int), sp2));
+            HIPCHK(ctx, hipMemsetAsync(ps.hp_fallctr, 0, sizeof(unsigned int), sp2));
             // Two passes (process_read's two attempts), the second over the few pairs whose other orientation has chains at all (k_hp_finish
             // settles the others in place).  CM_HP_ATTEMPTS=1 (diagnostic) sends those pairs whole to the fall-back kernel instead: its
             // long tail over a few hundred heavy pairs costs more than nine short launches (77.9 vs 75.9 ms per step).
             static const bool task_order = !(getenv("CM_HP_TASK_ORDER") && getenv("CM_HP_TASK_ORDER")[0] == '0');      // diagnostic: tasks in array order
             static const int n_attempts = (getenv("CM_HP_ATTEMPTS") && atoi(getenv("CM_HP_ATTEMPTS")) == 1) ? 1 : 2;
             for (int attempt = 0; attempt < n_attempts; ++attempt) {
-                if (attempt) hipLaunchKernelGGL(k_hp_reset, dim3(1), dim3(64), 0, sp2, ctx->d_hp_ctr);
+                if (attempt) hipLaunchKernelGGL(k_hp_reset, dim3(1), dim3(64), 0, sp2, ctx->hp.ctr);
                 hipLaunchKernelGGL(k_hp_plan, dim3(HP_PLAN_GRID), dim3(BLK_PAIR), lds_slots, sp2, core, rd, p0, (const uint32_t *)hlist, n_heavy,
-                                   (const uint32_t *)ctx->d_hp_list2, n_list2, attempt, (const cm_chain *)rb.chains, (const int32_t *)rb.nchain,
-                                   (const int32_t *)rb.high, (const cm_mapped_read *)ctx->d_state, hp, ctx->d_hp_lists, str_cap, ctx->d_counters);
+                                   (const uint32_t *)ctx->hp.list2, n_list2, attempt, (const cm_chain *)rb.chains, (const int32_t *)rb.nchain,
+                                   (const int32_t *)rb.high, (const cm_mapped_read *)ctx->d_state, hp, ctx->hp.lists, str_cap, ctx->d_counters);
                 hipLaunchKernelGGL(k_hp_dp, dim3(pipe_grid), dim3(BLK_PAIR), lds_bytes, sp2, core, rd, p0, attempt, hp, 0, str_cap);
                 if (task_order && attempt == 0) {       // (the second attempt's handful: array order) the tasks by work class, heaviest first (16-class counting sort over the tile's task array)
-                    const uint32_t nbt = (ctx->hp_tasks_cap + CLS_T - 1) / CLS_T;
-                    const unsigned int *n_t = ctx->d_hp_ctr + HC_TASKS;
+                    const uint32_t nbt = (ctx->hp.tasks_cap + CLS_T - 1) / CLS_T;
+                    const unsigned int *n_t = ctx->hp.ctr + HC_TASKS;
                     const uint32_t gt = std::min<uint32_t>(nbt, 2048u);        // (the count is on the device: a grid that walks the stretches in use)
-                    hipLaunchKernelGGL(k_cls_hist, dim3(gt), dim3(CLS_W), 0, sp2, (const int8_t *)ctx->d_hp_tcls, ctx->hp_tasks_cap, ctx->d_hp_tblk, nbt,
+                    hipLaunchKernelGGL(k_cls_hist, dim3(gt), dim3(CLS_W), 0, sp2, (const int8_t *)ctx->hp.tcls, ctx->hp.tasks_cap, ctx->hp.tblk, nbt,
                                        (const uint32_t *)nullptr, n_t);
-                    hipLaunchKernelGGL(k_cls_scan, dim3(1), dim3(SCAN_CLS_T), 0, sp2, ctx->d_hp_tblk, nbt, ctx->d_hp_tctr, -1, N_CLS, n_t);
-                    hipLaunchKernelGGL(k_cls_place, dim3(gt), dim3(CLS_W), 0, sp2, (const int8_t *)ctx->d_hp_tcls, ctx->hp_tasks_cap, ctx->d_hp_tblk, nbt,
-                                       ctx->d_hp_tctr, ctx->d_hp_tperm, (uint32_t *)nullptr, (const uint32_t *)nullptr, n_t);
+                    hipLaunchKernelGGL(k_cls_scan, dim3(1), dim3(SCAN_CLS_T), 0, sp2, ctx->hp.tblk, nbt, ctx->hp.tctr, -1, N_CLS, n_t);
+                    hipLaunchKernelGGL(k_cls_place, dim3(gt), dim3(CLS_W), 0, sp2, (const int8_t *)ctx->hp.tcls, ctx->hp.tasks_cap, ctx->hp.tblk, nbt,
+                                       ctx->hp.tctr, ctx->hp.tperm, (uint32_t *)nullptr, (const uint32_t *)nullptr, n_t);
                 }
                 hipLaunchKernelGGL(k_hp_tasks, dim3(pipe_grid), dim3(BLK_PAIR), lds_bytes, sp2, core, rd, p0, attempt, (const cm_chain *)rb.chains,
-                                   (const int32_t *)rb.nchain, hp, pair_err, str_cap, (task_order && attempt == 0) ? (const uint32_t *)ctx->d_hp_tperm : (const uint32_t *)nullptr,
-                                   (const unsigned int *)(ctx->d_hp_tctr + CTR_SUM));
-                hipLaunchKernelGGL(k_hp_fold, dim3(pipe_grid), dim3(BLK_PAIR), 0, sp2, core, p0, (const uint32_t *)ctx->d_hp_list2, n_list2, n_heavy, attempt, hp,
+                                   (const int32_t *)rb.nchain, hp, pair_err, str_cap, (task_order && attempt == 0) ? (const uint32_t *)ctx->hp.tperm : (const uint32_t *)nullptr,
+                                   (const unsigned int *)(ctx->hp.tctr + CTR_SUM));
+                hipLaunchKernelGGL(k_hp_fold, dim3(pipe_grid), dim3(BLK_PAIR), 0, sp2, core, p0, (const uint32_t *)ctx->hp.list2, n_list2, n_heavy, attempt, hp,
                                    ctx->d_counters);
                 hipLaunchKernelGGL(k_hp_unp_req, dim3(pipe_grid), dim3(BLK_PAIR), 0, sp2, core, rd, p0, attempt, (const cm_chain *)rb.chains, hp, str_cap);
                 hipLaunchKernelGGL(k_hp_dp, dim3(pipe_grid), dim3(BLK_PAIR), lds_bytes, sp2, core, rd, p0, attempt, hp, 1, str_cap);
                 hipLaunchKernelGGL(k_hp_unp, dim3(pipe_grid), dim3(BLK_PAIR), lds_bytes, sp2, core, rd, p0, attempt, (const cm_chain *)rb.chains, hp, pair_err,
                                    str_cap);
-                hipLaunchKernelGGL(k_hp_finish, dim3(pipe_grid), dim3(BLK_PAIR), 0, sp2, core, p0, (const uint32_t *)ctx->d_hp_list2, n_list2, n_heavy, attempt, hp,
+                hipLaunchKernelGGL(k_hp_finish, dim3(pipe_grid), dim3(BLK_PAIR), 0, sp2, core, p0, (const uint32_t *)ctx->hp.list2, n_list2, n_heavy, attempt, hp,
                                    ctx->d_state, act_out, ctx->d_cat, is_last_round, ctx->d_counters, ra1, (const int32_t *)rb.nchain, n_attempts == 1 ? 1 : 0);
             }
             // what did not fit goes through k_pair_heavy: now (one tile), or when the stage is settled and the list is known to hold something
             // (its own work cursor, cls_ctr + CTR_NEXT + 1, was zeroed with the light kernel's)
-            HIPCHK(ctx, hipMemcpyAsync((void *)(ctx->h_pin + 14 + b), ctx->d_hp_fallctr + b, sizeof(unsigned int), hipMemcpyDeviceToHost, sp2));
+            HIPCHK(ctx, hipMemcpyAsync((void *)(ctx->h_pin + 14 + b), ps.hp_fallctr, sizeof(unsigned int), hipMemcpyDeviceToHost, sp2));
             {
                 cm_ctx::Rerun &q = ctx->rerun[b];
                 q.fall = true;
-                q.fall_list = ctx->d_hp_fall + (size_t)b * ctx->tile;
-                q.fall_ctr = ctx->d_hp_fallctr + b;
-                q.fall_cursor = cls_ctr + CTR_NEXT + 1;
                 q.lds_heavy = lds_heavy;
                 q.str_cap = str_cap;
                 q.fall_grid = std::min(heavy_grid, 256u);
@@ -3428,33 +3407,30 @@ static int run_pair_tile(cm_ctx *ctx, const KCore &core, uint64_t p0, uint32_t n
         ++ctx->launches[4];
         }
     }
-    HIPCHK(ctx, hipEventRecord(ctx->ev_join_p, sp2));
+    HIPCHK(ctx, hipEventRecord(ctx->ev.join_p, sp2));
     {
         Timer t(ctx, 2, sp);      // = the pair stage: the light kernel and the wait for the second stream
-        static const unsigned slots_per_simd = (pair_waves >= 1 && pair_waves <= 3) ? (unsigned)pair_waves : 4u;
-        static const unsigned light_fix = getenv("CM_PAIR_GRID") ? (unsigned)atoi(getenv("CM_PAIR_GRID")) : 0u;       // tuning knob
-        const unsigned want = (nt + BLK_PAIR - 1) / BLK_PAIR, cap = light_fix ? light_fix
-                                                                          : (heavy_pipeline() && ctx->P.band == 3 && slots_per_simd == 4u) ? 2048u      // the pipeline's kernels come and go: half the slots (78.7 -> 76.3 ms per step)
-                                                                                                                                        : 256u * 4u * slots_per_simd;   // light takes the slots heavy leaves: full cap
+        const unsigned want = (nt + BLK_PAIR - 1) / BLK_PAIR, cap = (heavy_pipeline() && ctx->P.band == 3) ? 2048u      // the pipeline's kernels come and go: half the slots (78.7 -> 76.3 ms per step)
+                                                                                                           : 256u * 4u * slots_per_simd;   // light takes the slots heavy leaves: full cap
         hipLaunchKernelGGL(k_pair, dim3(want < cap ? want : cap), dim3(BLK_PAIR), lds_bytes, sp, core, rd, p0, nt, rb.chains, rb.nchain, rb.high,
                            ctx->d_state, act_out, ctx->d_cat, is_last_round, ctx->d_err, ctx->d_counters, str_cap, ctx->d_lane_clk, perm,
                            cls_ctr + CTR_SUM, cls_ctr + CTR_NEXT, ra1);
-        HIPCHK(ctx, hipStreamWaitEvent(sp, ctx->ev_join_p, 0));
+        HIPCHK(ctx, hipStreamWaitEvent(sp, ctx->ev.join_p, 0));
         ++ctx->launches[2];
     }
     // The re-run of whatever the two kernels queued (usually nothing: the launch reads the count on the device and ends): the same
     // code over the re-run list, one pair per lane, memo spill area, staging buffers for strings of any length a read of this
     // batch can produce.  On a stream of its own: a launch of 8 blocks behind kernels that fill the chip can wait milliseconds
     // for its turn (2.5 ms on average on the hg38-like bench), and only the consumers of this item's results have to wait for
-    // it -- ev_pair[b] (chain records of set b free, flags and states of the tile final) is recorded behind it.
+    // it -- ev.pair[b] (chain records of set b free, flags and states of the tile final) is recorded behind it.
     HIPCHK(ctx, hipMemcpyAsync((void *)(ctx->h_pin + 12 + b), retry_ctr, sizeof(unsigned int), hipMemcpyDeviceToHost, sp));
-    HIPCHK(ctx, hipEventRecord(ctx->ev_first[b], sp));
+    HIPCHK(ctx, hipEventRecord(ctx->ev.first[b], sp));
     ctx->rerun[b].deferred = defer;
     if (!defer) {
-        HIPCHK(ctx, hipStreamWaitEvent(sp3, ctx->ev_first[b], 0));
+        HIPCHK(ctx, hipStreamWaitEvent(sp3, ctx->ev.first[b], 0));
         int rc;
         if ((rc = launch_rerun(ctx, b))) return rc;
-        HIPCHK(ctx, hipEventRecord(ctx->ev_pair[b], sp3));
+        HIPCHK(ctx, hipEventRecord(ctx->ev.pair[b], sp3));
     }
     ctx->pair_pending[b] = true;
     HIPCHK(ctx, hipGetLastError());
@@ -3467,19 +3443,18 @@ static int map_rounds_issue(cm_ctx *ctx, const int *slots, int n_rounds, int las
     int rc;
     // Cross-batch prefetch (see the end of this function): possible when this call ends the batch and the next one is staged and fits
     // the workspace as it is sized now (nothing may be reallocated under the kernels in flight).
-    static const bool prefetch_on = !(getenv("CM_PREFETCH") && getenv("CM_PREFETCH")[0] == '0');
-    const bool prefetch = prefetch_on && last_is_final && ctx->staged && ctx->st_n_pairs <= ctx->n_pairs && ctx->st_max_len <= ctx->max_len;
+    const bool prefetch = last_is_final && ctx->staged && ctx->st_n_pairs <= ctx->n_pairs && ctx->st_max_len <= ctx->max_len;
     if (prefetch && ctx->ones_cap < ctx->st_n_pairs) {          // flags of a fresh batch: every pair active
         HIPCHK(ctx, ensure(ctx, ctx->d_ones, ctx->n_pairs));
-        HIPCHK(ctx, hipMemsetAsync(ctx->d_ones, 1, ctx->n_pairs, ctx->stream));
+        HIPCHK(ctx, hipMemsetAsync(ctx->d_ones, 1, ctx->n_pairs, ctx->st.B));
         ctx->ones_cap = ctx->n_pairs;
     }
     // everything queued on the main stream so far (uploads, resets, collects of the previous batch) comes first
-    HIPCHK(ctx, hipEventRecord(ctx->ev_tail, ctx->stream));
-    HIPCHK(ctx, hipStreamWaitEvent(ctx->stream_p, ctx->ev_tail, 0));
-    HIPCHK(ctx, hipStreamWaitEvent(ctx->stream_s, ctx->ev_tail, 0));
-    HIPCHK(ctx, hipStreamWaitEvent(ctx->stream_o, ctx->ev_tail, 0));
-    HIPCHK(ctx, hipEventRecord(ctx->ev_flags, ctx->stream));
+    HIPCHK(ctx, hipEventRecord(ctx->ev.tail, ctx->st.B));
+    HIPCHK(ctx, hipStreamWaitEvent(ctx->st.P, ctx->ev.tail, 0));
+    HIPCHK(ctx, hipStreamWaitEvent(ctx->st.S, ctx->ev.tail, 0));
+    HIPCHK(ctx, hipStreamWaitEvent(ctx->st.O, ctx->ev.tail, 0));
+    HIPCHK(ctx, hipEventRecord(ctx->ev.flags, ctx->st.B));
     uint8_t *A[2] = {ctx->d_active, ctx->d_active_b};      // A[0] = flags before the first of these rounds
     // The work items: (tile, round).  One tile per batch: its rounds in order.  Several tiles: ROUND-major -- every tile through
     // round r, then every tile through round r + 1 -- so that between the pair stage of (tile, r) and the seeding of (tile, r + 1)
@@ -3489,8 +3464,7 @@ static int map_rounds_issue(cm_ctx *ctx, const int *slots, int n_rounds, int las
     struct Item { uint64_t p0; uint32_t nt; int r; };
     std::vector<Item> items;
     const uint64_t n_tiles = (ctx->n_pairs + ctx->tile - 1) / ctx->tile;
-    static const bool tile_major_env = getenv("CM_TILE_MAJOR") && getenv("CM_TILE_MAJOR")[0] == '1';      // diagnostic: the round-2 order
-    const bool round_major = n_tiles >= 2 && !tile_major_env;
+    const bool round_major = n_tiles >= 2;
     auto tile_nt = [&](uint64_t t) { return (uint32_t)((ctx->n_pairs - t * ctx->tile < ctx->tile) ? ctx->n_pairs - t * ctx->tile : ctx->tile); };
     if (round_major) {
         for (int r = 0; r < n_rounds; ++r)
@@ -3518,10 +3492,9 @@ static int map_rounds_issue(cm_ctx *ctx, const int *slots, int n_rounds, int las
     // Seeding runs one item ahead of chaining.  The chain stage of an item ends with a long tail of a few heavy problems, one
     // wave each, and the host waits for it (the pair stage must not start on truncated improvement logs); seeding of the next
     // item used to start after that wait, with the chip nearly idle through the tail and the next chain stage waiting for the
-    // seeds.  Now seeding of item i + 1 is issued (stream_s, seed set (i + 1) & 1) as soon as the chain kernels of item i are
+    // seeds.  Now seeding of item i + 1 is issued (stream S, seed set (i + 1) & 1) as soon as the chain kernels of item i are
     // launched: it needs the flags of the pair stage of item i - 1 (two tiles; earlier with more), which ends during that chain
     // stage, so the seeds are computed under the tail and the next chain stage starts right behind this one.
-    static const bool seed_ahead = !(getenv("CM_SEED_AHEAD") && getenv("CM_SEED_AHEAD")[0] == '0');       // diagnostic: the round-3a order
     std::vector<char> seeded((size_t)n_items, 0);
     bool pre_seeded = false;
     // With three or more tiles the flags item i + 1 reads were written by the pair stage of item i - 2 or earlier, complete before the
@@ -3531,16 +3504,16 @@ static int map_rounds_issue(cm_ctx *ctx, const int *slots, int n_rounds, int las
     // Two tiles: the flags are the ones the pair kernels of item i - 1 write, and the host cannot issue anything when those end -- it
     // sits in the wait for the chain stage of item i, which ends later: the seeding of item i + 1 started when THAT was over, and the
     // chip idled for 5 - 6 ms of every 22-ms item with nothing but the tail of k_chain_heavy on it.  The seeds are queued on the device
-    // behind ev_first of that pair stage instead (its kernels and the heavy pairs' pipeline; a pair left to a late launch -- re-run,
+    // behind ev.first of that pair stage instead (its kernels and the heavy pairs' pipeline; a pair left to a late launch -- re-run,
     // fall-back -- counts as active until that launch writes its flag, a superset, and the classes below use the final flags).
-    const bool early_ok = round_major && n_tiles >= 2 && !(getenv("CM_SEED_EARLY") && getenv("CM_SEED_EARLY")[0] == '0');
+    const bool early_ok = round_major;
     auto issue_seed_early = [&](int i) -> int {
-        HIPCHK(ctx, hipStreamWaitEvent(ctx->stream_s, ctx->ev_flags, 0));
-        if (n_tiles == 2 && i >= 2) HIPCHK(ctx, hipStreamWaitEvent(ctx->stream_s, ctx->ev_first[(ctx->item_base + i) & 1], 0));
+        HIPCHK(ctx, hipStreamWaitEvent(ctx->st.S, ctx->ev.flags, 0));
+        if (n_tiles == 2 && i >= 2) HIPCHK(ctx, hipStreamWaitEvent(ctx->st.S, ctx->ev.first[(ctx->item_base + i) & 1], 0));
         // the whole seed stage: the classes too, into scratch of the seed set (the chain records they belong in are still being read;
         // run_chain_tile carries them over).  Under superset flags a pair the late launches retire gets chains nobody looks at.
-        const RoundBufs rbe = round_bufs(ctx, (ctx->item_base + i) & 1);
-        const int e = run_seed_tile(ctx, make_core(ctx, ctx->slots[slots[items[i].r]]), rd_cur, items[i].p0, items[i].nt, prep_flags(i), i & 1, ctx->stream_s, &rbe, true);
+        const ChainRecs &rbe = ctx->rec[(ctx->item_base + i) & 1];
+        const int e = run_seed_tile(ctx, make_core(ctx, ctx->slots[slots[items[i].r]]), rd_cur, items[i].p0, items[i].nt, prep_flags(i), i & 1, ctx->st.S, &rbe, true);
         seeded[(size_t)i] = 1;
         return e;
     };
@@ -3550,8 +3523,8 @@ static int map_rounds_issue(cm_ctx *ctx, const int *slots, int n_rounds, int las
         // stream queues the same wait before the chain stage and clears the mark
         int e;
         if ((e = settle_pair(ctx, b))) return e;
-        if (ctx->pair_pending[b]) HIPCHK(ctx, hipStreamWaitEvent(st, ctx->ev_pair[b], 0));
-        const RoundBufs rbi = round_bufs(ctx, b);
+        if (ctx->pair_pending[b]) HIPCHK(ctx, hipStreamWaitEvent(st, ctx->ev.pair[b], 0));
+        const ChainRecs &rbi = ctx->rec[b];
         e = run_seed_tile(ctx, make_core(ctx, ctx->slots[slots[items[i].r]]), rd_cur, items[i].p0, items[i].nt, prep_flags(i), i & 1, st, &rbi);
         seeded[(size_t)i] = 1;
         return e;
@@ -3562,54 +3535,47 @@ static int map_rounds_issue(cm_ctx *ctx, const int *slots, int n_rounds, int las
         const int r = items[i].r, b = (ctx->item_base + i) & 1;
         const Slot &sl = ctx->slots[slots[r]];
         const KCore core = make_core(ctx, sl);
-        const RoundBufs rb = round_bufs(ctx, b);
+        const ChainRecs &rb = ctx->rec[b];
         const uint8_t *act_prep = prep_flags(i);
         // ... if the pair stage whose flags it reads (item i - 1 with two tiles) is over by then.  Otherwise the host would sit in
         // settle_pair until it is, and this item's pair stage -- whose work classes and lists can be computed under that same stage
-        // (stream_o) -- would be issued late: then the seeding is issued behind this item's pair stage instead (`late`).
+        // (stream O) -- would be issued late: then the seeding is issued behind this item's pair stage instead (`late`).
         auto ahead = [&]() -> int {
-            if (!seed_ahead || i + 1 >= n_items || seeded[(size_t)i + 1]) return CM_OK;
+            if (i + 1 >= n_items || seeded[(size_t)i + 1]) return CM_OK;
             if (early_ok) return issue_seed_early(i + 1);      // queued on the device behind what it depends on: nothing left for later
             const int bn = (ctx->item_base + i + 1) & 1;
-            if (ctx->rerun[bn].deferred && hipEventQuery(ctx->ev_first[bn]) != hipSuccess) {
+            if (ctx->rerun[bn].deferred && hipEventQuery(ctx->ev.first[bn]) != hipSuccess) {
                 (void)hipGetLastError();                                  // not ready
                 return CM_OK;
             }
-            return issue_seed(i + 1, ctx->stream_s);
+            return issue_seed(i + 1, ctx->st.S);
         };
-        auto late = [&]() -> int { return (seed_ahead && i + 1 < n_items && !seeded[(size_t)i + 1]) ? issue_seed(i + 1, ctx->stream_s) : CM_OK; };
+        auto late = [&]() -> int { return (i + 1 < n_items && !seeded[(size_t)i + 1]) ? issue_seed(i + 1, ctx->st.S) : CM_OK; };
         // The last item has nothing of this batch to seed ahead: the seeds of the NEXT batch's first item instead (the prefetch below
         // then starts with its chain stage; without this the prefetched chains ended 3.7 ms after the batch's last pair stage and
         // held up the hand-over).  Seeds only: the chain records they will be chained into are still being read.
-        if (i == n_items - 1 && prefetch && seed_ahead && !pre_seeded) {
+        if (i == n_items - 1 && prefetch && !pre_seeded) {
             const Slot &sl0 = ctx->slots[slots[0]];
             const uint32_t nt0 = tile_for(ctx->st_n_pairs);                     // = that batch's first tile (<= this batch's: it has no more pairs)
-            const ReadsDev rd_next{ctx->st_seq1_base + cmc::CM_STAGE_PAD, ctx->st_seq2_base + cmc::CM_STAGE_PAD, ctx->st_off1, ctx->st_off2};
-            HIPCHK(ctx, hipStreamWaitEvent(ctx->stream_s, ctx->ev_staged, 0));
-            if ((rc = run_seed_tile(ctx, make_core(ctx, sl0), rd_next, 0, nt0, ctx->d_ones, n_items & 1, ctx->stream_s, nullptr))) return rc;
+            const ReadsDev rd_next = reads_dev(ctx->st_rd);
+            HIPCHK(ctx, hipStreamWaitEvent(ctx->st.S, ctx->ev.staged, 0));
+            if ((rc = run_seed_tile(ctx, make_core(ctx, sl0), rd_next, 0, nt0, ctx->d_ones, n_items & 1, ctx->st.S, nullptr))) return rc;
             pre_seeded = true;
         }
-        if (use_pre && i == 0) {                                          // set b holds this item's chains, ev_prep[b] is recorded
+        if (use_pre && i == 0) {                                          // set b holds this item's chains, ev.prep[b] is recorded
             if ((rc = ahead())) return rc;
         } else {
-            if (!seeded[(size_t)i] && (rc = issue_seed(i, ctx->stream))) return rc;
+            if (!seeded[(size_t)i] && (rc = issue_seed(i, ctx->st.B))) return rc;
             if ((rc = settle_pair(ctx, b))) return rc;
             if (ctx->pair_pending[b]) {                                   // chain buffers of set b: free once their pair stage is done
-                HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_pair[b], 0));
+                HIPCHK(ctx, hipStreamWaitEvent(ctx->st.B, ctx->ev.pair[b], 0));
                 ctx->pair_pending[b] = false;
             }
-            HIPCHK(ctx, hipEventRecord(ctx->ev_flags, ctx->stream));      // (pair stage of item i - 2 and everything before it)
-            // CM_CHAIN_EXACT=1 (diagnostic, one tile): the chain kernels wait for the pair stage of round r - 1 and use its output
-            // flags (chain kernels 8.4 -> 6.7 ms per step, step 24.0 -> 25.1 ms: the wait costs more than the work it saves)
-            static const bool exact_flags = getenv("CM_CHAIN_EXACT") && getenv("CM_CHAIN_EXACT")[0] == '1';
-            const bool wait_exact = exact_flags && !round_major && r > 0;
-            if (wait_exact && (rc = settle_pair(ctx, b ^ 1))) return rc;
-            if (wait_exact && ctx->pair_pending[b ^ 1]) {                 // item - 1 = the same tile's round r - 1
-                HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_pair[b ^ 1], 0));
-                ctx->pair_pending[b ^ 1] = false;
-            }
-            if ((rc = run_chain_tile(ctx, core, rd_cur, p0, nt, sl.chain_parallel_ok, wait_exact ? A[r & 1] : act_prep, rb, i & 1, ahead))) return rc;
-            HIPCHK(ctx, hipEventRecord(ctx->ev_prep[b], ctx->stream));
+            HIPCHK(ctx, hipEventRecord(ctx->ev.flags, ctx->st.B));      // (pair stage of item i - 2 and everything before it)
+            // (one tile: the chain kernels do not wait for the pair stage of round r - 1 to use its output flags -- chain kernels
+            // 8.4 -> 6.7 ms per step, step 24.0 -> 25.1 ms: the wait costs more than the work it saves)
+            if ((rc = run_chain_tile(ctx, core, rd_cur, p0, nt, sl.chain_parallel_ok, act_prep, rb, i & 1, ahead))) return rc;
+            HIPCHK(ctx, hipEventRecord(ctx->ev.prep[b], ctx->st.B));
         }
         const int is_last = (r == n_rounds - 1) ? (last_is_final != 0) : 0;
         const bool same_tile = i > 0 && items[i - 1].p0 == p0;
@@ -3617,11 +3583,6 @@ static int map_rounds_issue(cm_ctx *ctx, const int *slots, int n_rounds, int las
         if ((rc = late())) return rc;
         ++*items_done;
         if (++tiles_of_round[(size_t)r] == (int)n_tiles) ++*rounds_done;
-        static const bool no_overlap = getenv("CM_PIPELINE") && getenv("CM_PIPELINE")[0] == '0';      // diagnostic: items back to back
-        if (no_overlap) {
-            if ((rc = settle_pair(ctx, b))) return rc;
-            HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_pair[b], 0));
-        }
     }
     ctx->item_base = (ctx->item_base + n_items) & 1;
     *items_done = 0;                                   // accounted for
@@ -3636,20 +3597,20 @@ static int map_rounds_issue(cm_ctx *ctx, const int *slots, int n_rounds, int las
         const Slot &sl = ctx->slots[slots[0]];
         const KCore core = make_core(ctx, sl);
         const uint32_t nt = tile_for(ctx->st_n_pairs);     // = that batch's first tile (prepare_resident)
-        HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_staged, 0));
+        HIPCHK(ctx, hipStreamWaitEvent(ctx->st.B, ctx->ev.staged, 0));
         if ((rc = settle_pair(ctx, b))) return rc;
         if (ctx->pair_pending[b]) {
-            HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_pair[b], 0));
+            HIPCHK(ctx, hipStreamWaitEvent(ctx->st.B, ctx->ev.pair[b], 0));
             ctx->pair_pending[b] = false;
         }
-        const RoundBufs rbn = round_bufs(ctx, b);
-        const ReadsDev rd_next{ctx->st_seq1_base + cmc::CM_STAGE_PAD, ctx->st_seq2_base + cmc::CM_STAGE_PAD, ctx->st_off1, ctx->st_off2};
+        const ChainRecs &rbn = ctx->rec[b];
+        const ReadsDev rd_next = reads_dev(ctx->st_rd);
         if (pre_seeded) {                                      // seeds are there (or on their way): the classes, into the records now free
-            HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_seed[n_items & 1], 0));
-            if ((rc = seed_classes(ctx, 0, nt, ctx->d_ones, n_items & 1, ctx->stream, &rbn))) return rc;
-        } else if ((rc = run_seed_tile(ctx, core, rd_next, 0, nt, ctx->d_ones, n_items & 1, ctx->stream, &rbn))) return rc;
+            HIPCHK(ctx, hipStreamWaitEvent(ctx->st.B, ctx->ev.seed[n_items & 1], 0));
+            if ((rc = seed_classes(ctx, 0, nt, ctx->d_ones, n_items & 1, ctx->st.B, &rbn))) return rc;
+        } else if ((rc = run_seed_tile(ctx, core, rd_next, 0, nt, ctx->d_ones, n_items & 1, ctx->st.B, &rbn))) return rc;
         if ((rc = run_chain_tile(ctx, core, rd_next, 0, nt, sl.chain_parallel_ok, ctx->d_ones, rbn, n_items & 1))) return rc;
-        HIPCHK(ctx, hipEventRecord(ctx->ev_prep[b], ctx->stream));
+        HIPCHK(ctx, hipEventRecord(ctx->ev.prep[b], ctx->st.B));
         ctx->pre_launched = true;
         ctx->pre_slot = slots[0];
         ctx->pre_gen = sl.gen;
@@ -3657,12 +3618,12 @@ static int map_rounds_issue(cm_ctx *ctx, const int *slots, int n_rounds, int las
         ctx->pre_nt = nt;
     }
     // later work on the main stream (downloads, collects, the next batch) is ordered behind the last pair stage on the device
-    // (set item_base ^ 1 = the last item's goes second: stream p3's last entry then waits for stream p's last)
+    // (set item_base ^ 1 = the last item's goes second: stream R's last entry then waits for stream P's last)
     if ((rc = settle_pair(ctx, ctx->item_base, false)) || (rc = settle_pair(ctx, ctx->item_base ^ 1, false))) return rc;
-    HIPCHK(ctx, hipEventRecord(ctx->ev_tail, ctx->stream_p3));               // (p3's last launch waits for p's last)
-    HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_tail, 0));
+    HIPCHK(ctx, hipEventRecord(ctx->ev.tail, ctx->st.R));               // (R's last launch waits for P's last)
+    HIPCHK(ctx, hipStreamWaitEvent(ctx->st.B, ctx->ev.tail, 0));
     ctx->pair_pending[0] = ctx->pair_pending[1] = false;                     // covered by the wait above
-    if (n_rounds & 1) std::swap(ctx->d_active, ctx->d_active_b);             // the current flags are in the other array now
+    if (n_rounds & 1) swap(ctx->d_active, ctx->d_active_b);             // the current flags are in the other array now
     *rounds_done = 0;                                  // accounted for
     return CM_OK;
 }
@@ -3681,17 +3642,13 @@ int cm_map_rounds(cm_ctx *ctx, const int *slots, int n_rounds, int last_is_final
     // buffers, and the bookkeeping must describe what was actually issued -- the chain-record set parity (item_base), the
     // flags array that holds the latest flags (one swap per completed round), no prepared first item, no pending pair stage.
     // The states of the batch are unspecified after a failed call (upload or reset before mapping again).
-    (void)hipStreamSynchronize(ctx->stream);
-    (void)hipStreamSynchronize(ctx->stream2);
-    (void)hipStreamSynchronize(ctx->stream_p);
-    (void)hipStreamSynchronize(ctx->stream_p2);
-    (void)hipStreamSynchronize(ctx->stream_o);
-    (void)hipStreamSynchronize(ctx->stream_p3);
-    (void)hipStreamSynchronize(ctx->stream_s);
+    // (every stream but the copy stream: the staging copy of the next batch is none of this call's work and may go on)
+    for (const StreamDef &d : STREAMS)
+        if (d.st != &Streams::C) (void)hipStreamSynchronize(ctx->st.*d.st);
     ctx->rerun[0].deferred = ctx->rerun[1].deferred = false;
-    ctx->cls_deferred[0] = ctx->cls_deferred[1] = false;
+    ctx->seed[0].cls_deferred = ctx->seed[1].cls_deferred = false;
     ctx->item_base = (ctx->item_base + items_done) & 1;
-    if (rounds_done & 1) std::swap(ctx->d_active, ctx->d_active_b);
+    if (rounds_done & 1) swap(ctx->d_active, ctx->d_active_b);
     ctx->pair_pending[0] = ctx->pair_pending[1] = false;
     ctx->pre_ready = ctx->pre_launched = false;
     return rc;
@@ -3702,10 +3659,10 @@ int cm_map_round(cm_ctx *ctx, int slot, int is_last_round) { return cm_map_round
 int cm_sync(cm_ctx *ctx) {
     if (!ctx) return CM_EINVAL;
     HIPCHK(ctx, hipSetDevice(ctx->P.device));
-    // the main stream is ordered behind every other stream's work at the end of each call (ev_tail); the staging copy of
+    // the main stream is ordered behind every other stream's work at the end of each call (ev.tail); the staging copy of
     // cm_reads_stage is the one thing a caller can have in flight beside it
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream_copy));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->st.B));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->st.C));
     return check_dev_err(ctx);
 }
 
@@ -3715,7 +3672,7 @@ int cm_reads_reset(cm_ctx *ctx) {
     if (ctx->n_pairs == 0) return CM_OK;
     KCore k{};
     k.P = ctx->P;
-    hipLaunchKernelGGL(k_init_state, dim3((unsigned)((ctx->n_pairs + BLK - 1) / BLK)), dim3(BLK), 0, ctx->stream, k, ctx->d_state, ctx->d_active,
+    hipLaunchKernelGGL(k_init_state, dim3((unsigned)((ctx->n_pairs + BLK - 1) / BLK)), dim3(BLK), 0, ctx->st.B, k, ctx->d_state, ctx->d_active,
                        ctx->d_cat, ctx->n_pairs);
     HIPCHK(ctx, hipGetLastError());
     return CM_OK;
@@ -3735,23 +3692,23 @@ static int compact_active(cm_ctx *ctx) {
     if (n > 0xfffffff0ull) return fail(ctx, CM_ELIMIT, "cm_collect_*: too many pairs");
     const uint32_t nbk = (uint32_t)((n + CLS_T - 1) / CLS_T);
     // scratch sized for the whole batch, made on first use
-    HIPCHK(ctx, ensure(ctx, ctx->d_col_cls, n));
-    HIPCHK(ctx, ensure(ctx, ctx->d_col_perm, n * 4));
-    HIPCHK(ctx, ensure(ctx, ctx->d_col_blk, (size_t)N_CLS * (nbk + 2) * sizeof(unsigned int)));
-    HIPCHK(ctx, ensure(ctx, ctx->d_col_ctr, CTR_WORDS * sizeof(unsigned int)));
-    hipLaunchKernelGGL(k_active_cls, dim3((unsigned)((n + BLK - 1) / BLK)), dim3(BLK), 0, ctx->stream, ctx->d_active, n, ctx->d_col_cls);
-    hipLaunchKernelGGL(k_cls_hist, dim3(nbk), dim3(CLS_W), 0, ctx->stream, ctx->d_col_cls, (uint32_t)n, ctx->d_col_blk, nbk, (const uint32_t *)nullptr,
+    HIPCHK(ctx, ensure(ctx, ctx->col.cls, n));
+    HIPCHK(ctx, ensure(ctx, ctx->col.perm, n * 4));
+    HIPCHK(ctx, ensure(ctx, ctx->col.blk, (size_t)N_CLS * (nbk + 2) * sizeof(unsigned int)));
+    HIPCHK(ctx, ensure(ctx, ctx->col.ctr, CTR_WORDS * sizeof(unsigned int)));
+    hipLaunchKernelGGL(k_active_cls, dim3((unsigned)((n + BLK - 1) / BLK)), dim3(BLK), 0, ctx->st.B, ctx->d_active, n, ctx->col.cls);
+    hipLaunchKernelGGL(k_cls_hist, dim3(nbk), dim3(CLS_W), 0, ctx->st.B, ctx->col.cls, (uint32_t)n, ctx->col.blk, nbk, (const uint32_t *)nullptr,
                        (const unsigned int *)nullptr);
-    hipLaunchKernelGGL(k_cls_scan, dim3(1), dim3(SCAN_CLS_T), 0, ctx->stream, ctx->d_col_blk, nbk, ctx->d_col_ctr, -1, 1);
-    hipLaunchKernelGGL(k_cls_place, dim3(nbk), dim3(CLS_W), 0, ctx->stream, ctx->d_col_cls, (uint32_t)n, ctx->d_col_blk, nbk, ctx->d_col_ctr,
-                       ctx->d_col_perm, (uint32_t *)nullptr, (const uint32_t *)nullptr, (const unsigned int *)nullptr);
+    hipLaunchKernelGGL(k_cls_scan, dim3(1), dim3(SCAN_CLS_T), 0, ctx->st.B, ctx->col.blk, nbk, ctx->col.ctr, -1, 1);
+    hipLaunchKernelGGL(k_cls_place, dim3(nbk), dim3(CLS_W), 0, ctx->st.B, ctx->col.cls, (uint32_t)n, ctx->col.blk, nbk, ctx->col.ctr,
+                       ctx->col.perm, (uint32_t *)nullptr, (const uint32_t *)nullptr, (const unsigned int *)nullptr);
     return CM_OK;
 }
 // count + error flags through the pinned landing zone (one synchronisation)
 static int read_count(cm_ctx *ctx, uint64_t cap, unsigned int *cnt, const char *what) {
-    HIPCHK(ctx, hipMemcpyAsync(ctx->h_pin, ctx->d_col_ctr, sizeof(unsigned int), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->h_pin + 1, ctx->d_err, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->h_pin, ctx->col.ctr, sizeof(unsigned int), hipMemcpyDeviceToHost, ctx->st.B));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->h_pin + 1, ctx->d_err, sizeof(int), hipMemcpyDeviceToHost, ctx->st.B));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->st.B));
     *cnt = *(const unsigned int *)ctx->h_pin;
     if (*(const int *)(ctx->h_pin + 1)) return check_dev_err(ctx);
     if (*cnt > cap) return fail(ctx, CM_ELIMIT, "%s: %u active pairs > cap %llu", what, *cnt, (unsigned long long)cap);
@@ -3765,25 +3722,21 @@ int cm_collect_active(cm_ctx *ctx, uint64_t cap, uint64_t *out_idx, cm_mapped_re
     if (ctx->n_pairs == 0) return CM_OK;
     int rc = compact_active(ctx);
     if (rc) return rc;
-    if (cap > ctx->collect_cap) {                 // grow-only output staging
-        dfree(ctx, ctx->d_collect_idx);
-        dfree(ctx, ctx->d_collect_st);
-        ctx->collect_cap = 0;
-        HIPCHK(ctx, hipMalloc((void **)&ctx->d_collect_idx, cap * sizeof(unsigned long long)));
-        HIPCHK(ctx, hipMalloc((void **)&ctx->d_collect_st, cap * sizeof(cm_mapped_read)));
-        ctx->collect_cap = cap;
+    if (cap) {                                    // grow-only output staging
+        HIPCHK(ctx, ensure(ctx, ctx->col.idx, cap * sizeof(unsigned long long)));
+        HIPCHK(ctx, ensure(ctx, ctx->col.st, cap * sizeof(cm_mapped_read)));
     }
     if (cap)
-        hipLaunchKernelGGL(k_gather_active, dim3((unsigned)((cap + BLK - 1) / BLK)), dim3(BLK), 0, ctx->stream, ctx->d_col_perm, ctx->d_col_ctr,
-                           (unsigned long long)cap, ctx->d_state, ctx->d_collect_idx, ctx->d_collect_st);
+        hipLaunchKernelGGL(k_gather_active, dim3((unsigned)((cap + BLK - 1) / BLK)), dim3(BLK), 0, ctx->st.B, ctx->col.perm, ctx->col.ctr,
+                           (unsigned long long)cap, ctx->d_state, ctx->col.idx, ctx->col.st);
     unsigned int cnt = 0;
     rc = read_count(ctx, cap, &cnt, "cm_collect_active");
     *out_n = cnt;
     if (rc) return rc;
     if (cnt) {
-        HIPCHK(ctx, hipMemcpyAsync(out_idx, ctx->d_collect_idx, (size_t)cnt * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(ctx, hipMemcpyAsync(out_state, ctx->d_collect_st, (size_t)cnt * sizeof(cm_mapped_read), hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(out_idx, ctx->col.idx, (size_t)cnt * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->st.B));
+        HIPCHK(ctx, hipMemcpyAsync(out_state, ctx->col.st, (size_t)cnt * sizeof(cm_mapped_read), hipMemcpyDeviceToHost, ctx->st.B));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->st.B));
     }
     return CM_OK;
 }
@@ -3795,7 +3748,7 @@ static int collect_records_into(cm_ctx *ctx, uint64_t index_base, uint64_t cap, 
     int rc = compact_active(ctx);
     if (rc) return rc;
     if (cap)
-        hipLaunchKernelGGL(k_gather_records, dim3((unsigned)((cap + BLK - 1) / BLK)), dim3(BLK), 0, ctx->stream, ctx->d_col_perm, ctx->d_col_ctr,
+        hipLaunchKernelGGL(k_gather_records, dim3((unsigned)((cap + BLK - 1) / BLK)), dim3(BLK), 0, ctx->st.B, ctx->col.perm, ctx->col.ctr,
                            (unsigned long long)cap, ctx->d_state, (unsigned long long)index_base, d_dst);
     unsigned int cnt = 0;
     rc = read_count(ctx, cap, &cnt, what);
@@ -3806,17 +3759,12 @@ static int collect_records_into(cm_ctx *ctx, uint64_t index_base, uint64_t cap, 
 int cm_collect_records(cm_ctx *ctx, uint64_t index_base, uint64_t cap, cm_record *out, uint64_t *out_n) {
     if (!ctx || !out_n || (cap && !out)) return CM_EINVAL;
     HIPCHK(ctx, hipSetDevice(ctx->P.device));
-    if (cap > ctx->collect_rec_cap) {
-        dfree(ctx, ctx->d_collect_rec);
-        ctx->collect_rec_cap = 0;
-        HIPCHK(ctx, hipMalloc((void **)&ctx->d_collect_rec, cap * sizeof(cm_record)));
-        ctx->collect_rec_cap = cap;
-    }
-    int rc = collect_records_into(ctx, index_base, cap, ctx->d_collect_rec, out_n, "cm_collect_records");
+    if (cap) HIPCHK(ctx, ensure(ctx, ctx->col.rec, cap * sizeof(cm_record)));
+    int rc = collect_records_into(ctx, index_base, cap, ctx->col.rec, out_n, "cm_collect_records");
     if (rc) return rc;
     if (*out_n) {
-        HIPCHK(ctx, hipMemcpyAsync(out, ctx->d_collect_rec, (size_t)*out_n * sizeof(cm_record), hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(out, ctx->col.rec, (size_t)*out_n * sizeof(cm_record), hipMemcpyDeviceToHost, ctx->st.B));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->st.B));
     }
     return CM_OK;
 }
@@ -3867,12 +3815,12 @@ int cm_type_histogram(cm_ctx *ctx, uint64_t out[14]) {
     for (int i = 0; i < 14; ++i) out[i] = 0;
     if (ctx->n_pairs == 0) return CM_OK;
     HIPCHK(ctx, ensure(ctx, ctx->d_type_hist, 16 * sizeof(unsigned long long)));
-    HIPCHK(ctx, hipMemsetAsync(ctx->d_type_hist, 0, 16 * sizeof(unsigned long long), ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(ctx->d_type_hist, 0, 16 * sizeof(unsigned long long), ctx->st.B));
     const unsigned grid = (unsigned)std::min<uint64_t>((ctx->n_pairs + BLK - 1) / BLK, 1024);
-    hipLaunchKernelGGL(k_type_hist, dim3(grid), dim3(BLK), 0, ctx->stream, ctx->d_state, ctx->n_pairs, ctx->d_type_hist);
+    hipLaunchKernelGGL(k_type_hist, dim3(grid), dim3(BLK), 0, ctx->st.B, ctx->d_state, ctx->n_pairs, ctx->d_type_hist);
     unsigned long long h[16];
-    HIPCHK(ctx, hipMemcpyAsync(h, ctx->d_type_hist, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(h, ctx->d_type_hist, sizeof h, hipMemcpyDeviceToHost, ctx->st.B));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->st.B));
     for (int i = 0; i < 14; ++i) out[i] = h[i];
     return check_dev_err(ctx);
 }
@@ -3882,11 +3830,11 @@ int cm_reads_download(cm_ctx *ctx, cm_mapped_read *out_state, int32_t *out_categ
     HIPCHK(ctx, hipSetDevice(ctx->P.device));
     const uint64_t n = ctx->n_pairs;
     if (n) {
-        if (out_state) HIPCHK(ctx, hipMemcpyAsync(out_state, ctx->d_state, n * sizeof(cm_mapped_read), hipMemcpyDeviceToHost, ctx->stream));
-        if (out_category) HIPCHK(ctx, hipMemcpyAsync(out_category, ctx->d_cat, n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-        if (out_active) HIPCHK(ctx, hipMemcpyAsync(out_active, ctx->d_active, n, hipMemcpyDeviceToHost, ctx->stream));
+        if (out_state) HIPCHK(ctx, hipMemcpyAsync(out_state, ctx->d_state, n * sizeof(cm_mapped_read), hipMemcpyDeviceToHost, ctx->st.B));
+        if (out_category) HIPCHK(ctx, hipMemcpyAsync(out_category, ctx->d_cat, n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->st.B));
+        if (out_active) HIPCHK(ctx, hipMemcpyAsync(out_active, ctx->d_active, n, hipMemcpyDeviceToHost, ctx->st.B));
     }
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->st.B));
     return check_dev_err(ctx);
 }
 
@@ -3909,12 +3857,12 @@ int cm_seed_batch(cm_ctx *ctx, int slot, uint32_t *out_start, uint32_t *out_cnt,
     const KCore core = make_core(ctx, ctx->slots[slot]);
     for (uint64_t p0 = 0; p0 < ctx->n_pairs; p0 += ctx->tile) {
         const uint32_t nt = (uint32_t)((ctx->n_pairs - p0 < ctx->tile) ? ctx->n_pairs - p0 : ctx->tile);
-        if ((rc = run_seed_tile(ctx, core, current_reads(ctx), p0, nt, ctx->d_active, 0, ctx->stream, nullptr))) return rc;
+        if ((rc = run_seed_tile(ctx, core, current_reads(ctx), p0, nt, ctx->d_active, 0, ctx->st.B, nullptr))) return rc;
         const size_t cnt = (size_t)nt * 4 * ctx->n_seeds, o = (size_t)p0 * 4 * ctx->n_seeds;
-        HIPCHK(ctx, hipMemcpyAsync(out_start + o, ctx->d_sstart, cnt * 4, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(ctx, hipMemcpyAsync(out_cnt + o, ctx->d_scnt, cnt * 4, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(ctx, hipMemcpyAsync(out_raw + o, ctx->d_sraw, cnt * 4, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(out_start + o, ctx->seed[0].sstart, cnt * 4, hipMemcpyDeviceToHost, ctx->st.B));
+        HIPCHK(ctx, hipMemcpyAsync(out_cnt + o, ctx->seed[0].scnt, cnt * 4, hipMemcpyDeviceToHost, ctx->st.B));
+        HIPCHK(ctx, hipMemcpyAsync(out_raw + o, ctx->seed[0].sraw, cnt * 4, hipMemcpyDeviceToHost, ctx->st.B));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->st.B));
     }
     return CM_OK;
 }
@@ -3927,16 +3875,16 @@ int cm_chain_batch(cm_ctx *ctx, int slot, cm_chain *out_chains, int32_t *out_nch
     const KCore core = make_core(ctx, ctx->slots[slot]);
     for (uint64_t p0 = 0; p0 < ctx->n_pairs; p0 += ctx->tile) {
         const uint32_t nt = (uint32_t)((ctx->n_pairs - p0 < ctx->tile) ? ctx->n_pairs - p0 : ctx->tile);
-        HIPCHK(ctx, hipMemsetAsync(ctx->d_chains, 0, (size_t)nt * 4 * CM_BESTCHAINLIM * sizeof(cm_chain), ctx->stream));
-        const RoundBufs rb0 = round_bufs(ctx, 0);
-        if ((rc = run_seed_tile(ctx, core, current_reads(ctx), p0, nt, ctx->d_active, 0, ctx->stream, &rb0))) return rc;
+        HIPCHK(ctx, hipMemsetAsync(ctx->rec[0].chains, 0, (size_t)nt * 4 * CM_BESTCHAINLIM * sizeof(cm_chain), ctx->st.B));
+        const ChainRecs &rb0 = ctx->rec[0];
+        if ((rc = run_seed_tile(ctx, core, current_reads(ctx), p0, nt, ctx->d_active, 0, ctx->st.B, &rb0))) return rc;
         if ((rc = run_chain_tile(ctx, core, current_reads(ctx), p0, nt, ctx->slots[slot].chain_parallel_ok, ctx->d_active, rb0, 0))) return rc;
         const size_t np = (size_t)nt * 4, o = (size_t)p0 * 4;
-        HIPCHK(ctx, hipMemcpyAsync(out_chains + o * CM_BESTCHAINLIM, ctx->d_chains, np * CM_BESTCHAINLIM * sizeof(cm_chain), hipMemcpyDeviceToHost,
-                                   ctx->stream));
-        HIPCHK(ctx, hipMemcpyAsync(out_nchain + o, ctx->d_nchain, np * 4, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(ctx, hipMemcpyAsync(out_high + o, ctx->d_high, np * 4, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(out_chains + o * CM_BESTCHAINLIM, ctx->rec[0].chains, np * CM_BESTCHAINLIM * sizeof(cm_chain), hipMemcpyDeviceToHost,
+                                   ctx->st.B));
+        HIPCHK(ctx, hipMemcpyAsync(out_nchain + o, ctx->rec[0].nchain, np * 4, hipMemcpyDeviceToHost, ctx->st.B));
+        HIPCHK(ctx, hipMemcpyAsync(out_high + o, ctx->rec[0].high, np * 4, hipMemcpyDeviceToHost, ctx->st.B));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->st.B));
     }
     return check_dev_err(ctx);
 }
@@ -3946,8 +3894,8 @@ int cm_chain_batch(cm_ctx *ctx, int slot, cm_chain *out_chains, int32_t *out_nch
 int cm_debug_counters(cm_ctx *ctx, unsigned long long *out) {
     if (!ctx || !out) return CM_EINVAL;
     HIPCHK(ctx, hipSetDevice(ctx->P.device));
-    HIPCHK(ctx, hipMemcpyAsync(out, ctx->d_counters, 32 * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(out, ctx->d_counters, 32 * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->st.B));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->st.B));
     return CM_OK;
 }
 
@@ -3970,7 +3918,7 @@ int cm_prof_enable(cm_ctx *ctx, int on) {
 int cm_prof_reset(cm_ctx *ctx) {
     if (!ctx) return CM_EINVAL;
     HIPCHK(ctx, hipSetDevice(ctx->P.device));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->st.B));
     for (auto &r : ctx->recs) {
         ctx->ev_free.push_back(r.a);
         ctx->ev_free.push_back(r.b);
@@ -3980,15 +3928,15 @@ int cm_prof_reset(cm_ctx *ctx) {
         ctx->ms[i] = 0;
         ctx->launches[i] = 0;
     }
-    HIPCHK(ctx, hipMemsetAsync(ctx->d_counters, 0, 32 * sizeof(unsigned long long), ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(ctx->d_counters, 0, 32 * sizeof(unsigned long long), ctx->st.B));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->st.B));
     return CM_OK;
 }
 
 int cm_prof_get(cm_ctx *ctx, double ms[8], uint64_t launches[8]) {
     if (!ctx || !ms || !launches) return CM_EINVAL;
     HIPCHK(ctx, hipSetDevice(ctx->P.device));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->st.B));
     for (auto &r : ctx->recs) {
         float t = 0;
         if (hipEventElapsedTime(&t, r.a, r.b) == hipSuccess) ctx->ms[r.cls] += (double)t;
@@ -4007,8 +3955,8 @@ int cm_prof_counters(cm_ctx *ctx, uint64_t c[8]) {
     if (!ctx || !c) return CM_EINVAL;
     HIPCHK(ctx, hipSetDevice(ctx->P.device));
     unsigned long long h[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    HIPCHK(ctx, hipMemcpyAsync(h, ctx->d_counters, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(h, ctx->d_counters, sizeof h, hipMemcpyDeviceToHost, ctx->st.B));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->st.B));
     for (int i = 0; i < 8; ++i) c[i] = h[i];
     return CM_OK;
 }
