@@ -167,12 +167,14 @@ struct KCore {          // what the host passes as a kernel argument (plain poin
     cm_index_view X;
     AnnotDev A;
     const uint32_t *desc = nullptr;       // optional bucket descriptors (desc_pack below), null = none
+    const uint64_t *entry_near = nullptr; // optional: bit e = bit_at(A.near_border_bits, A.n_bits, X.pos[e]), one bit per index entry; null = none
 };
 struct Core {
     cm_params P;
     IndexV X;
     AnnotV A;
     g_u32 desc = nullptr;
+    g_u64 entry_near = nullptr;
 };
 CM_HD inline Core to_core(const KCore &k) {
     Core c;
@@ -180,6 +182,7 @@ CM_HD inline Core to_core(const KCore &k) {
     c.X = to_dev(k.X);
     c.A = to_dev(k.A);
     c.desc = (g_u32)k.desc;
+    c.entry_near = (g_u64)k.entry_near;
     return c;
 }
 
@@ -451,7 +454,10 @@ CM_HD inline bool check_junction(const Core &c, uint32_t s1, uint32_t s2, int ol
 
 // Storage policies of the chaining DP.
 //  * ChainStoreGlobal: cells (score, back pointer) in the launch's HBM workspace, hit positions read from
-//    the index, improvement log in the shared pool (grows by x4, flags ERR_POOL when the pool is exhausted);
+//    the index, improvement log in the shared pool (grows by x4, flags ERR_POOL when the pool is exhausted).
+//    A problem of at most MASK_CELLS cells (all that reach this store when the heavy ones have a kernel of their
+//    own: at most 96 hits) does not initialise its cells: an "improved" bit per cell, in registers, says which
+//    cells were ever stored, and the others are answered with the initial value without a load;
 //  * ChainStoreSmall: everything in lane-private arrays — for problems with at most SMALL_W (hit, later
 //    hit) pairs, i.e. at most SMALL_W improvements and SMALL_W + 1 cells: >95 % of all problems, and no
 //    global atomics, no scattered HBM cells for them.
@@ -466,8 +472,13 @@ struct ChainStoreGlobal {
     CM_G Event *ev;
     uint32_t n_ev, cap_ev;
     bool lost;
+    static constexpr uint32_t MASK_CELLS = 128;
+    uint64_t imp0_, imp1_;       // improved bits of cells 0 .. 63, 64 .. 127 (masked_ only)
+    bool masked_;
+    double init_;
     CM_HD ChainStoreGlobal(ChainWork &ww, g_u32 pos, const uint32_t *st, const uint32_t *cn, const uint32_t *bs)
-        : w(ww), POS(pos), start(st), cnt_(cn), base_(bs), ev(nullptr), n_ev(0), cap_ev(0), lost(false) {}
+        : w(ww), POS(pos), start(st), cnt_(cn), base_(bs), ev(nullptr), n_ev(0), cap_ev(0), lost(false), imp0_(0), imp1_(0), masked_(false), init_(0) {}
+    CM_HD inline bool stored(uint32_t x) const { return !masked_ || (((x < 64u ? imp0_ : imp1_) >> (x & 63u)) & 1ull); }
     CM_HD inline uint32_t cnt(int s) const { return cnt_[s]; }
     CM_HD inline uint32_t base(int s) const { return base_[s]; }
     CM_HD inline uint32_t total(int kc) const { return base_[kc]; }
@@ -475,17 +486,25 @@ struct ChainStoreGlobal {
     CM_HD inline uint32_t lb(int s) const { return lb_[s]; }
     CM_HD inline void set_lb(int s, uint32_t v) { lb_[s] = v; }
     CM_HD inline void init(uint32_t n_cells, double v) {
+        masked_ = n_cells <= MASK_CELLS;
+        init_ = v;
+        imp0_ = imp1_ = 0;
+        if (masked_) return;
         for (uint32_t x = 0; x < n_cells; ++x) {
             w.dp_score[x] = v;
             w.dp_prev[x] = -1;
         }
     }
     CM_HD inline uint32_t pos(int s, uint32_t i) const { return POS[start[s] + i]; }
-    CM_HD inline double score(uint32_t x) const { return w.dp_score[x]; }
-    CM_HD inline int32_t prev(uint32_t x) const { return w.dp_prev[x]; }
+    CM_HD inline double score(uint32_t x) const { return stored(x) ? w.dp_score[x] : init_; }
+    CM_HD inline int32_t prev(uint32_t x) const { return stored(x) ? w.dp_prev[x] : -1; }
     CM_HD inline void set(uint32_t x, double sc, int32_t pv) {
         w.dp_score[x] = sc;
         w.dp_prev[x] = pv;
+        if (masked_) {
+            if (x < 64u) imp0_ |= 1ull << x;
+            else imp1_ |= 1ull << (x & 63u);
+        }
     }
     CM_HD inline void push(double sc, uint32_t cell) {
         if (n_ev == cap_ev && !lost) {

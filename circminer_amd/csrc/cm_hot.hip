@@ -387,12 +387,20 @@ struct HeavyChainCtx {
     const Core *c;
     CM_L const uint32_t *LP;     // hit positions of every slot, concatenated (LDS)
     CM_L const uint32_t *NB;     // near-border bit of every cell of the slots that are evaluated (LDS bitmask, see k_chain_heavy)
+    CM_L const uint32_t *IM;     // "improved" bit of every cell (LDS bitmask, words per slot: heavy_im_word)
     const uint32_t *base, *cnt;  // per slot (uniform)
     int kc, seq_len;
     CM_G double *dps;
     CM_G int32_t *dpp;
 };
-// evaluates cell (ii, i); returns the number of strict improvements; stores them to ev[] when ev != null
+// The improved bit of cell (s, i) lies in word heavy_im_word(base[s], s) + (i >> 5), bit i & 31: every slot starts at a 64-bit
+// boundary of its own, so the bits of a batch of 64 cells are two whole words that one ballot writes (no LDS atomics).  A slot's
+// words begin at or behind the flat bit position of its first cell, shifted by one 64-bit word per earlier slot: slots never
+// overlap and all of them end within heavy_im_words(ncell, kc) words.
+__device__ inline uint32_t heavy_im_word(uint32_t base_s, uint32_t s) { return 2u * ((base_s >> 6) + s); }
+__host__ __device__ inline uint32_t heavy_im_words(uint32_t ncell, uint32_t kc) { return 2u * ((ncell >> 6) + kc + 1u); }
+// evaluates cell (ii, i); returns the number of strict improvements; stores them to ev[] when ev != null.  A cell of a later slot
+// that no evaluation improved still has its initial score, (double)kmer: only improved cells are in HBM (see k_chain_heavy).
 __device__ inline uint32_t heavy_cell(const HeavyChainCtx &h, int ii, uint32_t i, CM_G cmc::Event *ev, double &out_score, int32_t &out_prev,
                                      double &e0, double &e1) {
     const Core &c = *h.c;
@@ -427,6 +435,7 @@ __device__ inline uint32_t heavy_cell(const HeavyChainCtx &h, int ii, uint32_t i
         const uint32_t pcn = h.cnt[jj];
         if (pcn == 0) continue;
         CM_L const uint32_t *pp = h.LP + h.base[jj];
+        CM_L const uint32_t *im = h.IM + heavy_im_word(h.base[jj], (uint32_t)jj);
         uint32_t lo = 0, hi = pcn;                   // first hit of jj strictly right of this hit
         {
             CD_T0;
@@ -468,7 +477,8 @@ __device__ inline uint32_t heavy_cell(const HeavyChainCtx &h, int ii, uint32_t i
             const int maxd = distr < distt ? distt : distr, mind = distr < distt ? distr : distt;
             const double beta = 0.1 * (double)(maxd - mind);
             const double alpha = 2e4 * (double)kmer;
-            const double t1 = h.dps[h.base[jj] + j] + alpha;
+            const double prev_score = ((im[j >> 5] >> (j & 31)) & 1u) ? h.dps[h.base[jj] + j] : (double)kmer;
+            const double t1 = prev_score + alpha;
             const double temp_score = t1 - beta;
             if (temp_score > my_score) {
                 my_score = temp_score;
@@ -502,7 +512,7 @@ struct HeavyBackTrack {
 };
 
 #ifndef CM_CHEAVY_WAVES
-#define CM_CHEAVY_WAVES 3      // waves per SIMD k_chain_heavy is compiled for (158 VGPRs as it stands)
+#define CM_CHEAVY_WAVES 3      // waves per SIMD k_chain_heavy is compiled for (144 VGPRs as it stands)
 #endif
 __global__ void __launch_bounds__(64, CM_CHEAVY_WAVES) k_chain_heavy(KCore kc_, ReadsDev rd, uint64_t pair0, int S, const uint32_t *sstart, const uint32_t *scnt,
                                                     const unsigned long long *celloff, double *dp_score, int32_t *dp_prev, uint8_t *pool,
@@ -539,13 +549,24 @@ __global__ void __launch_bounds__(64, CM_CHEAVY_WAVES) k_chain_heavy(KCore kc_, 
         const uint32_t ncell = base[kc];
         CM_G double *dps = (CM_G double *)(dp_score + celloff[r]);
         CM_G int32_t *dpp = (CM_G int32_t *)(dp_prev + celloff[r]);
-        // hit positions -> LDS, cells initialised
+        // hit positions -> LDS.  The cells are not initialised: a cell is written to HBM when an evaluation improves it, and its bit
+        // in IM says so; every reader takes the initial value (score kmer, no back pointer) of a cell whose bit is clear from there.
+        CM_L uint32_t *NB = LP + ncell;
+        CM_L uint16_t *Q = (CM_L uint16_t *)(NB + 2 * ((ncell + 63) >> 6));
+        CM_L uint32_t *IM = (CM_L uint32_t *)(Q + 320);
+        // Where the slot has the near-border bits by index entry (Slot::entry_near), the bit of a hit comes with its position: the
+        // hits of a seed are consecutive entries, so a list's bits are a few words of one sector, read beside the positions (no
+        // further round trip); they ride in bit 31 of the position until the pre-pass below moves them into NB.  The position
+        // bitset would cost a sector and a dependent load per hit: a list's positions are copies of a repeat all over the contig.
+        const bool by_entry = c.entry_near != nullptr;
         for (int s = 0; s < kc; ++s)
-            for (uint32_t i = lane; i < cn[s]; i += 64) LP[base[s] + i] = c.X.pos[st[s] + i];
-        for (uint32_t x = lane; x < ncell; x += 64) {
-            dps[x] = (double)kmer;
-            dpp[x] = -1;
-        }
+            for (uint32_t i = lane; i < cn[s]; i += 64) {
+                const uint32_t e = st[s] + i;
+                uint32_t v = c.X.pos[e];
+                if (by_entry && s < kc - 1) v |= (uint32_t)((c.entry_near[e >> 6] >> (e & 63)) & 1ull) << 31;
+                LP[base[s] + i] = v;
+            }
+        for (uint32_t x = lane; x < heavy_im_words(ncell, (uint32_t)kc); x += 64) IM[x] = 0u;
         __threadfence_block();
         __syncthreads();
         // cmc::upper_bound of every hit the DP will evaluate (slots 0 .. kc - 2), ahead of the DP.  One hit in seven lies near an exon
@@ -553,8 +574,7 @@ __global__ void __launch_bounds__(64, CM_CHEAVY_WAVES) k_chain_heavy(KCore kc_, 
         // waited for its few such lanes (51 % of the DP's lane time, DESIGN note 30).  Here the near-border bits of all hits are read
         // first (one load each, every lane busy; they stay in LDS as a bitmask), the near hits are queued, and the look-ups run 64 to
         // a batch; the results are parked in the cells' own score / back-pointer slots (see heavy_cell).
-        CM_L uint32_t *NB = LP + ncell;
-        CM_L uint16_t *Q = (CM_L uint16_t *)(NB + 2 * ((ncell + 63) >> 6));
+        // (With Slot::entry_near the bits are in LDS already, see above: the first step is a read of LP.)
         {
             const uint32_t n_pre = kc >= 1 ? base[kc - 1] : 0u;
             const unsigned long long lt = (1ull << lane) - 1ull;
@@ -577,7 +597,10 @@ __global__ void __launch_bounds__(64, CM_CHEAVY_WAVES) k_chain_heavy(KCore kc_, 
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
                     const uint32_t x = x0 + 64 * u + lane;
-                    nr[u] = x < n_pre && cmc::bit_at(c.A.near_border_bits, c.A.n_bits, LP[x]);
+                    if (by_entry) {
+                        nr[u] = x < n_pre && (LP[x] >> 31);
+                        if (nr[u]) LP[x] &= 0x7fffffffu;
+                    } else nr[u] = x < n_pre && cmc::bit_at(c.A.near_border_bits, c.A.n_bits, LP[x]);
                 }
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
@@ -613,9 +636,9 @@ __global__ void __launch_bounds__(64, CM_CHEAVY_WAVES) k_chain_heavy(KCore kc_, 
 #if defined(CM_CHAIN_DIAG)
         unsigned long long tk[5] = {0, 0, 0, 0, 0};
         unsigned long long wv[4] = {0, 0, 0, 0};       // wave time: first evaluation, scan + log growth, store / second evaluation, barrier
-        HeavyChainCtx H{tk, &c, LP, NB, base, cn, kc, len, dps, dpp};
+        HeavyChainCtx H{tk, &c, LP, NB, IM, base, cn, kc, len, dps, dpp};
 #else
-        HeavyChainCtx H{&c, LP, NB, base, cn, kc, len, dps, dpp};
+        HeavyChainCtx H{&c, LP, NB, IM, base, cn, kc, len, dps, dpp};
 #endif
         CM_G cmc::Event *ev = nullptr;
         uint32_t n_ev = 0, cap_ev = 0;
@@ -633,6 +656,12 @@ __global__ void __launch_bounds__(64, CM_CHEAVY_WAVES) k_chain_heavy(KCore kc_, 
 #if defined(CM_CHAIN_DIAG)
                 const unsigned long long w1 = wall_clock64();
 #endif
+                {   // the improved bits of this batch: two whole words of the slot's part of IM (read by the slots below, after the barrier)
+                    const unsigned long long m = __ballot(mine > 0u);
+                    const uint32_t w = heavy_im_word(base[ii], (uint32_t)ii) + (i0 >> 5);
+                    if (lane == 0) IM[w] = (uint32_t)m;
+                    if (lane == 32) IM[w + 1] = (uint32_t)(m >> 32);
+                }
                 uint32_t total;
                 const uint32_t off = wave_excl_scan(mine, lane, total);
                 if (n_ev + total > cap_ev && !lost) {                 // grow the log (uniform decision)
@@ -652,8 +681,8 @@ __global__ void __launch_bounds__(64, CM_CHEAVY_WAVES) k_chain_heavy(KCore kc_, 
                         cap_ev = ncap;
                     }
                 }
-                if (on) {
-                    if (mine && !lost) {
+                if (on && mine) {               // an unimproved cell is not stored (a parked look-up may stay in it: its bit is clear)
+                    if (!lost) {
                         CM_G cmc::Event *dst = ev + n_ev + off;
                         if (mine <= 2) {
                             dst[0].score = e0;
@@ -758,7 +787,8 @@ __global__ void __launch_bounds__(64, CM_CHEAVY_WAVES) k_chain_heavy(KCore kc_, 
                         BT.cidx[lane][n] = (uint16_t)x;
                         BT.cbl[lane][n] = (uint8_t)bl;
                         ++n;
-                        const int32_t pv = dpp[x];
+                        const bool improved = (IM[heavy_im_word(BT.base[bl], bl) + (bi >> 5)] >> (bi & 31)) & 1u;
+                        const int32_t pv = improved ? dpp[x] : -1;
                         if (pv < 0 || n >= (uint32_t)CM_MAX_CHAIN_FRAGS) break;
                         bl = (uint32_t)pv >> 16;
                         bi = (uint32_t)pv & 0xffffu;
@@ -818,7 +848,7 @@ __global__ void __launch_bounds__(64, CM_CHEAVY_WAVES) k_chain_heavy(KCore kc_, 
             }
 #endif
         }
-        if (best_count == 0) {          // singletons (lane 0 emits; every lane keeps the count)
+        if (best_count == 0) {          // singletons: no cell was improved, every score is the initial one (lane 0 emits; every lane keeps the count)
             for (int ii = kc - 1; ii >= 0; --ii)
                 for (uint32_t i = 0; i < cn[ii]; ++i) {
                     if (best_count >= max_best) break;
@@ -827,7 +857,7 @@ __global__ void __launch_bounds__(64, CM_CHEAVY_WAVES) k_chain_heavy(KCore kc_, 
                         CM_G cm_chain &ch = out[best_count];
                         ch.rpos[0] = LP[base[ii] + i];
                         ch.qpos[0] = ii * kmer;
-                        ch.score = (float)dps[base[ii] + i];
+                        ch.score = (float)(double)kmer;
                         ch.chain_len = 1;
                     }
                     ++best_count;
@@ -1756,6 +1786,15 @@ __global__ void __launch_bounds__(BLK) k_ib_over_unpack(const uint32_t *bucket_o
     }
 }
 
+// Near-border bits by index entry (Slot::entry_near): bit e = the position bitset's bit of pos[e], through the function every
+// other reader of the bitset calls (a position at or beyond n_bits gives 0).  One lane per entry, one store per wave.
+__global__ void __launch_bounds__(BLK) k_entry_near(const uint32_t *pos, uint64_t n_entries, const uint64_t *bits, uint64_t n_bits, uint64_t *out) {
+    const uint64_t e = (uint64_t)blockIdx.x * BLK + threadIdx.x;
+    const bool b = e < n_entries && cmc::bit_at((cmc::g_u64)bits, n_bits, pos[e]);
+    const unsigned long long m = __ballot(b);
+    if ((threadIdx.x & 63) == 0 && e < n_entries) out[e >> 6] = m;
+}
+
 __global__ void k_init_state(KCore kc, cm_mapped_read *state, uint8_t *active, int32_t *cat, uint64_t n) {
     const uint64_t i = (uint64_t)blockIdx.x * BLK + threadIdx.x;
     if (i >= n) return;
@@ -1775,6 +1814,9 @@ struct Slot {
     cm_index_view X{};
     cmc::AnnotDev A{};
     std::vector<void *> idx_allocs, ann_allocs;
+    // near_border_bits by index entry, u64[(n_entries + 63) / 64], for k_chain_heavy.  Made from both halves of the slot: built by
+    // whichever load completes the pair (make_entry_near), dropped by every (un)load of either half, owned by neither list.
+    uint64_t *entry_near = nullptr;
 };
 
 struct ProfRec { hipEvent_t a, b; int cls; };
@@ -2065,6 +2107,10 @@ void free_all(cm_ctx *ctx, std::vector<void *> &v) {
     for (void *p : v) report_hip(ctx, "hipFree", hipFree(p));
     v.clear();
 }
+void drop_entry_near(cm_ctx *ctx, Slot &s) {
+    if (s.entry_near) report_hip(ctx, "hipFree", hipFree(s.entry_near));
+    s.entry_near = nullptr;
+}
 // Grow-only buffers: a batch re-uses the previous batch's allocation when it is large enough.  hipFree + hipMalloc
 // of the multi-GB workspaces cost ~0.85 s per 1 M-pair batch on MI355X, 85x the mapping itself (tests/diag/upload_rate.py).
 // On growth the old memory is freed first and the contents are lost; 0 bytes allocate 1.
@@ -2141,6 +2187,7 @@ KCore make_core(const cm_ctx *c, const Slot &s) {
     k.X = s.X;
     k.A = s.A;
     k.desc = s.d_desc;
+    k.entry_near = s.entry_near;
     return k;
 }
 
@@ -2271,10 +2318,17 @@ int run_chain_tile(cm_ctx *ctx, const KCore &core, const ReadsDev &rd, uint64_t 
     // k_chain_heavy keeps a problem's hit positions in LDS: sized for the largest problem of this tile (a multiple of 2 KB, so
     // that launches of similar tiles share a configuration), not for the n_seeds x seed_lim a problem could have in theory --
     // the kernel waits on memory most of the time and the LDS request decides how many waves a CU holds.
-    // (+ behind the hits: one bit per cell and a queue of 320 hits, see the kernel's upper_bound pass)
+    // (+ behind the hits: one bit per cell and a queue of 320 hits, see the kernel's upper_bound pass; behind those the improved
+    // bits, one per cell padded per slot.  Those go into the 2 KB of slack of the hits' part where it has them -- the request of
+    // such a tile is what it was without them -- and are added where the hits' part is the theoretical bound.)
     const size_t lds_extra = ((size_t)max_cells / 64 + 2) * 8 + 640;
-    const size_t heavy_lds = std::min<size_t>((size_t)S * (size_t)ctx->P.seed_lim * sizeof(uint32_t),
-                                              ((size_t)max_cells * sizeof(uint32_t) + 2047) / 2048 * 2048 + 2048) + (lds_extra + 255) / 256 * 256;
+    const size_t lds_need = (size_t)max_cells * sizeof(uint32_t) + lds_extra + (size_t)heavy_im_words((uint32_t)max_cells, (uint32_t)S) * sizeof(uint32_t);
+    const size_t heavy_lds = std::max<size_t>(std::min<size_t>((size_t)S * (size_t)ctx->P.seed_lim * sizeof(uint32_t),
+                                                               ((size_t)max_cells * sizeof(uint32_t) + 2047) / 2048 * 2048 + 2048) + (lds_extra + 255) / 256 * 256,
+                                              (lds_need + 255) / 256 * 256);
+#if defined(CM_CHAIN_DIAG)
+    fprintf(stderr, "heavy_lds %zu (largest problem %llu cells)\n", heavy_lds, max_cells);
+#endif
     // (otherwise everything stays on the sequential kernel and the class lists of run_seed_tile go unused)
     const bool split = ranges.size() == 1 && parallel_ok && heavy_lds <= 152u * 1024u;
     bool fresh = true;            // the cursors are still as run_seed_tile zeroed them
@@ -2478,6 +2532,7 @@ void cm_destroy(cm_ctx *ctx) {
     for (auto &s : ctx->slots) {
         free_all(ctx, s.idx_allocs);
         free_all(ctx, s.ann_allocs);
+        drop_entry_near(ctx, s);
     }
     release(ctx, CONTEXT);                 // (the grow-only output staging of cm_collect_* outlives a batch)
     if (ctx->h_pin) report_hip(ctx, "hipHostFree", hipHostFree(ctx->h_pin));
@@ -2489,6 +2544,26 @@ void cm_destroy(cm_ctx *ctx) {
 }
 
 const char *cm_last_error(const cm_ctx *ctx) { return ctx ? ctx->err.c_str() : "null context"; }
+
+// Slot::entry_near of a slot whose index and annotation are both in place (else nothing); synchronises ctx->st.B
+static int make_entry_near(cm_ctx *ctx, Slot &s) {
+    drop_entry_near(ctx, s);
+    if (!s.loaded || !s.has_annot || s.X.n_entries == 0) return CM_OK;
+    if (s.X.ref_len > 0x80000000u) return CM_OK;          // k_chain_heavy carries the bit in bit 31 of a position
+    const uint64_t n = s.X.n_entries;
+    uint64_t *d = nullptr;
+    if (hipMalloc((void **)&d, (size_t)((n + 63) / 64) * sizeof(uint64_t)) != hipSuccess) {      // not enough HBM: the kernel reads the position bitset
+        (void)hipGetLastError();
+        return CM_OK;
+    }
+    s.entry_near = d;
+    hipLaunchKernelGGL(k_entry_near, dim3((unsigned)((n + BLK - 1) / BLK)), dim3(BLK), 0, ctx->st.B, s.X.pos, n, s.A.near_border_bits, (uint64_t)s.A.n_bits, d);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->st.B);
+    if (e != hipSuccess) drop_entry_near(ctx, s);          // (the caller gives the slot up)
+    HIPCHK(ctx, e);
+    return CM_OK;
+}
 
 // bucket descriptors + the final synchronisation of a contig load (s.X holds the device arrays)
 static int finish_contig(cm_ctx *ctx, Slot &s) {
@@ -2508,7 +2583,7 @@ static int finish_contig(cm_ctx *ctx, Slot &s) {
     }
     HIPCHK(ctx, hipStreamSynchronize(ctx->st.B));
     s.loaded = true;
-    return CM_OK;
+    return make_entry_near(ctx, s);
 }
 
 int cm_load_contig(cm_ctx *ctx, int slot, const cm_index_view *iv) {
@@ -2518,6 +2593,7 @@ int cm_load_contig(cm_ctx *ctx, int slot, const cm_index_view *iv) {
     HIPCHK(ctx, hipSetDevice(ctx->P.device));
     Slot &s = ctx->slots[slot];
     free_all(ctx, s.idx_allocs);
+    drop_entry_near(ctx, s);
     s.d_desc = nullptr;
     s.loaded = false;
     ++s.gen;
@@ -2558,6 +2634,7 @@ int cm_load_contig_raw(cm_ctx *ctx, int slot, const cm_index_raw *raw) {
     HIPCHK(ctx, hipSetDevice(ctx->P.device));
     Slot &s = ctx->slots[slot];
     free_all(ctx, s.idx_allocs);
+    drop_entry_near(ctx, s);
     s.d_desc = nullptr;
     s.loaded = false;
     ++s.gen;
@@ -2785,6 +2862,7 @@ int cm_build_contig(cm_ctx *ctx, int slot, int32_t contig_num, const uint8_t *ge
     HIPCHK(ctx, hipSetDevice(ctx->P.device));
     Slot &s = ctx->slots[slot];
     free_all(ctx, s.idx_allocs);
+    drop_entry_near(ctx, s);
     s.d_desc = nullptr;
     s.loaded = false;
     ++s.gen;
@@ -2832,6 +2910,7 @@ int cm_load_annotation(cm_ctx *ctx, int slot, const cm_annot_view *av) {
     HIPCHK(ctx, hipSetDevice(ctx->P.device));
     Slot &s = ctx->slots[slot];
     free_all(ctx, s.ann_allocs);
+    drop_entry_near(ctx, s);
     s.has_annot = false;
     ++s.gen;
     cmc::AnnotAosHost aos;
@@ -2871,7 +2950,7 @@ int cm_load_annotation(cm_ctx *ctx, int slot, const cm_annot_view *av) {
         s.chain_parallel_ok = ok;
     }
     s.has_annot = true;
-    return CM_OK;
+    return make_entry_near(ctx, s);
 }
 
 int cm_unload_contig(cm_ctx *ctx, int slot) {
@@ -2880,6 +2959,7 @@ int cm_unload_contig(cm_ctx *ctx, int slot) {
     (void)hipStreamSynchronize(ctx->st.B);
     free_all(ctx, ctx->slots[slot].idx_allocs);
     free_all(ctx, ctx->slots[slot].ann_allocs);
+    drop_entry_near(ctx, ctx->slots[slot]);
     ctx->slots[slot].loaded = ctx->slots[slot].has_annot = false;
     ctx->slots[slot].d_desc = nullptr;
     ++ctx->slots[slot].gen;
