@@ -2587,4 +2587,66 @@ CM_HD inline void finish_round(const Core &c, int state, int is_last, int len1, 
     }
 }
 
+// ------------------------------------------------------------------------------------------
+// Test hook (cm_dp_batch: k_dp_probe in cm_hot.hip; emu_dp_batch in tests/hostemu.cpp): one
+// cm_dp_req through the wrapper its kind names, with the views as given.
+// ------------------------------------------------------------------------------------------
+CM_HD inline void dp_req_views(g_u8 arena, const cm_dp_req &q, SV &s, SV &t) {
+    s = SV{arena, q.s_off, q.s_step, q.s_mode};
+    t = SV{arena, q.t_off, q.t_step, q.t_mode};
+}
+// res: ret, sc_len, indel, score (0 where the kind has none)
+CM_HD inline void dp_req_run(const Core &c, const DpMem &sm, g_u8 arena, const cm_dp_req &q, int32_t res[4]) {
+    SV s, t;
+    dp_req_views(arena, q, s, t);
+    int sc_len = 0, indel = 0, score = 0, ret;
+    if (q.kind == 0) ret = one_side_banded(c, sm, s, q.n, t, q.m, q.arg);
+    else if (q.kind == 1) ret = local_alignment_side(c, sm, s, q.n, t, q.m, q.arg != 0, indel, score);
+    else ret = local_alignment_sc(c, sm, s, q.n, t, q.m, sc_len, indel, score);
+    res[0] = ret;
+    res[1] = sc_len;
+    res[2] = indel;
+    res[3] = score;
+}
+// The resumable band-3 X-drop DP as the heavy-pair pipeline runs it (hp_answer_or_queue + k_hp_dp in cm_heavy_pipe.h), up to the
+// point where the DP is in flight: closed form and capacity check answer at once (true), otherwise the strings are staged and L
+// is begun (false): the caller advances L while L.go and ends it with xdrop_w3_end.
+CM_HD inline bool dp_req_begin_w3(const Core &c, const DpMem &sm, g_u8 arena, const cm_dp_req &q, XdropLane &L, int32_t res[4]) {
+    SV s, t;
+    dp_req_views(arena, q, s, t);
+    res[0] = res[1] = res[2] = 0;
+    res[3] = q.m * SC_MAT;
+    if (sc_closed_form(s, q.n, t, q.m)) return true;
+    if (!dp_fits(sm, q.n, q.m)) {                              // what local_alignment_sc returns for strings beyond the buffers
+        res[0] = c.P.max_ed + 1;
+        res[1] = cmax(c.P.max_sc, q.m) + 1;
+        res[2] = c.P.band + 1;
+        res[3] = 0;
+        return true;
+    }
+    stage(s, q.n, sm.a, 4);
+    stage(t.rev(q.m), q.m, sm.b, 5);                           // the band-3 DP walks the read residual from its far end
+    xdrop_w3_begin(L, sm.a, q.n, sm.b, q.m, (sm.a.cap < sm.b.cap ? sm.a.cap : sm.b.cap) - 1);
+    return false;
+}
+// (host side) What is checked before a request batch runs: 0, or 1 + the index of the first bad request (-1: a bad argument).
+inline long long dp_req_check(const cm_params &P, uint64_t arena_len, const cm_dp_req *req, uint32_t n_req, int str_cap, int arrangement) {
+    if (str_cap < 8 || str_cap > 1016 || (str_cap & 7)) return -1;
+    if (P.band < 0 || P.band > MAX_BAND || P.max_ed < 0 || P.max_sc < 0) return -1;
+    if (arrangement != 0 && !(arrangement == 1 && P.band == 3)) return -1;
+    auto inside = [&](int32_t off, int32_t step, int32_t mode, int32_t len) {
+        if ((step != 1 && step != -1) || mode < 0 || mode > 2 || len < 0 || off < 0) return false;
+        const long long lo = step > 0 ? (long long)off : (long long)off - len + 1, hi = step > 0 ? (long long)off + len : (long long)off + 1;   // [lo, hi)
+        return lo - CM_STAGE_PAD >= 0 && hi + CM_STAGE_PAD <= (long long)arena_len;
+    };
+    for (uint32_t r = 0; r < n_req; ++r) {
+        const cm_dp_req &q = req[r];
+        bool ok = q.kind >= 0 && q.kind <= 2 && inside(q.s_off, q.s_step, q.s_mode, q.n) && inside(q.t_off, q.t_step, q.t_mode, q.m);
+        if (q.kind == 0) ok = ok && q.arg >= 0 && q.arg <= P.band && q.m == q.n + q.arg;      // "m == n + w in every call"
+        if (arrangement == 1) ok = ok && q.kind == 2;
+        if (!ok) return 1 + (long long)r;
+    }
+    return 0;
+}
+
 }  // namespace cmc

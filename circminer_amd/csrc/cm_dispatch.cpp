@@ -43,6 +43,7 @@ CM_VARIANTS(int, cm_reads_download, (void *, cm_mapped_read *, int32_t *, uint8_
 CM_VARIANTS(int, cm_map_batch, (void *, int, int, const cm_reads *, const cm_mapped_read *, cm_mapped_read *, int32_t *))
 CM_VARIANTS(int, cm_seed_batch, (void *, int, uint32_t *, uint32_t *, uint32_t *, uint32_t, uint32_t *))
 CM_VARIANTS(int, cm_chain_batch, (void *, int, void *, int32_t *, int32_t *))
+CM_VARIANTS(int, cm_dp_batch, (void *, const cm_params *, const uint8_t *, uint64_t, const cm_dp_req *, uint32_t, int, uint32_t, int, uint32_t, cm_dp_res *))
 CM_VARIANTS(int, cm_debug_lane_clk, (void *, unsigned long long *))
 CM_VARIANTS(int, cm_debug_counters, (void *, unsigned long long *))
 CM_VARIANTS(int, cm_prof_enable, (void *, int))
@@ -113,6 +114,10 @@ int cm_chain_batch(cm_ctx *ctx, int slot, cm_chain *out, int32_t *nchain, int32_
     if (!ctx) return CM_EINVAL;
     if (ctx->wide) return CM_ELIMIT;          // cm_chain of this ABI holds 16 fragments; the mapping entry points are not affected
     return cm_chain_batch_k16(ctx->inner, slot, out, nchain, high);
+}
+int cm_dp_batch(cm_ctx *ctx, const cm_params *P, const uint8_t *arena, uint64_t arena_len, const cm_dp_req *req, uint32_t n_req, int str_cap,
+                uint32_t lds_fill, int arrangement, uint32_t grid, cm_dp_res *out) {
+    return ctx ? GO(cm_dp_batch, P, arena, arena_len, req, n_req, str_cap, lds_fill, arrangement, grid, out) : CM_EINVAL;      // (the DP bodies are the same in both builds)
 }
 int cm_debug_lane_clk(cm_ctx *ctx, unsigned long long *out) { return ctx ? GO(cm_debug_lane_clk, out) : CM_EINVAL; }
 int cm_debug_counters(cm_ctx *ctx, unsigned long long *out) { return ctx ? GO(cm_debug_counters, out) : CM_EINVAL; }

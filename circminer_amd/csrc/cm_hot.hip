@@ -3969,6 +3969,19 @@ int cm_chain_batch(cm_ctx *ctx, int slot, cm_chain *out_chains, int32_t *out_nch
     return check_dev_err(ctx);
 }
 
+// test hook: kernel, validation and launch live in cm_dp_probe.hip (a translation unit of its own: the kernels of this file are
+// compiled exactly as they are without the hook); here only what needs the context
+extern "C" int cm_dp_probe_run(hipStream_t so, const cm_params *P, const uint8_t *arena, uint64_t arena_len, const cm_dp_req *req, uint32_t n_req,
+                               int str_cap, uint32_t lds_fill, int arrangement, uint32_t grid, cm_dp_res *out, char *err, size_t err_cap);
+int cm_dp_batch(cm_ctx *ctx, const cm_params *P, const uint8_t *arena, uint64_t arena_len, const cm_dp_req *req, uint32_t n_req, int str_cap,
+                uint32_t lds_fill, int arrangement, uint32_t grid, cm_dp_res *out) {
+    if (!ctx) return CM_EINVAL;
+    HIPCHK(ctx, hipSetDevice(ctx->P.device));
+    char msg[256] = "";
+    const int rc = cm_dp_probe_run(ctx->st.B, P, arena, arena_len, req, n_req, str_cap, lds_fill, arrangement, grid, out, msg, sizeof msg);
+    return rc == CM_OK ? CM_OK : fail(ctx, rc, "cm_dp_batch: %s", msg);
+}
+
 /* diagnostic: per-pair k_pair lane time in 100 MHz ticks (only when CM_LANE_CLK was set at upload) */
 // diagnostic builds (-DCM_CHAIN_DIAG ...): the 32 raw counter words, [8..31] = whatever the build accumulates there
 int cm_debug_counters(cm_ctx *ctx, unsigned long long *out) {

@@ -79,6 +79,19 @@ class BuildStats(C.Structure):
                 ("ms_device", C.c_double)]
 
 
+class DpReq(C.Structure):              # cm_dp_req (test hook cm_dp_batch)
+    _fields_ = [(n, C.c_int32) for n in ("kind", "s_off", "s_step", "s_mode", "n", "t_off", "t_step", "t_mode", "m", "arg")]
+
+
+class DpRes(C.Structure):              # cm_dp_res
+    _fields_ = [(n, C.c_int32) for n in ("ret", "sc_len", "indel", "score", "err")]
+
+
+DP_REQ_DTYPE = np.dtype([(n, "<i4") for n, _ in DpReq._fields_])
+DP_RES_DTYPE = np.dtype([(n, "<i4") for n, _ in DpRes._fields_])
+assert DP_REQ_DTYPE.itemsize == C.sizeof(DpReq) == 40 and DP_RES_DTYPE.itemsize == C.sizeof(DpRes) == 20
+
+
 class AnnotView(C.Structure):
     _fields_ = [("n_iv", C.c_uint32), ("iv_spos", u32p), ("iv_epos", u32p), ("iv_max_end", u32p), ("iv_min_end", u32p),
                 ("iv_max_next_exon", u32p), ("iv_seg_off", u32p), ("iv_seg", u32p),
@@ -207,6 +220,7 @@ def load(path: str = LIB_PATH) -> C.CDLL:
         "cm_type_histogram": (C.c_int, [vp, pp(C.c_uint64)]),
         "cm_seed_batch": (C.c_int, [vp, C.c_int, vp, vp, vp, C.c_uint32, pp(C.c_uint32)]),
         "cm_chain_batch": (C.c_int, [vp, C.c_int, vp, vp, vp]),
+        "cm_dp_batch": (C.c_int, [vp, pp(Params), vp, C.c_uint64, vp, C.c_uint32, C.c_int, C.c_uint32, C.c_int, C.c_uint32, vp]),
         "cm_prof_enable": (C.c_int, [vp, C.c_int]),
         "cm_prof_reset": (C.c_int, [vp]),
         "cm_prof_get": (C.c_int, [vp, pp(C.c_double), pp(C.c_uint64)]),
@@ -257,10 +271,10 @@ def load(path: str = LIB_PATH) -> C.CDLL:
         fn.restype = res
         fn.argtypes = args
     # the ctypes mirrors below must be the structs the library was compiled with
-    got = (C.c_uint32 * 16)()
-    n = L.cm_abi_sizes(got, 16)
+    got = (C.c_uint32 * 32)()
+    n = L.cm_abi_sizes(got, 32)
     mine = [C.sizeof(t) for t in (Params, IndexView, AnnotView, MappedRead, Reads, C.c_uint8 * RECORD_DTYPE.itemsize, ChrInfo, FastqBatch, MappingArgs,
-                                  MappingStats, CircRes, CircArgs, CircStats, IndexRaw, BuildStats)]
+                                  MappingStats, CircRes, CircArgs, CircStats, IndexRaw, BuildStats, DpReq, DpRes)]
     if n != len(mine) or list(got[:n]) != mine:
         raise RuntimeError(f"circminer_amd.lib: struct sizes differ from {path}: library {list(got[:max(n, 0)])}, ctypes {mine}")
     _lib = L
@@ -269,7 +283,7 @@ def load(path: str = LIB_PATH) -> C.CDLL:
 
 EXPORTED_SYMBOLS = ["cm_create", "cm_destroy", "cm_last_error", "cm_load_contig", "cm_load_contig_raw", "cm_host_next_contig_raw", "cm_load_annotation",
                     "cm_unload_contig", "cm_reads_upload", "cm_reads_stage", "cm_reads_swap", "cm_map_round", "cm_map_rounds", "cm_reads_download", "cm_map_batch",
-                    "cm_sync", "cm_reads_reset", "cm_collect_active", "cm_collect_records", "cm_collect_records_device", "cm_abi_sizes", "cm_host_alloc", "cm_host_free", "cm_host_register", "cm_host_unregister", "cm_type_histogram", "cm_write_remain_records", "cm_seed_batch", "cm_chain_batch", "cm_prof_enable", "cm_prof_reset", "cm_prof_get",
+                    "cm_sync", "cm_reads_reset", "cm_collect_active", "cm_collect_records", "cm_collect_records_device", "cm_abi_sizes", "cm_host_alloc", "cm_host_free", "cm_host_register", "cm_host_unregister", "cm_type_histogram", "cm_write_remain_records", "cm_seed_batch", "cm_chain_batch", "cm_dp_batch", "cm_prof_enable", "cm_prof_reset", "cm_prof_get",
                     "cm_prof_counters", "cm_host_build_index", "cm_host_free_index", "cm_host_index_stats", "cm_host_build_annotation",
                     "cm_host_free_annotation", "cm_host_pack_genome", "cm_host_read_index_info", "cm_host_free_index_info",
                     "cm_host_write_index", "cm_host_open_index", "cm_host_next_contig", "cm_host_next_contig_genome", "cm_host_free_loaded_contig",
@@ -768,6 +782,15 @@ class HotPath:
         hh = np.zeros(self.n * 4, np.int32)
         self._chk(self.L.cm_chain_batch(self.h, slot, ch.ctypes.data, nc.ctypes.data, hh.ctypes.data), "cm_chain_batch")
         return ch, nc, hh
+
+    def dp_batch(self, P, arena, req, str_cap, lds_fill=0, arrangement=0, grid=0):
+        """cm_dp_batch: the requests `req` (DP_REQ_DTYPE) over the byte array `arena` -> their results (DP_RES_DTYPE)"""
+        arena = np.ascontiguousarray(arena, dtype=np.uint8)
+        req = np.ascontiguousarray(req, dtype=DP_REQ_DTYPE)
+        out = np.zeros(len(req), dtype=DP_RES_DTYPE)
+        self._chk(self.L.cm_dp_batch(self.h, C.byref(P), arena.ctypes.data, arena.size, req.ctypes.data, len(req), int(str_cap), int(lds_fill) & 0xFFFFFFFF,
+                                     int(arrangement), int(grid), out.ctypes.data), "cm_dp_batch")
+        return out
 
     def prof(self, on=True):
         self._chk(self.L.cm_prof_enable(self.h, int(on)), "cm_prof_enable")

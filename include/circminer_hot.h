@@ -303,6 +303,30 @@ int cm_seed_batch(cm_ctx *ctx, int slot, uint32_t *out_start, uint32_t *out_cnt,
  * r = (pair*2 + mate)*2 + orient; out_nchain[r] chains stored at out_chains[r*CM_BESTCHAINLIM ...],
  * out_high[r] = high_hits of get_best_chains (src/filter.cpp:478-481). */
 int cm_chain_batch(cm_ctx *ctx, int slot, cm_chain *out_chains, int32_t *out_nchain, int32_t *out_high);
+/* The three alignment DPs behind every extension, one request at a time on the device (kernel k_dp_probe, one wave per
+ * workgroup).  Needs a context, but no contig, annotation or reads; `P` is the request batch's own parameter set (band, max_ed
+ * and max_sc are what the DPs read).  A string is a view into `arena`: character i is arena[off + i * step] (step +1 / -1),
+ * complemented when mode == 1, NUL when mode == 2. */
+typedef struct cm_dp_req {
+    int32_t kind;                      /* 0 one_side_banded, 1 local_alignment_side, 2 local_alignment_sc (cm_core.h) */
+    int32_t s_off, s_step, s_mode, n;  /* the first string (for kind 1, 2 the reference window) */
+    int32_t t_off, t_step, t_mode, m;  /* the second string (the read residual) */
+    int32_t arg;                       /* kind 0: w (0 .. band, m == n + w);  kind 1: rev;  kind 2: unused */
+} cm_dp_req;
+typedef struct cm_dp_res {
+    int32_t ret, sc_len, indel, score; /* the wrapper's return value and outputs (0 where the kind has none) */
+    int32_t err;                       /* the request's own device-capacity bits (8: a string longer than str_cap) */
+} cm_dp_res;
+/* str_cap: characters per staging buffer, a multiple of 8 in 8..1016 (the pair kernels' LDS layout: 2 buffers x 64 lanes).
+ * lds_fill: what every word of the workgroup's LDS holds before its first request.  grid: workgroups (0: one per 64 requests).
+ * arrangement 0: lane l of workgroup v runs requests 64 v + l, + 64 * grid, ...: the wrapper named by `kind`, as the pair
+ * kernels call it (closed forms, capacity check, staging, DP), 64 different requests in flight.
+ * arrangement 1 (kind 2 only, P->band == 3): the resumable form of the heavy-pair pipeline's DP kernel: lanes draw requests from
+ * a shared cursor when 16 or more are idle, stage, and advance their DPs in bursts of 4.
+ * Every view, extended by 64 bytes (the staging loads' pad) on both sides, must lie inside the arena: CM_EINVAL otherwise, and
+ * for a request that is none of the above.  Synchronous. */
+int cm_dp_batch(cm_ctx *ctx, const cm_params *P, const uint8_t *arena, uint64_t arena_len, const cm_dp_req *req, uint32_t n_req,
+                int str_cap, uint32_t lds_fill, int arrangement, uint32_t grid, cm_dp_res *out);
 
 /* ---------------- timing hooks for bench.py (HIP events on the ctx stream) ---------------- */
 /* Milliseconds spent in each kernel class since the last cm_prof_reset(), and launch counts:
@@ -544,7 +568,8 @@ typedef struct cm_circ_args {
 int cm_circ_run(const cm_circ_args *args, cm_circ_stats *stats, char *err, uint64_t err_cap);
 
 /* sizeof of the structs above, in this order: cm_params, cm_index_view, cm_annot_view, cm_mapped_read, cm_reads, cm_record,
- * cm_chr_info, cm_fastq_batch, cm_mapping_args, cm_mapping_stats, cm_circ_res, cm_circ_args, cm_circ_stats, cm_index_raw, cm_build_stats -- for a binding to
+ * cm_chr_info, cm_fastq_batch, cm_mapping_args, cm_mapping_stats, cm_circ_res, cm_circ_args, cm_circ_stats, cm_index_raw, cm_build_stats, cm_dp_req,
+ * cm_dp_res -- for a binding to
  * check its mirrors of them against the library it loaded.  Returns the number of entries written (cap must hold them). */
 int cm_abi_sizes(uint32_t *out, uint32_t cap);
 

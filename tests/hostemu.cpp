@@ -271,6 +271,39 @@ uint32_t emu_probe(const cm_params *P, const cm_index_view *X, const uint8_t *se
     *touches = pr.touches;
     return pr.raw;
 }
+// cm_dp_batch on the host: the same requests through the host build of the same wrappers (cmc::dp_req_run), one after the other
+// over ONE pair of staging buffers of str_cap characters -- exactly (str_cap / 8 + 1) words each, on the heap, so that an access
+// beyond them is visible to a sanitizer -- filled with lds_fill before the first request.  arrangement 1: the resumable band-3
+// DP (begin / advance / end) instead of the wrapper.  Returns CM_EINVAL for what cm_dp_batch refuses.
+int emu_dp_batch(const cm_params *P, const uint8_t *arena, uint64_t arena_len, const cm_dp_req *req, uint32_t n_req, int str_cap, uint32_t lds_fill,
+                 int arrangement, cm_dp_res *out) {
+    if (!P || !arena || (n_req && (!req || !out))) return CM_EINVAL;
+    if (cmc::dp_req_check(*P, arena_len, req, n_req, str_cap, arrangement) != 0) return CM_EINVAL;
+    Core c{};
+    c.P = *P;
+    const size_t words = (size_t)str_cap / 8 + 1;
+    std::vector<uint32_t> bufa(words, lds_fill), bufb(words, lds_fill);
+    for (uint32_t r = 0; r < n_req; ++r) {
+        int err = 0;
+        const cmc::DpMem sm{cmc::LBuf{(uint8_t *)bufa.data(), str_cap}, cmc::LBuf{(uint8_t *)bufb.data(), str_cap}, &err};
+        int32_t v[4];
+        if (arrangement == 0) cmc::dp_req_run(c, sm, arena, req[r], v);
+        else {
+            cmc::XdropLane L;
+            if (!cmc::dp_req_begin_w3(c, sm, arena, req[r], L, v)) {
+                const int top = str_cap - 1;
+                while (L.go) cmc::xdrop_w3_advance(L, sm.a, sm.b, top);
+                int sc_len, indel, score;
+                v[0] = cmc::xdrop_w3_end(c, L, sc_len, indel, score);
+                v[1] = sc_len;
+                v[2] = indel;
+                v[3] = score;
+            }
+        }
+        out[r] = cm_dp_res{v[0], v[1], v[2], v[3], err};
+    }
+    return 0;
+}
 int emu_one_side(const cm_params *P, const uint8_t *s, int n, const uint8_t *t, int m, int w) {
     Core c{};
     c.P = *P;

@@ -30,6 +30,7 @@ def test_struct_layouts_match_header():
     assert C.sizeof(cl.MappedRead) == 72 and cl.MAPPED_DTYPE.itemsize == 72
     assert cl.CHAIN_DTYPE.itemsize == 8 + 4 * 16 * 2
     assert C.sizeof(cl.Params) == 48
+    assert C.sizeof(cl.DpReq) == cl.DP_REQ_DTYPE.itemsize == 40 and C.sizeof(cl.DpRes) == cl.DP_RES_DTYPE.itemsize == 20      # cm_dp_req, cm_dp_res
 
 
 def test_no_cpu_fallback_without_device():
@@ -53,6 +54,7 @@ def test_bad_params_rejected():
     for kw in (dict(kmer=13), dict(kmer=23), dict(max_chain_len=31), dict(band=9), dict(seed_lim=0)):
         P = cl.default_params(**kw)
         assert L.cm_create(C.byref(P), C.byref(h)) == -1      # CM_EINVAL before any device is touched
+    assert L.cm_dp_batch(None, C.byref(cl.default_params()), None, 0, None, 0, 144, 0, 0, 0, None) == -1      # the test hook without a context
 
 
 def test_product_does_not_reference_oracle():
