@@ -3,7 +3,8 @@
 //
 // A translation unit of its own, compiled once: the DP bodies do not depend on CM_MAX_CHAIN_FRAGS, and with the probe in
 // cm_hot.hip the compiler inlines the bodies differently into k_pair, k_pair_heavy and k_hp_tasks (other scratch sizes and spill
-// counts) -- a test hook must not change the product's kernels.  What runs here is the same source as theirs, compiled apart.
+// counts) -- a test hook must not change the product's kernels.  What runs here is the same source as theirs (the DP bodies of
+// cm_core.h, the staging layout and the queue loop of cm_dp_engine.h), compiled apart.
 #include <hip/hip_runtime.h>
 
 #include <atomic>
@@ -17,26 +18,19 @@ using cmc::Core;
 
 namespace {
 
-constexpr int BLK_PAIR = 64;
-#ifndef CM_PAIR_WAVES
-#define CM_PAIR_WAVES 4
-#endif
-// as in cm_hot.hip: bytes one staged string of `cap` characters takes per lane (eight codes per word + one spare word)
-__host__ __device__ constexpr int lbuf_bytes(int cap) { return (cap / 8 + 1) * 4; }
+#include "cm_dp_engine.h"              // BLK_PAIR, lbuf_bytes, lane_dp_mem, dp_queue_loop: what the product's kernels use
 
-// DpMem exactly as pair_kernel (cm_hot.hip) sets it up: dynamic LDS of 2 * lbuf_bytes(str_cap) * 64 bytes, lane_base = lds + 4 * lane,
-// the second buffer lbuf_bytes(str_cap) * 64 bytes further; sm.err = the request's own err word.
-// arrangement 0: the call as k_pair / k_hp_tasks make it, 64 different requests per wave.  arrangement 1: the loop of k_hp_dp
-// (cm_heavy_pipe.h; a copy: that kernel takes its requests from the pipeline's tables), the queue being the request array itself.
+// DpMem as every pair kernel of cm_hot.hip sets it up (lane_dp_mem): dynamic LDS of 2 * lbuf_bytes(str_cap) * 64 bytes; sm.err = the
+// request's own err word.
+// arrangement 0: the call as k_pair / k_hp_tasks make it, 64 different requests per wave.  arrangement 1: dp_queue_loop, the loop
+// k_hp_dp (cm_heavy_pipe.h) runs -- that kernel's requests come from the pipeline's tables, here the queue is the request array itself.
 __global__ void __launch_bounds__(BLK_PAIR, CM_PAIR_WAVES) k_dp_probe(cm_params P, const uint8_t *arena, const cm_dp_req *req, uint32_t n_req, int str_cap,
                                                                        uint32_t lds_fill, int arrangement, unsigned int *cursor, cm_dp_res *out) {
     extern __shared__ uint32_t lds_words[];
     const int lane = threadIdx.x;
-    CM_S uint8_t *lane_base = (CM_S uint8_t *)lds_words + 4 * lane;
-    const int str_stride = lbuf_bytes(str_cap) * BLK_PAIR;
-    for (int i = lane; i < 2 * str_stride / 4; i += BLK_PAIR) lds_words[i] = lds_fill;      // what the buffers hold before the first request
+    for (int i = lane; i < 2 * lbuf_bytes(str_cap) * BLK_PAIR / 4; i += BLK_PAIR) lds_words[i] = lds_fill;      // what the buffers hold before the first request
     __syncthreads();
-    cmc::DpMem sm{cmc::LBuf{lane_base, str_cap}, cmc::LBuf{lane_base + str_stride, str_cap}, nullptr};
+    cmc::DpMem sm = lane_dp_mem((CM_S uint8_t *)lds_words, lane, str_cap, nullptr);
     Core c{};
     c.P = P;
     const cmc::g_u8 ar = (cmc::g_u8)arena;
@@ -56,46 +50,22 @@ __global__ void __launch_bounds__(BLK_PAIR, CM_PAIR_WAVES) k_dp_probe(cm_params 
         }
         return;
     }
-    const unsigned long long lt_mask = (1ull << lane) - 1ull;
-    constexpr int REFILL = 16, BURST = 4;
-    const int top = (sm.a.cap < sm.b.cap ? sm.a.cap : sm.b.cap) - 1;
-    cmc::XdropLane L;
-    L.go = false;
-    bool busy = false, dry = false;
     uint32_t my_r = 0;
-    for (;;) {
-        const unsigned long long idle_m = __ballot(!busy);
-        const int n_idle = __popcll(idle_m);
-        if (!dry && (n_idle >= REFILL)) {
-            unsigned int base = 0;
-            if (lane == 0) base = atomicAdd(cursor, (unsigned int)n_idle);
-            base = (unsigned int)__shfl((int)base, 0);
-            if (base + (unsigned int)n_idle >= n_req) dry = true;               // the queue has nothing beyond this hand-out
-            const unsigned int mine = base + (unsigned int)__popcll(idle_m & lt_mask);
-            if (!busy && mine < n_req) {
-                my_r = mine;
-                const cm_dp_req q = req[my_r];
-                sm.err = (cmc::g_err)&out[my_r].err;
-                int32_t v[4];
-                if (cmc::dp_req_begin_w3(c, sm, ar, q, L, v)) put(my_r, v);     // answered without a DP: the lane stays idle
-                else busy = true;
-            }
-        } else if (n_idle == 64) break;                                      // nothing in flight, nothing left to hand out
-        for (int it = 0; it < BURST; ++it) {
-            if (busy && L.go) cmc::xdrop_w3_advance(L, sm.a, sm.b, top);
-            if (__ballot(busy && L.go) == 0ull) break;
-        }
-        if (busy && !L.go) {                                                 // ended: its answer out, the lane is free
-            int sc_len, indel, score;
+    dp_queue_loop(sm, lane, cursor, n_req,
+        [&](unsigned int mine, cmc::XdropLane &L, int) {                    // (dp_req_begin_w3 works the band's top out itself)
+            my_r = mine;
+            const cm_dp_req q = req[my_r];
+            sm.err = (cmc::g_err)&out[my_r].err;
             int32_t v[4];
-            v[0] = cmc::xdrop_w3_end(c, L, sc_len, indel, score);
-            v[1] = sc_len;
-            v[2] = indel;
-            v[3] = score;
+            if (!cmc::dp_req_begin_w3(c, sm, ar, q, L, v)) return true;
+            put(my_r, v);                                                   // answered without a DP: the lane stays idle
+            return false;
+        },
+        [&](const cmc::XdropLane &L) {
+            int32_t v[4];
+            v[0] = cmc::xdrop_w3_end(c, L, v[1], v[2], v[3]);          // (ret, sc_len, indel, score)
             put(my_r, v);
-            busy = false;
-        }
-    }
+        });
 }
 
 }  // namespace

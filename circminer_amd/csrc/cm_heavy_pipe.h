@@ -8,7 +8,7 @@
 //
 //   plan     (wave = HG pairs, as before)  chain ends, pairing predicates -> the pairs' task lists (HBM) and the four fall-back
 //                                          DP requests of every task: exact matches answered in closed form, the rest queued
-//   dp       (lane = one DP in flight)     the tile's queue of DP requests through cmc::XdropLane, lanes refilled as their DPs end
+//   dp       (lane = one DP in flight)     the tile's queue of DP requests through dp_queue_loop (cm_dp_engine.h), lanes refilled as their DPs end
 //   tasks    (lane = one mate-pair task)   extend_task with its answers at hand -> outcome (HBM)
 //   fold     (lane = one pair)             the outcomes in (i, j) order into the pair's MatchedRead; which unpaired chains to extend
 //   unp_req  (lane = one chain end)        their DP requests;  dp again;
@@ -100,10 +100,10 @@ __device__ inline void hp_answer_or_queue(const cmc::DpMem &sm, bool in_range, b
     }
 }
 
-// cm_prof_counters [5] = pairs handed to the fall-back list, [6] = those handed over in the second attempt (rare paths: one atomic each)
+// cm_prof_counters [CN_FALL] = pairs handed to the fall-back list, [CN_FALL_2ND] = those handed over in the second attempt (rare paths: one atomic each)
 __device__ inline void hp_count_fall(unsigned long long *counters, int attempt) {
-    atomicAdd(&counters[5], 1ull);
-    if (attempt) atomicAdd(&counters[6], 1ull);
+    atomicAdd(&counters[CN_FALL], 1ull);
+    if (attempt) atomicAdd(&counters[CN_FALL_2ND], 1ull);
 }
 
 // ---- plan ------------------------------------------------------------------------------------------------------------------
@@ -324,58 +324,35 @@ __global__ void __launch_bounds__(BLK_PAIR, 6) k_hp_plan(KCore kc, ReadsDev rd, 
 __global__ void __launch_bounds__(BLK_PAIR, 8) k_hp_dp(KCore kc, ReadsDev rd, uint64_t pair0, int attempt, HPipe P, int mode, int str_cap) {
     extern __shared__ uint32_t lds_words[];
     const int lane = threadIdx.x;
-    CM_S uint8_t *lane_base = (CM_S uint8_t *)lds_words + 4 * lane;
-    const int str_stride = lbuf_bytes(str_cap) * BLK_PAIR;
-    cmc::DpMem sm{cmc::LBuf{lane_base, str_cap}, cmc::LBuf{lane_base + str_stride, str_cap}, nullptr};
+    cmc::DpMem sm = lane_dp_mem((CM_S uint8_t *)lds_words, lane, str_cap, nullptr);
     const Core c = cmc::to_core(kc);
     const uint32_t *queue = mode ? P.q2 : P.q;
     cmc::PreDP *pre = mode ? P.pre2 : P.pre;
     const unsigned int tail = P.ctr[mode ? HC_Q2 : HC_Q1];
     unsigned int *cursor = &P.ctr[mode ? HC_Q2CUR : HC_Q1CUR];
-    const unsigned long long lt_mask = (1ull << lane) - 1ull;
-    constexpr int REFILL = 16, BURST = 4;
-    const int top = (sm.a.cap < sm.b.cap ? sm.a.cap : sm.b.cap) - 1;
-    cmc::XdropLane L;
-    L.go = false;
-    bool busy = false, dry = false;
     uint32_t my_r = 0;
-    for (;;) {
-        const unsigned long long idle_m = __ballot(!busy);
-        const int n_idle = __popcll(idle_m);
-        if (!dry && (n_idle >= REFILL)) {
-            unsigned int base = 0;
-            if (lane == 0) base = atomicAdd(cursor, (unsigned int)n_idle);
-            base = (unsigned int)__shfl((int)base, 0);
-            if (base + (unsigned int)n_idle >= tail) dry = true;             // the queue has nothing beyond this hand-out
-            const unsigned int mine = base + (unsigned int)__popcll(idle_m & lt_mask);
-            if (!busy && mine < tail) {
-                my_r = queue[mine];
-                const cmc::PreDP e = pre[my_r];                            // the request's identity = the two views (cmc::pre_key)
-                const int n = (int)(e.key & 1023u), m = (int)((e.key >> 10) & 1023u), t_off = (int)((e.key >> 20) & 1023u);
-                const bool sneg = (e.key >> 30) & 1u, back = (e.key >> 31) & 1u;
-                const uint32_t h = mode ? P.U[my_r >> 1].h : P.T[my_r >> 2].h;
-                const HPair &hp = P.hp[h];
-                const HReadsOf R = hp_reads(rd, pair0, hp.t, (attempt == 0) == (hp.first != 0));
-                const cmc::SV sv{c.X.genome, (int32_t)e.s_off, sneg ? -1 : 1, 0};
-                const cmc::SV tv{back ? R.bseq : R.fseq, t_off, (back != sneg) ? -1 : 1, back ? 1 : 0};
-                cmc::stage(sv, n, sm.a, 4);
-                cmc::stage(tv.rev(m), m, sm.b, 5);                        // the band-3 DP walks the read residual from its far end
-                cmc::xdrop_w3_begin(L, sm.a, n, sm.b, m, top);
-                busy = true;
-            }
-        } else if (n_idle == 64) break;                                  // nothing in flight, nothing left to hand out
-        for (int it = 0; it < BURST; ++it) {
-            if (busy && L.go) cmc::xdrop_w3_advance(L, sm.a, sm.b, top);
-            if (__ballot(busy && L.go) == 0ull) break;
-        }
-        if (busy && !L.go) {                                             // ended: its answer into the table, the lane is free
+    dp_queue_loop(sm, lane, cursor, tail,
+        [&](unsigned int mine, cmc::XdropLane &L, int top) {
+            my_r = queue[mine];
+            const cmc::PreDP e = pre[my_r];                            // the request's identity = the two views (cmc::pre_key)
+            const int n = (int)(e.key & 1023u), m = (int)((e.key >> 10) & 1023u), t_off = (int)((e.key >> 20) & 1023u);
+            const bool sneg = (e.key >> 30) & 1u, back = (e.key >> 31) & 1u;
+            const uint32_t h = mode ? P.U[my_r >> 1].h : P.T[my_r >> 2].h;
+            const HPair &hp = P.hp[h];
+            const HReadsOf R = hp_reads(rd, pair0, hp.t, (attempt == 0) == (hp.first != 0));
+            const cmc::SV sv{c.X.genome, (int32_t)e.s_off, sneg ? -1 : 1, 0};
+            const cmc::SV tv{back ? R.bseq : R.fseq, t_off, (back != sneg) ? -1 : 1, back ? 1 : 0};
+            cmc::stage(sv, n, sm.a, 4);
+            cmc::stage(tv.rev(m), m, sm.b, 5);                        // the band-3 DP walks the read residual from its far end
+            cmc::xdrop_w3_begin(L, sm.a, n, sm.b, m, top);
+            return true;
+        },
+        [&](const cmc::XdropLane &L) {                                 // its answer into the table
             int sc_len, indel, score;
             const int ed = cmc::xdrop_w3_end(c, L, sc_len, indel, score);
             pre[my_r].res = cmc::pre_pack(ed, sc_len, indel);
             pre[my_r].score = score;
-            busy = false;
-        }
-    }
+        });
 }
 
 // ---- tasks -----------------------------------------------------------------------------------------------------------------
@@ -384,9 +361,7 @@ __global__ void __launch_bounds__(BLK_PAIR, CM_PAIR_WAVES) k_hp_tasks(KCore kc, 
                                                                        const uint32_t *order, const unsigned int *n_order) {
     extern __shared__ uint32_t lds_words[];
     const int lane = threadIdx.x;
-    CM_S uint8_t *lane_base = (CM_S uint8_t *)lds_words + 4 * lane;
-    const int str_stride = lbuf_bytes(str_cap) * BLK_PAIR;
-    cmc::DpMem sm{cmc::LBuf{lane_base, str_cap}, cmc::LBuf{lane_base + str_stride, str_cap}, nullptr};
+    cmc::DpMem sm = lane_dp_mem((CM_S uint8_t *)lds_words, lane, str_cap, nullptr);
     const Core c = cmc::to_core(kc);
     const cmc::Ext ext(c, sm);
     const int kmer = c.P.kmer;
@@ -451,9 +426,9 @@ __global__ void __launch_bounds__(BLK_PAIR, 8) k_hp_fold(KCore kc, uint64_t pair
             if (cmc::fold_task(c, r1, r2, o.is_left != 0, o.ok != 0, o.row, o.pair_type, r1_fwd, mr)) {
                 early = true;
 #if defined(CM_HP_DIAG)      // tasks the reference's sequential loop would have run (it returns from inside the loop here)
-                atomicAdd(&counters[26], (unsigned long long)(k + 1));
-                atomicAdd(&counters[27], 1ull);
-                if (k == 0) atomicAdd(&counters[28], 1ull);
+                atomicAdd(&counters[CN_HP_SEQ_TASKS], (unsigned long long)(k + 1));
+                atomicAdd(&counters[CN_HP_EARLY], 1ull);
+                if (k == 0) atomicAdd(&counters[CN_HP_EARLY_FIRST], 1ull);
 #endif
                 break;
             }
@@ -462,13 +437,13 @@ __global__ void __launch_bounds__(BLK_PAIR, 8) k_hp_fold(KCore kc, uint64_t pair
             g1 = (r1.exons_spos >= 0) || (r1.exons_epos >= 0);
             g2 = (r2.exons_spos >= 0) || (r2.exons_epos >= 0);
         }
-#if defined(CM_HP_DIAG)      // unpaired chains there are (counters[24]) against unpaired chains that get extended (HC_UNP)
-        atomicAdd(&counters[24], (unsigned long long)(__popc(~hp.fp & (hp.nf >= 32 ? 0xffffffffu : ((1u << hp.nf) - 1u))) +
+#if defined(CM_HP_DIAG)      // unpaired chains there are (CN_HP_UNPAIRED) against unpaired chains that get extended (HC_UNP)
+        atomicAdd(&counters[CN_HP_UNPAIRED], (unsigned long long)(__popc(~hp.fp & (hp.nf >= 32 ? 0xffffffffu : ((1u << hp.nf) - 1u))) +
                                                       __popc(~hp.bp & (hp.nb >= 32 ? 0xffffffffu : ((1u << hp.nb) - 1u)))));
-        atomicAdd(&counters[25], (unsigned long long)(hp.nf + hp.nb));
+        atomicAdd(&counters[CN_HP_CHAINS], (unsigned long long)(hp.nf + hp.nb));
 #endif
 #if defined(CM_HP_DIAG)
-        if (!early) atomicAdd(&counters[26], (unsigned long long)hp.ntask);
+        if (!early) atomicAdd(&counters[CN_HP_SEQ_TASKS], (unsigned long long)hp.ntask);
 #endif
         // does the pair go on to the unpaired-chain extensions? (src/filter.cpp:344-393)
         int a = -1;
@@ -560,9 +535,7 @@ __global__ void __launch_bounds__(BLK_PAIR, CM_PAIR_WAVES) k_hp_unp(KCore kc, Re
                                                                      uint32_t *pair_err, int str_cap) {
     extern __shared__ uint32_t lds_words[];
     const int lane = threadIdx.x;
-    CM_S uint8_t *lane_base = (CM_S uint8_t *)lds_words + 4 * lane;
-    const int str_stride = lbuf_bytes(str_cap) * BLK_PAIR;
-    cmc::DpMem sm{cmc::LBuf{lane_base, str_cap}, cmc::LBuf{lane_base + str_stride, str_cap}, nullptr};
+    cmc::DpMem sm = lane_dp_mem((CM_S uint8_t *)lds_words, lane, str_cap, nullptr);
     const Core c = cmc::to_core(kc);
     const cmc::Ext ext(c, sm);
     const int kmer = c.P.kmer;
@@ -602,9 +575,9 @@ __global__ void __launch_bounds__(BLK_PAIR, 8) k_hp_finish(KCore kc, uint64_t pa
     const Core c = cmc::to_core(kc);
     const unsigned int n_items = attempt == 0 ? *n_heavy_p : *n_lst_p;
     const unsigned int x = blockIdx.x * BLK_PAIR + threadIdx.x;
-#if defined(CM_HP_DIAG)      // per attempt: pairs, tasks, unpaired chains, DP requests of both queues, fall-backs -> counters[8 + 8 * attempt ..]
+#if defined(CM_HP_DIAG)      // per attempt: pairs, tasks, unpaired chains, DP requests of both queues, fall-backs -> counters[CN_HP_ATTEMPT + CN_HP_STRIDE * attempt ..]
     if (x == 0) {
-        unsigned long long *o = counters + 8 + 8 * attempt;
+        unsigned long long *o = counters + CN_HP_ATTEMPT + CN_HP_STRIDE * attempt;
         atomicAdd(&o[0], (unsigned long long)n_items);
         atomicAdd(&o[1], (unsigned long long)P.ctr[HC_TASKS]);
         atomicAdd(&o[2], (unsigned long long)P.ctr[HC_UNP]);
@@ -676,7 +649,7 @@ __global__ void __launch_bounds__(BLK_PAIR, 8) k_hp_finish(KCore kc, uint64_t pa
             state[p] = mr;
             active[p] = act;
             cat[p] = st;
-            atomicAdd(&counters[3], 1ull);
+            atomicAdd(&counters[CN_PAIR_ROUNDS], 1ull);
         }
     }
 }

@@ -38,10 +38,36 @@ constexpr uint32_t TILE_PAIRS = 1u << 20;          // pairs per launch group (wo
 constexpr uint32_t TILE_PAIRS_MAX = 1u << 21;      // ... up to this for batches of more than two such groups (prepare_resident)
 constexpr int BLK = 256;
 constexpr int BLK_CHAIN = 64;
-constexpr int BLK_PAIR = 64;
-// bytes one staged string of `cap` characters takes per lane (cm_core.h LBuf: eight codes per word + one spare word)
-__host__ __device__ constexpr int lbuf_bytes(int cap) { return (cap / 8 + 1) * 4; }
+#include "cm_dp_engine.h"          // BLK_PAIR, CM_PAIR_WAVES, lbuf_bytes, lane_dp_mem, dp_queue_loop
 
+// Profile classes: the index of cm_ctx::ms[] / launches[], of Timer, launch() and cm_prof_get (include/circminer_hot.h).  PC_NONE:
+// a launch no class counts (index build, collect, the small housekeeping kernels).
+enum ProfClass { PC_NONE = -1, PC_SEED = 0, PC_CHAIN = 1, PC_PAIR = 2, PC_SCAN = 3, PC_HEAVY = 4, PC_ORDER = 5, PC_CHAIN_HEAVY = 6, PC_PREFETCH = 7, PC_COUNT = 8 };
+// The words of cm_ctx::d_counters.  0 - 6 are public (cm_prof_counters, include/circminer_hot.h); from 8 on what a diagnostic build
+// accumulates, read by the scripts of tests/diag through cm_debug_counters at these indices.  The two diagnostic builds overlap (they
+// are never one build): both write word 24.
+enum Counter {
+    CN_PROBES = 0 /* + 1: touches, + 2: hits (k_seed) */, CN_PAIR_ROUNDS = 3, CN_RERUN = 4 /* ... mapped by the re-run launch */,
+    CN_FALL = 5, CN_FALL_2ND = 6,                    // pairs the pipeline handed to its fall-back list; those of the second attempt
+    // -DCM_CHAIN_DIAG (k_chain_heavy): lane sums [5], wave time per phase [3], wave time per DP step [4], shape of the back-tracking
+    CN_CD_LANE = 8, CN_CD_PHASE = 13, CN_CD_WAVE = 16, CN_CD_EVENTS = 20, CN_CD_LEVELS = 21, CN_CD_PROBLEMS = 22, CN_CD_PASSES = 23, CN_CD_CELLS = 24,
+    // -DCM_HP_DIAG (cm_heavy_pipe.h): list sizes per attempt [6] at CN_HP_ATTEMPT + CN_HP_STRIDE * attempt, then the fold's counts
+    CN_HP_ATTEMPT = 8, CN_HP_STRIDE = 8, CN_HP_UNPAIRED = 24, CN_HP_CHAINS = 25, CN_HP_SEQ_TASKS = 26, CN_HP_EARLY = 27, CN_HP_EARLY_FIRST = 28,
+    CN_WORDS = 32
+};
+static_assert(CN_CD_CELLS < CN_WORDS && CN_HP_EARLY_FIRST < CN_WORDS && CN_HP_ATTEMPT + CN_HP_STRIDE + 5 < CN_HP_UNPAIRED, "d_counters has CN_WORDS words");
+// The 64-bit words of the page-locked landing zone of the scalar read-backs (cm_ctx::h_pin).
+enum Pin {
+    PIN_COLLECT_N = 0, PIN_COLLECT_ERR = 1,          // cm_collect_*: active pairs, the device error word
+    PIN_DEV_ERR = 0,                                 // check_dev_err: the device error word (word 0 again: either caller waits for its copy at once)
+    PIN_POOL_ERR = 2,                                // run_chain_tile: the error word behind a launch group
+    PIN_HEAVY_LOAD = 4,                              // k_pair_cost's sum over the tile last sent (cm_ctx::h_pin_nt)
+    PIN_CELLS = 8,                                   // + 2 * seed set: DP cells of the tile, + 1: of its largest problem
+    PIN_RERUN_N = 12, PIN_FALL_N = 14,               // + chain-record set: length of the re-run list / of the pipeline's fall-back list
+    PIN_WORDS = 16
+};
+constexpr size_t PIN_BYTES = PIN_WORDS * sizeof(unsigned long long);        // allocated and cleared in cm_create
+static_assert(PIN_BYTES == 128 && PIN_FALL_N + 1 < PIN_WORDS && PIN_CELLS + 3 < PIN_RERUN_N, "the landing zone has 16 words");
 struct ReadsDev {
     const uint8_t *seq1, *seq2;
     const uint64_t *off1, *off2;
@@ -82,12 +108,12 @@ __global__ void __launch_bounds__(BLK) k_seed(KCore kc, ReadsDev rd, const uint8
         sraw[q] = rw;
     }
     __syncthreads();
-    if (threadIdx.x < 3 && sh[threadIdx.x]) atomicAdd(&counters[threadIdx.x], (unsigned long long)sh[threadIdx.x]);
+    if (threadIdx.x < 3 && sh[threadIdx.x]) atomicAdd(&counters[CN_PROBES + threadIdx.x], (unsigned long long)sh[threadIdx.x]);
 }
 
 // cells per chaining problem + exclusive scan over the problems of a tile (3 phases):
 // k_scan_a: per block of SCAN_ELEMS problems, cells[r] = sum of its seed counts, block-local
-// exclusive offsets and the block total; k_scan_b: one workgroup scans the block totals;
+// exclusive offsets and the block total; k_scan_mid: one workgroup scans the block totals;
 // k_scan_c: adds the block base.  out[n] = grand total.
 constexpr int SCAN_T = 256;
 constexpr int SCAN_ELEMS = 1024;       // 4 per thread
@@ -127,36 +153,39 @@ __global__ void __launch_bounds__(SCAN_T) k_scan_a(const uint32_t *scnt, int S, 
         bmax[blockIdx.x] = shmax;
     }
 }
-__global__ void __launch_bounds__(1024) k_scan_b(unsigned long long *bsum, uint32_t nb, unsigned long long *total, const unsigned int *bmax) {
-    __shared__ unsigned long long part[1024];
+// The middle kernel of both multi-block scans (this one and k_scan32_*): one workgroup scans the nb block totals in place.
+// WITH_MAX: also the grand total and the largest of bmax[] -> total[0], total[1] (else neither pointer is touched).
+template <class T, bool WITH_MAX>
+__global__ void __launch_bounds__(1024) k_scan_mid(T *bsum, uint32_t nb, T *total, const unsigned int *bmax) {
+    __shared__ T part[1024];
     __shared__ unsigned int gmax;
     const uint32_t t = threadIdx.x;
     const uint32_t chunk = (nb + 1023u) / 1024u;
     const uint32_t a = t * chunk, b = (a + chunk < nb) ? a + chunk : nb;
-    unsigned long long s = 0;
+    T s = 0;
     unsigned int m = 0;
-    if (t == 0) gmax = 0;
-    __syncthreads();
+    if (WITH_MAX && t == 0) gmax = 0;
+    if constexpr (WITH_MAX) __syncthreads();
     for (uint32_t i = a; i < b; ++i) {
         s += bsum[i];
-        m = bmax[i] > m ? bmax[i] : m;
+        if constexpr (WITH_MAX) m = bmax[i] > m ? bmax[i] : m;
     }
-    atomicMax(&gmax, m);
+    if constexpr (WITH_MAX) atomicMax(&gmax, m);
     part[t] = s;
     __syncthreads();
     for (uint32_t d = 1; d < 1024; d <<= 1) {
-        const unsigned long long v = (t >= d) ? part[t - d] : 0ull;
+        const T v = (t >= d) ? part[t - d] : (T)0;
         __syncthreads();
         part[t] += v;
         __syncthreads();
     }
-    unsigned long long run = t ? part[t - 1] : 0ull;
+    T run = t ? part[t - 1] : (T)0;
     for (uint32_t i = a; i < b; ++i) {
-        const unsigned long long x = bsum[i];
+        const T x = bsum[i];
         bsum[i] = run;
         run += x;
     }
-    if (t == 1023) {
+    if (WITH_MAX && t == 1023) {
         total[0] = part[1023];
         total[1] = gmax;                          // (every atomicMax above is followed by a barrier of the scan)
     }
@@ -235,9 +264,6 @@ struct RetryArgs {
     int first;                   // 1: first pass (record, skip, queue)   0: the re-run
 };
 
-#ifndef CM_PAIR_WAVES
-#define CM_PAIR_WAVES 4       // waves per SIMD the pair kernels are compiled for (128 VGPRs; LDS: 2 x lbuf_bytes x 64 per wave)
-#endif
 // The pair stage's light kernel and its re-run (RetryArgs) are the same code: FIRST = the first pass over the tile (a pair that
 // hits a device capacity is recorded, skipped and queued), !FIRST = the re-run of the queued pairs (k_pair_rerun: spill memo,
 // longer staging buffers, limits fail the call).  Two kernel symbols, so that profiles tell the two launches apart.
@@ -248,10 +274,8 @@ __device__ __forceinline__ void pair_kernel(const KCore &kc, const ReadsDev &rd,
                                             const uint32_t *perm, const unsigned int *n_light, unsigned int *next_chunk,
                                             const RetryArgs &ra) {
     const unsigned long long clk0 = lane_clk ? wall_clock64() : 0ull;
-    // per-lane staging buffers for the two DP strings, word-interleaved across the wave (cm_core.h LBuf)
+    // per-lane staging buffers for the two DP strings, word-interleaved across the wave (lane_dp_mem)
     extern __shared__ uint32_t lds_words[];
-    CM_S uint8_t *lane_base = (CM_S uint8_t *)lds_words + 4 * threadIdx.x;
-    const int str_stride = lbuf_bytes(str_cap) * BLK_PAIR;
 #if defined(CM_DIAG)
     __shared__ unsigned long long tick_w[65];
     cmc::Tick tick;
@@ -261,9 +285,9 @@ __device__ __forceinline__ void pair_kernel(const KCore &kc, const ReadsDev &rd,
     tick.wave_on = 1;
     for (int i = threadIdx.x; i < 65; i += BLK_PAIR) tick_w[i] = i == 0 ? tick.last : 0ull;
     __syncthreads();
-    cmc::DpMem sm{cmc::LBuf{lane_base, str_cap}, cmc::LBuf{lane_base + str_stride, str_cap}, (cmc::g_err)err, &tick};
+    cmc::DpMem sm = lane_dp_mem((CM_S uint8_t *)lds_words, threadIdx.x, str_cap, (cmc::g_err)err, &tick);
 #else
-    cmc::DpMem sm{cmc::LBuf{lane_base, str_cap}, cmc::LBuf{lane_base + str_stride, str_cap}, (cmc::g_err)err};
+    cmc::DpMem sm = lane_dp_mem((CM_S uint8_t *)lds_words, threadIdx.x, str_cap, (cmc::g_err)err);
 #endif
     if (ra.spill) {          // the exact re-run of the pairs the first pass gave up on: a memo that holds every exon piece
         sm.spill = (cmc::g_spill)(ra.spill + ((size_t)blockIdx.x * BLK_PAIR + threadIdx.x) * (size_t)ra.spill_cap);
@@ -320,8 +344,8 @@ __device__ __forceinline__ void pair_kernel(const KCore &kc, const ReadsDev &rd,
     {   // pair-rounds counter: one atomic per wave (a pair left to the re-run is counted there)
         const unsigned long long m = __ballot(1), mk = __ballot(keep);
         if ((threadIdx.x & 63) == (unsigned)__ffsll((long long)m) - 1 && mk) {
-            atomicAdd(&counters[3], (unsigned long long)__popcll(mk));
-            if (!FIRST) atomicAdd(&counters[4], (unsigned long long)__popcll(mk));       // pairs mapped by the re-run launch
+            atomicAdd(&counters[CN_PAIR_ROUNDS], (unsigned long long)__popcll(mk));
+            if (!FIRST) atomicAdd(&counters[CN_RERUN], (unsigned long long)__popcll(mk));       // pairs mapped by the re-run launch
         }
     }
 #if defined(CM_DIAG)
@@ -534,7 +558,7 @@ __global__ void __launch_bounds__(64, CM_CHEAVY_WAVES) k_chain_heavy(KCore kc_, 
         const uint64_t p = pair0 + (r >> 2);
         const int mate = (int)((r >> 1) & 1u);
         const int len = (int)(mate ? rd.off2[p + 1] - rd.off2[p] : rd.off1[p + 1] - rd.off1[p]);
-#if defined(CM_CHAIN_DIAG)      // wave time per phase (100 MHz ticks) into counters[13..15]: load + init, DP, back-tracking
+#if defined(CM_CHAIN_DIAG)      // wave time per phase (100 MHz ticks) into counters[CN_CD_PHASE ..]: load + init, DP, back-tracking
         const unsigned long long dg0 = wall_clock64();
 #endif
         uint32_t st[cmc::MAX_SEEDS], cn[cmc::MAX_SEEDS], base[cmc::MAX_SEEDS + 1];
@@ -713,9 +737,9 @@ __global__ void __launch_bounds__(64, CM_CHEAVY_WAVES) k_chain_heavy(KCore kc_, 
 #endif
         }
 #if defined(CM_CHAIN_DIAG)
-        for (int k = 0; k < 5; ++k) atomicAdd(&counters[8 + k], tk[k]);          // lane sums
+        for (int k = 0; k < 5; ++k) atomicAdd(&counters[CN_CD_LANE + k], tk[k]);          // lane sums
         if (lane == 0)
-            for (int k = 0; k < 4; ++k) atomicAdd(&counters[16 + k], wv[k]);      // wave times
+            for (int k = 0; k < 4; ++k) atomicAdd(&counters[CN_CD_WAVE + k], wv[k]);      // wave times
 #endif
         // ---- back-tracking (src/chain.cpp:242-298), wave-parallel.  The reference walks the scores downwards; per score it takes
         // the first <= maxChainLen logged cells in insertion order, skips one whose start is a non-first fragment of a chain
@@ -840,11 +864,11 @@ __global__ void __launch_bounds__(64, CM_CHEAVY_WAVES) k_chain_heavy(KCore kc_, 
             }
 #if defined(CM_CHAIN_DIAG)      // shape of the back-tracking: events, score levels walked, passes over the log (64 events each)
             if (lane == 0) {
-                atomicAdd(&counters[20], (unsigned long long)n_ev);
-                atomicAdd(&counters[21], dg_levels);
-                atomicAdd(&counters[22], 1ull);
-                atomicAdd(&counters[23], dg_levels * (unsigned long long)((n_ev + 63) / 64));
-                atomicAdd(&counters[24], (unsigned long long)ncell);
+                atomicAdd(&counters[CN_CD_EVENTS], (unsigned long long)n_ev);
+                atomicAdd(&counters[CN_CD_LEVELS], dg_levels);
+                atomicAdd(&counters[CN_CD_PROBLEMS], 1ull);
+                atomicAdd(&counters[CN_CD_PASSES], dg_levels * (unsigned long long)((n_ev + 63) / 64));
+                atomicAdd(&counters[CN_CD_CELLS], (unsigned long long)ncell);
             }
 #endif
         }
@@ -872,9 +896,9 @@ __global__ void __launch_bounds__(64, CM_CHEAVY_WAVES) k_chain_heavy(KCore kc_, 
             resid[r] = (uint16_t)rs;
 #if defined(CM_CHAIN_DIAG)
             const unsigned long long dg3 = wall_clock64();
-            atomicAdd(&counters[13], dg1 - dg0);
-            atomicAdd(&counters[14], dg2 - dg1);
-            atomicAdd(&counters[15], dg3 - dg2);
+            atomicAdd(&counters[CN_CD_PHASE + 0], dg1 - dg0);
+            atomicAdd(&counters[CN_CD_PHASE + 1], dg2 - dg1);
+            atomicAdd(&counters[CN_CD_PHASE + 2], dg3 - dg2);
 #endif
         }
         __syncthreads();
@@ -950,6 +974,8 @@ constexpr int N_CLS = 16;                // classes a sort can use (pairs: 0..13
 constexpr int CTR_SUM = 16, CTR_BASE = 32, CTR_WORDS = 64;
 constexpr int CTR_NEXT = 48;             // spare words of the pair stage's class counters: work cursors of k_pair / k_pair_heavy, then the
 constexpr int CTR_RETRY = 50;            // re-run list's length and the re-run launch's cursor (RetryArgs)
+constexpr int CTR_CHAIN_NEXT = 48;       // spare word of the CHAIN stage's class counters (SeedSet::cctr, its own array): work cursor of k_chain_heavy
+static_assert(CTR_CHAIN_NEXT >= CTR_BASE + N_CLS && CTR_CHAIN_NEXT < CTR_WORDS && CTR_NEXT >= CTR_BASE + N_CLS && CTR_RETRY + 1 < CTR_WORDS, "spare words");
 constexpr unsigned HEAVY_GRID_MAX = 4096;   // d_hres holds the task outcomes + scratch of this many k_pair_heavy blocks
 constexpr int RETRY_GRID = 8;            // blocks of the re-run launch of k_pair (pairs beyond the first pass's capacity: a handful per run, if any)
 constexpr int RETRY_SPILL = 2040;        // + MEMO_N in registers: 2048 memoised exon pieces per extend call
@@ -1246,9 +1272,7 @@ __global__ void __launch_bounds__(BLK_PAIR, CM_HEAVY_WAVES) k_pair_heavy(KCore k
     extern __shared__ uint32_t lds_words[];
     const int lane = threadIdx.x;
     CM_L uint8_t *base = (CM_L uint8_t *)lds_words;
-    CM_S uint8_t *lane_base = base + 4 * lane;
     const int lds_stage_bytes = 2 * lbuf_bytes(str_cap) * BLK_PAIR;
-    const int str_stride = lbuf_bytes(str_cap) * BLK_PAIR;
 #if defined(CM_DIAG)
     __shared__ unsigned long long tick_w[65];
     cmc::Tick tick{};
@@ -1257,9 +1281,9 @@ __global__ void __launch_bounds__(BLK_PAIR, CM_HEAVY_WAVES) k_pair_heavy(KCore k
     tick.last = wall_clock64();
     for (int i = threadIdx.x; i < 65; i += BLK_PAIR) tick_w[i] = i == 0 ? tick.last : 0ull;
     __syncthreads();
-    cmc::DpMem sm{cmc::LBuf{lane_base, str_cap}, cmc::LBuf{lane_base + str_stride, str_cap}, (cmc::g_err)err, &tick};
+    cmc::DpMem sm = lane_dp_mem(base, lane, str_cap, (cmc::g_err)err, &tick);
 #else
-    cmc::DpMem sm{cmc::LBuf{lane_base, str_cap}, cmc::LBuf{lane_base + str_stride, str_cap}, (cmc::g_err)err};
+    cmc::DpMem sm = lane_dp_mem(base, lane, str_cap, (cmc::g_err)err);
 #endif
     CM_L HSlot *S = (CM_L HSlot *)(base + lds_stage_bytes);
     CM_G HRes *res = (CM_G HRes *)(hres + (size_t)blockIdx.x * 64);
@@ -1523,7 +1547,7 @@ __global__ void __launch_bounds__(BLK_PAIR, CM_HEAVY_WAVES) k_pair_heavy(KCore k
                 state[p] = mr;
                 active[p] = act;
                 cat[p] = st;
-                atomicAdd(&counters[3], 1ull);
+                atomicAdd(&counters[CN_PAIR_ROUNDS], 1ull);
             }
         }
         __syncthreads();
@@ -1587,7 +1611,7 @@ __global__ void __launch_bounds__(BLK) k_build_desc(const uint32_t *bucket_off, 
 }
 // ---- cm_load_contig_raw: the index table flattened on the device --------------------------------------------------
 // Multi-block scan of uint32 (totals stay below 2^32 here: table slots / entries of one contig): k_scan32_a scans blocks of
-// S32_B items (8 consecutive items per thread) and leaves the block totals, k_scan32_b scans those in one workgroup,
+// S32_B items (8 consecutive items per thread) and leaves the block totals, k_scan_mid scans those in one workgroup,
 // k_scan32_c adds the block bases.  add = 1: the items are in[i] + 1; inclusive: out[i] includes item i.
 constexpr int S32_T = 1024, S32_E = 8, S32_B = S32_T * S32_E;
 __global__ void __launch_bounds__(S32_T) k_scan32_a(const uint32_t *in, uint64_t n, uint32_t *out, uint32_t *bsum, uint32_t add, int inclusive) {
@@ -1618,27 +1642,6 @@ __global__ void __launch_bounds__(S32_T) k_scan32_a(const uint32_t *in, uint64_t
         pre += v[k];
     }
     if (threadIdx.x == S32_T - 1) bsum[blockIdx.x] = pre;
-}
-__global__ void __launch_bounds__(1024) k_scan32_b(uint32_t *bsum, uint32_t nb) {
-    __shared__ uint32_t part[1024];
-    const uint32_t t = threadIdx.x, chunk = (nb + 1023u) / 1024u;
-    const uint32_t a = t * chunk, b = (a + chunk < nb) ? a + chunk : nb;
-    uint32_t sum = 0;
-    for (uint32_t i = a; i < b; ++i) sum += bsum[i];
-    part[t] = sum;
-    __syncthreads();
-    for (uint32_t d = 1; d < 1024; d <<= 1) {
-        const uint32_t v = (t >= d) ? part[t - d] : 0u;
-        __syncthreads();
-        part[t] += v;
-        __syncthreads();
-    }
-    uint32_t run = t ? part[t - 1] : 0u;
-    for (uint32_t i = a; i < b; ++i) {
-        const uint32_t x = bsum[i];
-        bsum[i] = run;
-        run += x;
-    }
 }
 __global__ void __launch_bounds__(S32_T) k_scan32_c(uint32_t *out, uint64_t n, const uint32_t *bsum) {
     const uint32_t add = bsum[blockIdx.x];
@@ -1819,7 +1822,7 @@ struct Slot {
     uint64_t *entry_near = nullptr;
 };
 
-struct ProfRec { hipEvent_t a, b; int cls; };
+struct ProfRec { hipEvent_t a, b; ProfClass cls; };
 
 // A device buffer that knows its size and who frees it.  Grow-only (ensure()); `Life` says when the memory goes: with the batch
 // (an empty cm_reads_upload, cm_destroy -- release(ctx, BATCH)) or with the context (cm_destroy only).  A buffer is declared once,
@@ -1861,7 +1864,7 @@ inline void swap(ReadBufs &a, ReadBufs &b) {
 }
 
 // What the seeding of a tile leaves for its chain stage: the seed ranges of every probe, the DP-cell offsets of every chaining
-// problem (+ total and largest problem, also copied to h_pin[8 + 2 s ..]).  Two sets: see map_rounds_issue.
+// problem (+ total and largest problem, also copied to h_pin[PIN_CELLS + 2 s ..]).  Two sets: see map_rounds_issue.
 // The work classes of the tile's chaining problems and their sorted list (k_chain_cls + counting sort), the zeroed cursors of the
 // chain kernels (improvement-log pool: cm_ctx::pool_cursor(s); heavy work list) -- everything the chain kernels need but the chain
 // records themselves.
@@ -2021,7 +2024,7 @@ struct cm_ctx {
     BatchBuf<uint8_t> d_ones;                 // all-active flags of a fresh batch
     uint64_t ones_cap = 0;
     unsigned long long *h_pin = nullptr;          // page-locked landing zone of the scalar read-backs (cell total, error flags, counts)
-    uint32_t h_pin_nt = 0;                        // pairs of the tile whose heavy load was last sent to h_pin[4] (0: none yet)
+    uint32_t h_pin_nt = 0;                        // pairs of the tile whose heavy load was last sent to h_pin[PIN_HEAVY_LOAD] (0: none yet)
     std::string err = "";
     Slot slots[MAX_SLOTS];
     // reads
@@ -2063,8 +2066,8 @@ struct cm_ctx {
     bool prof = false;
     std::vector<ProfRec> recs;
     std::vector<hipEvent_t> ev_free;           // timing events are recycled: creating them is slow and comes in bursts
-    double ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    uint64_t launches[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    double ms[PC_COUNT] = {};                  // [ProfClass]
+    uint64_t launches[PC_COUNT] = {};
 };
 
 namespace {
@@ -2161,11 +2164,11 @@ static hipEvent_t take_event(cm_ctx *c) {
 }
 struct Timer {
     cm_ctx *c;
-    int cls;
+    ProfClass cls;
     ProfRec r{};
     bool on;
     hipStream_t st;
-    Timer(cm_ctx *ctx, int k, hipStream_t stream = nullptr) : c(ctx), cls(k), on(ctx->prof), st(stream ? stream : ctx->st.B) {
+    Timer(cm_ctx *ctx, ProfClass k, hipStream_t stream = nullptr) : c(ctx), cls(k), on(ctx->prof), st(stream ? stream : ctx->st.B) {
         if (on) {
             r.a = take_event(c);
             r.b = take_event(c);
@@ -2180,6 +2183,40 @@ struct Timer {
         }
     }
 };
+
+// A kernel launch that its profile class counts: launch and count in one place, so that cm_prof_get's launches[] (which bench.py
+// prints and divides by) cannot drift from the kernel sequences.  The arguments convert implicitly to the kernel's parameter types.
+template <class T> struct AsIs { using type = T; };          // (keeps `args` out of the deduction: KArgs comes from the kernel alone)
+template <class... KArgs>
+void launch(cm_ctx *ctx, ProfClass cls, void (*kernel)(KArgs...), dim3 grid, dim3 block, size_t lds, hipStream_t st, typename AsIs<KArgs>::type... args) {
+    hipLaunchKernelGGL(kernel, grid, block, lds, st, args...);
+    if (cls != PC_NONE) ++ctx->launches[cls];
+}
+// The counting sort of n elements by class, 16 classes at most: k_cls_hist -> k_cls_scan -> k_cls_place on one stream, counted by
+// the profile class pc (PC_NONE: by nobody).
+struct CountingSort {
+    hipStream_t st;
+    const int8_t *cls;                       // class of element i (negative: left out)
+    uint32_t n;
+    unsigned int *blk;                       // scratch: [class][block] counts; nb = blocks of CLS_T elements that n makes
+    uint32_t nb;
+    unsigned int *ctr;                       // out: CTR_WORDS words (totals, CTR_SUM, CTR_BASE + class)
+    uint32_t *perm;                          // out: the elements by class, highest class first, stable
+    int n_used = N_CLS;                      // classes the caller produces
+    uint32_t *hlist = nullptr;               // optional: the list of HEAVY_CLS, when the bit mask `separate` of classes kept out of perm
+    int separate = -1;                       //           (none: -1) names it
+    const uint32_t *order = nullptr;         // optional: visit the elements in this order (a later pass of an LSD radix sort) ...
+    const unsigned int *n_order = nullptr;   // ... its length, on the device
+    const unsigned int *n_dev = nullptr;     // optional: the elements there are, on the device (at most n); only the blocks in use are visited
+    uint32_t grid_cap = 0;                   // workgroups of hist / place at most (0: one per block)
+};
+void counting_sort(cm_ctx *ctx, ProfClass pc, const CountingSort &a) {
+    const dim3 grid(a.grid_cap && a.grid_cap < a.nb ? a.grid_cap : a.nb);
+    const unsigned int *count = a.order ? a.n_order : a.n_dev;
+    launch(ctx, pc, k_cls_hist, grid, dim3(CLS_W), 0, a.st, a.cls, a.n, a.blk, a.nb, a.order, count);
+    launch(ctx, pc, k_cls_scan, dim3(1), dim3(SCAN_CLS_T), 0, a.st, a.blk, a.nb, a.ctr, a.separate, a.n_used, a.n_dev);
+    launch(ctx, pc, k_cls_place, grid, dim3(CLS_W), 0, a.st, a.cls, a.n, a.blk, a.nb, a.ctr, a.perm, a.hlist, a.order, count);
+}
 
 KCore make_core(const cm_ctx *c, const Slot &s) {
     KCore k;
@@ -2230,21 +2267,15 @@ static int seed_classes(cm_ctx *ctx, uint64_t pair0, uint32_t n_tile, const uint
     // Light problems: one lane each, index order.  Heavy problems (many hits): one wave each (k_chain_heavy), heaviest class
     // first.  (Used by run_chain_tile when it takes the split path; computed here because these five small launches, queued
     // behind the persistent pair kernels of the previous item, took 6 ms of the chain stage's critical path.)
-    Timer t(ctx, 5, st);
-    const uint32_t nbk = (n_prob + CLS_T - 1) / CLS_T;
+    Timer t(ctx, PC_ORDER, st);
     // defer: the chain records rb are still read by an earlier pair stage -- nothing is written into them here, run_chain_tile does that
     // (k_chain_apply) when it is ordered behind that stage
-    hipLaunchKernelGGL(k_chain_cls, dim3((n_prob + BLK - 1) / BLK), dim3(BLK), 0, st, sb.scnt, sb.sraw, S, n_prob, sb.cls4, defer ? sb.thigh : rb->high,
-                       chain_light_w(), chain_light_cells(), defer ? (int32_t *)nullptr : rb->nchain, defer ? (uint16_t *)nullptr : rb->resid, act, pair0);
+    launch(ctx, PC_ORDER, k_chain_cls, dim3((n_prob + BLK - 1) / BLK), dim3(BLK), 0, st, sb.scnt, sb.sraw, S, n_prob, sb.cls4, defer ? sb.thigh : rb->high,
+           chain_light_w(), chain_light_cells(), defer ? (int32_t *)nullptr : rb->nchain, defer ? (uint16_t *)nullptr : rb->resid, act, pair0);
     ctx->seed[s].cls_deferred = defer;
-    hipLaunchKernelGGL(k_cls_hist, dim3(nbk), dim3(CLS_W), 0, st, sb.cls4, n_prob, sb.cblk, nbk, (const uint32_t *)nullptr,
-                       (const unsigned int *)nullptr);
-    hipLaunchKernelGGL(k_cls_scan, dim3(1), dim3(SCAN_CLS_T), 0, st, sb.cblk, nbk, sb.cctr, -1, N_CLS);
-    hipLaunchKernelGGL(k_cls_place, dim3(nbk), dim3(CLS_W), 0, st, sb.cls4, n_prob, sb.cblk, nbk, sb.cctr, sb.perm4,
-                       (uint32_t *)nullptr, (const uint32_t *)nullptr, (const unsigned int *)nullptr);
-    ctx->launches[5] += 4;
+    counting_sort(ctx, PC_ORDER, {st, sb.cls4, n_prob, sb.cblk, (n_prob + CLS_T - 1) / CLS_T, sb.cctr, sb.perm4});
     HIPCHK(ctx, hipMemsetAsync(ctx->pool_cursor(s), 0, sizeof(unsigned long long), st));
-    HIPCHK(ctx, hipMemsetAsync(sb.cctr + 48, 0, sizeof(unsigned int), st));       // spare word of the class counters: work cursor of k_chain_heavy
+    HIPCHK(ctx, hipMemsetAsync(sb.cctr + CTR_CHAIN_NEXT, 0, sizeof(unsigned int), st));
     HIPCHK(ctx, hipGetLastError());
     return CM_OK;
 }
@@ -2255,21 +2286,19 @@ int run_seed_tile(cm_ctx *ctx, const KCore &core, const ReadsDev &rd, uint64_t p
     if (total == 0) return CM_OK;
     const SeedSet &sb = ctx->seed[s];
     {
-        Timer t(ctx, 0, st);
-        hipLaunchKernelGGL(k_seed, dim3((unsigned)((total + BLK - 1) / BLK)), dim3(BLK), 0, st, core, rd, act, pair0, n_tile, S,
-                           sb.sstart, sb.scnt, sb.sraw, ctx->d_counters);
-        ++ctx->launches[0];
+        Timer t(ctx, PC_SEED, st);
+        launch(ctx, PC_SEED, k_seed, dim3((unsigned)((total + BLK - 1) / BLK)), dim3(BLK), 0, st, core, rd, act, pair0, n_tile, S, sb.sstart, sb.scnt, sb.sraw,
+               ctx->d_counters);
     }
     const uint32_t n_prob = n_tile * 4u;
     {
-        Timer t(ctx, 3, st);
+        Timer t(ctx, PC_SCAN, st);
         const uint32_t nb = (n_prob + SCAN_ELEMS - 1) / SCAN_ELEMS;
-        hipLaunchKernelGGL(k_scan_a, dim3(nb), dim3(SCAN_T), 0, st, sb.scnt, S, n_prob, sb.celloff, sb.bsum, sb.bmax);
-        hipLaunchKernelGGL(k_scan_b, dim3(1), dim3(1024), 0, st, sb.bsum, nb, sb.celloff + n_prob, (const unsigned int *)sb.bmax);
-        hipLaunchKernelGGL(k_scan_c, dim3((n_prob + SCAN_T - 1) / SCAN_T), dim3(SCAN_T), 0, st, sb.celloff, sb.bsum, n_prob);
-        ctx->launches[3] += 3;
+        launch(ctx, PC_SCAN, k_scan_a, dim3(nb), dim3(SCAN_T), 0, st, sb.scnt, S, n_prob, sb.celloff, sb.bsum, sb.bmax);
+        launch(ctx, PC_SCAN, k_scan_mid<unsigned long long, true>, dim3(1), dim3(1024), 0, st, sb.bsum, nb, sb.celloff + n_prob, sb.bmax);
+        launch(ctx, PC_SCAN, k_scan_c, dim3((n_prob + SCAN_T - 1) / SCAN_T), dim3(SCAN_T), 0, st, sb.celloff, sb.bsum, n_prob);
     }
-    HIPCHK(ctx, hipMemcpyAsync(ctx->h_pin + 8 + 2 * s, sb.celloff + n_prob, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->h_pin + PIN_CELLS + 2 * s, sb.celloff + n_prob, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
     if (rb) {
         const int rc = seed_classes(ctx, pair0, n_tile, act, s, st, rb, defer_rb);
         if (rc) return rc;
@@ -2294,8 +2323,8 @@ int run_chain_tile(cm_ctx *ctx, const KCore &core, const ReadsDev &rd, uint64_t 
                            rb.high, rb.nchain, rb.resid);
         ctx->seed[s].cls_deferred = false;
     }
-    const unsigned long long total = ctx->h_pin[8 + 2 * s];
-    const unsigned long long max_cells = ctx->h_pin[9 + 2 * s];       // of one problem
+    const unsigned long long total = ctx->h_pin[PIN_CELLS + 2 * s];
+    const unsigned long long max_cells = ctx->h_pin[PIN_CELLS + 2 * s + 1];      // of one problem
     // problem ranges whose DP cells fit the workspace
     std::vector<std::pair<uint32_t, uint32_t>> ranges;
     if (total <= ctx->dp.cells_cap) {
@@ -2338,14 +2367,14 @@ int run_chain_tile(cm_ctx *ctx, const KCore &core, const ReadsDev &rd, uint64_t 
         const uint32_t n = b - a;
         if (!fresh) {
             HIPCHK(ctx, hipMemsetAsync(ctx->pool_cursor(s), 0, sizeof(unsigned long long), ctx->st.B));
-            HIPCHK(ctx, hipMemsetAsync(sb.cctr + 48, 0, sizeof(unsigned int), ctx->st.B));       // spare word of the class counters: work cursor
+            HIPCHK(ctx, hipMemsetAsync(sb.cctr + CTR_CHAIN_NEXT, 0, sizeof(unsigned int), ctx->st.B));
         }
         fresh = false;
         if (use_split) {          // the few long problems run on the second stream, concurrently with the bulk
             HIPCHK(ctx, hipEventRecord(ctx->ev.fork, ctx->st.B));
             HIPCHK(ctx, hipStreamWaitEvent(ctx->st.B2, ctx->ev.fork, 0));
             {
-            Timer t(ctx, 6, ctx->st.B2);
+            Timer t(ctx, PC_CHAIN_HEAVY, ctx->st.B2);
             // (a property of the function, process-wide: only ever raised, so a launch in flight from another context of this
             // process never sees its limit lowered)
             static std::atomic<size_t> heavy_attr{64u * 1024u};
@@ -2354,28 +2383,25 @@ int run_chain_tile(cm_ctx *ctx, const KCore &core, const ReadsDev &rd, uint64_t 
                 heavy_attr.store(heavy_lds);
             }
             const uint32_t hb = n < 8192u ? n : 8192u;
-            hipLaunchKernelGGL(k_chain_heavy, dim3(hb), dim3(64), heavy_lds, ctx->st.B2, core, rd, pair0, S, sb.sstart, sb.scnt, sb.celloff,
-                               ctx->dp.score, ctx->dp.prev, ctx->dp.pool, ctx->dp.pool_bytes, ctx->pool_cursor(s), rb.chains, rb.nchain, ctx->d_err,
-                               rb.resid, sb.perm4, sb.cctr + CTR_BASE + CHAIN_LIGHT_CLS - 1, sb.cctr + 48, ctx->d_counters);
-            ++ctx->launches[6];
+            launch(ctx, PC_CHAIN_HEAVY, k_chain_heavy, dim3(hb), dim3(64), heavy_lds, ctx->st.B2, core, rd, pair0, S, sb.sstart, sb.scnt, sb.celloff,
+                   ctx->dp.score, ctx->dp.prev, ctx->dp.pool, ctx->dp.pool_bytes, ctx->pool_cursor(s), rb.chains, rb.nchain, ctx->d_err, rb.resid, sb.perm4,
+                   sb.cctr + CTR_BASE + CHAIN_LIGHT_CLS - 1, sb.cctr + CTR_CHAIN_NEXT, ctx->d_counters);
             }
             HIPCHK(ctx, hipEventRecord(ctx->ev.join, ctx->st.B2));
         }
-        Timer t(ctx, 1);
-        hipLaunchKernelGGL(k_chain, dim3((n + BLK_CHAIN - 1) / BLK_CHAIN), dim3(BLK_CHAIN), 0, ctx->st.B, core, rd, act, pair0, a, b, S,
-                           sb.sstart, sb.scnt, sb.sraw, sb.celloff, base, ctx->dp.score, ctx->dp.prev, ctx->dp.pool,
-                           ctx->dp.pool_bytes, ctx->pool_cursor(s), rb.chains, rb.nchain, rb.high, ctx->d_err, rb.resid,
-                           use_split ? sb.perm4 : (const uint32_t *)nullptr, sb.cctr + CTR_BASE + CHAIN_LIGHT_CLS - 1, sb.cctr + CTR_SUM);
+        Timer t(ctx, PC_CHAIN);
+        launch(ctx, PC_CHAIN, k_chain, dim3((n + BLK_CHAIN - 1) / BLK_CHAIN), dim3(BLK_CHAIN), 0, ctx->st.B, core, rd, act, pair0, a, b, S, sb.sstart, sb.scnt,
+               sb.sraw, sb.celloff, base, ctx->dp.score, ctx->dp.prev, ctx->dp.pool, ctx->dp.pool_bytes, ctx->pool_cursor(s), rb.chains, rb.nchain, rb.high,
+               ctx->d_err, rb.resid, use_split ? sb.perm4 : (const uint32_t *)nullptr, sb.cctr + CTR_BASE + CHAIN_LIGHT_CLS - 1, sb.cctr + CTR_SUM);
         if (use_split) HIPCHK(ctx, hipStreamWaitEvent(ctx->st.B, ctx->ev.join, 0));       // timed with the light kernel: the stage ends here
-        ++ctx->launches[1];
         HIPCHK(ctx, hipGetLastError());
         return CM_OK;
     };
     // did the group run out of log space?  (one small read-back per group; the pair stage must not start on truncated logs)
     auto pool_lost = [&](bool *lost) -> int {
-        HIPCHK(ctx, hipMemcpyAsync(ctx->h_pin + 2, ctx->d_err, sizeof(int), hipMemcpyDeviceToHost, ctx->st.B));
+        HIPCHK(ctx, hipMemcpyAsync(ctx->h_pin + PIN_POOL_ERR, ctx->d_err, sizeof(int), hipMemcpyDeviceToHost, ctx->st.B));
         HIPCHK(ctx, hipStreamSynchronize(ctx->st.B));
-        const int e = *(const int *)(ctx->h_pin + 2);
+        const int e = *(const int *)(ctx->h_pin + PIN_POOL_ERR);
         *lost = (e & cmc::ERR_POOL) != 0;
         if (*lost) {                                          // the other flags stay for cm_sync to report (the pair stage of the
             hipLaunchKernelGGL(k_err_clear, dim3(1), dim3(64), 0, ctx->st.B, ctx->d_err, (int)cmc::ERR_POOL);   // previous round may be setting some right now)
@@ -2430,9 +2456,9 @@ int run_chain_tile(cm_ctx *ctx, const KCore &core, const ReadsDev &rd, uint64_t 
 }
 
 int check_dev_err(cm_ctx *ctx) {
-    HIPCHK(ctx, hipMemcpyAsync(ctx->h_pin, ctx->d_err, sizeof(int), hipMemcpyDeviceToHost, ctx->st.B));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->h_pin + PIN_DEV_ERR, ctx->d_err, sizeof(int), hipMemcpyDeviceToHost, ctx->st.B));
     HIPCHK(ctx, hipStreamSynchronize(ctx->st.B));
-    const int e = *(const int *)ctx->h_pin;
+    const int e = *(const int *)(ctx->h_pin + PIN_DEV_ERR);
     if (e) {
         (void)hipMemsetAsync(ctx->d_err, 0, sizeof(int), ctx->st.B);       // reported once: the next batch starts clean
         return fail(ctx, CM_ELIMIT, "device capacity limit hit:%s%s%s", (e & cmc::ERR_POOL) ? " chain improvement-log pool exhausted;" : "",
@@ -2493,14 +2519,14 @@ int cm_create(const cm_params *p, cm_ctx **out) {
         }
     if (ensure(ctx, ctx->d_pool_cursor, 2 * sizeof(unsigned long long)) != hipSuccess ||
         ensure(ctx, ctx->d_err, sizeof(int)) != hipSuccess ||
-        ensure(ctx, ctx->d_counters, 32 * sizeof(unsigned long long)) != hipSuccess ||
-        hipHostMalloc((void **)&ctx->h_pin, 128, hipHostMallocDefault) != hipSuccess) {
+        ensure(ctx, ctx->d_counters, CN_WORDS * sizeof(unsigned long long)) != hipSuccess ||
+        hipHostMalloc((void **)&ctx->h_pin, PIN_BYTES, hipHostMallocDefault) != hipSuccess) {
         cm_destroy(ctx);
         return CM_ENOMEM;
     }
-    memset(ctx->h_pin, 0, 128);
+    memset(ctx->h_pin, 0, PIN_BYTES);
     (void)hipMemsetAsync(ctx->d_err, 0, sizeof(int), ctx->st.B);
-    (void)hipMemsetAsync(ctx->d_counters, 0, 32 * sizeof(unsigned long long), ctx->st.B);
+    (void)hipMemsetAsync(ctx->d_counters, 0, CN_WORDS * sizeof(unsigned long long), ctx->st.B);
     if (hwq_low) {
         ctx->err = "note: GPU_MAX_HW_QUEUES was " + std::string(hwq ? hwq : "unset") +
                    " when this context was created; if HIP was initialised earlier in this process the seven streams of a context share the "
@@ -2620,7 +2646,7 @@ static int scan32(cm_ctx *ctx, const uint32_t *in, uint64_t n, uint32_t *out, ui
     const uint32_t nb = (uint32_t)((n + S32_B - 1) / S32_B);
     if (nb == 0) return CM_OK;
     hipLaunchKernelGGL(k_scan32_a, dim3(nb), dim3(S32_T), 0, ctx->st.B, in, n, out, tmp, add, inclusive);
-    hipLaunchKernelGGL(k_scan32_b, dim3(1), dim3(1024), 0, ctx->st.B, tmp, nb);
+    hipLaunchKernelGGL((k_scan_mid<uint32_t, false>), dim3(1), dim3(1024), 0, ctx->st.B, tmp, nb, (uint32_t *)nullptr, (const unsigned int *)nullptr);
     hipLaunchKernelGGL(k_scan32_c, dim3(nb), dim3(S32_T), 0, ctx->st.B, out, n, (const uint32_t *)tmp);
     HIPCHK(ctx, hipGetLastError());
     return CM_OK;
@@ -3277,11 +3303,9 @@ static int launch_fall_back(cm_ctx *ctx, int b, hipStream_t st) {
     const cm_ctx::Rerun &q = ctx->rerun[b];
     const PairSet &ps = ctx->pset[b];
     const RetryArgs ra1{ps.pair_err, ps.retry_list, ps.retry_ctr, nullptr, 0, 1};
-    hipLaunchKernelGGL(k_pair_heavy, dim3(q.fall_grid), dim3(BLK_PAIR), q.lds_heavy, st, q.core, q.rd, q.p0, (const uint32_t *)ps.hp_fall, (const unsigned int *)ps.hp_fallctr, q.chains,
-                       q.nchain, q.high, ctx->d_state, q.act_out, ctx->d_cat, q.is_last, ctx->d_err, ctx->d_counters, q.str_cap, (unsigned long long *)nullptr,
-                       ctx->d_hres, ps.cls_ctr + CTR_NEXT + 1, ra1);
+    launch(ctx, PC_HEAVY, k_pair_heavy, dim3(q.fall_grid), dim3(BLK_PAIR), q.lds_heavy, st, q.core, q.rd, q.p0, ps.hp_fall, ps.hp_fallctr, q.chains, q.nchain, q.high,
+           ctx->d_state, q.act_out, ctx->d_cat, q.is_last, ctx->d_err, ctx->d_counters, q.str_cap, nullptr, ctx->d_hres, ps.cls_ctr + CTR_NEXT + 1, ra1);
     HIPCHK(ctx, hipGetLastError());
-    ++ctx->launches[4];
     return CM_OK;
 }
 // wait = false: without blocking the host (the end of cm_map_rounds, which stays asynchronous): the re-run is launched whatever the count
@@ -3291,12 +3315,12 @@ static int settle_pair(cm_ctx *ctx, int b, bool wait = true) {
     if (wait) HIPCHK(ctx, hipEventSynchronize(ctx->ev.first[b]));
     HIPCHK(ctx, hipStreamWaitEvent(ctx->st.R, ctx->ev.first[b], 0));
     bool fell = false;
-    if (ctx->rerun[b].fall && (!wait || *(const volatile unsigned int *)(ctx->h_pin + 14 + b) != 0u)) {
+    if (ctx->rerun[b].fall && (!wait || *(const volatile unsigned int *)(ctx->h_pin + PIN_FALL_N + b) != 0u)) {
         const int rc = launch_fall_back(ctx, b, ctx->st.R);        // (may queue pairs for the re-run: that one unconditionally then)
         if (rc) return rc;
         fell = true;
     }
-    if (!wait || fell || *(const volatile unsigned int *)(ctx->h_pin + 12 + b) != 0u) {
+    if (!wait || fell || *(const volatile unsigned int *)(ctx->h_pin + PIN_RERUN_N + b) != 0u) {
         const int rc = launch_rerun(ctx, b);
         if (rc) return rc;
     }
@@ -3353,7 +3377,7 @@ static int run_pair_tile(cm_ctx *ctx, const KCore &core, uint64_t p0, uint32_t n
             }
     }
     {
-        Timer t(ctx, 5, so);
+        Timer t(ctx, PC_ORDER, so);
         const uint32_t nbk = (nt + CLS_T - 1) / CLS_T;
         static const bool fixed_cost = getenv("CM_HEAVY_COST") != nullptr;             // tuning knob: no adaptive threshold
         static const int heavy_cost = fixed_cost ? atoi(getenv("CM_HEAVY_COST")) : HEAVY_COST;
@@ -3361,32 +3385,19 @@ static int run_pair_tile(cm_ctx *ctx, const KCore &core, uint64_t p0, uint32_t n
         if (!fixed_cost) {
             load = ctx->d_heavy_load;
             HIPCHK(ctx, hipMemsetAsync(load, 0, sizeof(unsigned long long), so));
-            hipLaunchKernelGGL(k_pair_cost, dim3((nt + BLK - 1) / BLK), dim3(BLK), 0, so, rb.nchain, act_in, p0, nt, HEAVY_COST, load);
+            // (PC_NONE: the class has counted ten launches per stage, k_pair_cls + the sort, since before this kernel came)
+            launch(ctx, PC_NONE, k_pair_cost, dim3((nt + BLK - 1) / BLK), dim3(BLK), 0, so, rb.nchain, act_in, p0, nt, HEAVY_COST, load);
             // the host learns the load of a tile one or two items late (no wait): good enough to size the next heavy grid
-            HIPCHK(ctx, hipMemcpyAsync((void *)(ctx->h_pin + 4), load, sizeof(unsigned long long), hipMemcpyDeviceToHost, so));
+            HIPCHK(ctx, hipMemcpyAsync((void *)(ctx->h_pin + PIN_HEAVY_LOAD), load, sizeof(unsigned long long), hipMemcpyDeviceToHost, so));
             ctx->h_pin_nt = nt;
         }
-        hipLaunchKernelGGL(k_pair_cls, dim3((nt + BLK - 1) / BLK), dim3(BLK), 0, so, core, rb.chains, rb.resid, rb.nchain, act_in, p0, nt, ctx->sort.cls,
-                           ctx->d_cat, heavy_cost, ctx->sort.sub, ctx->sort.sub2, act_out, (const unsigned long long *)load);
-        // three-pass LSD radix sort, 16 x 16 x 16 classes: by the longest residual, by the set of extensions a pair needs,
-        // then (stable) by its class
-        const uint32_t *no_order = nullptr;
-        const unsigned int *no_count = nullptr;
-        hipLaunchKernelGGL(k_cls_hist, dim3(nbk), dim3(CLS_W), 0, so, ctx->sort.sub2, nt, ctx->sort.blk_cnt, nbk, no_order, no_count);
-        hipLaunchKernelGGL(k_cls_scan, dim3(1), dim3(SCAN_CLS_T), 0, so, ctx->sort.blk_cnt, nbk, ctx->sort.ctr3, -1, N_CLS);
-        hipLaunchKernelGGL(k_cls_place, dim3(nbk), dim3(CLS_W), 0, so, ctx->sort.sub2, nt, ctx->sort.blk_cnt, nbk, ctx->sort.ctr3, ctx->sort.perm0,
-                           (uint32_t *)nullptr, no_order, no_count);
-        hipLaunchKernelGGL(k_cls_hist, dim3(nbk), dim3(CLS_W), 0, so, ctx->sort.sub, nt, ctx->sort.blk_cnt, nbk, (const uint32_t *)ctx->sort.perm0,
-                           (const unsigned int *)(ctx->sort.ctr3 + CTR_SUM));
-        hipLaunchKernelGGL(k_cls_scan, dim3(1), dim3(SCAN_CLS_T), 0, so, ctx->sort.blk_cnt, nbk, ctx->sort.ctr2, -1, N_CLS);
-        hipLaunchKernelGGL(k_cls_place, dim3(nbk), dim3(CLS_W), 0, so, ctx->sort.sub, nt, ctx->sort.blk_cnt, nbk, ctx->sort.ctr2, ctx->sort.perm1,
-                           (uint32_t *)nullptr, (const uint32_t *)ctx->sort.perm0, (const unsigned int *)(ctx->sort.ctr3 + CTR_SUM));
-        hipLaunchKernelGGL(k_cls_hist, dim3(nbk), dim3(CLS_W), 0, so, ctx->sort.cls, nt, ctx->sort.blk_cnt, nbk, (const uint32_t *)ctx->sort.perm1,
-                           (const unsigned int *)(ctx->sort.ctr2 + CTR_SUM));
-        hipLaunchKernelGGL(k_cls_scan, dim3(1), dim3(SCAN_CLS_T), 0, so, ctx->sort.blk_cnt, nbk, cls_ctr, 1 << HEAVY_CLS, N_CLS);
-        hipLaunchKernelGGL(k_cls_place, dim3(nbk), dim3(CLS_W), 0, so, ctx->sort.cls, nt, ctx->sort.blk_cnt, nbk, cls_ctr, perm,
-                           hlist, (const uint32_t *)ctx->sort.perm1, (const unsigned int *)(ctx->sort.ctr2 + CTR_SUM));
-        ctx->launches[5] += 10;
+        launch(ctx, PC_ORDER, k_pair_cls, dim3((nt + BLK - 1) / BLK), dim3(BLK), 0, so, core, rb.chains, rb.resid, rb.nchain, act_in, p0, nt, ctx->sort.cls, ctx->d_cat,
+               heavy_cost, ctx->sort.sub, ctx->sort.sub2, act_out, load);
+        // three-pass LSD radix sort, 16 x 16 x 16 classes: by the longest residual, by the set of extensions a pair needs, then (stable) by its class
+        const PairSort &w = ctx->sort;
+        counting_sort(ctx, PC_ORDER, {so, w.sub2, nt, w.blk_cnt, nbk, w.ctr3, w.perm0});
+        counting_sort(ctx, PC_ORDER, {so, w.sub, nt, w.blk_cnt, nbk, w.ctr2, w.perm1, N_CLS, nullptr, -1, w.perm0, w.ctr3 + CTR_SUM});
+        counting_sort(ctx, PC_ORDER, {so, w.cls, nt, w.blk_cnt, nbk, cls_ctr, perm, N_CLS, hlist, 1 << HEAVY_CLS, w.perm1, w.ctr2 + CTR_SUM});
     }
     HIPCHK(ctx, hipMemsetAsync(cls_ctr + CTR_NEXT, 0, 2 * sizeof(unsigned int), so));     // both work cursors
     HIPCHK(ctx, hipMemsetAsync(retry_ctr, 0, 2 * sizeof(unsigned int), so));                     // re-run count + cursor of this set
@@ -3408,14 +3419,14 @@ static int run_pair_tile(cm_ctx *ctx, const KCore &core, uint64_t p0, uint32_t n
     HIPCHK(ctx, hipStreamWaitEvent(sp2, ctx->ev.prep[b], 0));
     HIPCHK(ctx, hipStreamWaitEvent(sp2, ctx->ev.order[b], 0));
     {
-        Timer t(ctx, 4, sp2);
+        Timer t(ctx, PC_HEAVY, sp2);
         // both pair kernels are persistent: together they fill the wave slots of every SIMD (256 CUs x 4 SIMDs), half each
         const unsigned cap = 256u * 4u * slots_per_simd;
         // Heavy grid: half the wave capacity, or all of it when the tiles of this run carry a large heavy load (the value
         // k_pair_cost left for an earlier item, read without waiting): on the dense genome the heavy kernel has work for every
         // slot (19.9 vs 18.9 M pairs/s); with little heavy work the extra waves only sit on registers the next item's chain
         // stage is waiting for (round-2 genome: 43.3 vs 44.4 M pairs/s).
-        const volatile unsigned long long *seen = (const volatile unsigned long long *)(ctx->h_pin + 4);
+        const volatile unsigned long long *seen = (const volatile unsigned long long *)(ctx->h_pin + PIN_HEAVY_LOAD);
         const bool loaded_run = ctx->h_pin_nt && *seen > HEAVY_LOAD * (unsigned long long)ctx->h_pin_nt;
         const unsigned heavy_cap = cap / (loaded_run ? 1u : 2u);
         const unsigned heavy_lim = std::min(heavy_cap, HEAVY_GRID_MAX);     // d_hres is sized for HEAVY_GRID_MAX blocks
@@ -3430,42 +3441,39 @@ static int run_pair_tile(cm_ctx *ctx, const KCore &core, uint64_t p0, uint32_t n
             const size_t lds_slots = HG * sizeof(HSlot);
             HIPCHK(ctx, hipMemsetAsync(ctx->hp.ctr, 0, HC_WORDS * sizeof(unsigned int), sp2));
             HIPCHK(ctx, hipMemsetAsync(ps.hp_fallctr, 0, sizeof(unsigned int), sp2));
+            const dim3 g(pipe_grid), wg(BLK_PAIR);
             // Two passes (process_read's two attempts), the second over the few pairs whose other orientation has chains at all (k_hp_finish
             // settles the others in place).  CM_HP_ATTEMPTS=1 (diagnostic) sends those pairs whole to the fall-back kernel instead: its
             // long tail over a few hundred heavy pairs costs more than nine short launches (77.9 vs 75.9 ms per step).
             static const bool task_order = !(getenv("CM_HP_TASK_ORDER") && getenv("CM_HP_TASK_ORDER")[0] == '0');      // diagnostic: tasks in array order
             static const int n_attempts = (getenv("CM_HP_ATTEMPTS") && atoi(getenv("CM_HP_ATTEMPTS")) == 1) ? 1 : 2;
             for (int attempt = 0; attempt < n_attempts; ++attempt) {
-                if (attempt) hipLaunchKernelGGL(k_hp_reset, dim3(1), dim3(64), 0, sp2, ctx->hp.ctr);
-                hipLaunchKernelGGL(k_hp_plan, dim3(HP_PLAN_GRID), dim3(BLK_PAIR), lds_slots, sp2, core, rd, p0, (const uint32_t *)hlist, n_heavy,
-                                   (const uint32_t *)ctx->hp.list2, n_list2, attempt, (const cm_chain *)rb.chains, (const int32_t *)rb.nchain,
-                                   (const int32_t *)rb.high, (const cm_mapped_read *)ctx->d_state, hp, ctx->hp.lists, str_cap, ctx->d_counters);
-                hipLaunchKernelGGL(k_hp_dp, dim3(pipe_grid), dim3(BLK_PAIR), lds_bytes, sp2, core, rd, p0, attempt, hp, 0, str_cap);
-                if (task_order && attempt == 0) {       // (the second attempt's handful: array order) the tasks by work class, heaviest first (16-class counting sort over the tile's task array)
-                    const uint32_t nbt = (ctx->hp.tasks_cap + CLS_T - 1) / CLS_T;
+                // An attempt starts from zeroed counters: the memset above, k_hp_reset between the two.  The class counts that step in both
+                // (nine steps per attempt since the pipeline came: the reset and the eight item kernels; the task sort is not among them).
+                if (attempt) launch(ctx, PC_HEAVY, k_hp_reset, dim3(1), dim3(64), 0, sp2, ctx->hp.ctr);
+                else ++ctx->launches[PC_HEAVY];
+                launch(ctx, PC_HEAVY, k_hp_plan, dim3(HP_PLAN_GRID), wg, lds_slots, sp2, core, rd, p0, hlist, n_heavy, ctx->hp.list2, n_list2, attempt,
+                       rb.chains, rb.nchain, rb.high, ctx->d_state, hp, ctx->hp.lists, str_cap, ctx->d_counters);
+                launch(ctx, PC_HEAVY, k_hp_dp, g, wg, lds_bytes, sp2, core, rd, p0, attempt, hp, 0, str_cap);
+                const bool ordered = task_order && attempt == 0;       // (the second attempt's handful: array order)
+                if (ordered) {       // the tasks by work class, heaviest first: 16 classes over the tile's task array, whose length is on the device
                     const unsigned int *n_t = ctx->hp.ctr + HC_TASKS;
-                    const uint32_t gt = std::min<uint32_t>(nbt, 2048u);        // (the count is on the device: a grid that walks the stretches in use)
-                    hipLaunchKernelGGL(k_cls_hist, dim3(gt), dim3(CLS_W), 0, sp2, (const int8_t *)ctx->hp.tcls, ctx->hp.tasks_cap, ctx->hp.tblk, nbt,
-                                       (const uint32_t *)nullptr, n_t);
-                    hipLaunchKernelGGL(k_cls_scan, dim3(1), dim3(SCAN_CLS_T), 0, sp2, ctx->hp.tblk, nbt, ctx->hp.tctr, -1, N_CLS, n_t);
-                    hipLaunchKernelGGL(k_cls_place, dim3(gt), dim3(CLS_W), 0, sp2, (const int8_t *)ctx->hp.tcls, ctx->hp.tasks_cap, ctx->hp.tblk, nbt,
-                                       ctx->hp.tctr, ctx->hp.tperm, (uint32_t *)nullptr, (const uint32_t *)nullptr, n_t);
+                    CountingSort ts{sp2, ctx->hp.tcls, ctx->hp.tasks_cap, ctx->hp.tblk, (ctx->hp.tasks_cap + CLS_T - 1) / CLS_T, ctx->hp.tctr, ctx->hp.tperm};
+                    ts.n_dev = n_t, ts.grid_cap = 2048u;               // a grid that walks the stretches in use
+                    counting_sort(ctx, PC_NONE, ts);
                 }
-                hipLaunchKernelGGL(k_hp_tasks, dim3(pipe_grid), dim3(BLK_PAIR), lds_bytes, sp2, core, rd, p0, attempt, (const cm_chain *)rb.chains,
-                                   (const int32_t *)rb.nchain, hp, pair_err, str_cap, (task_order && attempt == 0) ? (const uint32_t *)ctx->hp.tperm : (const uint32_t *)nullptr,
-                                   (const unsigned int *)(ctx->hp.tctr + CTR_SUM));
-                hipLaunchKernelGGL(k_hp_fold, dim3(pipe_grid), dim3(BLK_PAIR), 0, sp2, core, p0, (const uint32_t *)ctx->hp.list2, n_list2, n_heavy, attempt, hp,
-                                   ctx->d_counters);
-                hipLaunchKernelGGL(k_hp_unp_req, dim3(pipe_grid), dim3(BLK_PAIR), 0, sp2, core, rd, p0, attempt, (const cm_chain *)rb.chains, hp, str_cap);
-                hipLaunchKernelGGL(k_hp_dp, dim3(pipe_grid), dim3(BLK_PAIR), lds_bytes, sp2, core, rd, p0, attempt, hp, 1, str_cap);
-                hipLaunchKernelGGL(k_hp_unp, dim3(pipe_grid), dim3(BLK_PAIR), lds_bytes, sp2, core, rd, p0, attempt, (const cm_chain *)rb.chains, hp, pair_err,
-                                   str_cap);
-                hipLaunchKernelGGL(k_hp_finish, dim3(pipe_grid), dim3(BLK_PAIR), 0, sp2, core, p0, (const uint32_t *)ctx->hp.list2, n_list2, n_heavy, attempt, hp,
-                                   ctx->d_state, act_out, ctx->d_cat, is_last_round, ctx->d_counters, ra1, (const int32_t *)rb.nchain, n_attempts == 1 ? 1 : 0);
+                launch(ctx, PC_HEAVY, k_hp_tasks, g, wg, lds_bytes, sp2, core, rd, p0, attempt, rb.chains, rb.nchain, hp, pair_err, str_cap, ordered ? (uint32_t *)ctx->hp.tperm : nullptr,
+                     ctx->hp.tctr + CTR_SUM);
+                launch(ctx, PC_HEAVY, k_hp_fold, g, wg, 0, sp2, core, p0, ctx->hp.list2, n_list2, n_heavy, attempt, hp, ctx->d_counters);
+                launch(ctx, PC_HEAVY, k_hp_unp_req, g, wg, 0, sp2, core, rd, p0, attempt, rb.chains, hp, str_cap);
+                launch(ctx, PC_HEAVY, k_hp_dp, g, wg, lds_bytes, sp2, core, rd, p0, attempt, hp, 1, str_cap);
+                launch(ctx, PC_HEAVY, k_hp_unp, g, wg, lds_bytes, sp2, core, rd, p0, attempt, rb.chains, hp, pair_err, str_cap);
+                launch(ctx, PC_HEAVY, k_hp_finish, g, wg, 0, sp2, core, p0, ctx->hp.list2, n_list2, n_heavy, attempt, hp, ctx->d_state, act_out, ctx->d_cat, is_last_round, ctx->d_counters, ra1,
+                     rb.nchain, n_attempts == 1 ? 1 : 0);
             }
             // what did not fit goes through k_pair_heavy: now (one tile), or when the stage is settled and the list is known to hold something
             // (its own work cursor, cls_ctr + CTR_NEXT + 1, was zeroed with the light kernel's)
-            HIPCHK(ctx, hipMemcpyAsync((void *)(ctx->h_pin + 14 + b), ps.hp_fallctr, sizeof(unsigned int), hipMemcpyDeviceToHost, sp2));
+            HIPCHK(ctx, hipMemcpyAsync((void *)(ctx->h_pin + PIN_FALL_N + b), ps.hp_fallctr, sizeof(unsigned int), hipMemcpyDeviceToHost, sp2));
             {
                 cm_ctx::Rerun &q = ctx->rerun[b];
                 q.fall = true;
@@ -3478,32 +3486,27 @@ static int run_pair_tile(cm_ctx *ctx, const KCore &core, uint64_t p0, uint32_t n
                 if ((rc = launch_fall_back(ctx, b, sp2))) return rc;
                 ctx->rerun[b].fall = false;
             }
-            ctx->launches[4] += 9 * n_attempts;
         } else {
-        hipLaunchKernelGGL(k_pair_heavy, dim3(heavy_grid), dim3(BLK_PAIR), lds_heavy, sp2, core, rd, p0, hlist, cls_ctr + HEAVY_CLS, rb.chains,
-                           rb.nchain, rb.high, ctx->d_state, act_out, ctx->d_cat, is_last_round, ctx->d_err, ctx->d_counters, str_cap,
-                           ctx->d_lane_clk ? ctx->d_lane_clk + (size_t)nt * 16 + (size_t)(nt / 64 + 1) * 64 : nullptr, ctx->d_hres,
-                           cls_ctr + CTR_NEXT + 1, ra1);
-        ++ctx->launches[4];
+            launch(ctx, PC_HEAVY, k_pair_heavy, dim3(heavy_grid), dim3(BLK_PAIR), lds_heavy, sp2, core, rd, p0, hlist, cls_ctr + HEAVY_CLS, rb.chains, rb.nchain, rb.high,
+                   ctx->d_state, act_out, ctx->d_cat, is_last_round, ctx->d_err, ctx->d_counters, str_cap,
+                   ctx->d_lane_clk ? ctx->d_lane_clk + (size_t)nt * 16 + (size_t)(nt / 64 + 1) * 64 : nullptr, ctx->d_hres, cls_ctr + CTR_NEXT + 1, ra1);
         }
     }
     HIPCHK(ctx, hipEventRecord(ctx->ev.join_p, sp2));
     {
-        Timer t(ctx, 2, sp);      // = the pair stage: the light kernel and the wait for the second stream
+        Timer t(ctx, PC_PAIR, sp);      // = the pair stage: the light kernel and the wait for the second stream
         const unsigned want = (nt + BLK_PAIR - 1) / BLK_PAIR, cap = (heavy_pipeline() && ctx->P.band == 3) ? 2048u      // the pipeline's kernels come and go: half the slots (78.7 -> 76.3 ms per step)
                                                                                                            : 256u * 4u * slots_per_simd;   // light takes the slots heavy leaves: full cap
-        hipLaunchKernelGGL(k_pair, dim3(want < cap ? want : cap), dim3(BLK_PAIR), lds_bytes, sp, core, rd, p0, nt, rb.chains, rb.nchain, rb.high,
-                           ctx->d_state, act_out, ctx->d_cat, is_last_round, ctx->d_err, ctx->d_counters, str_cap, ctx->d_lane_clk, perm,
-                           cls_ctr + CTR_SUM, cls_ctr + CTR_NEXT, ra1);
+        launch(ctx, PC_PAIR, k_pair, dim3(want < cap ? want : cap), dim3(BLK_PAIR), lds_bytes, sp, core, rd, p0, nt, rb.chains, rb.nchain, rb.high, ctx->d_state,
+               act_out, ctx->d_cat, is_last_round, ctx->d_err, ctx->d_counters, str_cap, ctx->d_lane_clk, perm, cls_ctr + CTR_SUM, cls_ctr + CTR_NEXT, ra1);
         HIPCHK(ctx, hipStreamWaitEvent(sp, ctx->ev.join_p, 0));
-        ++ctx->launches[2];
     }
     // The re-run of whatever the two kernels queued (usually nothing: the launch reads the count on the device and ends): the same
     // code over the re-run list, one pair per lane, memo spill area, staging buffers for strings of any length a read of this
     // batch can produce.  On a stream of its own: a launch of 8 blocks behind kernels that fill the chip can wait milliseconds
     // for its turn (2.5 ms on average on the hg38-like bench), and only the consumers of this item's results have to wait for
     // it -- ev.pair[b] (chain records of set b free, flags and states of the tile final) is recorded behind it.
-    HIPCHK(ctx, hipMemcpyAsync((void *)(ctx->h_pin + 12 + b), retry_ctr, sizeof(unsigned int), hipMemcpyDeviceToHost, sp));
+    HIPCHK(ctx, hipMemcpyAsync((void *)(ctx->h_pin + PIN_RERUN_N + b), retry_ctr, sizeof(unsigned int), hipMemcpyDeviceToHost, sp));
     HIPCHK(ctx, hipEventRecord(ctx->ev.first[b], sp));
     ctx->rerun[b].deferred = defer;
     if (!defer) {
@@ -3559,7 +3562,7 @@ static int map_rounds_issue(cm_ctx *ctx, const int *slots, int n_rounds, int las
     const bool use_pre = ctx->pre_ready && slots[0] == ctx->pre_slot && ctx->slots[slots[0]].gen == ctx->pre_gen && ctx->n_pairs == ctx->pre_n &&
                          items[0].nt == ctx->pre_nt && (ctx->item_base & 1) == ctx->pre_b;
     ctx->pre_ready = ctx->pre_launched = false;            // the items below reuse both sets of chain records
-    if (use_pre) ++ctx->launches[7];
+    if (use_pre) ++ctx->launches[PC_PREFETCH];       // (no launch: a take-over)
     const ReadsDev rd_cur = current_reads(ctx);
     // Seeds and chains of round r depend on the reads and the contig only; the flags merely skip pairs that are retired.
     // Round-major: A[r & 1], what the pair stage of (tile, r - 1) wrote -- item i - n_tiles, complete before item i - 2, for
@@ -3777,20 +3780,17 @@ static int compact_active(cm_ctx *ctx) {
     HIPCHK(ctx, ensure(ctx, ctx->col.blk, (size_t)N_CLS * (nbk + 2) * sizeof(unsigned int)));
     HIPCHK(ctx, ensure(ctx, ctx->col.ctr, CTR_WORDS * sizeof(unsigned int)));
     hipLaunchKernelGGL(k_active_cls, dim3((unsigned)((n + BLK - 1) / BLK)), dim3(BLK), 0, ctx->st.B, ctx->d_active, n, ctx->col.cls);
-    hipLaunchKernelGGL(k_cls_hist, dim3(nbk), dim3(CLS_W), 0, ctx->st.B, ctx->col.cls, (uint32_t)n, ctx->col.blk, nbk, (const uint32_t *)nullptr,
-                       (const unsigned int *)nullptr);
-    hipLaunchKernelGGL(k_cls_scan, dim3(1), dim3(SCAN_CLS_T), 0, ctx->st.B, ctx->col.blk, nbk, ctx->col.ctr, -1, 1);
-    hipLaunchKernelGGL(k_cls_place, dim3(nbk), dim3(CLS_W), 0, ctx->st.B, ctx->col.cls, (uint32_t)n, ctx->col.blk, nbk, ctx->col.ctr,
-                       ctx->col.perm, (uint32_t *)nullptr, (const uint32_t *)nullptr, (const unsigned int *)nullptr);
+    counting_sort(ctx, PC_NONE, {ctx->st.B, ctx->col.cls, (uint32_t)n, ctx->col.blk, nbk, ctx->col.ctr, ctx->col.perm, 1});      // one class: active
     return CM_OK;
 }
-// count + error flags through the pinned landing zone (one synchronisation)
+// count + error flags through the pinned landing zone (one synchronisation).  check_dev_err lands its copy in word 0 again
+// (PIN_DEV_ERR = PIN_COLLECT_N): it is called here only after the count has been taken out of that word.
 static int read_count(cm_ctx *ctx, uint64_t cap, unsigned int *cnt, const char *what) {
-    HIPCHK(ctx, hipMemcpyAsync(ctx->h_pin, ctx->col.ctr, sizeof(unsigned int), hipMemcpyDeviceToHost, ctx->st.B));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->h_pin + 1, ctx->d_err, sizeof(int), hipMemcpyDeviceToHost, ctx->st.B));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->h_pin + PIN_COLLECT_N, ctx->col.ctr, sizeof(unsigned int), hipMemcpyDeviceToHost, ctx->st.B));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->h_pin + PIN_COLLECT_ERR, ctx->d_err, sizeof(int), hipMemcpyDeviceToHost, ctx->st.B));
     HIPCHK(ctx, hipStreamSynchronize(ctx->st.B));
-    *cnt = *(const unsigned int *)ctx->h_pin;
-    if (*(const int *)(ctx->h_pin + 1)) return check_dev_err(ctx);
+    *cnt = *(const unsigned int *)(ctx->h_pin + PIN_COLLECT_N);
+    if (*(const int *)(ctx->h_pin + PIN_COLLECT_ERR)) return check_dev_err(ctx);
     if (*cnt > cap) return fail(ctx, CM_ELIMIT, "%s: %u active pairs > cap %llu", what, *cnt, (unsigned long long)cap);
     return CM_OK;
 }
@@ -3983,11 +3983,11 @@ int cm_dp_batch(cm_ctx *ctx, const cm_params *P, const uint8_t *arena, uint64_t 
 }
 
 /* diagnostic: per-pair k_pair lane time in 100 MHz ticks (only when CM_LANE_CLK was set at upload) */
-// diagnostic builds (-DCM_CHAIN_DIAG ...): the 32 raw counter words, [8..31] = whatever the build accumulates there
+// diagnostic builds (-DCM_CHAIN_DIAG ...): the CN_WORDS raw counter words, [8 ..] = whatever the build accumulates there (enum Counter)
 int cm_debug_counters(cm_ctx *ctx, unsigned long long *out) {
     if (!ctx || !out) return CM_EINVAL;
     HIPCHK(ctx, hipSetDevice(ctx->P.device));
-    HIPCHK(ctx, hipMemcpyAsync(out, ctx->d_counters, 32 * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->st.B));
+    HIPCHK(ctx, hipMemcpyAsync(out, ctx->d_counters, CN_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->st.B));
     HIPCHK(ctx, hipStreamSynchronize(ctx->st.B));
     return CM_OK;
 }
@@ -4017,11 +4017,11 @@ int cm_prof_reset(cm_ctx *ctx) {
         ctx->ev_free.push_back(r.b);
     }
     ctx->recs.clear();
-    for (int i = 0; i < 8; ++i) {
+    for (int i = 0; i < PC_COUNT; ++i) {
         ctx->ms[i] = 0;
         ctx->launches[i] = 0;
     }
-    HIPCHK(ctx, hipMemsetAsync(ctx->d_counters, 0, 32 * sizeof(unsigned long long), ctx->st.B));
+    HIPCHK(ctx, hipMemsetAsync(ctx->d_counters, 0, CN_WORDS * sizeof(unsigned long long), ctx->st.B));
     HIPCHK(ctx, hipStreamSynchronize(ctx->st.B));
     return CM_OK;
 }
@@ -4037,7 +4037,7 @@ int cm_prof_get(cm_ctx *ctx, double ms[8], uint64_t launches[8]) {
         ctx->ev_free.push_back(r.b);
     }
     ctx->recs.clear();
-    for (int i = 0; i < 8; ++i) {
+    for (int i = 0; i < PC_COUNT; ++i) {
         ms[i] = ctx->ms[i];
         launches[i] = ctx->launches[i];
     }
