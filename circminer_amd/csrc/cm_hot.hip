@@ -51,6 +51,7 @@ enum Counter {
     CN_FALL = 5, CN_FALL_2ND = 6,                    // pairs the pipeline handed to its fall-back list; those of the second attempt
     // -DCM_CHAIN_DIAG (k_chain_heavy): lane sums [5], wave time per phase [3], wave time per DP step [4], shape of the back-tracking
     CN_CD_LANE = 8, CN_CD_PHASE = 13, CN_CD_WAVE = 16, CN_CD_EVENTS = 20, CN_CD_LEVELS = 21, CN_CD_PROBLEMS = 22, CN_CD_PASSES = 23, CN_CD_CELLS = 24,
+    CN_CD_REGLOG = 25, CN_CD_BATCHES = 26, CN_CD_PRE_USED = 27, CN_CD_PRE_UNUSED = 28,      // problems whose log fits registers, candidate batches, scores asked for ahead
     // -DCM_HP_DIAG (cm_heavy_pipe.h): list sizes per attempt [6] at CN_HP_ATTEMPT + CN_HP_STRIDE * attempt, then the fold's counts
     CN_HP_ATTEMPT = 8, CN_HP_STRIDE = 8, CN_HP_UNPAIRED = 24, CN_HP_CHAINS = 25, CN_HP_SEQ_TASKS = 26, CN_HP_EARLY = 27, CN_HP_EARLY_FIRST = 28,
     CN_WORDS = 32
@@ -404,9 +405,12 @@ template <class T> __device__ inline T wave_excl_scan(T v, int lane, T &total) {
     total = __shfl(x, 63);
     return x - v;
 }
+#ifndef CM_CHEAVY_LOG_REGS
+#define CM_CHEAVY_LOG_REGS 4   // k_chain_heavy back-tracks a log of up to 64 x this many events from registers (a test build: 1)
+#endif
 struct HeavyChainCtx {
 #if defined(CM_CHAIN_DIAG)
-    unsigned long long *tk;      // per-lane ticks: [0] binary searches, [1] upper_bound, [2] window loops, [3] cells, [4] pair evaluations
+    unsigned long long *tk;      // per-lane ticks: [0] binary searches, [1] upper_bound, [2] window loops, [3] cells, [4] pair evaluations, [5] / [6] see k_chain_heavy
 #endif
     const Core *c;
     CM_L const uint32_t *LP;     // hit positions of every slot, concatenated (LDS)
@@ -455,11 +459,33 @@ __device__ inline uint32_t heavy_cell(const HeavyChainCtx &h, int ii, uint32_t i
 #define CD_T0
 #define CD_ADD(k)
 #endif
-    for (int jj = ii + 1; jj < h.kc; ++jj) {
+    // The later slots are taken four at a time, in two passes.  The first runs the binary searches and asks for the score of each
+    // slot's first hit right of this one (where it is within maxIntronLen, improved, and inside the window of a hit away from
+    // every exon border: a near-border hit's window is still on its way, so its load is speculative -- the cell is one of this
+    // problem's own); the second is the evaluation in the reference's (jj, j) order, which finds those scores in registers.
+    // A cell with hits in three later slots waits for one round trip instead of three; further hits of a window (one evaluation
+    // in eight) are loaded in place.
+    const uint32_t own_lim = seg_start + read_remain + (uint32_t)c.P.max_ed;
+    for (int j0 = ii + 1; j0 < h.kc; j0 += 4) {
+    uint32_t g_lo[4];
+    double g_sc[4];
+    bool g_ok[4];
+#if defined(CM_CHAIN_DIAG)
+    bool g_ld[4];
+#endif
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        const int jj = j0 + g;
+        g_ok[g] = false;
+        g_lo[g] = 0;
+        g_sc[g] = (double)kmer;
+#if defined(CM_CHAIN_DIAG)
+        g_ld[g] = false;
+#endif
+        if (jj >= h.kc) continue;
         const uint32_t pcn = h.cnt[jj];
         if (pcn == 0) continue;
         CM_L const uint32_t *pp = h.LP + h.base[jj];
-        CM_L const uint32_t *im = h.IM + heavy_im_word(h.base[jj], (uint32_t)jj);
         uint32_t lo = 0, hi = pcn;                   // first hit of jj strictly right of this hit
         {
             CD_T0;
@@ -471,7 +497,28 @@ __device__ inline uint32_t heavy_cell(const HeavyChainCtx &h, int ii, uint32_t i
             CD_ADD(0);
         }
         if (lo >= pcn) continue;
-        if (cur_info + c.P.max_intron < (int32_t)pp[lo]) continue;      // nothing within maxIntronLen
+        const uint32_t first = pp[lo];
+        if (cur_info + c.P.max_intron < (int32_t)first) continue;       // nothing within maxIntronLen
+        g_ok[g] = true;
+        g_lo[g] = lo;
+        if ((near || first <= own_lim) && ((h.IM[heavy_im_word(h.base[jj], (uint32_t)jj) + (lo >> 5)] >> (lo & 31)) & 1u)) {
+            g_sc[g] = h.dps[h.base[jj] + lo];
+#if defined(CM_CHAIN_DIAG)
+            g_ld[g] = true;
+#endif
+        }
+    }
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        if (!g_ok[g]) continue;
+        const int jj = j0 + g;
+        const uint32_t pcn = h.cnt[jj];
+        CM_L const uint32_t *pp = h.LP + h.base[jj];
+        CM_L const uint32_t *im = h.IM + heavy_im_word(h.base[jj], (uint32_t)jj);
+        const uint32_t lo = g_lo[g];
+#if defined(CM_CHAIN_DIAG)
+        bool g_used = false;
+#endif
         if (max_lpos_lim == cmc::MAXUB) {           // cmc::upper_bound with its bit test hoisted (see `near`)
             CD_T0;
             if (near) {
@@ -501,7 +548,10 @@ __device__ inline uint32_t heavy_cell(const HeavyChainCtx &h, int ii, uint32_t i
             const int maxd = distr < distt ? distt : distr, mind = distr < distt ? distr : distt;
             const double beta = 0.1 * (double)(maxd - mind);
             const double alpha = 2e4 * (double)kmer;
-            const double prev_score = ((im[j >> 5] >> (j & 31)) & 1u) ? h.dps[h.base[jj] + j] : (double)kmer;
+            const double prev_score = j == lo ? g_sc[g] : ((im[j >> 5] >> (j & 31)) & 1u) ? h.dps[h.base[jj] + j] : (double)kmer;
+#if defined(CM_CHAIN_DIAG)
+            if (j == lo) g_used = true;
+#endif
             const double t1 = prev_score + alpha;
             const double temp_score = t1 - beta;
             if (temp_score > my_score) {
@@ -511,12 +561,16 @@ __device__ inline uint32_t heavy_cell(const HeavyChainCtx &h, int ii, uint32_t i
                     ev[n].score = temp_score;
                     ev[n].cell = ((uint32_t)ii << 16) | i;
                 }
-                if (n == 0) e0 = temp_score;           // the first two improvements are handed back: most cells have no more,
-                else if (n == 1) e1 = temp_score;      // and the caller then skips the second (storing) evaluation
+                e1 = n == 1 ? temp_score : e1;         // the first two improvements are handed back: most cells have no more,
+                e0 = n == 0 ? temp_score : e0;         // and the caller then skips the second (storing) evaluation
                 ++n;
             }
         }
         CD_ADD(2);
+#if defined(CM_CHAIN_DIAG)
+        if (!ev && g_ld[g]) h.tk[g_used ? 5 : 6] += 1;
+#endif
+    }
     }
     out_score = my_score;
     out_prev = my_prev;
@@ -552,27 +606,49 @@ __global__ void __launch_bounds__(64, CM_CHEAVY_WAVES) k_chain_heavy(KCore kc_, 
     const uint32_t max_best = (uint32_t)c.P.max_chain_len;
     const unsigned int n_heavy = *n_perm;
     // the list starts with the heaviest class; a wave takes the next problem from a shared cursor when it is done with its last
-    auto take = [&]() { return (unsigned int)__shfl((int)(lane == 0 ? atomicAdd(next_problem, 1u) : 0u), 0); };
-    for (unsigned int hidx = take(); hidx < n_heavy; hidx = take()) {
-        const uint32_t r = perm[hidx];
-        const uint64_t p = pair0 + (r >> 2);
-        const int mate = (int)((r >> 1) & 1u);
-        const int len = (int)(mate ? rd.off2[p + 1] - rd.off2[p] : rd.off1[p + 1] - rd.off1[p]);
+    // A problem's header (its index in the list, perm[], then seed ranges, cell offset and read length: three round trips in a
+    // row) depends on nothing the previous problem computes, so it is asked for during that problem: the index at its top, perm[]
+    // before its DP, the rest at the start of its back-tracking.  Seed ranges ride one per lane (lane s: seed s) and are read back
+    // lane by lane at the next turn, which makes the header wave-uniform.  Every wave ends on one index beyond the list, as before.
+    auto take_raw = [&]() { return lane == 0 ? atomicAdd(next_problem, 1u) : 0u; };
+    uint32_t nx_r = 0, nx_st = 0, nx_cn = 0;
+    unsigned long long nx_coff = 0, nx_o0 = 0, nx_o1 = 0;
+    auto ask_header = [&](uint32_t rr) {
+        nx_st = lane < S ? sstart[(uint64_t)rr * S + lane] : 0u;
+        nx_cn = lane < S ? scnt[(uint64_t)rr * S + lane] : 0u;
+        nx_coff = celloff[rr];
+        const uint64_t pp = pair0 + (rr >> 2);
+        const uint64_t *of = ((rr >> 1) & 1u) ? rd.off2 : rd.off1;
+        nx_o0 = of[pp];
+        nx_o1 = of[pp + 1];
+    };
+    unsigned int hidx = (unsigned int)__builtin_amdgcn_readfirstlane((int)take_raw());
+    if (hidx < n_heavy) {
+        nx_r = perm[hidx];
+        ask_header(nx_r);
+    }
+    while (hidx < n_heavy) {
+        const uint32_t r = (uint32_t)__builtin_amdgcn_readfirstlane((int)nx_r);
+        const unsigned int nx_raw = take_raw();
+        const int len = __builtin_amdgcn_readfirstlane((int)(nx_o1 - nx_o0));
+        const unsigned long long coff = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(nx_coff >> 32)) << 32) |
+                                        (unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)nx_coff);
 #if defined(CM_CHAIN_DIAG)      // wave time per phase (100 MHz ticks) into counters[CN_CD_PHASE ..]: load + init, DP, back-tracking
         const unsigned long long dg0 = wall_clock64();
 #endif
         uint32_t st[cmc::MAX_SEEDS], cn[cmc::MAX_SEEDS], base[cmc::MAX_SEEDS + 1];
         int kc = S;
-        for (int s = 0; s < S; ++s) {
-            st[s] = sstart[(uint64_t)r * S + s];
-            cn[s] = scnt[(uint64_t)r * S + s];
+#pragma unroll
+        for (int s = 0; s < cmc::MAX_SEEDS; ++s) {         // (lanes from S on hold zeros)
+            st[s] = (uint32_t)__builtin_amdgcn_readlane((int)nx_st, s);
+            cn[s] = (uint32_t)__builtin_amdgcn_readlane((int)nx_cn, s);
         }
         while (kc >= 1 && cn[kc - 1] == 0) --kc;
         base[0] = 0;
         for (int s = 0; s < kc; ++s) base[s + 1] = base[s] + cn[s];
         const uint32_t ncell = base[kc];
-        CM_G double *dps = (CM_G double *)(dp_score + celloff[r]);
-        CM_G int32_t *dpp = (CM_G int32_t *)(dp_prev + celloff[r]);
+        CM_G double *dps = (CM_G double *)(dp_score + coff);
+        CM_G int32_t *dpp = (CM_G int32_t *)(dp_prev + coff);
         // hit positions -> LDS.  The cells are not initialised: a cell is written to HBM when an evaluation improves it, and its bit
         // in IM says so; every reader takes the initial value (score kmer, no back pointer) of a cell whose bit is clear from there.
         CM_L uint32_t *NB = LP + ncell;
@@ -658,15 +734,19 @@ __global__ void __launch_bounds__(64, CM_CHEAVY_WAVES) k_chain_heavy(KCore kc_, 
         const unsigned long long dg1 = wall_clock64();
 #endif
 #if defined(CM_CHAIN_DIAG)
-        unsigned long long tk[5] = {0, 0, 0, 0, 0};
+        unsigned long long tk[7] = {0, 0, 0, 0, 0, 0, 0};      // ([5], [6]: scores asked for ahead of the window loop, used / unused)
         unsigned long long wv[4] = {0, 0, 0, 0};       // wave time: first evaluation, scan + log growth, store / second evaluation, barrier
         HeavyChainCtx H{tk, &c, LP, NB, IM, base, cn, kc, len, dps, dpp};
 #else
         HeavyChainCtx H{&c, LP, NB, IM, base, cn, kc, len, dps, dpp};
 #endif
+        const unsigned int hnext = (unsigned int)__builtin_amdgcn_readfirstlane((int)nx_raw);
+        if (hnext < n_heavy) nx_r = perm[hnext];
         CM_G cmc::Event *ev = nullptr;
         uint32_t n_ev = 0, cap_ev = 0;
         bool lost = false;
+        double lane_best = -1.0;      // largest final score of the cells this lane improved: a cell's events rise strictly, so the
+                                      // wave's maximum is the best score of the log
         for (int ii = kc - 2; ii >= 0; --ii) {
             for (uint32_t i0 = 0; i0 < cn[ii]; i0 += 64) {
                 const uint32_t i = i0 + lane;
@@ -719,6 +799,7 @@ __global__ void __launch_bounds__(64, CM_CHEAVY_WAVES) k_chain_heavy(KCore kc_, 
                     }
                     dps[base[ii] + i] = sc;
                     dpp[base[ii] + i] = pv;
+                    lane_best = sc > lane_best ? sc : lane_best;
                 }
                 if (!lost) n_ev += total;
 #if defined(CM_CHAIN_DIAG)
@@ -738,6 +819,8 @@ __global__ void __launch_bounds__(64, CM_CHEAVY_WAVES) k_chain_heavy(KCore kc_, 
         }
 #if defined(CM_CHAIN_DIAG)
         for (int k = 0; k < 5; ++k) atomicAdd(&counters[CN_CD_LANE + k], tk[k]);          // lane sums
+        atomicAdd(&counters[CN_CD_PRE_USED], tk[5]);
+        atomicAdd(&counters[CN_CD_PRE_UNUSED], tk[6]);
         if (lane == 0)
             for (int k = 0; k < 4; ++k) atomicAdd(&counters[CN_CD_WAVE + k], wv[k]);      // wave times
 #endif
@@ -756,53 +839,132 @@ __global__ void __launch_bounds__(64, CM_CHEAVY_WAVES) k_chain_heavy(KCore kc_, 
 #if defined(CM_CHAIN_DIAG)
         const unsigned long long dg2 = wall_clock64();
 #endif
+        if (hnext < n_heavy) ask_header((uint32_t)__builtin_amdgcn_readfirstlane((int)nx_r));
+        // The candidates of every score level are fixed once the log is complete, and a candidate's walk depends on its cell
+        // alone: only the skip rule is sequential.  So the log is read once -- a log of up to 64 * CM_CHEAVY_LOG_REGS events
+        // into registers (lane l: events l, l + 64, ...), where the levels are then iterated without a load -- and the
+        // candidates of successive levels are gathered, in the reference's order, into one batch of up to CM_BESTCHAINLIM, whose
+        // chains are walked together; the skip rule and the writes then run over the batch, every candidate under its own score.
+        // A batch may end within a level (among its first maxChainLen logged cells): the next one resumes there.  A longer log is
+        // read from memory once per level, as before, score and cell in one load.
         if (n_ev > 0) {
-            double best_score = -1.0;
-            for (uint32_t q = lane; q < n_ev; q += 64) best_score = ev[q].score > best_score ? ev[q].score : best_score;
+            constexpr int LR = CM_CHEAVY_LOG_REGS;
+            constexpr uint32_t CAP = CM_BESTCHAINLIM;
+            const unsigned long long lt = (1ull << lane) - 1ull;
+            double best_score = lane_best;
             for (int o = 32; o >= 1; o >>= 1) {
                 const double u = __shfl_xor(best_score, o);
                 best_score = u > best_score ? u : best_score;
             }
+            const bool in_regs = n_ev <= 64u * (uint32_t)LR;
+            const int n_u = (int)((n_ev + 63u) >> 6);
+            double es[LR];                 // (every logged score is above kmer: -1 is "no event")
+            uint32_t ec[LR];
+#pragma unroll
+            for (int u = 0; u < LR; ++u) {
+                es[u] = -1.0;
+                ec[u] = 0u;
+                const uint32_t q = (uint32_t)lane + 64u * (uint32_t)u;
+                if (in_regs && q < n_ev) {
+                    const cmc::Event e = ev[q];
+                    es[u] = e.score;
+                    ec[u] = e.cell;
+                }
+            }
             double cur = best_score;
             bool have = true;
             uint32_t n_rep = 0;
+            int lv_u = 0;                        // where the iteration of level `cur` stands: the register it is at, the lanes of
+            unsigned long long lv_done = 0;      // that register already taken, the candidates of the level so far
+            uint32_t lv_taken = 0;
+            double my_cs = 0.0;                  // score of the candidate this lane walks
 #if defined(CM_CHAIN_DIAG)
-            unsigned long long dg_levels = 0;
+            unsigned long long dg_levels = 0, dg_passes = 0, dg_batches = 0;
 #endif
             while (have && best_count < max_best) {
-#if defined(CM_CHAIN_DIAG)
-                ++dg_levels;
-#endif
-                // (1) + next lower score, one pass over the log
                 uint32_t n_c = 0;
-                double nxt = -1.0;
-                bool hv = false;
-                for (uint32_t q0 = 0; q0 < n_ev; q0 += 64) {
-                    const uint32_t q = q0 + lane;
-                    const double v = q < n_ev ? ev[q].score : 0.0;
-                    const bool hit = q < n_ev && v == cur;
-                    if (q < n_ev && v < cur && (!hv || v > nxt)) {
-                        nxt = v;
-                        hv = true;
+#if defined(CM_CHAIN_DIAG)
+                ++dg_batches;
+#endif
+                if (in_regs) {
+#if defined(CM_CHAIN_DIAG)
+                    if (dg_passes == 0) dg_passes = (unsigned long long)n_u;
+#endif
+                    while (have && n_c < CAP) {
+                        const uint32_t n_c0 = n_c;
+#if defined(CM_CHAIN_DIAG)
+                        if (lv_u == 0 && lv_taken == 0 && lv_done == 0ull) ++dg_levels;
+#endif
+#pragma unroll
+                        for (int u = 0; u < LR; ++u) {
+                            if (u < lv_u || u >= n_u || lv_taken >= max_best || n_c >= CAP) continue;
+                            const bool hit = es[u] == cur && !((lv_done >> lane) & 1ull);
+                            const unsigned long long m = __ballot(hit);
+                            const uint32_t n_m = (uint32_t)__popcll(m);
+                            const uint32_t room = max_best - lv_taken < CAP - n_c ? max_best - lv_taken : CAP - n_c;
+                            const bool tk = hit && (uint32_t)__popcll(m & lt) < room;
+                            if (tk) BT.cand[n_c + (uint32_t)__popcll(m & lt)] = ec[u];
+                            if (n_m > room) {            // the level or the batch is full: this register is resumed
+                                lv_done |= __ballot(tk);
+                                lv_u = u;
+                                n_c += room;
+                                lv_taken += room;
+                            } else {
+                                lv_done = 0ull;
+                                lv_u = u + 1;
+                                n_c += n_m;
+                                lv_taken += n_m;
+                            }
+                        }
+                        if ((uint32_t)lane >= n_c0 && (uint32_t)lane < n_c) my_cs = cur;
+                        if (lv_taken >= max_best || lv_u >= n_u) {       // the level is done: the next lower score
+                            double nxt = -1.0;
+#pragma unroll
+                            for (int u = 0; u < LR; ++u)
+                                if (es[u] < cur && es[u] > nxt) nxt = es[u];
+                            for (int o = 32; o >= 1; o >>= 1) {
+                                const double v = __shfl_xor(nxt, o);
+                                nxt = v > nxt ? v : nxt;
+                            }
+                            have = nxt >= 0.0;
+                            cur = nxt;
+                            lv_u = 0;
+                            lv_done = 0ull;
+                            lv_taken = 0;
+                        }
                     }
-                    const unsigned long long m = __ballot(hit);
-                    if (m && n_c < max_best) {
-                        const uint32_t rank = n_c + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-                        if (hit && rank < max_best) BT.cand[rank] = ev[q].cell;
-                        n_c += (uint32_t)__popcll(m);
-                        if (n_c > max_best) n_c = max_best;
+                } else {
+#if defined(CM_CHAIN_DIAG)
+                    ++dg_levels;
+                    dg_passes += (unsigned long long)n_u;
+#endif
+                    double nxt = -1.0;
+                    for (uint32_t q0 = 0; q0 < n_ev; q0 += 64) {
+                        const uint32_t q = q0 + lane;
+                        cmc::Event e;
+                        e.score = -1.0;
+                        e.cell = 0u;
+                        if (q < n_ev) e = ev[q];
+                        const bool hit = q < n_ev && e.score == cur;
+                        if (q < n_ev && e.score < cur && e.score > nxt) nxt = e.score;
+                        const unsigned long long m = __ballot(hit);
+                        if (m && n_c < max_best) {
+                            const uint32_t rank = n_c + (uint32_t)__popcll(m & lt);
+                            if (hit && rank < max_best) BT.cand[rank] = e.cell;
+                            n_c += (uint32_t)__popcll(m);
+                            if (n_c > max_best) n_c = max_best;
+                        }
                     }
-                }
-                for (int o = 32; o >= 1; o >>= 1) {
-                    const double u = __shfl_xor(nxt, o);
-                    const int uh = __shfl_xor((int)hv, o);
-                    if (uh && (!hv || u > nxt)) {
-                        nxt = u;
-                        hv = true;
+                    for (int o = 32; o >= 1; o >>= 1) {
+                        const double v = __shfl_xor(nxt, o);
+                        nxt = v > nxt ? v : nxt;
                     }
+                    if ((uint32_t)lane < n_c) my_cs = cur;
+                    have = nxt >= 0.0;
+                    cur = nxt;
                 }
                 __syncthreads();
-                // (2) one lane per candidate walks its chain
+                // one lane per candidate walks its chain
                 if ((uint32_t)lane < n_c) {
                     const uint32_t cell = BT.cand[lane];
                     uint32_t bl = cell >> 16, bi = cell & 0xffffu, n = 0;
@@ -820,11 +982,11 @@ __global__ void __launch_bounds__(64, CM_CHEAVY_WAVES) k_chain_heavy(KCore kc_, 
                     BT.clen[lane] = (uint8_t)n;
                 }
                 __syncthreads();
-                // (3) the skip rule, candidates in order
+                // the skip rule, candidates in order
                 const uint32_t first = best_count;
                 uint32_t n_emit = 0;
                 for (uint32_t a = 0; a < n_c && best_count < max_best; ++a) {
-                    if (cur < best_score) {
+                    if (__shfl(my_cs, (int)a) < best_score) {
                         const uint32_t spos = LP[BT.cidx[a][0]];
                         bool mine = false;
                         for (uint32_t x = lane; x < n_rep; x += 64) mine = mine || BT.rep[x] == spos;
@@ -843,7 +1005,7 @@ __global__ void __launch_bounds__(64, CM_CHEAVY_WAVES) k_chain_heavy(KCore kc_, 
                     __syncthreads();
                 }
                 __syncthreads();
-                // (4) write the chains emitted for this score
+                // write the chains emitted from this batch
                 for (uint32_t x = lane; x < n_emit * (uint32_t)CM_MAX_CHAIN_FRAGS; x += 64) {
                     const uint32_t k = x / (uint32_t)CM_MAX_CHAIN_FRAGS, f = x % (uint32_t)CM_MAX_CHAIN_FRAGS;
                     const uint32_t a = BT.emit[k];
@@ -853,22 +1015,23 @@ __global__ void __launch_bounds__(64, CM_CHEAVY_WAVES) k_chain_heavy(KCore kc_, 
                         ch.qpos[f] = (int32_t)BT.cbl[a][f] * kmer;
                     }
                 }
+                const double cs = __shfl(my_cs, (uint32_t)lane < n_emit ? (int)BT.emit[lane] : 0);
                 if ((uint32_t)lane < n_emit) {
                     CM_G cm_chain &ch = out[first + lane];
-                    ch.score = (float)cur;
+                    ch.score = (float)cs;
                     ch.chain_len = BT.clen[BT.emit[lane]];
                 }
                 __syncthreads();
-                have = hv;
-                cur = nxt;
             }
 #if defined(CM_CHAIN_DIAG)      // shape of the back-tracking: events, score levels walked, passes over the log (64 events each)
             if (lane == 0) {
                 atomicAdd(&counters[CN_CD_EVENTS], (unsigned long long)n_ev);
                 atomicAdd(&counters[CN_CD_LEVELS], dg_levels);
                 atomicAdd(&counters[CN_CD_PROBLEMS], 1ull);
-                atomicAdd(&counters[CN_CD_PASSES], dg_levels * (unsigned long long)((n_ev + 63) / 64));
+                atomicAdd(&counters[CN_CD_PASSES], dg_passes);
                 atomicAdd(&counters[CN_CD_CELLS], (unsigned long long)ncell);
+                atomicAdd(&counters[CN_CD_REGLOG], in_regs ? 1ull : 0ull);
+                atomicAdd(&counters[CN_CD_BATCHES], dg_batches);
             }
 #endif
         }
@@ -902,6 +1065,7 @@ __global__ void __launch_bounds__(64, CM_CHEAVY_WAVES) k_chain_heavy(KCore kc_, 
 #endif
         }
         __syncthreads();
+        hidx = hnext;
     }
 }
 
