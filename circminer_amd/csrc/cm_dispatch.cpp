@@ -23,6 +23,8 @@ CM_VARIANTS(int, cm_load_annotation, (void *, int, const cm_annot_view *))
 CM_VARIANTS(int, cm_unload_contig, (void *, int))
 CM_VARIANTS(int, cm_reads_upload, (void *, const cm_reads *, const cm_mapped_read *))
 CM_VARIANTS(int, cm_reads_stage, (void *, const cm_reads *, const cm_mapped_read *))
+CM_VARIANTS(int, cm_reads_stage_text, (void *, const uint8_t *, uint64_t, const uint8_t *, uint64_t, uint64_t, uint32_t, uint64_t *, uint64_t *, cm_text_batch *))
+CM_VARIANTS(int, cm_reads_peek, (void *, uint8_t *, uint64_t, uint64_t *, uint8_t *, uint64_t, uint64_t *, uint64_t *))
 CM_VARIANTS(int, cm_reads_swap, (void *))
 CM_VARIANTS(int, cm_map_rounds, (void *, const int *, int, int))
 CM_VARIANTS(int, cm_map_round, (void *, int, int))
@@ -81,6 +83,13 @@ int cm_load_annotation(cm_ctx *ctx, int slot, const cm_annot_view *av) { return 
 int cm_unload_contig(cm_ctx *ctx, int slot) { return ctx ? GO(cm_unload_contig, slot) : CM_EINVAL; }
 int cm_reads_upload(cm_ctx *ctx, const cm_reads *r, const cm_mapped_read *prior) { return ctx ? GO(cm_reads_upload, r, prior) : CM_EINVAL; }
 int cm_reads_stage(cm_ctx *ctx, const cm_reads *r, const cm_mapped_read *prior) { return ctx ? GO(cm_reads_stage, r, prior) : CM_EINVAL; }
+int cm_reads_stage_text(cm_ctx *ctx, const uint8_t *text1, uint64_t len1, const uint8_t *text2, uint64_t len2, uint64_t max_pairs, uint32_t flags, uint64_t *rec1,
+                        uint64_t *rec2, cm_text_batch *out) {
+    return ctx ? GO(cm_reads_stage_text, text1, len1, text2, len2, max_pairs, flags, rec1, rec2, out) : CM_EINVAL;
+}
+int cm_reads_peek(cm_ctx *ctx, uint8_t *seq1, uint64_t cap1, uint64_t *off1, uint8_t *seq2, uint64_t cap2, uint64_t *off2, uint64_t *n_pairs) {
+    return ctx ? GO(cm_reads_peek, seq1, cap1, off1, seq2, cap2, off2, n_pairs) : CM_EINVAL;
+}
 int cm_reads_swap(cm_ctx *ctx) { return ctx ? GO(cm_reads_swap) : CM_EINVAL; }
 int cm_map_rounds(cm_ctx *ctx, const int *slots, int n, int last) { return ctx ? GO(cm_map_rounds, slots, n, last) : CM_EINVAL; }
 int cm_map_round(cm_ctx *ctx, int slot, int is_last) { return ctx ? GO(cm_map_round, slot, is_last) : CM_EINVAL; }

@@ -27,6 +27,7 @@
 #include "cm_core.h"
 #include "cm_aos.h"
 #include "cm_index_build.h"
+#include "cm_fastq_text.h"
 
 using cmc::Core;
 using cmc::KCore;
@@ -65,10 +66,11 @@ enum Pin {
     PIN_HEAVY_LOAD = 4,                              // k_pair_cost's sum over the tile last sent (cm_ctx::h_pin_nt)
     PIN_CELLS = 8,                                   // + 2 * seed set: DP cells of the tile, + 1: of its largest problem
     PIN_RERUN_N = 12, PIN_FALL_N = 14,               // + chain-record set: length of the re-run list / of the pipeline's fall-back list
-    PIN_WORDS = 16
+    PIN_TEXT = 16,                                   // cm_reads_stage_text: the result block of the tokeniser (cmft::RES_WORDS words)
+    PIN_WORDS = 32
 };
 constexpr size_t PIN_BYTES = PIN_WORDS * sizeof(unsigned long long);        // allocated and cleared in cm_create
-static_assert(PIN_BYTES == 128 && PIN_FALL_N + 1 < PIN_WORDS && PIN_CELLS + 3 < PIN_RERUN_N, "the landing zone has 16 words");
+static_assert(PIN_BYTES == 256 && PIN_FALL_N + 1 < PIN_TEXT && PIN_CELLS + 3 < PIN_RERUN_N && PIN_TEXT + cmft::RES_WORDS <= PIN_WORDS, "the landing zone has 32 words");
 struct ReadsDev {
     const uint8_t *seq1, *seq2;
     const uint64_t *off1, *off2;
@@ -1972,6 +1974,99 @@ __global__ void k_init_state(KCore kc, cm_mapped_read *state, uint8_t *active, i
     cat[i] = -1;
 }
 
+// ---- cm_reads_stage_text: FASTQ text tokenised on the device (bodies and the plan: cm_fastq_text.h) ----------------
+constexpr int FT_T = 256;                       // threads of a tokeniser workgroup: 4 waves, one newline chunk each
+constexpr int FT_WAVES = FT_T / 64;
+// What the kernels behind the line tables need to know the batch: n = pair_count() of both files' lines, on the device.
+struct FtShape {
+    const uint32_t *nl1, *nl2;                  // newlines of the block: the grand-total slot of the scanned chunk counts
+    uint32_t trail1, trail2;                    // a last line without '\n' counts (end of input)
+    uint64_t max_pairs;
+    __device__ uint32_t lines(int f) const { return cmft::line_count(f ? *nl2 : *nl1, (f ? trail2 : trail1) != 0); }
+    __device__ uint32_t pairs() const { return cmft::pair_count(lines(0), lines(1), max_pairs); }
+};
+// cnt[c] = newlines of chunk c; cnt[n_chunks] = 0, the slot the exclusive scan leaves the total in
+__global__ void __launch_bounds__(FT_T) k_ft_count(const uint8_t *text, uint64_t len, uint32_t n_chunks, uint32_t *cnt) {
+    const uint32_t lane = threadIdx.x & 63, c = blockIdx.x * FT_WAVES + (threadIdx.x >> 6);
+    if (c > n_chunks) return;                   // (the whole wave)
+    uint32_t k = c < n_chunks ? cmft::popcount16(cmft::nl_mask16(text, (uint64_t)c * cmft::NL_CHUNK + lane * cmft::LANE_BYTES, len)) : 0u;
+    for (int o = 32; o; o >>= 1) k += __shfl_xor(k, o);
+    if (lane == 0) cnt[c] = k;
+}
+// the line-start table from the scanned counts: base[c] = newlines in front of chunk c
+__global__ void __launch_bounds__(FT_T) k_ft_lines(const uint8_t *text, uint64_t len, uint32_t n_chunks, const uint32_t *base, uint32_t trailing, uint32_t *ls,
+                                                   uint32_t ls_cap) {
+    const uint32_t lane = threadIdx.x & 63, c = blockIdx.x * FT_WAVES + (threadIdx.x >> 6);
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        ls[0] = 0;
+        const uint32_t end = base[n_chunks] + 1;                    // the sentinel behind a last line without '\n'
+        if (trailing && end < ls_cap) ls[end] = (uint32_t)len + 1u;
+    }
+    if (c >= n_chunks) return;
+    const uint64_t at = (uint64_t)c * cmft::NL_CHUNK + lane * cmft::LANE_BYTES;
+    const uint32_t mask = cmft::nl_mask16(text, at, len), k = cmft::popcount16(mask);
+    uint32_t incl = k;
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t y = __shfl_up(incl, o);
+        if (lane >= (uint32_t)o) incl += y;
+    }
+    cmft::put_line_starts(mask, at, base[c] + incl - k, ls, ls_cap);
+}
+// one lane per record: verdict, sequence length (0 for i in [n, nb]: the scan's input), the first malformed record and the
+// longest read through one atomic per workgroup at most
+__global__ void __launch_bounds__(FT_T) k_ft_records(const uint8_t *text, const uint32_t *ls, FtShape sh, int file, uint32_t nb, uint32_t *slen,
+                                                     unsigned long long *res) {
+    __shared__ uint32_t wmax[FT_WAVES];
+    const uint32_t i = blockIdx.x * FT_T + threadIdx.x, n = sh.pairs();
+    uint32_t sl = 0;
+    if (i < n) {
+        const uint32_t bad = cmft::check_record(text, ls, i, file == 0, &sl);
+        if (bad) atomicMin(&res[cmft::RES_BAD1 + file], cmft::bad_key(i, bad));       // (malformed input only)
+    }
+    if (i <= nb) slen[i] = sl;
+    uint32_t m = sl;
+    for (int o = 32; o; o >>= 1) m = max(m, (uint32_t)__shfl_xor(m, o));
+    if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = m;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < FT_WAVES; ++w) m = max(m, wmax[w]);
+        if (m) atomicMax(&res[cmft::RES_MAX_LEN], (unsigned long long)m);
+    }
+}
+// off[0 .. n] from the scanned lengths (soff[n] = all bases: the lengths behind record n - 1 are zero) and the record starts
+__global__ void __launch_bounds__(FT_T) k_ft_offsets(const uint32_t *ls, const uint32_t *soff, FtShape sh, uint64_t len, uint64_t *off, uint64_t *rec) {
+    const uint32_t i = blockIdx.x * FT_T + threadIdx.x, n = sh.pairs();
+    if (i > n) return;
+    off[i] = soff[i];
+    const uint32_t r = ls[4 * (uint64_t)i];
+    rec[i] = r > len ? len : r;                  // (the sentinel behind a last line without '\n' is len + 1)
+}
+// COPY_LANES lanes per record move its bases to seq_base + CM_STAGE_PAD + off[i]; workgroup 0 clears the slack on both sides
+__global__ void __launch_bounds__(FT_T) k_ft_copy(const uint8_t *text, const uint32_t *ls, const uint64_t *off, FtShape sh, uint8_t *seq_base) {
+    constexpr uint32_t pad = cmc::CM_STAGE_PAD;
+    static_assert(pad <= FT_T && pad % 4 == 0, "one thread per byte of slack; the reads start on a word");
+    const uint32_t n = sh.pairs();
+    if (blockIdx.x == 0 && threadIdx.x < pad) {
+        seq_base[threadIdx.x] = 0;
+        seq_base[pad + off[n] + threadIdx.x] = 0;
+    }
+    const uint32_t groups = gridDim.x * (FT_T / cmft::COPY_LANES), lane = threadIdx.x % cmft::COPY_LANES;
+    for (uint32_t i = (blockIdx.x * FT_T + threadIdx.x) / cmft::COPY_LANES; i < n; i += groups) {
+        const uint32_t s = ls[4 * (uint64_t)i + 1], l = ls[4 * (uint64_t)i + 2] - 1u - s;
+        cmft::copy_bases(seq_base, pad + off[i], text, s, l, (int)lane, cmft::COPY_LANES);
+    }
+}
+__global__ void k_ft_finish(FtShape sh, const uint64_t *off1, const uint64_t *off2, const uint64_t *rec1, const uint64_t *rec2, unsigned long long *res) {
+    const uint32_t n = sh.pairs();
+    res[cmft::RES_LINES1] = sh.lines(0);
+    res[cmft::RES_LINES2] = sh.lines(1);
+    res[cmft::RES_PAIRS] = n;
+    res[cmft::RES_BASES1] = off1[n];
+    res[cmft::RES_BASES2] = off2[n];
+    res[cmft::RES_USED1] = rec1[n];
+    res[cmft::RES_USED2] = rec2[n];
+}
+
 // ------------------------------------------------------------------ host side
 struct Slot {
     bool loaded = false, has_annot = false;
@@ -2108,6 +2203,16 @@ struct Collect {
     CtxBuf<cm_record> rec;
 };
 
+// cm_reads_stage_text: per file the block's text, the newline counts per chunk (scanned in place), the line-start table, the
+// sequence lengths (scanned in place) and the record starts; the scans' block totals and the result block (cmft::Res).
+struct TextStage {
+    BatchBuf<uint8_t> text[2];
+    BatchBuf<uint32_t> cnt[2], ls[2], slen[2];
+    BatchBuf<uint64_t> rec[2];
+    BatchBuf<uint32_t> tmp;
+    BatchBuf<unsigned long long> res;
+};
+
 // The streams of a context, under the letters of DESIGN §4.  STREAMS lists them in creation order, which decides the hardware
 // queue a stream lands on; everything that walks the streams walks that table.
 struct Streams {
@@ -2206,6 +2311,7 @@ struct cm_ctx {
     BatchBuf<cm_mapped_read> st_prior;
     bool st_has_prior = false;
     int st_max_len = 0;
+    TextStage ft;                             // cm_reads_stage_text
     // workspace of one tile
     uint32_t tile = 0;
     SeedSet seed[2];                          // item i + 1 is seeded into one while the chain stage of item i reads the other
@@ -2805,15 +2911,19 @@ int cm_load_contig(cm_ctx *ctx, int slot, const cm_index_view *iv) {
     return finish_contig(ctx, s);
 }
 
-// exclusive (or inclusive) scan of n uint32 items on ctx->st.B; tmp: (n / S32_B + 2) words
-static int scan32(cm_ctx *ctx, const uint32_t *in, uint64_t n, uint32_t *out, uint32_t *tmp, uint32_t add, int inclusive) {
+// exclusive (or inclusive) scan of n uint32 items on stream st; tmp: (n / S32_B + 2) words
+static int scan32_on(cm_ctx *ctx, hipStream_t st, const uint32_t *in, uint64_t n, uint32_t *out, uint32_t *tmp, uint32_t add, int inclusive) {
     const uint32_t nb = (uint32_t)((n + S32_B - 1) / S32_B);
     if (nb == 0) return CM_OK;
-    hipLaunchKernelGGL(k_scan32_a, dim3(nb), dim3(S32_T), 0, ctx->st.B, in, n, out, tmp, add, inclusive);
-    hipLaunchKernelGGL((k_scan_mid<uint32_t, false>), dim3(1), dim3(1024), 0, ctx->st.B, tmp, nb, (uint32_t *)nullptr, (const unsigned int *)nullptr);
-    hipLaunchKernelGGL(k_scan32_c, dim3(nb), dim3(S32_T), 0, ctx->st.B, out, n, (const uint32_t *)tmp);
+    hipLaunchKernelGGL(k_scan32_a, dim3(nb), dim3(S32_T), 0, st, in, n, out, tmp, add, inclusive);
+    hipLaunchKernelGGL((k_scan_mid<uint32_t, false>), dim3(1), dim3(1024), 0, st, tmp, nb, (uint32_t *)nullptr, (const unsigned int *)nullptr);
+    hipLaunchKernelGGL(k_scan32_c, dim3(nb), dim3(S32_T), 0, st, out, n, (const uint32_t *)tmp);
     HIPCHK(ctx, hipGetLastError());
     return CM_OK;
+}
+// ... on the main stream (the index loaders)
+static int scan32(cm_ctx *ctx, const uint32_t *in, uint64_t n, uint32_t *out, uint32_t *tmp, uint32_t add, int inclusive) {
+    return scan32_on(ctx, ctx->st.B, in, n, out, tmp, add, inclusive);
 }
 
 int cm_load_contig_raw(cm_ctx *ctx, int slot, const cm_index_raw *raw) {
@@ -3412,6 +3522,147 @@ int cm_reads_stage(cm_ctx *ctx, const cm_reads *rd, const cm_mapped_read *prior)
     ctx->st_n_pairs = rd->n_pairs;
     ctx->st_max_len = max_len;
     ctx->staged = true;
+    return CM_OK;
+}
+
+// cm_reads_stage for FASTQ text: the two blocks go over PCIe as they are and the kernels k_ft_* (bodies: cm_fastq_text.h) find the
+// lines, check every record and fill the staged read buffers, all on the staging stream.  The batch's shape is known on the device
+// only; the host sizes everything from the text lengths (bases <= bytes, a record has at least four bytes) and learns the shape and
+// the verdicts from one small read-back.
+int cm_reads_stage_text(cm_ctx *ctx, const uint8_t *text1, uint64_t len1, const uint8_t *text2, uint64_t len2, uint64_t max_pairs, uint32_t flags,
+                        uint64_t *rec1, uint64_t *rec2, cm_text_batch *out) {
+    if (!ctx || !out) return CM_EINVAL;
+    memset(out, 0, sizeof *out);
+    HIPCHK(ctx, hipSetDevice(ctx->P.device));
+    const uint8_t *text[2] = {text1, text2};
+    const uint64_t len[2] = {len1, len2};
+    uint32_t trail[2];
+    for (int f = 0; f < 2; ++f) {
+        if (len[f] && !text[f]) return fail(ctx, CM_EINVAL, "cm_reads_stage_text: null text");
+        trail[f] = ((flags >> f) & 1u) && len[f] && text[f][len[f] - 1] != '\n';
+        // (the sentinel behind a last line without '\n' is len + 1, a uint32 like every line start)
+        if (len[f] > 0xffffffffull - trail[f]) return fail(ctx, CM_ELIMIT, "cm_reads_stage_text: a block of %llu bytes", (unsigned long long)len[f]);
+    }
+    const uint64_t mp = std::min<uint64_t>(max_pairs, 1ull << 30);           // (a block below 2^32 bytes holds fewer records than that)
+    const uint32_t nb = (uint32_t)std::min<uint64_t>(mp, std::min(len1, len2) / 4);      // no more pairs than this: four bytes per record at least
+    HIPCHK(ctx, hipStreamSynchronize(ctx->st.C));          // an earlier staged batch that was never swapped in is dropped
+    ctx->staged = false;
+    ctx->pre_launched = false;
+    TextStage &T = ctx->ft;
+    hipStream_t st = ctx->st.C;
+    const size_t pad = cmc::CM_STAGE_PAD;
+    uint32_t n_chunks[2], ls_cap[2];
+    ReadBufs &to = ctx->st_rd;
+    HIPCHK(ctx, ensure(ctx, to.seq1_base, len1 + 2 * pad));
+    HIPCHK(ctx, ensure(ctx, to.seq2_base, len2 + 2 * pad));
+    HIPCHK(ctx, ensure(ctx, to.off1, ((size_t)nb + 1) * sizeof(uint64_t)));
+    HIPCHK(ctx, ensure(ctx, to.off2, ((size_t)nb + 1) * sizeof(uint64_t)));
+    HIPCHK(ctx, ensure(ctx, T.res, cmft::RES_WORDS * sizeof(unsigned long long)));
+    uint64_t scan_items = (uint64_t)nb + 1;
+    for (int f = 0; f < 2; ++f) {
+        n_chunks[f] = (uint32_t)((len[f] + cmft::NL_CHUNK - 1) / cmft::NL_CHUNK);
+        ls_cap[f] = (uint32_t)std::min<uint64_t>(len[f] + 2, 4 * mp + 1);
+        scan_items = std::max<uint64_t>(scan_items, (uint64_t)n_chunks[f] + 1);
+        HIPCHK(ctx, ensure(ctx, T.text[f], (len[f] + 15) / 16 * 16 + cmft::TEXT_SLACK));
+        HIPCHK(ctx, ensure(ctx, T.cnt[f], ((size_t)n_chunks[f] + 1) * sizeof(uint32_t)));
+        HIPCHK(ctx, ensure(ctx, T.ls[f], (size_t)ls_cap[f] * sizeof(uint32_t)));
+        HIPCHK(ctx, ensure(ctx, T.slen[f], ((size_t)nb + 1) * sizeof(uint32_t)));
+        HIPCHK(ctx, ensure(ctx, T.rec[f], ((size_t)nb + 1) * sizeof(uint64_t)));
+    }
+    HIPCHK(ctx, ensure(ctx, T.tmp, (size_t)(scan_items / S32_B + 2) * sizeof(uint32_t)));
+    HIPCHK(ctx, hipMemsetAsync(T.res, 0xff, 2 * sizeof(unsigned long long), st));                          // RES_BAD1, RES_BAD2: none
+    HIPCHK(ctx, hipMemsetAsync(T.res + cmft::RES_MAX_LEN, 0, sizeof(unsigned long long), st));
+    int rc;
+    for (int f = 0; f < 2; ++f)
+        if (len[f]) HIPCHK(ctx, hipMemcpyAsync(T.text[f], text[f], len[f], hipMemcpyHostToDevice, st));
+    hipEvent_t t_a = nullptr, t_b = nullptr;                // cm_prof_enable: the kernels' time, copies excluded (cm_text_batch.reserved)
+    if (ctx->prof) {
+        t_a = take_event(ctx);
+        t_b = take_event(ctx);
+        if (t_a) HIPCHK(ctx, hipEventRecord(t_a, st));
+    }
+    for (int f = 0; f < 2; ++f) {                           // lines of both files
+        hipLaunchKernelGGL(k_ft_count, dim3(n_chunks[f] / FT_WAVES + 1), dim3(FT_T), 0, st, (const uint8_t *)T.text[f], len[f], n_chunks[f], (uint32_t *)T.cnt[f]);
+        if ((rc = scan32_on(ctx, st, T.cnt[f], (uint64_t)n_chunks[f] + 1, T.cnt[f], T.tmp, 0u, 0))) return rc;
+        hipLaunchKernelGGL(k_ft_lines, dim3((n_chunks[f] + FT_WAVES - 1) / FT_WAVES + 1), dim3(FT_T), 0, st, (const uint8_t *)T.text[f], len[f], n_chunks[f],
+                           (const uint32_t *)T.cnt[f], trail[f], (uint32_t *)T.ls[f], ls_cap[f]);
+    }
+    const FtShape sh{T.cnt[0] + n_chunks[0], T.cnt[1] + n_chunks[1], trail[0], trail[1], mp};
+    for (int f = 0; f < 2; ++f) {                           // records of both files: the batch is the shorter file's
+        uint8_t *seq_base = f ? to.seq2_base : to.seq1_base;
+        uint64_t *off = f ? to.off2 : to.off1;
+        const unsigned gb = nb / FT_T + 1;                  // covers i = 0 .. nb
+        hipLaunchKernelGGL(k_ft_records, dim3(gb), dim3(FT_T), 0, st, (const uint8_t *)T.text[f], (const uint32_t *)T.ls[f], sh, f, nb, (uint32_t *)T.slen[f],
+                           (unsigned long long *)T.res);
+        if ((rc = scan32_on(ctx, st, T.slen[f], (uint64_t)nb + 1, T.slen[f], T.tmp, 0u, 0))) return rc;
+        hipLaunchKernelGGL(k_ft_offsets, dim3(gb), dim3(FT_T), 0, st, (const uint32_t *)T.ls[f], (const uint32_t *)T.slen[f], sh, len[f], off, (uint64_t *)T.rec[f]);
+        const unsigned gc = (unsigned)std::min<uint64_t>(((uint64_t)nb * cmft::COPY_LANES + FT_T - 1) / FT_T + 1, 1u << 16);
+        hipLaunchKernelGGL(k_ft_copy, dim3(gc), dim3(FT_T), 0, st, (const uint8_t *)T.text[f], (const uint32_t *)T.ls[f], (const uint64_t *)off, sh, seq_base);
+    }
+    hipLaunchKernelGGL(k_ft_finish, dim3(1), dim3(1), 0, st, sh, (const uint64_t *)to.off1, (const uint64_t *)to.off2, (const uint64_t *)T.rec[0],
+                       (const uint64_t *)T.rec[1], (unsigned long long *)T.res);
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipEventRecord(ctx->ev.staged, st));       // behind the last tokeniser kernel: the cross-batch prefetch reads the buffers behind it
+    if (t_a && t_b) HIPCHK(ctx, hipEventRecord(t_b, st));
+    unsigned long long *R = ctx->h_pin + PIN_TEXT;
+    HIPCHK(ctx, hipMemcpyAsync(R, T.res, cmft::RES_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    if (t_a && t_b) {
+        float ms = 0.f;
+        if (hipEventElapsedTime(&ms, t_a, t_b) == hipSuccess) out->reserved = (int32_t)std::min(ms * 1000.f, 2.0e9f);
+    }
+    for (hipEvent_t e : {t_a, t_b})
+        if (e) ctx->ev_free.push_back(e);
+    const uint64_t n = R[cmft::RES_PAIRS], lines[2] = {R[cmft::RES_LINES1], R[cmft::RES_LINES2]};
+    // the verdicts of next_plain / build_side / check_reads
+    for (int f = 0; f < 2; ++f)
+        if (((flags >> f) & 1u) && lines[f] % 4 != 0 && lines[f] / 4 < max_pairs)
+            return fail(ctx, CM_EINVAL, "FASTQ file %d: %llu lines behind its last whole record", f + 1, (unsigned long long)(lines[f] % 4));
+    if ((flags & 2u) && lines[1] / 4 < std::min<uint64_t>(lines[0] / 4, max_pairs)) return fail(ctx, CM_EINVAL, "FASTQ file 2 ends before file 1");
+    for (int f = 0; f < 2; ++f) {
+        const unsigned long long key = R[cmft::RES_BAD1 + f];
+        if (key == cmft::NO_BAD || (key & 7u) == cmft::BAD_CARRIED) continue;
+        static const char *const what[] = {"", "the header line is empty or does not start with '@'", "the third line is empty or does not start with '+'",
+                                           "the quality line is not as long as the sequence line"};
+        return fail(ctx, CM_EINVAL, "FASTQ file %d, record %llu of the block: %s", f + 1, key >> 3, what[key & 3u]);
+    }
+    if (R[cmft::RES_BAD1] != cmft::NO_BAD)
+        return fail(ctx, CM_EINVAL, "FASTQ file 1, record %llu of the block: a 23-token header (carried state: take cm_fastq_next)", R[cmft::RES_BAD1] >> 3);
+    const uint64_t max_len = R[cmft::RES_MAX_LEN];
+    if (max_len > (uint64_t)ctx->P.max_read_len) return fail(ctx, CM_EINVAL, "a read of %llu bases is longer than max_read_len %d", (unsigned long long)max_len, ctx->P.max_read_len);
+    if ((int)max_len / ctx->P.kmer > cmc::MAX_SEEDS) return fail(ctx, CM_ELIMIT, "%d seeds per read > %d supported", (int)max_len / ctx->P.kmer, cmc::MAX_SEEDS);
+    out->n_pairs = n;
+    out->used1 = R[cmft::RES_USED1];
+    out->used2 = R[cmft::RES_USED2];
+    out->max_len = (int32_t)max_len;
+    if (n == 0) return CM_OK;                               // nothing staged: the caller supplies more bytes
+    if (rec1) HIPCHK(ctx, hipMemcpyAsync(rec1, T.rec[0], (n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    if (rec2) HIPCHK(ctx, hipMemcpyAsync(rec2, T.rec[1], (n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    if (rec1 || rec2) HIPCHK(ctx, hipStreamSynchronize(st));
+    ctx->st_has_prior = false;
+    ctx->st_n_pairs = n;
+    ctx->st_max_len = (int)max_len;
+    ctx->staged = true;
+    return CM_OK;
+}
+
+// test hook: the resident batch's read bytes and offsets copied back
+int cm_reads_peek(cm_ctx *ctx, uint8_t *seq1, uint64_t cap1, uint64_t *off1, uint8_t *seq2, uint64_t cap2, uint64_t *off2, uint64_t *n_pairs) {
+    if (!ctx || !n_pairs) return CM_EINVAL;
+    HIPCHK(ctx, hipSetDevice(ctx->P.device));
+    const uint64_t n = ctx->n_pairs;
+    *n_pairs = n;
+    if (n == 0 || (!seq1 && !seq2 && !off1 && !off2)) return CM_OK;
+    uint64_t total[2] = {0, 0};
+    HIPCHK(ctx, hipMemcpyAsync(&total[0], ctx->rd.off1 + n, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->st.B));
+    HIPCHK(ctx, hipMemcpyAsync(&total[1], ctx->rd.off2 + n, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->st.B));
+    if (off1) HIPCHK(ctx, hipMemcpyAsync(off1, ctx->rd.off1, (n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->st.B));
+    if (off2) HIPCHK(ctx, hipMemcpyAsync(off2, ctx->rd.off2, (n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->st.B));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->st.B));
+    if ((seq1 && cap1 < total[0]) || (seq2 && cap2 < total[1])) return fail(ctx, CM_ELIMIT, "cm_reads_peek: %llu / %llu read bytes", (unsigned long long)total[0], (unsigned long long)total[1]);
+    if (seq1 && total[0]) HIPCHK(ctx, hipMemcpyAsync(seq1, ctx->rd.seq1_base + cmc::CM_STAGE_PAD, total[0], hipMemcpyDeviceToHost, ctx->st.B));
+    if (seq2 && total[1]) HIPCHK(ctx, hipMemcpyAsync(seq2, ctx->rd.seq2_base + cmc::CM_STAGE_PAD, total[1], hipMemcpyDeviceToHost, ctx->st.B));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->st.B));
     return CM_OK;
 }
 

@@ -298,11 +298,22 @@ struct cm_fastq {
     // cm_fastq_open_shard on input that cannot be cut at a byte offset (gzip, pipes): this reader inflates the stream from its start,
     // steps over the first skip_left records and hands out take_left (~0: to the end of the input)
     uint64_t skip_left = 0, take_left = ~0ull;
+    // raw-block mode (cm_fastq_next_text): four generations of text buffers per file, used in turn like the batches.  A block is
+    // the unconsumed tail of the block before it followed by freshly read bytes: the bytes are read behind head room at the
+    // front of the generation's buffer and the tail is copied into that room, so the block itself is never moved.
+    struct TextGen {
+        RawVec<uint8_t> buf[2];
+    } tgen[4];
+    int tcur = 3;
+    const uint8_t *block[2] = {nullptr, nullptr};    // the block handed out last ...
+    uint64_t block_len[2] = {0, 0};
+    uint64_t block_used[2] = {0, 0};                 // ... and what cm_fastq_text_consumed said of it (0: nothing yet)
     cm_fastq() {
         for (Gen &g : gen) {                 // the arrays cm_fastq_batch::reads / prior point into
             g.a.seq.hook = g.a.off.hook = g.b.seq.hook = g.b.off.hook = &hook;
             g.prior.hook = &hook;
         }
+        for (TextGen &g : tgen) g.buf[0].hook = g.buf[1].hook = &hook;
     }
 };
 
@@ -1007,6 +1018,100 @@ static int fastq_next(cm_fastq *f, uint64_t max_pairs, cm_fastq_batch *out) {
     return CM_OK;
 }
 
+// ---- raw-block mode: the text itself, for cm_reads_stage_text --------------------------------------------------------
+static int fastq_next_text(cm_fastq *f, uint64_t want, const uint8_t **text, uint64_t *len, int *eof) {
+    constexpr size_t HEAD_MIN = 64u << 10;                 // head room in front of the fresh bytes: a tail is a few records as a rule
+    if (want == 0) want = 1;
+    if (want > (1ull << 31)) want = 1ull << 31;            // (a block stays below cm_reads_stage_text's 2^32 - 1 bytes)
+    // Nothing consumed of the last block (it held no whole pair): the same generation again, fresh bytes appended in place, so that
+    // the blocks a caller still holds keep their three calls of life.
+    const bool again = f->block[0] && f->block_used[0] == 0 && f->block_used[1] == 0 && (f->block_len[0] || f->block_len[1]);
+    if (!again) f->tcur = (f->tcur + 1) % 4;
+    Stream *ss[2] = {&f->s1, &f->s2};
+    int nt = f->n_threads > 0 ? f->n_threads : (int)std::thread::hardware_concurrency();
+    nt = nt > 16 ? 16 : (nt < 2 ? 2 : nt);
+    int rc[2] = {CM_OK, CM_OK};
+    auto side = [&](int x) {
+        RawVec<uint8_t> &B = f->tgen[f->tcur].buf[x];
+        const uint64_t tl = f->block_len[x] - f->block_used[x];
+        const uint8_t *tail = f->block[x] + f->block_used[x];
+        // a block of `want` bytes, tail included (files whose records differ in length then keep a steady tail); a tail that is
+        // most of that -- nothing was consumed: a record larger than the block -- still gets half a block of fresh bytes
+        const uint64_t fresh = tl < want / 2 ? want - tl : (want + 1) / 2;
+        uint8_t *data;
+        if (again) {
+            const size_t at = (size_t)(tail - B.data());
+            B.n = at + (size_t)tl;                          // (kept if the buffer has to grow)
+            B.resize(at + (size_t)tl + (size_t)fresh);
+            data = B.data() + at + tl;
+        } else {
+            const size_t head = std::max<size_t>(HEAD_MIN, ((size_t)tl + 4095) / 4096 * 4096);
+            B.clear();                                      // (nothing of the old block is kept when the buffer has to grow)
+            B.resize(head + (size_t)fresh);
+            data = B.data() + head;
+            if (tl) memcpy(data - tl, tail, (size_t)tl);
+        }
+        Stream &s = *ss[x];
+        s.read_threads = nt / 2;
+        uint64_t got = 0;
+        while (got < fresh) {
+            const int r = s.read_some((char *)data + got, (size_t)(fresh - got));
+            if (r < 0) {
+                rc[x] = CM_EIO;
+                return;
+            }
+            if (r == 0) break;
+            got += (uint64_t)r;
+        }
+        struct stat sb;
+        const uint64_t size = fstat(fileno(s.plain), &sb) == 0 ? (uint64_t)sb.st_size : ~0ull;
+        eof[x] = got < fresh || s.file_pos >= std::min(size, s.file_end);
+        text[x] = data - tl;
+        len[x] = tl + got;
+    };
+    {
+        std::thread t2([&]() { guarded([&]() { side(1); }); });
+        try {
+            side(0);
+        } catch (const std::bad_alloc &) {
+            g_raw_oom = 1;
+        }
+        t2.join();
+    }
+    if (g_raw_oom.exchange(0)) return CM_ENOMEM;
+    if (rc[0] != CM_OK || rc[1] != CM_OK) return CM_EIO;
+    for (int x = 0; x < 2; ++x) {
+        f->block[x] = text[x];
+        f->block_len[x] = len[x];
+        f->block_used[x] = 0;
+    }
+    return CM_OK;
+}
+int cm_fastq_next_text(cm_fastq *f, uint64_t want_bytes, const uint8_t **text1, uint64_t *len1, int *eof1, const uint8_t **text2, uint64_t *len2,
+                       int *eof2) {
+    if (!f || !text1 || !len1 || !eof1 || !text2 || !len2 || !eof2) return CM_EINVAL;
+    // regular plain-text files only, and not behind cm_fastq_next calls that have buffered text of their own
+    if (!f->s1.plain || !f->s2.plain || f->s1.end != f->s1.pos || f->s2.end != f->s2.pos) return CM_EINVAL;
+    const uint8_t *text[2] = {nullptr, nullptr};
+    uint64_t len[2] = {0, 0};
+    int eof[2] = {0, 0};
+    const int rc = fastq_next_text(f, want_bytes, text, len, eof);
+    if (rc != CM_OK) return rc;
+    *text1 = text[0];
+    *len1 = len[0];
+    *eof1 = eof[0];
+    *text2 = text[1];
+    *len2 = len[1];
+    *eof2 = eof[1];
+    return CM_OK;
+}
+int cm_fastq_text_consumed(cm_fastq *f, uint64_t used1, uint64_t used2) {
+    if (!f || used1 > f->block_len[0] || used2 > f->block_len[1]) return CM_EINVAL;
+    f->block_used[0] = used1;
+    f->block_used[1] = used2;
+    return CM_OK;
+}
+
 void cm_fastq_close(cm_fastq *f) {
     if (!f) return;
     f->s1.close();
@@ -1042,17 +1147,25 @@ static const char *chr_name(const cm_writer *w, int id) { return (id >= 0 && (si
 // write_read_category (PE) for the selected pairs of a batch; sel == NULL selects every pair
 }  // extern "C"
 // write_read_category for n pairs: pair(k) = index in the batch, state(k) = its MatchedRead
-template <class PairOf, class StateOf>
-static int write_remain_rows(cm_writer *w, const cm_fastq_batch *b, uint64_t n, PairOf pair, StateOf state) {
+// what a row takes from the input: name, bases and quality of mate s of pair i
+struct RowText {
+    const char *name;
+    size_t name_len;
+    const uint8_t *seq, *qual;
+    size_t len;
+};
+template <class PairOf, class StateOf, class TextOf>
+static int write_remain_rows(cm_writer *w, uint64_t n_pairs, uint64_t n, PairOf pair, StateOf state, TextOf text_of) {
     for (uint64_t k = 0; k < n; ++k) {
         const uint64_t i = pair(k);
-        if (i >= b->reads.n_pairs) return CM_EINVAL;
+        if (i >= n_pairs) return CM_EINVAL;
         const cm_mapped_read &m = state(k);
         Out *os[2] = {&w->o1, &w->o2};
         for (int s = 0; s < 2; ++s) {
             Out &o = *os[s];
+            const RowText t = text_of(s, i);
             o.ch('@');
-            o.str((s ? b->names2 : b->names1) + (s ? b->name_off2 : b->name_off1)[i]);
+            o.raw(t.name, t.name_len);
             if (mapped_type(m.type)) {
                 const char *cn = chr_name(w, m.chr_id);
                 const uint32_t shift = (m.chr_id >= 0 && (size_t)m.chr_id < w->chr_shift.size()) ? w->chr_shift[(size_t)m.chr_id] : 0u;
@@ -1085,29 +1198,62 @@ static int write_remain_rows(cm_writer *w, const cm_fastq_batch *b, uint64_t n, 
                 o.i64(m.type);
                 o.str(" * * * * * * * * * * * * * * * * * * * *");
             }
-            const uint8_t *seq = s ? b->reads.seq2 : b->reads.seq1, *q = s ? b->qual2 : b->qual1;
-            const uint64_t *off = s ? b->reads.off2 : b->reads.off1;
-            const size_t len = (size_t)(off[i + 1] - off[i]);
             o.ch('\n');
-            o.raw(seq + off[i], len);
+            o.raw(t.seq, t.len);
             o.str("\n+\n");
-            o.raw(q + off[i], len);
+            o.raw(t.qual, t.len);
             o.ch('\n');
         }
     }
     return (w->o1.failed || w->o2.failed) ? CM_EIO : CM_OK;
 }
+// ... of a parsed batch
+static auto batch_text(const cm_fastq_batch *b) {
+    return [b](int s, uint64_t i) {
+        const char *name = (s ? b->names2 : b->names1) + (s ? b->name_off2 : b->name_off1)[i];
+        const uint64_t *off = s ? b->reads.off2 : b->reads.off1;
+        return RowText{name, strlen(name), (s ? b->reads.seq2 : b->reads.seq1) + off[i], (s ? b->qual2 : b->qual1) + off[i], (size_t)(off[i + 1] - off[i])};
+    };
+}
 
 extern "C" {
 int cm_write_remain(cm_writer *w, const cm_fastq_batch *b, const cm_mapped_read *states, const uint64_t *sel, uint64_t n_sel) {
     if (!w || !w->f2 || !b || !states) return CM_EINVAL;
-    return write_remain_rows(w, b, sel ? n_sel : b->reads.n_pairs, [&](uint64_t k) { return sel ? sel[k] : k; },
-                             [&](uint64_t k) -> const cm_mapped_read & { return states[sel ? sel[k] : k]; });
+    return write_remain_rows(w, b->reads.n_pairs, sel ? n_sel : b->reads.n_pairs, [&](uint64_t k) { return sel ? sel[k] : k; },
+                             [&](uint64_t k) -> const cm_mapped_read & { return states[sel ? sel[k] : k]; }, batch_text(b));
 }
 
 int cm_write_remain_records(cm_writer *w, const cm_fastq_batch *b, const cm_record *recs, uint64_t n) {
     if (!w || !w->f2 || !b || (n && !recs)) return CM_EINVAL;
-    return write_remain_rows(w, b, n, [&](uint64_t k) { return recs[k].pair; }, [&](uint64_t k) -> const cm_mapped_read & { return recs[k].state; });
+    return write_remain_rows(w, b->reads.n_pairs, n, [&](uint64_t k) { return recs[k].pair; }, [&](uint64_t k) -> const cm_mapped_read & { return recs[k].state; },
+                             batch_text(b));
+}
+
+// cm_write_remain_records for a batch that cm_reads_stage_text tokenised: name, bases and quality of a selected pair are sliced
+// from the block's text at the record starts the stage returned (the records were checked there: four lines each, quality as
+// long as the bases)
+int cm_write_remain_text(cm_writer *w, const uint8_t *text1, const uint64_t *rec1, const uint8_t *text2, const uint64_t *rec2, const cm_record *recs,
+                         uint64_t n_rec) {
+    if (!w || !w->f2 || (n_rec && (!recs || !text1 || !rec1 || !text2 || !rec2))) return CM_EINVAL;
+    auto text_of = [&](int s, uint64_t i) {
+        const uint8_t *p = (s ? text2 : text1) + (s ? rec2 : rec1)[i], *end = (s ? text2 : text1) + (s ? rec2 : rec1)[i + 1];
+        const uint8_t *nl = (const uint8_t *)memchr(p, '\n', (size_t)(end - p));
+        const size_t hl = (size_t)((nl ? nl : end) - p);                     // the header line, '@' included
+        const char *tok[FQCOMMENTCNT + 1];
+        size_t tl[FQCOMMENTCNT + 1];
+        const int nt = split_header((const char *)p, hl, tok, tl);
+        RowText t{nt ? tok[0] : (const char *)p, name_len(nt, tok, tl), nullptr, nullptr, 0};
+        const uint8_t *q = nl ? nl + 1 : end;                                // the sequence line
+        nl = (const uint8_t *)memchr(q, '\n', (size_t)(end - q));
+        t.seq = q;
+        t.len = (size_t)((nl ? nl : end) - q);
+        q = nl ? nl + 1 : end;                                               // the '+' line
+        nl = (const uint8_t *)memchr(q, '\n', (size_t)(end - q));
+        t.qual = nl ? nl + 1 : end;
+        if ((size_t)(end - t.qual) < t.len) t.len = (size_t)(end - t.qual); // (never for a record the stage accepted)
+        return t;
+    };
+    return write_remain_rows(w, ~0ull, n_rec, [&](uint64_t k) { return recs[k].pair; }, [&](uint64_t k) -> const cm_mapped_read & { return recs[k].state; }, text_of);
 }
 
 // write_pam_rec_pe for the selected pairs (names of R1)

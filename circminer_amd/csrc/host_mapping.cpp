@@ -20,12 +20,17 @@
 // Only what the rows need leaves the device: with report 0 (the reference's default, src/commandline_parser.cpp:26) that is the
 // (pair, state) records of the re-queued pairs and a 14-bin type histogram.
 //
+// With CM_FASTQ_DEVICE=1 and report 0 the parser thread only reads: raw text blocks (cm_fastq_next_text) are tokenised by the device
+// (cm_reads_stage_text) and the remain rows of the re-queued pairs are sliced from the text (cm_write_remain_text); same pipeline,
+// same files.  Opt-in: see DESIGN.md §7 for what it costs and gains.
+//
 // One process per GPU: rank r of w maps the r-th contiguous block of pairs (cm_fastq_open_shard) and writes .part<r> files;
 // cm_merge_parts on rank 0 concatenates them in rank order -- the bytes one process would have written.
 #include <algorithm>
 #include <chrono>
 #include <cstdarg>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <string>
 #include <mutex>
@@ -322,7 +327,7 @@ extern "C" int cm_mapping_run(const cm_mapping_args *a, cm_mapping_stats *stats,
         MAP_TRY(cm_writer_open(r1.c_str(), r2.c_str(), chrs, n_chr, &w_rem), "cm_writer_open (remain)");
     }
     MAP_TRY(cm_fastq_open_shard(a->fastq1, a->fastq2, chrs, n_chr, P.max_ed, rank, world, n_threads, &fq, nullptr, nullptr), "cm_fastq_open_shard");
-    cm_fastq_set_release_hook(fq, [](void *user, const void *ptr, uint64_t bytes) {
+    void (*const release_fn)(void *, const void *, uint64_t) = [](void *user, const void *ptr, uint64_t bytes) {
         Pinned *pn = (Pinned *)user;
         std::lock_guard<std::mutex> lk(pn->mu);
         const char *lo = (const char *)ptr, *hi = lo + bytes;
@@ -333,7 +338,8 @@ extern "C" int cm_mapping_run(const cm_mapping_args *a, cm_mapping_stats *stats,
                 it = pn->v.erase(it);
             } else ++it;
         }
-    }, &pin);
+    };
+    cm_fastq_set_release_hook(fq, release_fn, &pin);
 
     // ---- batches: write k-1 (worker) | rounds of k (device, driven by this thread) | H2D + first round of k+1 | parse k+2 (worker) ----
     const double t1 = now();
@@ -368,6 +374,156 @@ extern "C" int cm_mapping_run(const cm_mapping_args *a, cm_mapping_stats *stats,
         }
         return CM_OK;
     };
+    // page-lock [p, p + bytes); a registration it overlaps (the same buffer, handed out at another offset) is widened to cover both
+    auto pin_range = [&](const void *p0, uint64_t bytes) {
+        std::lock_guard<std::mutex> lk(pin.mu);
+        const char *lo = (const char *)p0, *hi = lo + bytes;
+        if (!bytes) return;
+        for (auto it = pinned.begin(); it != pinned.end();) {
+            const char *a0 = (const char *)it->first, *a1 = a0 + it->second;
+            if (lo >= a0 && hi <= a1) return;
+            if (lo < a1 && hi > a0) {
+                lo = std::min(lo, a0);
+                hi = std::max(hi, a1);
+                (void)cm_host_unregister(cm, it->first);
+                it = pinned.erase(it);
+            } else ++it;
+        }
+        if (pinned.size() >= 64) return;
+        if (cm_host_register(cm, (void *)lo, (uint64_t)(hi - lo)) == CM_OK) pinned.emplace_back((void *)lo, (uint64_t)(hi - lo));
+    };
+    // ---- the device-side tokeniser's path (opt-in): read k+2 (worker) | stage k+1 | rounds of k | write k-1 (worker) ----
+    bool text_path = false;
+    {
+        const char *e = getenv("CM_FASTQ_DEVICE");
+        text_path = e && atoi(e) == 1 && a->report == 0;
+    }
+    struct TextBlock {
+        const uint8_t *t1 = nullptr, *t2 = nullptr;
+        uint64_t l1 = 0, l2 = 0;
+        int e1 = 0, e2 = 0;
+        cm_text_batch tb{};
+        std::vector<uint64_t> rec1, rec2;
+    } tq[4];                                                    // block k in tq[k & 3]: its text is the reader's for three more reads
+    // bytes per file and block: what batch_pairs records take, first by a guess (a 150-bp record with its name and qualities is
+    // ~ 350 bytes), then by what the records of the last batch took -- a block that holds much more than a batch only grows the tail
+    uint64_t want = batch_pairs * 400 + (1u << 16);
+    bool want_fixed = false;
+    if (const char *e = getenv("CM_FASTQ_DEVICE_BLOCK")) {
+        const unsigned long long v = strtoull(e, nullptr, 10);
+        if (v >= 16) {
+            want = v;
+            want_fixed = true;
+        }
+    }
+    auto read_block = [&](TextBlock &B, uint64_t bytes) { return cm_fastq_next_text(fq, bytes, &B.t1, &B.l1, &B.e1, &B.t2, &B.l2, &B.e2); };
+    // block -> staged batch; B.tb.n_pairs == 0: the input is at its end.  A block that holds no whole pair is read again, larger.
+    auto stage_block = [&](TextBlock &B) -> int {
+        uint64_t bytes = want;
+        for (;;) {
+            memset(&B.tb, 0, sizeof B.tb);
+            if (B.l1 == 0 && B.e1) return CM_OK;                 // R1 is through (what is left of R2 is surplus)
+            B.rec1.resize(batch_pairs + 1);
+            B.rec2.resize(batch_pairs + 1);
+            pin_range(B.t1, B.l1);
+            pin_range(B.t2, B.l2);
+            int r = cm_reads_stage_text(cm, B.t1, B.l1, B.t2, B.l2, batch_pairs, (B.e1 ? 1u : 0u) | (B.e2 ? 2u : 0u), B.rec1.data(), B.rec2.data(), &B.tb);
+            if (r != CM_OK) return r;
+            if (B.tb.n_pairs) {
+                if (!want_fixed) want = std::max(B.tb.used1, B.tb.used2) / B.tb.n_pairs * batch_pairs / 100 * 101 + (1u << 16);
+                return cm_fastq_text_consumed(fq, B.tb.used1, B.tb.used2);
+            }
+            if (B.e1 && B.e2) return CM_OK;                      // (nothing more to read: no whole pair is left)
+            bytes *= 2;
+            if ((r = cm_fastq_text_consumed(fq, 0, 0)) != CM_OK || (r = read_block(B, bytes)) != CM_OK) return r;
+        }
+    };
+    if (text_path) {
+        const int r = read_block(tq[0], want);
+        if (r == CM_EINVAL) text_path = false;                   // gzip input or a pipe: the host parser's
+        else MAP_TRY(r, "cm_fastq_next_text");
+    }
+    if (text_path) {                                             // a carried state in the first R1 header: the host parser's, for the run
+        const uint8_t *p = tq[0].t1, *nl = tq[0].l1 ? (const uint8_t *)memchr(p, '\n', tq[0].l1) : nullptr;
+        int nt = 0;
+        bool in = false;
+        for (const uint8_t *q = p + 1; nl && q < nl; ++q) {
+            nt += (*q != ' ' && !in) ? 1 : 0;
+            in = *q != ' ';
+        }
+        if (nt == 23) {
+            text_path = false;
+            cm_fastq_close(fq);
+            fq = nullptr;
+            MAP_TRY(cm_fastq_open_shard(a->fastq1, a->fastq2, chrs, n_chr, P.max_ed, rank, world, n_threads, &fq, nullptr, nullptr), "cm_fastq_open_shard");
+            cm_fastq_set_release_hook(fq, release_fn, &pin);
+        }
+    }
+    if (text_path) {
+        double write_s = 0.0;
+        bool more = false;
+        {
+            const double td = now();
+            MAP_TRY(stage_block(tq[0]), "cm_reads_stage_text");
+            st.seconds_device += now() - td;
+        }
+        if (tq[0].tb.n_pairs) {
+            MAP_TRY(cm_reads_swap(cm), "cm_reads_swap");
+            const double tp = now();
+            MAP_TRY(read_block(tq[1], want), "cm_fastq_next_text");
+            st.seconds_parse += now() - tp;
+            more = true;
+        }
+        for (uint64_t k = 0; tq[k & 3].tb.n_pairs; ++k) {
+            TextBlock &B = tq[k & 3], &N = tq[(k + 1) & 3];
+            const uint64_t n = B.tb.n_pairs;
+            ++st.device_parsed_batches;
+            Result &R = res[k & 1];
+            double parse_s = 0.0;
+            parser_rc = CM_OK;
+            const double td = now();
+            if (more) {
+                MAP_TRY(stage_block(N), "cm_reads_stage_text");
+                more = N.tb.n_pairs != 0;
+            } else memset(&N.tb, 0, sizeof N.tb);
+            if (more)
+                parser = std::thread([&]() {
+                    const double tp = now();
+                    parser_rc = read_block(tq[(k + 2) & 3], want);
+                    parse_s = now() - tp;
+                });
+            MAP_TRY(cm_map_rounds(cm, all.data(), (int)n_con, 1), "cm_map_rounds");
+            uint64_t n_rec = 0;
+            if (R.recs.size() < n) R.recs.resize(n);
+            MAP_TRY(cm_collect_records(cm, 0, n, R.recs.data(), &n_rec), "cm_collect_records");
+            uint64_t h[14];
+            MAP_TRY(cm_type_histogram(cm, h), "cm_type_histogram");
+            for (int t = 0; t < 14; ++t) st.by_type[t] += h[t];
+            R.n_rec = n_rec;
+            if (more) MAP_TRY(cm_reads_swap(cm), "cm_reads_swap");
+            st.seconds_device += now() - td;
+            st.pairs += n;
+            st.bsj_pairs += n_rec;
+            if (writer.joinable()) writer.join();                    // rows of batch k-1 are out: file order = batch order
+            MAP_TRY(writer_rc, "writer");
+            writer = std::thread([&R, &B, &writer_rc, &write_s, w_rem]() {
+                const double tw = now();
+                writer_rc = R.n_rec ? cm_write_remain_text(w_rem, B.t1, B.rec1.data(), B.t2, B.rec2.data(), R.recs.data(), R.n_rec) : CM_OK;
+                write_s += now() - tw;
+            });
+            if (parser.joinable()) parser.join();
+            st.seconds_parse += parse_s;
+            MAP_TRY(parser_rc, "cm_fastq_next_text");
+        }
+        if (writer.joinable()) writer.join();
+        MAP_TRY(writer_rc, "writer");
+        MAP_TRY(cm_writer_flush(w_rem), "writing the remain files");
+        st.seconds_map = now() - t1;
+        st.seconds_write = write_s;
+        cleanup();
+        if (stats) *stats = st;
+        return CM_OK;
+    }
     cm_fastq_batch cur, nxt, nn;
     memset(&nxt, 0, sizeof nxt);
     memset(&nn, 0, sizeof nn);

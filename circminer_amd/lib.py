@@ -47,7 +47,7 @@ class CircStats(C.Structure):
 
 class MappingStats(C.Structure):
     _fields_ = [("pairs", C.c_uint64), ("bsj_pairs", C.c_uint64), ("by_type", C.c_uint64 * 14), ("rounds", C.c_int32),
-                ("reserved", C.c_int32), ("seconds_load", C.c_double), ("seconds_map", C.c_double), ("seconds_parse", C.c_double),
+                ("device_parsed_batches", C.c_int32), ("seconds_load", C.c_double), ("seconds_map", C.c_double), ("seconds_parse", C.c_double),
                 ("seconds_device", C.c_double), ("seconds_write", C.c_double)]
 
 
@@ -124,6 +124,10 @@ RECORD_DTYPE = np.dtype([("pair", "<u8"), ("state", MAPPED_DTYPE)])      # cm_re
 CHAIN_DTYPE = np.dtype([("score", "<f4"), ("chain_len", "<u4"), ("rpos", "<u4", (CM_MAX_CHAIN_FRAGS,)),
                         ("qpos", "<i4", (CM_MAX_CHAIN_FRAGS,))])
 assert CHAIN_DTYPE.itemsize == 136
+
+
+class TextBatch(C.Structure):         # cm_text_batch
+    _fields_ = [("n_pairs", C.c_uint64), ("used1", C.c_uint64), ("used2", C.c_uint64), ("max_len", C.c_int32), ("reserved", C.c_int32)]
 
 
 class Reads(C.Structure):
@@ -204,6 +208,11 @@ def load(path: str = LIB_PATH) -> C.CDLL:
         "cm_reads_upload": (C.c_int, [vp, pp(Reads), vp]),
         "cm_reads_stage": (C.c_int, [vp, pp(Reads), vp]),
         "cm_reads_swap": (C.c_int, [vp]),
+        "cm_reads_stage_text": (C.c_int, [vp, vp, C.c_uint64, vp, C.c_uint64, C.c_uint64, C.c_uint32, vp, vp, pp(TextBatch)]),
+        "cm_reads_peek": (C.c_int, [vp, vp, C.c_uint64, vp, vp, C.c_uint64, vp, pp(C.c_uint64)]),
+        "cm_fastq_next_text": (C.c_int, [vp, C.c_uint64, pp(vp), pp(C.c_uint64), pp(C.c_int), pp(vp), pp(C.c_uint64), pp(C.c_int)]),
+        "cm_fastq_text_consumed": (C.c_int, [vp, C.c_uint64, C.c_uint64]),
+        "cm_write_remain_text": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_uint64]),
         "cm_map_round": (C.c_int, [vp, C.c_int, C.c_int]),
         "cm_map_rounds": (C.c_int, [vp, i32p, C.c_int, C.c_int]),
         "cm_reads_download": (C.c_int, [vp, vp, vp, vp]),
@@ -289,7 +298,8 @@ EXPORTED_SYMBOLS = ["cm_create", "cm_destroy", "cm_last_error", "cm_load_contig"
                     "cm_host_write_index", "cm_host_open_index", "cm_host_next_contig", "cm_host_next_contig_genome", "cm_host_free_loaded_contig",
                     "cm_host_close_index", "cm_fastq_open", "cm_fastq_open_shard", "cm_merge_parts", "cm_fastq_next", "cm_fastq_set_release_hook", "cm_fastq_close", "cm_writer_open", "cm_write_remain",
                     "cm_write_pam", "cm_write_sam_header", "cm_write_sam", "cm_writer_flush", "cm_writer_close", "cm_mapping_run", "cm_sort_remain", "cm_circ_report", "cm_circ_call", "cm_circ_run", "cm_host_gene_overlap", "cm_regional_table_build", "cm_regional_table_free",
-                    "cm_build_contig", "cm_index_download"]
+                    "cm_build_contig", "cm_index_download", "cm_reads_stage_text", "cm_reads_peek", "cm_fastq_next_text", "cm_fastq_text_consumed",
+                    "cm_write_remain_text"]
 
 
 class HostIndex:
@@ -575,6 +585,25 @@ class FastqReader:
             raise RuntimeError(f"cm_fastq_next failed ({rc}): malformed FASTQ")
         return ParsedBatch(fb) if fb.reads.n_pairs else None
 
+    def next_text(self, want_bytes: int):
+        """cm_fastq_next_text: the next raw block of both files as (text1, eof1, text2, eof2); the uint8 arrays are views of the
+        reader's buffers (valid over the next three calls).  Regular plain-text files only."""
+        t1, t2 = C.c_void_p(), C.c_void_p()
+        l1, l2, e1, e2 = C.c_uint64(0), C.c_uint64(0), C.c_int(0), C.c_int(0)
+        rc = self.L.cm_fastq_next_text(self.h, int(want_bytes), C.byref(t1), C.byref(l1), C.byref(e1), C.byref(t2), C.byref(l2), C.byref(e2))
+        if rc != 0:
+            raise RuntimeError(f"cm_fastq_next_text failed ({rc})")
+
+        def view(p, n):
+            return np.ctypeslib.as_array(C.cast(p, u8p), (n,)) if n else np.zeros(0, np.uint8)
+        return view(t1, l1.value), bool(e1.value), view(t2, l2.value), bool(e2.value)
+
+    def consumed(self, used1: int, used2: int):
+        """cm_fastq_text_consumed: the bytes of the last block that were taken; the rest is the front of the next block"""
+        rc = self.L.cm_fastq_text_consumed(self.h, int(used1), int(used2))
+        if rc != 0:
+            raise RuntimeError(f"cm_fastq_text_consumed failed ({rc})")
+
     def close(self):
         if self.h:
             self.L.cm_fastq_close(self.h)
@@ -604,6 +633,16 @@ class RecordWriter:
 
     def write_remain(self, batch, states, sel=None):
         self._call(self.L.cm_write_remain, batch, states, sel)
+
+    def write_remain_text(self, text1, rec1, text2, rec2, recs):
+        """cm_write_remain_text: the rows of write_remain for the (pair, state) records `recs` (RECORD_DTYPE) of a batch that
+        HotPath.stage_text tokenised: text1 / text2 its blocks, rec1 / rec2 the record starts it returned"""
+        t1, t2 = np.ascontiguousarray(text1, dtype=np.uint8), np.ascontiguousarray(text2, dtype=np.uint8)
+        r1, r2 = np.ascontiguousarray(rec1, dtype=np.uint64), np.ascontiguousarray(rec2, dtype=np.uint64)
+        rr = np.ascontiguousarray(recs, dtype=RECORD_DTYPE)
+        rc = self.L.cm_write_remain_text(self.h, t1.ctypes.data, r1.ctypes.data, t2.ctypes.data, r2.ctypes.data, rr.ctypes.data, len(rr))
+        if rc != 0:
+            raise RuntimeError(f"writer failed ({rc})")
 
     def write_pam(self, batch, states, sel=None):
         self._call(self.L.cm_write_pam, batch, states, sel)
@@ -682,6 +721,31 @@ class HotPath:
         self._staged_n = batch.n
         p = prior.ctypes.data if prior is not None else None
         self._chk(self.L.cm_reads_stage(self.h, C.byref(batch.c), p), "cm_reads_stage")
+
+    def stage_text(self, text1, text2, max_pairs, eof1=True, eof2=True):
+        """cm_reads_stage_text: the next batch staged from FASTQ text, tokenised on the device.  text1 / text2: uint8 arrays or
+        bytes.  Returns (TextBatch, rec1, rec2); n_pairs == 0: nothing was staged."""
+        t1 = np.frombuffer(text1, np.uint8) if isinstance(text1, (bytes, bytearray)) else np.ascontiguousarray(text1, dtype=np.uint8)
+        t2 = np.frombuffer(text2, np.uint8) if isinstance(text2, (bytes, bytearray)) else np.ascontiguousarray(text2, dtype=np.uint8)
+        cap = int(min(max_pairs, min(t1.size, t2.size) // 4)) + 1           # a record has four bytes at least
+        rec1, rec2 = np.zeros(cap, np.uint64), np.zeros(cap, np.uint64)
+        tb = TextBatch()
+        self._chk(self.L.cm_reads_stage_text(self.h, t1.ctypes.data if t1.size else None, t1.size, t2.ctypes.data if t2.size else None, t2.size, int(max_pairs),
+                                             int(bool(eof1)) | int(bool(eof2)) << 1, rec1.ctypes.data, rec2.ctypes.data, C.byref(tb)), "cm_reads_stage_text")
+        self._staged_n = int(tb.n_pairs)
+        return tb, rec1[:self._staged_n + 1], rec2[:self._staged_n + 1]
+
+    def peek_reads(self):
+        """cm_reads_peek: (seq1, off1, seq2, off2) of the resident batch, copied back from the device"""
+        n = C.c_uint64(0)
+        self._chk(self.L.cm_reads_peek(self.h, None, 0, None, None, 0, None, C.byref(n)), "cm_reads_peek")
+        off1, off2 = np.zeros(n.value + 1, np.uint64), np.zeros(n.value + 1, np.uint64)
+        if n.value == 0:
+            return np.zeros(0, np.uint8), off1, np.zeros(0, np.uint8), off2
+        self._chk(self.L.cm_reads_peek(self.h, None, 0, off1.ctypes.data, None, 0, off2.ctypes.data, C.byref(n)), "cm_reads_peek")
+        s1, s2 = np.zeros(max(int(off1[-1]), 1), np.uint8), np.zeros(max(int(off2[-1]), 1), np.uint8)
+        self._chk(self.L.cm_reads_peek(self.h, s1.ctypes.data, s1.size, None, s2.ctypes.data, s2.size, None, C.byref(n)), "cm_reads_peek")
+        return s1[:int(off1[-1])], off1, s2[:int(off2[-1])], off2
 
     def swap(self):
         self._chk(self.L.cm_reads_swap(self.h), "cm_reads_swap")

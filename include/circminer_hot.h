@@ -221,6 +221,39 @@ int cm_reads_upload(cm_ctx *ctx, const cm_reads *reads, const cm_mapped_read *pr
 int cm_reads_stage(cm_ctx *ctx, const cm_reads *reads, const cm_mapped_read *prior);
 int cm_reads_swap(cm_ctx *ctx);
 
+/* cm_reads_stage for FASTQ TEXT: the tokeniser runs on the device.  text1 / text2 are blocks of the two files of a pair as they
+ * are on disk (page-locked -- cm_host_alloc / cm_host_register -- or pageable), both starting at a record.  They go over PCIe as
+ * they are and kernels on the staging stream find the lines, check every record, build off1 / off2 and copy the bases into the
+ * staged read buffers; afterwards cm_reads_swap, cm_map_rounds and the cross-batch prefetch behave exactly as after
+ * cm_reads_stage(reads, NULL).  The semantics are those of cm_fastq_next on files holding the same bytes:
+ *   - lines end at '\n' only ('\r' is an ordinary byte); record i is lines 4 i .. 4 i + 3, records are counted by line;
+ *     a_X = lines of file X / 4, n = min(a_1, a_2, max_pairs) pairs are staged; n = 0 is CM_OK with nothing staged (the caller
+ *     supplies more bytes).  What follows record n - 1 (whole records, a record cut by the end of the block) is not looked at and
+ *     not consumed: used1 / used2 are the byte offsets of the first record not staged;
+ *   - flags bit 0 / bit 1: text1 / text2 ends at the end of its input.  Then bytes behind the last '\n' are a last line, lines
+ *     behind the last whole record are CM_EINVAL when the batch is not full without them (a_X < max_pairs), and so is an R2
+ *     that ends before R1 (bit 1 with a_2 < min(a_1, max_pairs)).  Surplus R2 records at the end of the input are ignored and,
+ *     unlike in cm_fastq_next, NOT validated;
+ *   - CM_EINVAL, with the file and the record's index in the block in cm_last_error, for a record in [0, n) whose header line is
+ *     empty or does not start with '@', whose third line is empty or does not start with '+', or whose quality line is not as
+ *     long as its sequence line (an empty sequence with an empty quality line is legal, and so is a quality line that starts
+ *     with '@'); for an R1 header of exactly 23 tokens (runs of bytes other than ' ': a carried MatchedRead needs the host
+ *     parser, take cm_fastq_next; R2's tokens are not looked at); for a read longer than max_read_len.  CM_ELIMIT for more than
+ *     CM_MAX_SEEDS_PER_READ seeds in the longest read, and for a block of more than 2^32 - 1 bytes (2^32 - 2 when its last line
+ *     has no '\n'); a block that size cannot hold 2^30 pairs, the limit of a batch.
+ * On any error nothing is staged; an earlier staged batch is dropped in every case, as in cm_reads_stage.  The call waits for the
+ * staging stream only (one small read-back of the batch's shape and verdicts, and the record starts when asked for), never for
+ * the mapping streams.  rec1 / rec2 (nullable; max_pairs + 1 words each, n + 1 are written): byte offset of each staged record's
+ * '@' in its block, rec[n] = used: what cm_write_remain_text slices names and qualities from. */
+typedef struct cm_text_batch {
+    uint64_t n_pairs;        /* pairs staged */
+    uint64_t used1, used2;   /* bytes of text1 / text2 consumed = start of the first record not staged */
+    int32_t  max_len;        /* longest read of the batch */
+    int32_t  reserved;       /* (diagnostic: after cm_prof_enable(ctx, 1) the tokeniser kernels' time in microseconds, HIP events, copies excluded) */
+} cm_text_batch;
+int cm_reads_stage_text(cm_ctx *ctx, const uint8_t *text1, uint64_t len1, const uint8_t *text2, uint64_t len2,
+                        uint64_t max_pairs, uint32_t flags, uint64_t *rec1, uint64_t *rec2, cm_text_batch *out);
+
 /* One mapping round of the resident batch against contig `slot`:
  * FilterRead::process_read for every pair still active + the skip rule of
  * map_reads (src/circminer.cpp:386-397).  Pairs whose carried state says they were
@@ -327,6 +360,12 @@ typedef struct cm_dp_res {
  * for a request that is none of the above.  Synchronous. */
 int cm_dp_batch(cm_ctx *ctx, const cm_params *P, const uint8_t *arena, uint64_t arena_len, const cm_dp_req *req, uint32_t n_req,
                 int str_cap, uint32_t lds_fill, int arrangement, uint32_t grid, cm_dp_res *out);
+
+/* The resident batch's read bytes and offsets copied back (what cm_reads_upload / cm_reads_swap made resident): off1 / off2 take
+ * n_pairs + 1 words, seq1 / seq2 off[n_pairs] bytes (CM_ELIMIT when cap1 / cap2 is smaller).  A NULL pointer skips that array; all
+ * four NULL return only *n_pairs. */
+int cm_reads_peek(cm_ctx *ctx, uint8_t *seq1, uint64_t cap1, uint64_t *off1, uint8_t *seq2, uint64_t cap2, uint64_t *off2,
+                  uint64_t *n_pairs);
 
 /* ---------------- timing hooks for bench.py (HIP events on the ctx stream) ---------------- */
 /* Milliseconds spent in each kernel class since the last cm_prof_reset(), and launch counts:
@@ -456,6 +495,16 @@ int cm_fastq_next(cm_fastq *f, uint64_t max_pairs, cm_fastq_batch *out);   /* ou
  * caller can unregister it first.  No copy out of that block may still be in flight then: the block belongs to the generation
  * handed out four cm_fastq_next calls ago. */
 void cm_fastq_set_release_hook(cm_fastq *f, void (*fn)(void *user, const void *ptr, uint64_t bytes), void *user);
+/* Raw-block mode, for cm_reads_stage_text: the next block of both files as text, nothing parsed.  A block is what the caller has
+ * not consumed of the block before it (cm_fastq_text_consumed; without that call: all of it) followed by fresh bytes, about
+ * want_bytes per file in all -- half of want_bytes fresh at least, so a caller whose block held no whole pair gets more by
+ * asking again; *eofX: the block ends at the end of the reader's share of file X (cm_fastq_open_shard's byte range is respected).
+ * Regular plain-text files only: CM_EINVAL for gzip input and pipes (which stay on cm_fastq_next), and on a reader that
+ * cm_fastq_next has read from.  Four generations of blocks take turns: a block stays valid over the next three calls.  The tail
+ * is copied into head room in front of the fresh bytes; the blocks are malloc'ed, the release hook announces one that goes. */
+int cm_fastq_next_text(cm_fastq *f, uint64_t want_bytes, const uint8_t **text1, uint64_t *len1, int *eof1,
+                       const uint8_t **text2, uint64_t *len2, int *eof2);
+int cm_fastq_text_consumed(cm_fastq *f, uint64_t used1, uint64_t used2);
 void cm_fastq_close(cm_fastq *f);
 
 /* Writers.  cm_write_remain = FilterRead::write_read_category PE (src/filter.cpp:413-455) into
@@ -469,6 +518,11 @@ int cm_write_remain(cm_writer *w, const cm_fastq_batch *b, const cm_mapped_read 
 /* cm_write_remain for (pair index, state) records as cm_collect_records delivers them (index_base 0): only the re-queued
  * pairs' states have to leave the device. */
 int cm_write_remain_records(cm_writer *w, const cm_fastq_batch *batch, const cm_record *recs, uint64_t n);
+/* The bytes of cm_write_remain_records for a batch that went through cm_reads_stage_text: name (first header token, trailing
+ * "/x" cut), bases and quality of pair recs[k].pair are sliced from the blocks' text at rec1 / rec2, the record starts that call
+ * returned. */
+int cm_write_remain_text(cm_writer *w, const uint8_t *text1, const uint64_t *rec1, const uint8_t *text2, const uint64_t *rec2,
+                         const cm_record *recs, uint64_t n_rec);
 int cm_write_pam(cm_writer *w, const cm_fastq_batch *b, const cm_mapped_read *states, const uint64_t *sel, uint64_t n_sel);
 /* <out>.mapping.sam (--sam): header = SAMOutput::print_header (src/output.cpp:301-311, one @SQ per row of the chromosome
  * table), records = write_sam_rec_pe with set_flag_pe / set_output_pe (src/output.cpp:118-277): two lines per pair,
@@ -489,7 +543,12 @@ void cm_writer_close(cm_writer *w);
  * The per-round remain files of the reference (its way of carrying pairs from one contig to the next) are not
  * written: the carried state stays in HBM.  params.kmer == 0 takes the index file's k.
  * index_path may name the packed FASTA itself (no index file on disk): every contig's table is built on the device
- * (cm_build_contig) while the next contig's sequence is read; params.kmer must be given then (0 is CM_EINVAL). */
+ * (cm_build_contig) while the next contig's sequence is read; params.kmer must be given then (0 is CM_EINVAL).
+ * With CM_FASTQ_DEVICE=1 in the environment, report == 0 and two regular plain-text FASTQ files of fresh reads (any rank / world)
+ * the batches are tokenised on the device: cm_fastq_next_text -> cm_reads_stage_text -> cm_write_remain_text, the same files
+ * byte for byte; in every other case (PAM / SAM rows need every pair's name on the host; gzip, pipes and carried 23-token headers
+ * need the host parser) and with the variable unset the host parser feeds the device as before.  CM_FASTQ_DEVICE_BLOCK=<bytes>
+ * (a test knob) sets the bytes per file and block; the default is sized for batch_pairs. */
 typedef struct cm_mapping_args {
     const char *index_path;        /* <ref>.packed.fa.index        */
     const char *index_info_path;   /* <ref>.packed.fa.index.info   */
@@ -509,7 +568,8 @@ typedef struct cm_mapping_args {
 typedef struct cm_mapping_stats {
     uint64_t pairs, bsj_pairs;
     uint64_t by_type[14];          /* final MatchedRead::type histogram (CM_CONCRD ... ) */
-    int32_t rounds, reserved;
+    int32_t rounds;
+    int32_t device_parsed_batches; /* batches tokenised on the device (CM_FASTQ_DEVICE=1, see cm_mapping_run); 0 on the host parser's path */
     double seconds_load, seconds_map;
     /* where seconds_map went, summed over the batches (the three overlap, so they add up to more than seconds_map):
      * parsing FASTQ (parser thread), driving the device (stage + rounds + results + swap, calling thread), writing rows
