@@ -276,6 +276,48 @@ template <class CK> CM_HD inline void desc_pack(uint32_t b0, uint32_t n, const C
     out[2] = (uint32_t)(lo >> 32);
     out[3] = hi;
 }
+// hashVal / checkSumVal of one k-mer, k <= KMER_SPAN, from the KMER_SPAN bytes around it, eight bases to a 64-bit word (no per-base
+// chain).  a[0..2] = the span in ascending address order, little-endian: forward strand (rc == 0) the KMER_SPAN bytes that BEGIN
+// with the k-mer's first base, reverse strand (rc == 1) the KMER_SPAN bytes that END with it (the k-mer runs down from the last
+// byte).  What the span holds beyond the k bases does not matter.  The rules are those of the byte loop of seed_probe: a forward
+// base is taken as stored, a reverse base is upper-cased first; it is valid iff it then is A / C / G / T; its code is
+// ((u >> 1) ^ (u >> 2)) & 3 whether valid or not, complemented on the reverse strand; the first CM_WINDOW_SIZE codes make hv, the
+// rest cv; bad = some base is not valid.
+constexpr int KMER_SPAN = 24;
+struct KmerCode { int hv, cv; uint32_t bad; };
+CM_HD inline KmerCode kmer_from_span(const uint64_t a[3], int k, uint32_t rc) {
+    // t[j]: bases 8 j .. 8 j + 7, the first of them in the TOP byte -- which is where the reverse strand has them already
+    uint64_t t[3];
+    if (rc) { t[0] = a[2]; t[1] = a[1]; t[2] = a[0]; }
+    else { t[0] = __builtin_bswap64(a[0]); t[1] = __builtin_bswap64(a[1]); t[2] = __builtin_bswap64(a[2]); }
+    const uint64_t ONES = 0x0101010101010101ull;
+    uint64_t all = 0, diff = 0;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        const int nb = k - 8 * j;                                                   // bases of the k-mer in this word
+        const uint64_t keep = nb >= 8 ? ~0ull : (nb <= 0 ? 0ull : ~0ull << (8 * (8 - nb)));
+        const uint64_t u = rc ? (t[j] & 0xDFDFDFDFDFDFDFDFull) : t[j];
+        uint64_t code = ((u >> 1) ^ (u >> 2)) & (3u * ONES);                        // A 0, C 1, G 2, T 3, per byte
+        // the one letter that has this code: 0x41, 0x43, 0x47, 0x54 -- a base is valid iff it is that letter
+        const uint64_t b0 = code & ONES, b1 = (code >> 1) & ONES, both = b0 & b1;
+        const uint64_t letter = (0x40u * ONES) | (both ^ ONES) | ((b0 ^ b1) << 1) | (b1 << 2) | (both << 4);
+        diff |= (u ^ letter) & keep;
+        code = (code | (code >> 6)) & 0x000F000F000F000Full;                        // eight codes -> 16 bits, the first base on top
+        code = (code | (code >> 12)) & 0x000000FF000000FFull;
+        code = (code | (code >> 24)) & 0xFFFFull;
+        all = (all << 16) | code;
+    }
+    if (rc) all ^= 0xFFFFFFFFFFFFull;                                               // 3 - code
+    const uint64_t v = all >> (2 * (KMER_SPAN - k));                                // the k-mer's 2 k bits
+    const int nc = k > CM_WINDOW_SIZE ? k - CM_WINDOW_SIZE : 0;                     // bases of the checksum
+    KmerCode r;
+    r.hv = (int)(uint32_t)(v >> (2 * nc));
+    r.cv = (int)(uint32_t)(v & ((1ull << (2 * nc)) - 1ull));
+    r.bad = diff != 0 ? 1u : 0u;
+    return r;
+}
+// where the span of the k-mer at qpos of a read's view begins (forward: at the k-mer; reverse: KMER_SPAN - 1 bytes below its first base)
+CM_HD inline g_u8 kmer_span_at(const SV &s, int qpos) { return s.mode == 1 ? s.p + s.off - qpos - (KMER_SPAN - 1) : s.p + s.off + qpos; }
 CM_HD inline Probe seed_probe(const Core &c, const SV &s, int qpos) {
     Probe r{0u, 0u, 0u};
     // hashVal / checkSumVal without branches (a 4-way switch per base made k_seed scalar-ALU bound): a base is
@@ -284,14 +326,40 @@ CM_HD inline Probe seed_probe(const Core &c, const SV &s, int qpos) {
     int hv = 0, cv = 0;
     uint32_t bad = 0;
     const uint32_t rc = s.mode == 1 ? 1u : 0u;
-    for (int i = 0; i < c.P.kmer; ++i) {
-        uint32_t u = s.mode == 2 ? 0u : (uint32_t)s.p[s.off + (qpos + i) * s.step];
-        u = rc ? (u & 0xDFu) : u;
-        bad |= (uint32_t)!((u == 'A') | (u == 'C') | (u == 'G') | (u == 'T'));
-        uint32_t code = ((u >> 1) ^ (u >> 2)) & 3u;                  // A 0, C 1, G 2, T 3
-        code = rc ? 3u - code : code;
-        if (i < CM_WINDOW_SIZE) hv = (hv << 2) | (int)code;
-        else cv = (cv << 2) | (int)code;
+    const int k = c.P.kmer;
+    if (k >= 1 && k <= KMER_SPAN && ((s.step == 1 && s.mode == 0) || (s.step == -1 && s.mode == 1))) {
+        // a read in either orientation (Read::view): the whole k-mer in one trip to memory
+        uint64_t a[3];
+#if defined(__HIP_DEVICE_COMPILE__)
+        // Two unaligned loads, issued together, of KMER_SPAN bytes: up to KMER_SPAN - k of them lie behind the k-mer (forward) or
+        // in front of it (reverse), so at most KMER_SPAN - 1 bytes outside the read.  This rests on the guarantee that stage() and
+        // load_codes16 use: every read buffer on the device has CM_STAGE_PAD (>= KMER_SPAN) readable bytes on both sides of the
+        // reads, whichever way they got there (the copy helper of cm_reads_upload / cm_reads_stage, k_ft_copy of
+        // cm_reads_stage_text; cm_reads_swap hands the same buffers over); between two reads of a buffer lie other reads.
+        __builtin_memcpy(a, kmer_span_at(s, qpos), KMER_SPAN);
+#else
+        // the host emulation reads the k bases and nothing else (its callers' strings have no slack)
+        uint8_t span[KMER_SPAN] = {0};
+        for (int i = 0; i < k; ++i) span[rc ? KMER_SPAN - 1 - i : i] = s.p[s.off + (qpos + i) * s.step];
+        for (int j = 0; j < 3; ++j) {
+            a[j] = 0;
+            for (int b = 7; b >= 0; --b) a[j] = (a[j] << 8) | span[8 * j + b];
+        }
+#endif
+        const KmerCode kc = kmer_from_span(a, k, rc);
+        hv = kc.hv;
+        cv = kc.cv;
+        bad = kc.bad;
+    } else {
+        for (int i = 0; i < k; ++i) {
+            uint32_t u = s.mode == 2 ? 0u : (uint32_t)s.p[s.off + (qpos + i) * s.step];
+            u = rc ? (u & 0xDFu) : u;
+            bad |= (uint32_t)!((u == 'A') | (u == 'C') | (u == 'G') | (u == 'T'));
+            uint32_t code = ((u >> 1) ^ (u >> 2)) & 3u;                  // A 0, C 1, G 2, T 3
+            code = rc ? 3u - code : code;
+            if (i < CM_WINDOW_SIZE) hv = (hv << 2) | (int)code;
+            else cv = (cv << 2) | (int)code;
+        }
     }
     if (bad) return r;
     const int target = (int)(int16_t)cv;     // int16 quirk, src/match_read.cpp:77
@@ -829,6 +897,7 @@ CM_HD inline uint8_t code1(uint8_t ch, bool comp, uint8_t other) { return (uint8
 // Device build: 16-byte global loads (the caller guarantees CM_STAGE_PAD readable bytes on both
 // sides of every global string, see cm_hot.hip) + whole-word LDS stores.
 constexpr int CM_STAGE_PAD = 64;
+static_assert(CM_STAGE_PAD >= KMER_SPAN, "seed_probe's word loads reach up to KMER_SPAN - 1 bytes outside a read");
 #if defined(__HIP_DEVICE_COMPILE__)
 // codes of characters 4*w0 .. 4*w0+15 of view v, four per word
 CM_HD inline void load_codes16(const SV &v, int w0, uint8_t other, uint32_t q[4]) {

@@ -84,31 +84,59 @@ __global__ void __launch_bounds__(BLK) k_seed(KCore kc, ReadsDev rd, const uint8
     if (threadIdx.x < 3) sh[threadIdx.x] = 0;
     __syncthreads();
     const uint64_t q = (uint64_t)blockIdx.x * BLK + threadIdx.x;
-    const uint64_t total = (uint64_t)n_tile * 4u * (uint64_t)S;
-    if (q < total) {
-        const uint32_t s = (uint32_t)(q % (uint64_t)S);
-        const uint64_t r = q / (uint64_t)S;
-        const int orient = (int)(r & 1u), mate = (int)((r >> 1) & 1u);
-        const uint64_t p = pair0 + (r >> 2);
-        uint32_t st = 0, cn = 0, rw = 0;
-        if (active[p]) {
-            const uint64_t o0 = mate ? rd.off2[p] : rd.off1[p], o1 = mate ? rd.off2[p + 1] : rd.off1[p + 1];
-            const int len = (int)(o1 - o0);
-            const int k = c.P.kmer;
-            if ((int)(s + 1) * k <= len) {
-                const cmc::Read R{(cmc::g_u8)((mate ? rd.seq2 : rd.seq1) + o0), len, orient};
-                const cmc::Probe pr = cmc::seed_probe(c, R.view(), (int)s * k);
-                st = pr.start;
-                rw = pr.raw;
-                cn = (pr.raw > (uint32_t)c.P.seed_lim) ? 0u : pr.raw;
-                atomicAdd(&sh[0], 1u);
-                atomicAdd(&sh[1], pr.touches);
-                atomicAdd(&sh[2], cn);
-            }
-        }
+    const uint64_t total = (uint64_t)n_tile * 4u * (uint64_t)S;         // > 0: the grid has ceil(total / BLK) blocks
+    const bool in = q < total;
+    const uint64_t qc = in ? q : total - 1;                            // a lane past the end asks for what the last probe asks for
+    uint32_t s;
+    uint64_t r;
+    if ((total >> 32) == 0) {                                          // (uniform) the usual tile: 32-bit division
+        s = (uint32_t)qc % (uint32_t)S;
+        r = (uint32_t)qc / (uint32_t)S;
+    } else {
+        s = (uint32_t)(qc % (uint64_t)S);
+        r = qc / (uint64_t)S;
+    }
+    const int orient = (int)(r & 1u), mate = (int)((r >> 1) & 1u);
+    const uint64_t p = pair0 + (r >> 2);
+    // the flag and both offsets leave together (off[p + 1] exists for every pair), the branch comes after them
+    const uint8_t act = active[p];
+    uint64_t o[2];
+    __builtin_memcpy(o, (mate ? rd.off2 : rd.off1) + p, sizeof(o));
+    const int len = (int)(o[1] - o[0]);
+    const int k = c.P.kmer;
+    uint32_t st = 0, cn = 0, rw = 0, pt = 0;                           // pt = 1 << 16 | touches of a lane that probed
+    if ((int)in & (int)(act != 0) & (int)((int)(s + 1) * k <= len)) {   // (one condition, no short cut: it needs all three loads)
+        const cmc::Read R{(cmc::g_u8)((mate ? rd.seq2 : rd.seq1) + o[0]), len, orient};
+        const cmc::Probe pr = cmc::seed_probe(c, R.view(), (int)s * k);
+        st = pr.start;
+        rw = pr.raw;
+        cn = (pr.raw > (uint32_t)c.P.seed_lim) ? 0u : pr.raw;
+        pt = 0x10000u | pr.touches;                                    // touches <= 2 * 32 + 2 per probe (probe_search over n < 2^32)
+    }
+    if (in) {
         sstart[q] = st;
         scnt[q] = cn;
         sraw[q] = rw;
+    }
+    // The three counters, one sum per wave: every lane of every wave is here (no lane has left, the branches above have joined),
+    // so the cross-lane adds see all 64 values.  Rows of 16 by rotation, the four row sums through lane reads.
+    uint32_t a = pt, b = cn;
+#define CM_ROW_ADD(v, n) v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x120 | (n), 0xF, 0xF, false)      /* DPP row_ror:n */
+    CM_ROW_ADD(a, 1); CM_ROW_ADD(b, 1);
+    CM_ROW_ADD(a, 2); CM_ROW_ADD(b, 2);
+    CM_ROW_ADD(a, 4); CM_ROW_ADD(b, 4);
+    CM_ROW_ADD(a, 8); CM_ROW_ADD(b, 8);
+#undef CM_ROW_ADD
+    uint32_t wa = 0, wb = 0;
+#pragma unroll
+    for (int row = 0; row < 4; ++row) {
+        wa += (uint32_t)__builtin_amdgcn_readlane((int)a, 16 * row);
+        wb += (uint32_t)__builtin_amdgcn_readlane((int)b, 16 * row);
+    }
+    if ((threadIdx.x & 63u) == 0 && wa) {
+        atomicAdd(&sh[0], wa >> 16);
+        atomicAdd(&sh[1], wa & 0xFFFFu);
+        if (wb) atomicAdd(&sh[2], wb);
     }
     __syncthreads();
     if (threadIdx.x < 3 && sh[threadIdx.x]) atomicAdd(&counters[CN_PROBES + threadIdx.x], (unsigned long long)sh[threadIdx.x]);
