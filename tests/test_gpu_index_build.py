@@ -189,6 +189,72 @@ def test_a_slot_is_reused_across_loaders(ds_tiny2r):
     hp.close()
 
 
+def _tiny2r_index_file(ds, tmp_path, kmer):
+    packed = str(tmp_path / f"ref_k{kmer}.fa.packed.fa")
+    with open(packed, "w") as f:
+        for i, c in enumerate(ds.d.contigs):
+            f.write(f">{i + 1}\n{c.tobytes().decode()}\n")
+    return cl.write_index(packed, kmer=kmer, n_threads=4)
+
+
+def _wide_params():
+    """18 seeds per read: cm_create takes the build for reads of up to 24 seeds (cm_dispatch.cpp)"""
+    return cl.default_params(max_read_len=300, kmer=16)
+
+
+def _one_round_on_slot_0(hp, ds, rec):
+    hp.upload(ds.batch)
+    hp.load_contig_raw(0, rec, ds.hi.annots[0])
+    seeds = [x.copy() if isinstance(x, np.ndarray) else x for x in hp.seeds(0)]
+    hp.map_round(0, False)
+    return seeds, hp.download()
+
+
+@pytest.mark.parametrize("wide", [False, True], ids=["k16", "k24"])
+def test_a_failed_raw_load_leaves_a_clean_slot(wide, ds_tiny2r, tmp_path):
+    """A record whose first bucket header claims 2^20 entries is refused after the slot gave up its contig: the slot is then
+    unloaded (the old contig does not come back), and loading the good record again maps as in a context that never failed."""
+    ds, P = ds_tiny2r, _wide_params() if wide else cl.default_params()
+    f = cl.IndexFile(_tiny2r_index_file(ds, tmp_path, P.kmer), n_threads=2, raw=True)
+    good = next(f)
+    tab = np.ctypeslib.as_array(C.cast(good.table, C.POINTER(C.c_int32)), (int(good.table_slots) * 2,)).copy()
+    tab[1] = 1 << 20                                   # info of the first bucket's header (only in-range reads follow from it)
+    bad = cl.IndexRaw(good.contig_num, good.ref_len, good.genome, good.n_buckets, good.hv, good.count14, tab.ctypes.data, good.table_slots)
+    fresh = cl.HotPath(P)
+    want_seeds, want_res = _one_round_on_slot_0(fresh, ds, good)
+    fresh.close()
+    hp = cl.HotPath(P)
+    hp.upload(ds.batch)
+    hp.load_contig_raw(0, good, ds.hi.annots[0])
+    with pytest.raises(RuntimeError, match="malformed"):
+        hp.load_contig_raw(0, bad)
+    n = C.c_uint64(0)
+    assert hp.L.cm_index_download(hp.h, 0, None, None, None, 0, C.byref(n)) == -5          # CM_ESTATE
+    assert hp.L.cm_map_round(hp.h, 0, 0) == -5
+    seeds, res = _one_round_on_slot_0(hp, ds, good)
+    hp.close()
+    f.close()
+    assert seeds[3] == want_seeds[3] and all(a.tobytes() == b.tobytes() for a, b in zip(seeds[:3], want_seeds[:3]))
+    assert res[0].tobytes() == want_res[0].tobytes() and (res[1] == want_res[1]).all() and (res[2] == want_res[2]).all()
+    assert (want_seeds[2] > 0).any()                   # (probes with hits: the comparison is not one of empty rounds)
+
+
+def test_build_contig_from_the_build_for_long_reads(ds_tiny2r):
+    """cm_build_contig from the build for long reads: the host builder's arrays, and the statistics the other build reports"""
+    g = ds_tiny2r.hi.contigs[0]
+    want = _host_arrays(cl.load(), g, 16)
+    seen = []
+    for what, P in (("k16", cl.default_params(max_read_len=150, kmer=16)), ("k24", _wide_params())):
+        hp = cl.HotPath(P)
+        st = hp.build_contig(0, 0, g)
+        _print_stats(f"tiny2r contig 0 k 16, {what} build", g, st)
+        if what == "k24":
+            _assert_slot_is(hp, 0, want, what)
+        seen.append((st.n_entries, st.max_bucket, st.reserved, list(st.buckets_by_path)))
+        hp.close()
+    assert seen[0] == seen[1] and seen[0][0] == len(want[1])
+
+
 def test_files_to_files_without_an_index_file(tmp_path):
     """FASTA + GTF + FASTQ -> circ_report with index_path = the packed FASTA: every output byte-equal to the run through the index file;
     then the same from plain C++ (examples/cm_map.cpp) in a directory that never held an index file."""

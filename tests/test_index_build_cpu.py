@@ -112,6 +112,15 @@ def test_emulated_builder_edges(emu_ib):
             assert len(cks) == 1 and pos[0] == 1 and paths == [1, 0, 0]
 
 
+def test_device_allocation_list_over_malloc(tmp_path):
+    """DevList (cm_index_dev.h), the owner of a slot's device arrays, with malloc / free in place of the device allocator: hand-over,
+    scope exit on a failure at every allocation, double release, empty lists -- the program counts its live blocks itself"""
+    exe = str(tmp_path / "devlist")
+    subprocess.check_call(["g++", "-O1", "-std=c++17", "-I", os.path.join(ROOT, "circminer_amd", "csrc"),
+                           os.path.join(ROOT, "tests", "diag", "devlist_san_main.cpp"), "-o", exe])
+    assert subprocess.check_output([exe], text=True).strip() == "devlist: 0 mismatches, 0 blocks live"
+
+
 def _write_packed(tmp_path):
     """a FASTA of two chromosomes with lower-case and IUPAC letters, packed into two contigs"""
     rng = np.random.default_rng(3)
