@@ -25,6 +25,8 @@ CM_VARIANTS(int, cm_reads_upload, (void *, const cm_reads *, const cm_mapped_rea
 CM_VARIANTS(int, cm_reads_stage, (void *, const cm_reads *, const cm_mapped_read *))
 CM_VARIANTS(int, cm_reads_stage_text, (void *, const uint8_t *, uint64_t, const uint8_t *, uint64_t, uint64_t, uint32_t, uint64_t *, uint64_t *, cm_text_batch *))
 CM_VARIANTS(int, cm_reads_peek, (void *, uint8_t *, uint64_t, uint64_t *, uint8_t *, uint64_t, uint64_t *, uint64_t *))
+CM_VARIANTS(int, cm_format_pam, (void *, const cm_chr_info *, uint32_t, uint64_t, uint64_t, void *, uint64_t, uint64_t *, uint64_t *))
+CM_VARIANTS(int, cm_state_poke, (void *, const cm_mapped_read *))
 CM_VARIANTS(int, cm_reads_swap, (void *))
 CM_VARIANTS(int, cm_map_rounds, (void *, const int *, int, int))
 CM_VARIANTS(int, cm_map_round, (void *, int, int))
@@ -90,6 +92,11 @@ int cm_reads_stage_text(cm_ctx *ctx, const uint8_t *text1, uint64_t len1, const 
 int cm_reads_peek(cm_ctx *ctx, uint8_t *seq1, uint64_t cap1, uint64_t *off1, uint8_t *seq2, uint64_t cap2, uint64_t *off2, uint64_t *n_pairs) {
     return ctx ? GO(cm_reads_peek, seq1, cap1, off1, seq2, cap2, off2, n_pairs) : CM_EINVAL;
 }
+int cm_format_pam(cm_ctx *ctx, const cm_chr_info *chrs, uint32_t n_chr, uint64_t first, uint64_t count, void *out, uint64_t cap, uint64_t *out_bytes,
+                  uint64_t stats[4]) {
+    return ctx ? GO(cm_format_pam, chrs, n_chr, first, count, out, cap, out_bytes, stats) : CM_EINVAL;
+}
+int cm_state_poke(cm_ctx *ctx, const cm_mapped_read *states) { return ctx ? GO(cm_state_poke, states) : CM_EINVAL; }
 int cm_reads_swap(cm_ctx *ctx) { return ctx ? GO(cm_reads_swap) : CM_EINVAL; }
 int cm_map_rounds(cm_ctx *ctx, const int *slots, int n, int last) { return ctx ? GO(cm_map_rounds, slots, n, last) : CM_EINVAL; }
 int cm_map_round(cm_ctx *ctx, int slot, int is_last) { return ctx ? GO(cm_map_round, slot, is_last) : CM_EINVAL; }

@@ -28,6 +28,7 @@
 #include "cm_aos.h"
 #include "cm_index_build.h"
 #include "cm_fastq_text.h"
+#include "cm_pam_text.h"
 
 using cmc::Core;
 using cmc::KCore;
@@ -43,7 +44,8 @@ constexpr int BLK_CHAIN = 64;
 
 // Profile classes: the index of cm_ctx::ms[] / launches[], of Timer, launch() and cm_prof_get (include/circminer_hot.h).  PC_NONE:
 // a launch no class counts (index build, collect, the small housekeeping kernels).
-enum ProfClass { PC_NONE = -1, PC_SEED = 0, PC_CHAIN = 1, PC_PAIR = 2, PC_SCAN = 3, PC_HEAVY = 4, PC_ORDER = 5, PC_CHAIN_HEAVY = 6, PC_PREFETCH = 7, PC_COUNT = 8 };
+enum ProfClass { PC_NONE = -1, PC_SEED = 0, PC_CHAIN = 1, PC_PAIR = 2, PC_SCAN = 3, PC_HEAVY = 4, PC_ORDER = 5, PC_CHAIN_HEAVY = 6, PC_PREFETCH = 7,
+                 PC_PAM = 7 /* the same slot: PC_PREFETCH counts launches and has no time, cm_format_pam has time and counts none */, PC_COUNT = 8 };
 // The words of cm_ctx::d_counters.  0 - 6 are public (cm_prof_counters, include/circminer_hot.h); from 8 on what a diagnostic build
 // accumulates, read by the scripts of tests/diag through cm_debug_counters at these indices.  The two diagnostic builds overlap (they
 // are never one build): both write word 24.
@@ -67,10 +69,12 @@ enum Pin {
     PIN_CELLS = 8,                                   // + 2 * seed set: DP cells of the tile, + 1: of its largest problem
     PIN_RERUN_N = 12, PIN_FALL_N = 14,               // + chain-record set: length of the re-run list / of the pipeline's fall-back list
     PIN_TEXT = 16,                                   // cm_reads_stage_text: the result block of the tokeniser (cmft::RES_WORDS words)
+    PIN_PAM = 26,                                    // cm_format_pam: the bytes of the rows
     PIN_WORDS = 32
 };
 constexpr size_t PIN_BYTES = PIN_WORDS * sizeof(unsigned long long);        // allocated and cleared in cm_create
-static_assert(PIN_BYTES == 256 && PIN_FALL_N + 1 < PIN_TEXT && PIN_CELLS + 3 < PIN_RERUN_N && PIN_TEXT + cmft::RES_WORDS <= PIN_WORDS, "the landing zone has 32 words");
+static_assert(PIN_BYTES == 256 && PIN_FALL_N + 1 < PIN_TEXT && PIN_CELLS + 3 < PIN_RERUN_N && PIN_TEXT + cmft::RES_WORDS <= PIN_PAM && PIN_PAM < PIN_WORDS,
+              "the landing zone has 32 words");
 struct ReadsDev {
     const uint8_t *seq1, *seq2;
     const uint64_t *off1, *off2;
@@ -2095,6 +2099,74 @@ __global__ void k_ft_finish(FtShape sh, const uint64_t *off1, const uint64_t *of
     res[cmft::RES_USED2] = rec2[n];
 }
 
+// ---- the names cm_reads_stage_text keeps (flag bit 2) and cm_format_pam (bodies and the plan: cm_pam_text.h) ----------------
+// one lane per record of file 1: where its name starts in the text and how long it is; item n is 0, the slot the scan leaves the total in
+__global__ void __launch_bounds__(FT_T) k_ft_name_len(const uint8_t *text, const uint32_t *ls, uint32_t n, uint32_t *nstart, uint32_t *nlen) {
+    const uint32_t i = blockIdx.x * FT_T + threadIdx.x;
+    if (i > n) return;
+    uint32_t s = 0, l = 0;
+    if (i < n) {
+        const uint32_t h = ls[4 * (uint64_t)i];
+        cmpt::name_span(text + h, ls[4 * (uint64_t)i + 1] - 1u - h, &s, &l);
+        s += h;
+    }
+    nstart[i] = s;
+    nlen[i] = l;
+}
+// COPY_LANES lanes per record move its name to names[name_off[i] ..), word by word
+__global__ void __launch_bounds__(FT_T) k_ft_name_copy(const uint8_t *text, const uint32_t *nstart, const uint32_t *name_off, uint32_t n, uint8_t *names) {
+    const uint32_t groups = gridDim.x * (FT_T / cmft::COPY_LANES), lane = threadIdx.x % cmft::COPY_LANES;
+    for (uint32_t i = (blockIdx.x * FT_T + threadIdx.x) / cmft::COPY_LANES; i < n; i += groups)
+        cmft::copy_bases(names, name_off[i], text, nstart[i], name_off[i + 1] - name_off[i], (int)lane, cmft::COPY_LANES);
+}
+// one lane per row k of the call (pair first + k): its length; item count is 0, the slot the scan leaves the total in
+__global__ void __launch_bounds__(BLK) k_pam_len(const cm_mapped_read *state, const uint32_t *name_off, cmpt::ChrTab ct, uint64_t first, uint32_t count, uint32_t *len) {
+    const uint32_t k = blockIdx.x * BLK + threadIdx.x;
+    if (k > count) return;
+    uint32_t l = 0;
+    if (k < count) {
+        const cm_mapped_read m = state[first + k];
+        l = cmpt::row_len(m, name_off[first + k + 1] - name_off[first + k], ct);
+    }
+    len[k] = l;
+}
+// the 64-bit sum of the lengths (one workgroup; launched only where the rows of a call could reach 2^32 bytes)
+__global__ void __launch_bounds__(BLK) k_pam_total(const uint32_t *len, uint32_t count, unsigned long long *total) {
+    __shared__ unsigned long long part[BLK];
+    unsigned long long t = 0;
+    for (uint32_t k = threadIdx.x; k < count; k += BLK) t += len[k];
+    part[threadIdx.x] = t;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int i = 1; i < BLK; ++i) t += part[i];
+        *total = t;
+    }
+}
+// One wave (a workgroup of its own) per span of SPAN_ROWS rows: formatted in the wave's LDS window and streamed out as words, or,
+// for a span larger than the window, stored by every lane itself.  path[span] = 1 / 0 says which.
+__global__ void __launch_bounds__(cmpt::SPAN_ROWS) k_pam_rows(const cm_mapped_read *state, const uint8_t *names, const uint32_t *name_off, cmpt::ChrTab ct,
+                                                              uint64_t first, uint32_t count, const uint32_t *off, uint8_t *out, uint8_t *path) {
+    __shared__ uint32_t win[cmpt::WINDOW_WORDS];
+    const uint32_t lane = threadIdx.x, k0 = blockIdx.x * cmpt::SPAN_ROWS, k = k0 + lane;
+    const uint32_t k1 = count - k0 < cmpt::SPAN_ROWS ? count : k0 + cmpt::SPAN_ROWS;
+    const uint32_t s = off[k0], e = off[k1];
+    const bool staged = cmpt::span_in_window(s, e);                  // (uniform)
+    if (lane == 0) path[blockIdx.x] = staged ? 1 : 0;
+    if (staged) {
+        if (k < count) {
+            const cm_mapped_read m = state[first + k];
+            const uint32_t a = name_off[first + k];
+            cmpt::format_row((uint8_t *)win + cmpt::window_at(s, off[k]), m, names + a, name_off[first + k + 1] - a, ct);
+        }
+        __syncthreads();
+        cmpt::stream_span(out, (const uint8_t *)win, s, e, lane, cmpt::SPAN_ROWS);
+    } else if (k < count) {
+        const cm_mapped_read m = state[first + k];
+        const uint32_t a = name_off[first + k];
+        cmpt::format_row(out + off[k], m, names + a, name_off[first + k + 1] - a, ct);
+    }
+}
+
 // ------------------------------------------------------------------ host side
 struct Slot {
     bool loaded = false, has_annot = false;
@@ -2142,12 +2214,21 @@ template <class T> using CtxBuf = DevBuf<T, CONTEXT>;
 struct ReadBufs {
     BatchBuf<uint8_t> seq1_base, seq2_base;      // CM_STAGE_PAD readable bytes in front of and behind the reads
     BatchBuf<uint64_t> off1, off2;
+    // cm_reads_stage_text with flag bit 2: the R1 names of the batch, name i = names[name_off[i] .. name_off[i + 1]) (cm_format_pam)
+    BatchBuf<uint8_t> names;
+    BatchBuf<uint32_t> name_off;
+    bool has_names = false;
+    uint64_t name_bytes_max = 0;                 // no more name bytes than this (the host never learns the exact number)
 };
 inline void swap(ReadBufs &a, ReadBufs &b) {
     swap(a.seq1_base, b.seq1_base);
     swap(a.seq2_base, b.seq2_base);
     swap(a.off1, b.off1);
     swap(a.off2, b.off2);
+    swap(a.names, b.names);
+    swap(a.name_off, b.name_off);
+    std::swap(a.has_names, b.has_names);
+    std::swap(a.name_bytes_max, b.name_bytes_max);
 }
 
 // What the seeding of a tile leaves for its chain stage: the seed ranges of every probe, the DP-cell offsets of every chaining
@@ -2239,6 +2320,20 @@ struct TextStage {
     BatchBuf<uint64_t> rec[2];
     BatchBuf<uint32_t> tmp;
     BatchBuf<unsigned long long> res;
+    BatchBuf<uint32_t> nstart;                   // flag bit 2 only: where each R1 name starts in text[0]
+};
+// cm_format_pam: the chromosome names last uploaded (host copy: the table is compared, not uploaded, when it is the same), the rows'
+// lengths scanned in place into offsets, the scan's block totals, the rows, the path every span took
+struct PamRows {
+    std::vector<uint32_t> h_chr_off;
+    std::string h_chr_text;
+    bool chr_valid = false;
+    CtxBuf<uint8_t> chr_text;
+    CtxBuf<uint32_t> chr_off;
+    CtxBuf<unsigned long long> total;
+    BatchBuf<uint32_t> off, tmp;
+    BatchBuf<uint8_t> out, path;
+    std::vector<uint8_t> h_path;
 };
 
 // The streams of a context, under the letters of DESIGN §4.  STREAMS lists them in creation order, which decides the hardware
@@ -2340,6 +2435,7 @@ struct cm_ctx {
     bool st_has_prior = false;
     int st_max_len = 0;
     TextStage ft;                             // cm_reads_stage_text
+    PamRows pam;                              // cm_format_pam
     // workspace of one tile
     uint32_t tile = 0;
     SeedSet seed[2];                          // item i + 1 is seeded into one while the chain stage of item i reads the other
@@ -3515,6 +3611,7 @@ int cm_reads_upload(cm_ctx *ctx, const cm_reads *rd, const cm_mapped_read *prior
     int max_len = 0;
     int rc = check_reads(ctx, rd, &max_len);
     if (rc) return rc;
+    ctx->rd.has_names = false;
     if ((rc = copy_reads(ctx, rd, ctx->st.B, ctx->rd))) return rc;
     if ((rc = prepare_resident(ctx, n, max_len))) return rc;
     ctx->n_pairs = n;
@@ -3540,6 +3637,7 @@ int cm_reads_stage(cm_ctx *ctx, const cm_reads *rd, const cm_mapped_read *prior)
     HIPCHK(ctx, hipStreamSynchronize(ctx->st.C));          // an earlier staged batch that was never swapped in is dropped
     ctx->staged = false;
     ctx->pre_launched = false;
+    ctx->st_rd.has_names = false;
     if ((rc = copy_reads(ctx, rd, ctx->st.C, ctx->st_rd))) return rc;
     ctx->st_has_prior = prior != nullptr;
     if (prior) {
@@ -3581,6 +3679,7 @@ int cm_reads_stage_text(cm_ctx *ctx, const uint8_t *text1, uint64_t len1, const 
     const size_t pad = cmc::CM_STAGE_PAD;
     uint32_t n_chunks[2], ls_cap[2];
     ReadBufs &to = ctx->st_rd;
+    to.has_names = false;
     HIPCHK(ctx, ensure(ctx, to.seq1_base, len1 + 2 * pad));
     HIPCHK(ctx, ensure(ctx, to.seq2_base, len2 + 2 * pad));
     HIPCHK(ctx, ensure(ctx, to.off1, ((size_t)nb + 1) * sizeof(uint64_t)));
@@ -3667,6 +3766,27 @@ int cm_reads_stage_text(cm_ctx *ctx, const uint8_t *text1, uint64_t len1, const 
     if (rec1) HIPCHK(ctx, hipMemcpyAsync(rec1, T.rec[0], (n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
     if (rec2) HIPCHK(ctx, hipMemcpyAsync(rec2, T.rec[1], (n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
     if (rec1 || rec2) HIPCHK(ctx, hipStreamSynchronize(st));
+    if (flags & 4u) {
+        // Keep the R1 names: their lengths (a lane per record), a scan, a word-wise copy into a compact array.  Queued here, behind
+        // the read-back, because only now the host can size the array: the names are no longer than the header lines, which are
+        // what the consumed text holds besides bases and qualities.  ev.staged moves behind them: the formatter reads the names on
+        // the mapping stream, which waits for that event in cm_reads_swap.  Nobody waits here.
+        const uint64_t name_max = R[cmft::RES_USED1] - std::min<uint64_t>(R[cmft::RES_USED1], 2 * R[cmft::RES_BASES1]);
+        HIPCHK(ctx, ensure(ctx, to.names, (size_t)name_max + 4));
+        HIPCHK(ctx, ensure(ctx, to.name_off, ((size_t)n + 1) * sizeof(uint32_t)));
+        HIPCHK(ctx, ensure(ctx, T.nstart, ((size_t)n + 1) * sizeof(uint32_t)));
+        const unsigned gn = (unsigned)(n / FT_T + 1);            // covers i = 0 .. n
+        hipLaunchKernelGGL(k_ft_name_len, dim3(gn), dim3(FT_T), 0, st, (const uint8_t *)T.text[0], (const uint32_t *)T.ls[0], (uint32_t)n, (uint32_t *)T.nstart,
+                           (uint32_t *)to.name_off);
+        if ((rc = scan32_on(ctx, st, to.name_off, n + 1, to.name_off, T.tmp, 0u, 0))) return rc;
+        const unsigned gc = (unsigned)std::min<uint64_t>((n * cmft::COPY_LANES + FT_T - 1) / FT_T, 1u << 16);
+        hipLaunchKernelGGL(k_ft_name_copy, dim3(gc), dim3(FT_T), 0, st, (const uint8_t *)T.text[0], (const uint32_t *)T.nstart, (const uint32_t *)to.name_off,
+                           (uint32_t)n, (uint8_t *)to.names);
+        HIPCHK(ctx, hipGetLastError());
+        HIPCHK(ctx, hipEventRecord(ctx->ev.staged, st));
+        to.has_names = true;
+        to.name_bytes_max = name_max;
+    }
     ctx->st_has_prior = false;
     ctx->st_n_pairs = n;
     ctx->st_max_len = (int)max_len;
@@ -4303,6 +4423,103 @@ int cm_collect_records_device(cm_ctx *ctx, uint64_t index_base, uint64_t cap, vo
         }
     }
     return collect_records_into(ctx, index_base, cap, (cm_record *)d_out, out_n, "cm_collect_records_device");
+}
+
+// The PAM rows of pairs [first, first + count) of the resident batch, formatted on the device (bodies and the plan: cm_pam_text.h)
+// on the mapping stream, behind everything queued for the batch.  Two waits: for the rows' total (the caller's buffer may be too
+// small, the device buffer is sized by it), then for the bytes.
+int cm_format_pam(cm_ctx *ctx, const cm_chr_info *chrs, uint32_t n_chr, uint64_t first, uint64_t count, void *out, uint64_t cap, uint64_t *out_bytes,
+                  uint64_t stats[4]) {
+    if (!ctx || !out_bytes || (n_chr && !chrs)) return CM_EINVAL;
+    *out_bytes = 0;
+    if (stats) stats[0] = stats[1] = stats[2] = stats[3] = 0;
+    HIPCHK(ctx, hipSetDevice(ctx->P.device));
+    if (ctx->n_pairs == 0) return fail(ctx, CM_ESTATE, "cm_format_pam: no resident batch");
+    if (!ctx->rd.has_names) return fail(ctx, CM_ESTATE, "cm_format_pam: the resident batch was not staged with cm_reads_stage_text, flag bit 2 (no names)");
+    if (first > ctx->n_pairs || count > ctx->n_pairs - first)
+        return fail(ctx, CM_EINVAL, "cm_format_pam: pairs [%llu, +%llu) of %llu", (unsigned long long)first, (unsigned long long)count, (unsigned long long)ctx->n_pairs);
+    if (!out && cap) return fail(ctx, CM_EINVAL, "cm_format_pam: null out");
+    if (count == 0) return CM_OK;
+    if (count >= 0xffffffffull) return fail(ctx, CM_ELIMIT, "cm_format_pam: %llu rows in one call", (unsigned long long)count);
+    PamRows &F = ctx->pam;
+    hipStream_t st = ctx->st.B;
+    {   // the chromosome names: uploaded when they differ from the table on the device
+        std::vector<uint32_t> o((size_t)n_chr + 1, 0u);
+        std::string text;
+        for (uint32_t c = 0; c < n_chr; ++c) {
+            if (chrs[c].name) text += chrs[c].name;
+            o[c + 1] = (uint32_t)text.size();
+        }
+        if (!F.chr_valid || o != F.h_chr_off || text != F.h_chr_text) {
+            F.chr_valid = false;
+            HIPCHK(ctx, hipStreamSynchronize(st));              // (rows of an earlier call are out, but be sure nothing reads the old table)
+            F.h_chr_off.swap(o);
+            F.h_chr_text.swap(text);
+            HIPCHK(ctx, ensure(ctx, F.chr_text, F.h_chr_text.size() + 4));
+            HIPCHK(ctx, ensure(ctx, F.chr_off, F.h_chr_off.size() * sizeof(uint32_t)));
+            if (!F.h_chr_text.empty()) HIPCHK(ctx, hipMemcpyAsync(F.chr_text, F.h_chr_text.data(), F.h_chr_text.size(), hipMemcpyHostToDevice, st));
+            HIPCHK(ctx, hipMemcpyAsync(F.chr_off, F.h_chr_off.data(), F.h_chr_off.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+            HIPCHK(ctx, hipStreamSynchronize(st));
+            F.chr_valid = true;
+        }
+    }
+    uint32_t chr_max = 1;
+    for (uint32_t c = 0; c < n_chr; ++c) chr_max = std::max(chr_max, F.h_chr_off[c + 1] - F.h_chr_off[c]);
+    const cmpt::ChrTab ct{F.chr_text, F.chr_off, n_chr};
+    const uint32_t cnt = (uint32_t)count, spans = (cnt + cmpt::SPAN_ROWS - 1) / cmpt::SPAN_ROWS;
+    HIPCHK(ctx, ensure(ctx, F.off, ((size_t)cnt + 1) * sizeof(uint32_t)));
+    HIPCHK(ctx, ensure(ctx, F.tmp, (size_t)(((uint64_t)cnt + 1) / S32_B + 2) * sizeof(uint32_t)));
+    HIPCHK(ctx, ensure(ctx, F.path, spans));
+    HIPCHK(ctx, ensure(ctx, F.total, sizeof(unsigned long long)));
+    // offsets are uint32: where the rows could come to 2^32 bytes (the names at their most, every field at its widest) the lengths
+    // are summed in 64 bits first
+    const bool wide = ctx->rd.name_bytes_max + count * (uint64_t)(cmpt::ROW_FIXED_MAX + 2 * chr_max) >= (1ull << 32);
+    unsigned long long *land = ctx->h_pin + PIN_PAM;
+    int rc;
+    {
+        Timer t(ctx, PC_PAM, st);
+        hipLaunchKernelGGL(k_pam_len, dim3(cnt / BLK + 1), dim3(BLK), 0, st, (const cm_mapped_read *)ctx->d_state, (const uint32_t *)ctx->rd.name_off, ct, first, cnt,
+                           (uint32_t *)F.off);
+        if (wide) hipLaunchKernelGGL(k_pam_total, dim3(1), dim3(BLK), 0, st, (const uint32_t *)F.off, cnt, (unsigned long long *)F.total);
+        if ((rc = scan32_on(ctx, st, F.off, (uint64_t)cnt + 1, F.off, F.tmp, 0u, 0))) return rc;
+    }
+    *land = 0;
+    if (wide) HIPCHK(ctx, hipMemcpyAsync(land, F.total, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    else HIPCHK(ctx, hipMemcpyAsync(land, F.off + cnt, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    const uint64_t total = *land;
+    *out_bytes = total;
+    if (total >= (1ull << 32)) return fail(ctx, CM_ELIMIT, "cm_format_pam: %llu bytes of rows in one call (offsets are 32 bits: format in ranges)", (unsigned long long)total);
+    if (total > cap) return fail(ctx, CM_ELIMIT, "cm_format_pam: %llu bytes of rows > cap %llu", (unsigned long long)total, (unsigned long long)cap);
+    HIPCHK(ctx, ensure(ctx, F.out, (size_t)total + 4));
+    {
+        Timer t(ctx, PC_PAM, st);
+        hipLaunchKernelGGL(k_pam_rows, dim3(spans), dim3(cmpt::SPAN_ROWS), 0, st, (const cm_mapped_read *)ctx->d_state, (const uint8_t *)ctx->rd.names,
+                           (const uint32_t *)ctx->rd.name_off, ct, first, cnt, (const uint32_t *)F.off, (uint8_t *)F.out, (uint8_t *)F.path);
+    }
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipMemcpyAsync(out, F.out, (size_t)total, hipMemcpyDeviceToHost, st));
+    if (stats) {
+        F.h_path.resize(spans);
+        HIPCHK(ctx, hipMemcpyAsync(F.h_path.data(), F.path, spans, hipMemcpyDeviceToHost, st));
+    }
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    if (stats) {
+        stats[0] = count;
+        stats[1] = total;
+        for (uint32_t i = 0; i < spans; ++i) ++stats[F.h_path[i] ? 2 : 3];
+    }
+    return CM_OK;
+}
+
+// test hook: the carried states of the resident batch overwritten, behind everything queued for it
+int cm_state_poke(cm_ctx *ctx, const cm_mapped_read *states) {
+    if (!ctx || !states) return CM_EINVAL;
+    HIPCHK(ctx, hipSetDevice(ctx->P.device));
+    if (ctx->n_pairs == 0) return fail(ctx, CM_ESTATE, "cm_state_poke: no resident batch");
+    HIPCHK(ctx, hipMemcpyAsync(ctx->d_state, states, ctx->n_pairs * sizeof(cm_mapped_read), hipMemcpyHostToDevice, ctx->st.B));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->st.B));
+    return CM_OK;
 }
 
 int cm_host_alloc(cm_ctx *ctx, uint64_t bytes, void **out) {

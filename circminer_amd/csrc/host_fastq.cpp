@@ -1326,6 +1326,20 @@ int cm_write_pam(cm_writer *w, const cm_fastq_batch *b, const cm_mapped_read *st
     return w->o1.failed ? CM_EIO : CM_OK;
 }
 
+// rows somebody else formatted (cm_format_pam): small pieces go through the buffer, a piece the buffer cannot hold goes to the file
+// behind what the buffer holds
+int cm_write_bytes(cm_writer *w, const void *p, uint64_t n) {
+    if (!w || (n && !p)) return CM_EINVAL;
+    Out &o = w->o1;
+    if (n <= o.buf.size()) {
+        if (n) o.raw(p, (size_t)n);
+    } else {
+        o.flush();
+        if (o.f && fwrite(p, 1, (size_t)n, o.f) != n) o.failed = true;
+    }
+    return o.failed ? CM_EIO : CM_OK;
+}
+
 // SAMOutput::print_header (src/output.cpp:301-311)
 int cm_write_sam_header(cm_writer *w) {
     if (!w) return CM_EINVAL;

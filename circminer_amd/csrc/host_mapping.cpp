@@ -91,6 +91,11 @@ extern "C" int cm_mapping_run(const cm_mapping_args *a, cm_mapping_stats *stats,
         uint64_t n_rec = 0;
         cm_fastq_batch batch;
     } res[2];
+    // CM_PAM_DEVICE=1: the PAM rows of batch k as the device formatted them, in page-locked set k & 1 (cm_host_alloc)
+    struct RowBuf {
+        void *p = nullptr;
+        uint64_t cap = 0, n = 0;
+    } rows[2];
     // parser arrays registered with the runtime (cm_host_register).  The parser tells us (release hook, on its own thread) before
     // one of them is freed -- a generation's array that has to grow is allocated anew -- so that no registration outlives its block.
     struct Pinned {
@@ -109,6 +114,8 @@ extern "C" int cm_mapping_run(const cm_mapping_args *a, cm_mapping_stats *stats,
         if (writer.joinable()) writer.join();
         if (w_map) cm_writer_close(w_map);
         if (w_rem) cm_writer_close(w_rem);
+        for (RowBuf &rb : rows)
+            if (rb.p) (void)cm_host_free(cm, rb.p);
         if (cm) (void)cm_sync(cm);                             // drains the copy stream too: no copy out of the parser's arrays is in flight any more
         {
             std::lock_guard<std::mutex> lk(pin.mu);
@@ -392,11 +399,14 @@ extern "C" int cm_mapping_run(const cm_mapping_args *a, cm_mapping_stats *stats,
         if (pinned.size() >= 64) return;
         if (cm_host_register(cm, (void *)lo, (uint64_t)(hi - lo)) == CM_OK) pinned.emplace_back((void *)lo, (uint64_t)(hi - lo));
     };
-    // ---- the device-side tokeniser's path (opt-in): read k+2 (worker) | stage k+1 | rounds of k | write k-1 (worker) ----
-    bool text_path = false;
+    // ---- the device-side tokeniser's path (opt-in): read k+2 (worker) | stage k+1 | rounds of k (+ its PAM rows with CM_PAM_DEVICE=1)
+    //      | write k-1 (worker) ----
+    bool text_path = false, pam_device = false;
     {
         const char *e = getenv("CM_FASTQ_DEVICE");
-        text_path = e && atoi(e) == 1 && a->report == 0;
+        const char *ep = getenv("CM_PAM_DEVICE");
+        pam_device = a->report == 1 && ep && atoi(ep) == 1;      // the rows of report 1 formatted on the device: needs the text path
+        text_path = e && atoi(e) == 1 && (a->report == 0 || pam_device);
     }
     struct TextBlock {
         const uint8_t *t1 = nullptr, *t2 = nullptr;
@@ -427,7 +437,7 @@ extern "C" int cm_mapping_run(const cm_mapping_args *a, cm_mapping_stats *stats,
             B.rec2.resize(batch_pairs + 1);
             pin_range(B.t1, B.l1);
             pin_range(B.t2, B.l2);
-            int r = cm_reads_stage_text(cm, B.t1, B.l1, B.t2, B.l2, batch_pairs, (B.e1 ? 1u : 0u) | (B.e2 ? 2u : 0u), B.rec1.data(), B.rec2.data(), &B.tb);
+            int r = cm_reads_stage_text(cm, B.t1, B.l1, B.t2, B.l2, batch_pairs, (B.e1 ? 1u : 0u) | (B.e2 ? 2u : 0u) | (pam_device ? 4u : 0u), B.rec1.data(), B.rec2.data(), &B.tb);
             if (r != CM_OK) return r;
             if (B.tb.n_pairs) {
                 if (!want_fixed) want = std::max(B.tb.used1, B.tb.used2) / B.tb.n_pairs * batch_pairs / 100 * 101 + (1u << 16);
@@ -493,6 +503,35 @@ extern "C" int cm_mapping_run(const cm_mapping_args *a, cm_mapping_stats *stats,
                     parse_s = now() - tp;
                 });
             MAP_TRY(cm_map_rounds(cm, all.data(), (int)n_con, 1), "cm_map_rounds");
+            RowBuf &RB = rows[k & 1];
+            RB.n = 0;
+            if (pam_device) {
+                // the rows of the batch, in ranges: a range whose rows would not fit 32-bit offsets is halved, a buffer that is too
+                // small is replaced by one that holds what is there plus what the device asks for
+                uint64_t done = 0, step = std::min<uint64_t>(n, 1ull << 22);
+                while (done < n) {
+                    const uint64_t c = std::min(step, n - done);
+                    uint64_t got = 0;
+                    const int r = cm_format_pam(cm, chrs, n_chr, done, c, RB.p ? (char *)RB.p + RB.n : nullptr, RB.cap - RB.n, &got, nullptr);
+                    if (r == CM_ELIMIT && got >= (1ull << 32) && c > 1) {
+                        step = c / 2;
+                        continue;
+                    }
+                    if (r == CM_ELIMIT && got > RB.cap - RB.n) {
+                        const uint64_t cap = RB.n + got + got / c * (n - done - c) + (1u << 16);
+                        void *np = nullptr;
+                        MAP_TRY(cm_host_alloc(cm, cap, &np), "cm_host_alloc (PAM rows)");
+                        if (RB.n) memcpy(np, RB.p, RB.n);
+                        if (RB.p) (void)cm_host_free(cm, RB.p);
+                        RB.p = np;
+                        RB.cap = cap;
+                        continue;
+                    }
+                    MAP_TRY(r, "cm_format_pam");
+                    RB.n += got;
+                    done += c;
+                }
+            }
             uint64_t n_rec = 0;
             if (R.recs.size() < n) R.recs.resize(n);
             MAP_TRY(cm_collect_records(cm, 0, n, R.recs.data(), &n_rec), "cm_collect_records");
@@ -506,9 +545,11 @@ extern "C" int cm_mapping_run(const cm_mapping_args *a, cm_mapping_stats *stats,
             st.bsj_pairs += n_rec;
             if (writer.joinable()) writer.join();                    // rows of batch k-1 are out: file order = batch order
             MAP_TRY(writer_rc, "writer");
-            writer = std::thread([&R, &B, &writer_rc, &write_s, w_rem]() {
+            writer = std::thread([&R, &B, &RB, &writer_rc, &write_s, w_map, w_rem, pam_device]() {
                 const double tw = now();
-                writer_rc = R.n_rec ? cm_write_remain_text(w_rem, B.t1, B.rec1.data(), B.t2, B.rec2.data(), R.recs.data(), R.n_rec) : CM_OK;
+                int r = pam_device ? cm_write_bytes(w_map, RB.p, RB.n) : CM_OK;
+                if (r == CM_OK && R.n_rec) r = cm_write_remain_text(w_rem, B.t1, B.rec1.data(), B.t2, B.rec2.data(), R.recs.data(), R.n_rec);
+                writer_rc = r;
                 write_s += now() - tw;
             });
             if (parser.joinable()) parser.join();
@@ -517,6 +558,7 @@ extern "C" int cm_mapping_run(const cm_mapping_args *a, cm_mapping_stats *stats,
         }
         if (writer.joinable()) writer.join();
         MAP_TRY(writer_rc, "writer");
+        if (w_map) MAP_TRY(cm_writer_flush(w_map), "writing the mapping file");
         MAP_TRY(cm_writer_flush(w_rem), "writing the remain files");
         st.seconds_map = now() - t1;
         st.seconds_write = write_s;

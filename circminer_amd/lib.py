@@ -213,6 +213,9 @@ def load(path: str = LIB_PATH) -> C.CDLL:
         "cm_fastq_next_text": (C.c_int, [vp, C.c_uint64, pp(vp), pp(C.c_uint64), pp(C.c_int), pp(vp), pp(C.c_uint64), pp(C.c_int)]),
         "cm_fastq_text_consumed": (C.c_int, [vp, C.c_uint64, C.c_uint64]),
         "cm_write_remain_text": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_uint64]),
+        "cm_format_pam": (C.c_int, [vp, pp(ChrInfo), C.c_uint32, C.c_uint64, C.c_uint64, vp, C.c_uint64, pp(C.c_uint64), pp(C.c_uint64)]),
+        "cm_state_poke": (C.c_int, [vp, vp]),
+        "cm_write_bytes": (C.c_int, [vp, vp, C.c_uint64]),
         "cm_map_round": (C.c_int, [vp, C.c_int, C.c_int]),
         "cm_map_rounds": (C.c_int, [vp, i32p, C.c_int, C.c_int]),
         "cm_reads_download": (C.c_int, [vp, vp, vp, vp]),
@@ -299,7 +302,7 @@ EXPORTED_SYMBOLS = ["cm_create", "cm_destroy", "cm_last_error", "cm_load_contig"
                     "cm_host_close_index", "cm_fastq_open", "cm_fastq_open_shard", "cm_merge_parts", "cm_fastq_next", "cm_fastq_set_release_hook", "cm_fastq_close", "cm_writer_open", "cm_write_remain",
                     "cm_write_pam", "cm_write_sam_header", "cm_write_sam", "cm_writer_flush", "cm_writer_close", "cm_mapping_run", "cm_sort_remain", "cm_circ_report", "cm_circ_call", "cm_circ_run", "cm_host_gene_overlap", "cm_regional_table_build", "cm_regional_table_free",
                     "cm_build_contig", "cm_index_download", "cm_reads_stage_text", "cm_reads_peek", "cm_fastq_next_text", "cm_fastq_text_consumed",
-                    "cm_write_remain_text"]
+                    "cm_write_remain_text", "cm_format_pam", "cm_state_poke", "cm_write_bytes"]
 
 
 class HostIndex:
@@ -647,6 +650,13 @@ class RecordWriter:
     def write_pam(self, batch, states, sel=None):
         self._call(self.L.cm_write_pam, batch, states, sel)
 
+    def write_bytes(self, data):
+        """cm_write_bytes: raw bytes (the rows HotPath.format_pam returns) appended to the first file"""
+        a = np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray)) else np.ascontiguousarray(data, dtype=np.uint8)
+        rc = self.L.cm_write_bytes(self.h, a.ctypes.data if a.size else None, a.size)
+        if rc != 0:
+            raise RuntimeError(f"writer failed ({rc})")
+
     def write_sam_header(self):
         if self.L.cm_write_sam_header(self.h) != 0:
             raise RuntimeError("cm_write_sam_header failed")
@@ -722,18 +732,44 @@ class HotPath:
         p = prior.ctypes.data if prior is not None else None
         self._chk(self.L.cm_reads_stage(self.h, C.byref(batch.c), p), "cm_reads_stage")
 
-    def stage_text(self, text1, text2, max_pairs, eof1=True, eof2=True):
+    def stage_text(self, text1, text2, max_pairs, eof1=True, eof2=True, keep_names=False):
         """cm_reads_stage_text: the next batch staged from FASTQ text, tokenised on the device.  text1 / text2: uint8 arrays or
-        bytes.  Returns (TextBatch, rec1, rec2); n_pairs == 0: nothing was staged."""
+        bytes.  Returns (TextBatch, rec1, rec2); n_pairs == 0: nothing was staged.  keep_names (flag bit 2): the R1 names stay on
+        the device with the batch, for format_pam."""
         t1 = np.frombuffer(text1, np.uint8) if isinstance(text1, (bytes, bytearray)) else np.ascontiguousarray(text1, dtype=np.uint8)
         t2 = np.frombuffer(text2, np.uint8) if isinstance(text2, (bytes, bytearray)) else np.ascontiguousarray(text2, dtype=np.uint8)
         cap = int(min(max_pairs, min(t1.size, t2.size) // 4)) + 1           # a record has four bytes at least
         rec1, rec2 = np.zeros(cap, np.uint64), np.zeros(cap, np.uint64)
         tb = TextBatch()
         self._chk(self.L.cm_reads_stage_text(self.h, t1.ctypes.data if t1.size else None, t1.size, t2.ctypes.data if t2.size else None, t2.size, int(max_pairs),
-                                             int(bool(eof1)) | int(bool(eof2)) << 1, rec1.ctypes.data, rec2.ctypes.data, C.byref(tb)), "cm_reads_stage_text")
+                                             int(bool(eof1)) | int(bool(eof2)) << 1 | int(bool(keep_names)) << 2, rec1.ctypes.data, rec2.ctypes.data, C.byref(tb)), "cm_reads_stage_text")
         self._staged_n = int(tb.n_pairs)
         return tb, rec1[:self._staged_n + 1], rec2[:self._staged_n + 1]
+
+    def format_pam(self, chrs=(), first=0, count=None, cap=None):
+        """cm_format_pam: the PAM rows of pairs [first, first + count) of the resident batch (staged with keep_names), formatted on
+        the device.  chrs: chromosome table rows (name, contig id, start, length).  Returns (bytes, stats); cap: the size of the
+        buffer offered (default: what the rows need, asked for first)."""
+        table = chr_array(list(chrs))
+        n = self.n - first if count is None else count
+        got = C.c_uint64(0)
+        stats = (C.c_uint64 * 4)()
+        if cap is None:
+            rc = self.L.cm_format_pam(self.h, table, len(chrs), int(first), int(n), None, 0, C.byref(got), None)
+            if rc not in (0, -6) or (rc == -6 and got.value >= 1 << 32):        # CM_ELIMIT with the needed size is the answer here
+                self._chk(rc, "cm_format_pam")
+            cap = got.value
+        buf = np.full(int(cap) + 64, 0xA5, np.uint8)                             # (the bytes behind cap show a write past it)
+        self._chk(self.L.cm_format_pam(self.h, table, len(chrs), int(first), int(n), buf.ctypes.data, int(cap), C.byref(got), stats), "cm_format_pam")
+        assert got.value <= cap and bool((buf[int(cap):] == 0xA5).all())
+        return buf[:got.value].tobytes(), list(stats)
+
+    def poke_states(self, states):
+        """cm_state_poke (test hook): the carried states of the resident batch overwritten (MAPPED_DTYPE, n records)"""
+        st = np.ascontiguousarray(states, dtype=MAPPED_DTYPE)
+        if len(st) != self.n:
+            raise ValueError(f"{len(st)} states for a batch of {self.n} pairs")
+        self._chk(self.L.cm_state_poke(self.h, st.ctypes.data), "cm_state_poke")
 
     def peek_reads(self):
         """cm_reads_peek: (seq1, off1, seq2, off2) of the resident batch, copied back from the device"""

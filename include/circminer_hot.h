@@ -244,7 +244,13 @@ int cm_reads_swap(cm_ctx *ctx);
  * On any error nothing is staged; an earlier staged batch is dropped in every case, as in cm_reads_stage.  The call waits for the
  * staging stream only (one small read-back of the batch's shape and verdicts, and the record starts when asked for), never for
  * the mapping streams.  rec1 / rec2 (nullable; max_pairs + 1 words each, n + 1 are written): byte offset of each staged record's
- * '@' in its block, rec[n] = used: what cm_write_remain_text slices names and qualities from. */
+ * '@' in its block, rec[n] = used: what cm_write_remain_text slices names and qualities from.
+ *   - flags bit 2 (value 4, "keep names"): the stage also leaves on the device the R1 name of each of the n staged pairs, as
+ *     cm_fastq_next would put it into names1: token 0 of the header line (tokens are runs of bytes other than ' ' behind the
+ *     '@') without a trailing "/x", up to its first NUL byte; empty for a header without a token.  The names belong to the batch:
+ *     they travel with its read buffers through cm_reads_swap and stay valid while the batch is resident, also while the next
+ *     cm_reads_stage_text overwrites the text.  cm_format_pam is their reader.  R2 names are not kept.  Without the bit the
+ *     kernels launched, the buffers and the results are those of a stage without names. */
 typedef struct cm_text_batch {
     uint64_t n_pairs;        /* pairs staged */
     uint64_t used1, used2;   /* bytes of text1 / text2 consumed = start of the first record not staged */
@@ -366,12 +372,15 @@ int cm_dp_batch(cm_ctx *ctx, const cm_params *P, const uint8_t *arena, uint64_t 
  * four NULL return only *n_pairs. */
 int cm_reads_peek(cm_ctx *ctx, uint8_t *seq1, uint64_t cap1, uint64_t *off1, uint8_t *seq2, uint64_t cap2, uint64_t *off2,
                   uint64_t *n_pairs);
+/* test hook, the counterpart of cm_reads_download: overwrite the carried states of the resident batch (n_pairs records), behind
+ * everything queued for it.  CM_ESTATE without a resident batch.  Flags and categories are not touched. */
+int cm_state_poke(cm_ctx *ctx, const cm_mapped_read *states);
 
 /* ---------------- timing hooks for bench.py (HIP events on the ctx stream) ---------------- */
 /* Milliseconds spent in each kernel class since the last cm_prof_reset(), and launch counts:
  * [0]=k_seed [1]=k_chain (light problems) [2]=k_pair (light pairs) [3]=k_scan_* [4]=k_pair_heavy
- * [5]=class / counting-sort kernels [6]=k_chain_heavy [7]=no time; launches[7] = first rounds taken over from the
- * cross-batch prefetch of cm_map_rounds.  [1] and [2] are timed up to the join with the second
+ * [5]=class / counting-sort kernels [6]=k_chain_heavy [7]=the kernels of cm_format_pam (no launch count); launches[7] = first
+ * rounds taken over from the cross-batch prefetch of cm_map_rounds.  [1] and [2] are timed up to the join with the second
  * stream, on which the heavy kernels [6] / [4] run concurrently. */
 int cm_prof_enable(cm_ctx *ctx, int on);
 int cm_prof_reset(cm_ctx *ctx);
@@ -524,6 +533,27 @@ int cm_write_remain_records(cm_writer *w, const cm_fastq_batch *batch, const cm_
 int cm_write_remain_text(cm_writer *w, const uint8_t *text1, const uint64_t *rec1, const uint8_t *text2, const uint64_t *rec2,
                          const cm_record *recs, uint64_t n_rec);
 int cm_write_pam(cm_writer *w, const cm_fastq_batch *b, const cm_mapped_read *states, const uint64_t *sel, uint64_t n_sel);
+/* <out>.mapping.pam rows (cm_write_pam / SAMOutput::write_pam_rec_pe, src/output.cpp:279-299) of pairs [first, first + count)
+ * of the resident batch, formatted BY THE DEVICE from the states in HBM and the names kept by cm_reads_stage_text (flag bit 2):
+ * the bytes cm_write_pam writes for the same pairs, in pair order -- "%u" / "%d" as there (mlen_* through (int), junc_num a
+ * uint16, gm_compatible as != 0), the unmapped form (21 "*" fields and the type) for every type outside CONCRD, DISCRD, CHIORF,
+ * CHIBSJ, CHI2BSJ, CONGNM, CONGEN (negative or > 13 included), "-" for a chr_id outside [0, n_chr).  chrs: the chromosome table
+ * (names only are used); it is uploaded when it differs from the one last given to this context.
+ * Ordering is that of cm_collect_records: the work is queued behind everything queued for the resident batch (pair stages, the
+ * re-run launch, fall-backs) and the call returns when the bytes are in out (page-locked or pageable, cap bytes); it neither
+ * waits for nor disturbs the staging stream or a cross-batch prefetch in flight.
+ * CM_ESTATE: no resident batch, or one without names (cm_reads_upload, cm_reads_stage, cm_reads_stage_text without bit 2).
+ * CM_EINVAL: first + count > n_pairs, or out == NULL with cap > 0.  CM_ELIMIT with the needed size in *out_bytes and nothing
+ * written: cap is too small; CM_ELIMIT also when the rows of one call come to 2^32 bytes or more (offsets are 32 bits: format in
+ * ranges).  count == 0 is CM_OK with *out_bytes == 0.  A refusal leaves the resident batch as it was.
+ * stats (nullable): [0] rows, [1] bytes, [2] / [3] spans of 64 rows (one wave each) that were formatted in the wave's LDS window
+ * and streamed out as whole words / that were larger than the window (long names) and stored byte by byte by their lanes.
+ * After cm_prof_enable(ctx, 1) the formatter's kernels are timed by HIP events into ms[7] of cm_prof_get. */
+int cm_format_pam(cm_ctx *ctx, const cm_chr_info *chrs, uint32_t n_chr, uint64_t first, uint64_t count,
+                  void *out, uint64_t cap, uint64_t *out_bytes, uint64_t stats[4] /* nullable */);
+/* Appends n raw bytes to the writer's first file through its buffer (the rows cm_format_pam delivers); CM_EIO like the other
+ * cm_write_* calls. */
+int cm_write_bytes(cm_writer *w, const void *p, uint64_t n);
 /* <out>.mapping.sam (--sam): header = SAMOutput::print_header (src/output.cpp:301-311, one @SQ per row of the chromosome
  * table), records = write_sam_rec_pe with set_flag_pe / set_output_pe (src/output.cpp:118-277): two lines per pair,
  * CIGAR "*", MAPQ 255, tags AT / NM / JC / TC; TLEN is printed with %u like the reference does. */
@@ -548,7 +578,11 @@ void cm_writer_close(cm_writer *w);
  * the batches are tokenised on the device: cm_fastq_next_text -> cm_reads_stage_text -> cm_write_remain_text, the same files
  * byte for byte; in every other case (PAM / SAM rows need every pair's name on the host; gzip, pipes and carried 23-token headers
  * need the host parser) and with the variable unset the host parser feeds the device as before.  CM_FASTQ_DEVICE_BLOCK=<bytes>
- * (a test knob) sets the bytes per file and block; the default is sized for batch_pairs. */
+ * (a test knob) sets the bytes per file and block; the default is sized for batch_pairs.
+ * With CM_PAM_DEVICE=1 in addition to CM_FASTQ_DEVICE=1 the device tokeniser's path also covers report == 1 (same conditions on
+ * the input): the batches are staged with their names (flag bit 2), the PAM rows of a batch are formatted on the device
+ * (cm_format_pam, into one of two page-locked buffers) and the writer thread appends them with cm_write_bytes -- the same
+ * <out>.mapping.pam byte for byte.  report == 2 (SAM rows need bases and qualities) stays with the host parser. */
 typedef struct cm_mapping_args {
     const char *index_path;        /* <ref>.packed.fa.index        */
     const char *index_info_path;   /* <ref>.packed.fa.index.info   */
