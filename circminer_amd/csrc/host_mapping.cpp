@@ -26,88 +26,112 @@
 //
 // One process per GPU: rank r of w maps the r-th contiguous block of pairs (cm_fastq_open_shard) and writes .part<r> files;
 // cm_merge_parts on rank 0 concatenates them in rank order -- the bytes one process would have written.
+//
+// The run is one object (Run): cm_mapping_run walks its phases, a phase returns a code, and what the phases acquired -- threads, files,
+// page-locked ranges, the context, host tables -- is released by ~Run, in one order, on every way out.
 #include <algorithm>
 #include <chrono>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <string>
-#include <mutex>
 #include <thread>
 #include <vector>
 
 #include "circminer_hot.h"
+#include "cm_pinned_ranges.h"
 
 namespace {
 
-struct Fail {
-    char *buf;
-    size_t cap;
-    int operator()(int code, const char *fmt, ...) const {
-        if (buf && cap) {
-            va_list ap;
-            va_start(ap, fmt);
-            vsnprintf(buf, cap, fmt, ap);
-            va_end(ap);
-        }
-        return code;
-    }
-};
-
 double now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
-}  // namespace
+// results of batch k live in set k & 1: the writer thread of batch k reads them while batch k+1 is downloaded
+struct Result {
+    std::vector<cm_mapped_read> state;
+    std::vector<uint8_t> active;
+    std::vector<uint64_t> sel;
+    std::vector<cm_record> recs;
+    uint64_t n_rec = 0;
+    cm_fastq_batch batch;
+};
+// CM_PAM_DEVICE=1: the PAM rows of batch k as the device formatted them, in page-locked set k & 1 (cm_host_alloc)
+struct RowBuf {
+    void *p = nullptr;
+    uint64_t cap = 0, n = 0;
+};
+// CM_FASTQ_DEVICE=1: block k in tq[k & 3]: its text is the reader's for three more reads
+struct TextBlock {
+    const uint8_t *t1 = nullptr, *t2 = nullptr;
+    uint64_t l1 = 0, l2 = 0;
+    int e1 = 0, e2 = 0;
+    cm_text_batch tb{};
+    std::vector<uint64_t> rec1, rec2;
+};
+// one packed contig as its source hands it out: a view (its arrays, or lengths only) and, from a full-format index, the raw record
+struct Contig { cm_index_view iv; cm_index_raw raw; };
+struct Run;
+// what differs between the three sources of the contig loop (Run::load_contigs_from has the rest)
+struct ContigSource {
+    const char *next_name, *load_name;
+    int (*next)(Run &, Contig *, int *loaded);
+    int (*load)(Run &, int slot, const Contig &);
+    bool frees_host_copy;                          // the contig's arrays are malloc'ed per contig and go back after the upload
+    const char *lap_first, *lap_ahead, *lap_load;
+};
 
-extern "C" int cm_mapping_run(const cm_mapping_args *a, cm_mapping_stats *stats, char *err, uint64_t err_cap) {
-    Fail fail{err, (size_t)err_cap};
-    if (err && err_cap) err[0] = 0;
-    if (!a || !a->index_path || !a->index_info_path || !a->gtf_path || !a->fastq1 || !a->fastq2 || !a->out_prefix)
-        return fail(CM_EINVAL, "cm_mapping_run: null argument");
-    if (a->report < 0 || a->report > 2) return fail(CM_EINVAL, "report must be 0 (none), 1 (PAM) or 2 (SAM)");
-    cm_mapping_stats st;
-    memset(&st, 0, sizeof st);
+struct Run {
+    const cm_mapping_args *const a;
+    char *const err;
+    const size_t err_cap;
+    const char *what = nullptr;                    // the call that failed, for cm_mapping_run's message; null when the text is set already
+    cm_mapping_stats st{};
     const double t0 = now();
-    const int n_threads = a->n_threads > 0 ? a->n_threads : 1;
-    const uint64_t batch_pairs = a->batch_pairs ? a->batch_pairs : (1ull << 18);
-    const int world = a->world > 1 ? a->world : 1, rank = a->world > 1 ? a->rank : 0;
-    if (rank < 0 || rank >= world) return fail(CM_EINVAL, "rank %d of %d", a->rank, a->world);
-    const std::string part = world > 1 ? ".part" + std::to_string(rank) : "";
-
+    double t1 = 0.0;
+    int n_threads = 1, world = 1, rank = 0;
+    uint64_t batch_pairs = 0, want = 0;            // want: bytes per file and text block
+    std::string part;
+    const bool trace = getenv("CM_INDEX_TRACE") != nullptr;
+    cm_params P;
+    int32_t full = 0;
+    uint32_t n_con = 0, n_chr = 0;
+    std::vector<int> all;
+    // ---- what the run owns (~Run) ----
     cm_chr_info *chrs = nullptr;
-    uint32_t n_chr = 0;
     cm_index_file *idx = nullptr;
     cm_ctx *cm = nullptr;
     cm_fastq *fq = nullptr;
     cm_writer *w_map = nullptr, *w_rem = nullptr;
     std::vector<cm_index_view> views;
-    std::vector<cm_annot_view> annots;
-    // results of batch k live in set k & 1: the writer thread of batch k reads them while batch k+1 is downloaded
-    struct Result {
-        std::vector<cm_mapped_read> state;
-        std::vector<uint8_t> active;
-        std::vector<uint64_t> sel;
-        std::vector<cm_record> recs;
-        uint64_t n_rec = 0;
-        cm_fastq_batch batch;
-    } res[2];
-    // CM_PAM_DEVICE=1: the PAM rows of batch k as the device formatted them, in page-locked set k & 1 (cm_host_alloc)
-    struct RowBuf {
-        void *p = nullptr;
-        uint64_t cap = 0, n = 0;
-    } rows[2];
-    // parser arrays registered with the runtime (cm_host_register).  The parser tells us (release hook, on its own thread) before
-    // one of them is freed -- a generation's array that has to grow is allocated anew -- so that no registration outlives its block.
-    struct Pinned {
-        std::mutex mu;
-        std::vector<std::pair<void *, uint64_t>> v;
-        cm_ctx *cm = nullptr;
-    } pin;
-    std::vector<std::pair<void *, uint64_t>> &pinned = pin.v;
+    std::vector<cm_annot_view> annots, annots_early;             // _early: the GTF thread's, until load_annotation() takes or frees them
+    Result res[2];
+    RowBuf rows[2];
+    // parser arrays and text blocks registered with the runtime.  The parser tells us (release hook, on its own thread) before one of
+    // them is freed -- a generation's array that has to grow is allocated anew -- so that no registration outlives its block.
+    PinnedRanges pins;
     std::thread writer, parser, gtf_thread, free_thread;
-    int writer_rc = CM_OK, parser_rc = CM_OK;
-    int rc = CM_OK;
-    auto cleanup = [&]() {
+    // ---- what the threads use: members, so that it outlives every phase's frame until ~Run has joined them ----
+    std::vector<uint32_t> clen_guess;
+    int early_rc = CM_EINVAL, writer_rc = CM_OK, parser_rc = CM_OK;
+    double write_s = 0.0, parse_s = 0.0;           // read after the join
+    bool text_path = false, pam_device = false, want_fixed = false;
+    TextBlock tq[4];
+    cm_fastq_batch cur{}, nxt{}, nn{};
+    Run(const cm_mapping_args *args, char *e, uint64_t cap) : a(args), err(e), err_cap((size_t)cap) {
+        if (err && err_cap) err[0] = 0;
+        pins.user = this;
+        pins.reg = [](void *u, void *p, uint64_t bytes) { return cm_host_register(((Run *)u)->cm, p, bytes); };
+        pins.unreg = [](void *u, void *p, const char **msg) {
+            const int r = cm_host_unregister(((Run *)u)->cm, p);
+            if (r != CM_OK) *msg = cm_last_error(((Run *)u)->cm);
+            return r;
+        };
+    }
+    // The order is load-bearing.  The threads first: they use everything below.  cm_sync drains the copy stream too, so no copy out
+    // of the parser's arrays is in flight when they are unregistered; they are unregistered before cm_fastq_close frees them, so no
+    // registration outlives its block; the context goes after the last call that needs it and before the host tables it was fed from.
+    ~Run() {
         if (free_thread.joinable()) free_thread.join();
         if (gtf_thread.joinable()) gtf_thread.join();           // it reads chrs
         if (parser.joinable()) parser.join();
@@ -116,187 +140,144 @@ extern "C" int cm_mapping_run(const cm_mapping_args *a, cm_mapping_stats *stats,
         if (w_rem) cm_writer_close(w_rem);
         for (RowBuf &rb : rows)
             if (rb.p) (void)cm_host_free(cm, rb.p);
-        if (cm) (void)cm_sync(cm);                             // drains the copy stream too: no copy out of the parser's arrays is in flight any more
-        {
-            std::lock_guard<std::mutex> lk(pin.mu);
-            for (auto &pr : pinned) (void)cm_host_unregister(cm, pr.first);
-            pinned.clear();
-        }
+        if (cm) (void)cm_sync(cm);
+        pins.clear();
+        if (pins.failed)
+            fprintf(stderr, "cm_mapping_run: %llu page-locked range(s) could not be unregistered; first: %s\n", (unsigned long long)pins.failed, pins.first_message.c_str());
         if (fq) cm_fastq_close(fq);
         if (cm) cm_destroy(cm);
         if (!annots.empty()) cm_host_free_annotation(annots.data(), (uint32_t)annots.size());
+        if (early_rc == CM_OK && !annots_early.empty()) cm_host_free_annotation(annots_early.data(), (uint32_t)annots_early.size());
         for (auto &v : views) cm_host_free_loaded_contig(&v);
         if (idx) cm_host_close_index(idx);
         if (chrs) cm_host_free_index_info(chrs, n_chr);
-    };
-#define MAP_TRY(call, what)                                                                                  \
-    do {                                                                                                     \
-        rc = (call);                                                                                         \
-        if (rc != CM_OK) {                                                                                   \
-            rc = fail(rc, "%s failed (%d)%s%s", what, rc, cm ? ": " : "", cm ? cm_last_error(cm) : "");       \
-            cleanup();                                                                                       \
-            return rc;                                                                                       \
-        }                                                                                                    \
-    } while (0)
-
-    // ---- index info, index file, context (genome_packer.load_index_info, checkHashTable, initLoadingHashTableMeta) ----
-    MAP_TRY(cm_host_read_index_info(a->index_info_path, &chrs, &n_chr), "cm_host_read_index_info");
-    int32_t kmer = 0, full = 0;
-    uint32_t n_rec = 0;
-    MAP_TRY(cm_host_open_index(a->index_path, &idx, &kmer, &full, &n_rec), "cm_host_open_index");
-    cm_params P = a->params;
-    const bool from_sequence = full < 0;          // index_path is the packed FASTA itself: the tables are built on the device
-    if (from_sequence && P.kmer == 0) {
-        rc = fail(CM_EINVAL, "%s is a packed FASTA, not an index file: there is no k to read, params.kmer must be given", a->index_path);
-        cleanup();
-        return rc;
     }
-    if (P.kmer == 0) P.kmer = kmer;
-    if (!from_sequence && P.kmer != kmer) {
-        rc = fail(CM_EINVAL, "index was built for k = %d, params ask for k = %d", kmer, P.kmer);
-        cleanup();
-        return rc;
+    // ---- failures: the one place the message is written ----
+    int refuse(int code, const char *fmt, ...) {
+        if (err && err_cap) {
+            va_list ap;
+            va_start(ap, fmt);
+            vsnprintf(err, err_cap, fmt, ap);
+            va_end(ap);
+        }
+        return code;
     }
-    MAP_TRY(cm_create(&P, &cm), "cm_create");
-    pin.cm = cm;
-
-    // ---- every packed contig into its own slot (loadHashTable + pac2char_whole_contig per round in the reference) ----
-    // Contig c + 1 is read and decoded from the index file (host threads) while contig c goes over PCIe and gets its bucket
-    // descriptors built (cm_load_contig), and the GTF is parsed meanwhile on a thread of its own (it needs the contig lengths
-    // only at the end: they are in the .index.info rows already).
-    const bool trace = getenv("CM_INDEX_TRACE") != nullptr;
-    auto lap = [&](const char *what, double since) {
-        if (trace) fprintf(stderr, "[load] %s %.3f s (at %.3f s)\n", what, now() - since, now() - t0);
-    };
-    lap("index info + header + context", t0);
-    // the GTF model is built on a thread of its own meanwhile; the contig lengths it needs follow from the .index.info rows
-    // (a packed contig ends with its last chromosome) and are checked against the index file's afterwards
-    std::vector<uint32_t> clen_guess;
-    for (uint32_t i = 0; i < n_chr; ++i) {
-        if (chrs[i].contig_id == 0) continue;
-        if (clen_guess.size() < chrs[i].contig_id) clen_guess.resize(chrs[i].contig_id, 0);
-        clen_guess[chrs[i].contig_id - 1] = std::max(clen_guess[chrs[i].contig_id - 1], chrs[i].start_pos + chrs[i].len);
+    int failed(int rc, const char *name) { return what = name, rc; }          // `rc` of the call `name`: cm_mapping_run names the call
+    void lap(const char *text, double since) const { if (trace) fprintf(stderr, "[load] %s %.3f s (at %.3f s)\n", text, now() - since, now() - t0); }
+    // ---- phase 1: arguments and refusals ----
+    int check_args() {
+        if (!a || !a->index_path || !a->index_info_path || !a->gtf_path || !a->fastq1 || !a->fastq2 || !a->out_prefix)
+            return refuse(CM_EINVAL, "cm_mapping_run: null argument");
+        if (a->report < 0 || a->report > 2) return refuse(CM_EINVAL, "report must be 0 (none), 1 (PAM) or 2 (SAM)");
+        n_threads = a->n_threads > 0 ? a->n_threads : 1;
+        batch_pairs = a->batch_pairs ? a->batch_pairs : (1ull << 18);
+        world = a->world > 1 ? a->world : 1, rank = a->world > 1 ? a->rank : 0;
+        if (rank < 0 || rank >= world) return refuse(CM_EINVAL, "rank %d of %d", a->rank, a->world);
+        if (world > 1) part = ".part" + std::to_string(rank);
+        return CM_OK;
     }
-    std::vector<cm_annot_view> annots_early(clen_guess.size());
-    int early_rc = CM_EINVAL;
-    if (!clen_guess.empty())
-        gtf_thread = std::thread([&]() {
-            const double tg = now();
-            early_rc = cm_host_build_annotation(a->gtf_path, chrs, n_chr, clen_guess.data(), (uint32_t)clen_guess.size(), P.max_read_len, annots_early.data());
-            lap("GTF -> annotation tables (under the contig loads)", tg);
-        });
-    if (from_sequence) {
-        // no index file: contig c + 1 is read from the packed FASTA (one host thread) while the device builds the table of
-        // contig c from its sequence (cm_build_contig)
-        cm_index_view nxt_iv;
-        int nxt_loaded = 0, nxt_rc = CM_OK;
-        double tl = now();
-        nxt_rc = cm_host_next_contig_genome(idx, &nxt_iv, &nxt_loaded);
-        lap("contig sequence read", tl);
-        for (;;) {
-            MAP_TRY(nxt_rc, "cm_host_next_contig_genome");
-            if (!nxt_loaded) break;
-            cm_index_view iv = nxt_iv;
-            views.push_back(iv);
-            if (iv.contig_num != (int32_t)views.size() - 1) {
-                rc = fail(CM_EINVAL, "packed contigs out of order: record %zu is contig %d", views.size(), iv.contig_num + 1);
-                cleanup();
+    // ---- phase 2: index info, index file, context (genome_packer.load_index_info, checkHashTable, initLoadingHashTableMeta) ----
+    int open_index() {
+        int rc;
+        if ((rc = cm_host_read_index_info(a->index_info_path, &chrs, &n_chr)) != CM_OK) return failed(rc, "cm_host_read_index_info");
+        int32_t kmer = 0;
+        uint32_t n_rec = 0;
+        if ((rc = cm_host_open_index(a->index_path, &idx, &kmer, &full, &n_rec)) != CM_OK) return failed(rc, "cm_host_open_index");
+        P = a->params;
+        // full < 0: index_path is the packed FASTA itself, the tables are built on the device
+        if (full < 0 && P.kmer == 0)
+            return refuse(CM_EINVAL, "%s is a packed FASTA, not an index file: there is no k to read, params.kmer must be given", a->index_path);
+        if (P.kmer == 0) P.kmer = kmer;
+        if (full >= 0 && P.kmer != kmer) return refuse(CM_EINVAL, "index was built for k = %d, params ask for k = %d", kmer, P.kmer);
+        if ((rc = cm_create(&P, &cm)) != CM_OK) return failed(rc, "cm_create");
+        lap("index info + header + context", t0);
+        return CM_OK;
+    }
+    // ---- phase 3: every packed contig into its own slot (loadHashTable + pac2char_whole_contig per round in the reference) ----
+    // Contig c + 1 is read from the file (host threads) while contig c goes over PCIe and gets its table flattened or built and its
+    // bucket descriptors made, and the GTF is parsed meanwhile on a thread of its own: the contig lengths it needs follow from the
+    // .index.info rows (a packed contig ends with its last chromosome) and are checked against the index file's afterwards.
+    int load_contigs() {
+        for (uint32_t i = 0; i < n_chr; ++i) {
+            if (chrs[i].contig_id == 0) continue;
+            if (clen_guess.size() < chrs[i].contig_id) clen_guess.resize(chrs[i].contig_id, 0);
+            clen_guess[chrs[i].contig_id - 1] = std::max(clen_guess[chrs[i].contig_id - 1], chrs[i].start_pos + chrs[i].len);
+        }
+        annots_early.resize(clen_guess.size());
+        if (!clen_guess.empty())
+            gtf_thread = std::thread([this]() {
+                const double tg = now();
+                early_rc = cm_host_build_annotation(a->gtf_path, chrs, n_chr, clen_guess.data(), (uint32_t)clen_guess.size(), P.max_read_len, annots_early.data());
+                lap("GTF -> annotation tables (under the contig loads)", tg);
+            });
+        // no index file: the sequence is read from the packed FASTA (one host thread) and the device builds the table from it
+        static const ContigSource from_sequence = {
+            "cm_host_next_contig_genome", "cm_build_contig",
+            [](Run &r, Contig *c, int *loaded) { return cm_host_next_contig_genome(r.idx, &c->iv, loaded); },
+            [](Run &r, int slot, const Contig &c) { return cm_build_contig(r.cm, slot, c.iv.contig_num, c.iv.genome, c.iv.ref_len, nullptr); },
+            true, "contig sequence read", "next contig sequence read (under the build)", "contig uploaded, table built on the device + descriptors"};
+        // full-format index: the table crosses PCIe as it is in the file and the device flattens it; the host only reads and decodes
+        // the bucket headers.  The view holds the lengths only: the arrays stay with the file handle.
+        static const ContigSource from_full_index = {
+            "cm_host_next_contig_raw", "cm_load_contig_raw",
+            [](Run &r, Contig *c, int *loaded) {
+                const int rc = cm_host_next_contig_raw(r.idx, r.n_threads, &c->raw, loaded);
+                memset(&c->iv, 0, sizeof c->iv);
+                if (rc == CM_OK && *loaded) c->iv.contig_num = c->raw.contig_num, c->iv.ref_len = c->raw.ref_len;
                 return rc;
-            }
-            std::thread ahead([&]() {
+            },
+            [](Run &r, int slot, const Contig &c) { return cm_load_contig_raw(r.cm, slot, &c.raw); },
+            false, "contig record read", "next contig record read (under the upload)", "contig uploaded, flattened on the device + descriptors"};
+        // compact index: the host decodes the table.  Its host copy is dead once it is in HBM: returned to the system after each upload,
+        // while the next contig is still being decoded, rather than in one 25-GB sweep next to the FASTQ parser's first page faults
+        static const ContigSource from_compact_index = {
+            "cm_host_next_contig", "cm_load_contig",
+            [](Run &r, Contig *c, int *loaded) { return cm_host_next_contig(r.idx, r.n_threads, &c->iv, loaded); },
+            [](Run &r, int slot, const Contig &c) { return cm_load_contig(r.cm, slot, &c.iv); },
+            true, "contig decoded", "next contig decoded (under the upload)", "contig uploaded + descriptors"};
+        const int rc = load_contigs_from(full < 0 ? from_sequence : full ? from_full_index : from_compact_index);
+        if (rc != CM_OK) return rc;
+        n_con = (uint32_t)views.size();
+        return n_con ? CM_OK : refuse(CM_EINVAL, "index file holds no contig");
+    }
+    int load_contigs_from(const ContigSource &S) {
+        Contig nxt;
+        int nxt_loaded = 0;
+        double tl = now();
+        int nxt_rc = S.next(*this, &nxt, &nxt_loaded);
+        lap(S.lap_first, tl);
+        for (;;) {
+            if (nxt_rc != CM_OK) return failed(nxt_rc, S.next_name);
+            if (!nxt_loaded) return CM_OK;
+            const Contig c = nxt;
+            views.push_back(c.iv);
+            if (c.iv.contig_num != (int32_t)views.size() - 1)
+                return refuse(CM_EINVAL, "packed contigs out of order: record %zu is contig %d", views.size(), c.iv.contig_num + 1);
+            std::thread ahead([&]() {                            // (joined below, before anything it writes goes out of scope)
                 const double ta = now();
-                nxt_rc = cm_host_next_contig_genome(idx, &nxt_iv, &nxt_loaded);
-                lap("next contig sequence read (under the build)", ta);
+                nxt_rc = S.next(*this, &nxt, &nxt_loaded);
+                lap(S.lap_ahead, ta);
             });
             tl = now();
-            const int lrc = cm_build_contig(cm, (int)views.size() - 1, iv.contig_num, iv.genome, iv.ref_len, nullptr);
-            lap("contig uploaded, table built on the device + descriptors", tl);
-            cm_host_free_loaded_contig(&views.back());
+            const int lrc = S.load(*this, (int)views.size() - 1, c);
+            lap(S.lap_load, tl);
+            if (S.frees_host_copy) cm_host_free_loaded_contig(&views.back());
             ahead.join();
-            if (nxt_rc == CM_OK && nxt_loaded && lrc != CM_OK) cm_host_free_loaded_contig(&nxt_iv);
-            MAP_TRY(lrc, "cm_build_contig");
-        }
-    } else if (full) {
-        // full-format index: the table crosses PCIe as it is in the file and the device flattens it (cm_load_contig_raw); the
-        // host only reads and decodes the bucket headers -- of contig c + 1 while contig c uploads
-        cm_index_raw nxt_raw;
-        int nxt_loaded = 0, nxt_rc = CM_OK;
-        double tl = now();
-        nxt_rc = cm_host_next_contig_raw(idx, n_threads, &nxt_raw, &nxt_loaded);
-        lap("contig record read", tl);
-        for (;;) {
-            MAP_TRY(nxt_rc, "cm_host_next_contig_raw");
-            if (!nxt_loaded) break;
-            const cm_index_raw raw = nxt_raw;
-            cm_index_view iv;
-            memset(&iv, 0, sizeof iv);
-            iv.contig_num = raw.contig_num;
-            iv.ref_len = raw.ref_len;
-            views.push_back(iv);                                  // (lengths only: the arrays stay with the file handle)
-            if (iv.contig_num != (int32_t)views.size() - 1) {
-                rc = fail(CM_EINVAL, "packed contigs out of order: record %zu is contig %d", views.size(), iv.contig_num + 1);
-                cleanup();
-                return rc;
-            }
-            std::thread ahead([&]() {
-                const double ta = now();
-                nxt_rc = cm_host_next_contig_raw(idx, n_threads, &nxt_raw, &nxt_loaded);
-                lap("next contig record read (under the upload)", ta);
-            });
-            tl = now();
-            const int lrc = cm_load_contig_raw(cm, (int)views.size() - 1, &raw);
-            lap("contig uploaded, flattened on the device + descriptors", tl);
-            ahead.join();
-            MAP_TRY(lrc, "cm_load_contig_raw");
-        }
-    } else {
-        cm_index_view nxt_iv;
-        int nxt_loaded = 0, nxt_rc = CM_OK;
-        double tl = now();
-        nxt_rc = cm_host_next_contig(idx, n_threads, &nxt_iv, &nxt_loaded);
-        lap("contig decoded", tl);
-        for (;;) {
-            MAP_TRY(nxt_rc, "cm_host_next_contig");
-            if (!nxt_loaded) break;
-            cm_index_view iv = nxt_iv;
-            views.push_back(iv);
-            if (iv.contig_num != (int32_t)views.size() - 1) {
-                rc = fail(CM_EINVAL, "packed contigs out of order: record %zu is contig %d", views.size(), iv.contig_num + 1);
-                cleanup();
-                return rc;
-            }
-            std::thread ahead([&]() {
-                const double ta = now();
-                nxt_rc = cm_host_next_contig(idx, n_threads, &nxt_iv, &nxt_loaded);
-                lap("next contig decoded (under the upload)", ta);
-            });
-            tl = now();
-            const int lrc = cm_load_contig(cm, (int)views.size() - 1, &iv);
-            lap("contig uploaded + descriptors", tl);
-            // its host copy is dead now (everything is in HBM): returned to the system here, while the next contig is still being
-            // decoded, rather than in one 25-GB sweep next to the FASTQ parser's first page faults
-            cm_host_free_loaded_contig(&views.back());
-            ahead.join();
-            if (nxt_rc == CM_OK && nxt_loaded && lrc != CM_OK) cm_host_free_loaded_contig(&nxt_iv);
-            MAP_TRY(lrc, "cm_load_contig");
+            if (lrc == CM_OK) continue;
+            if (S.frees_host_copy && nxt_rc == CM_OK && nxt_loaded) cm_host_free_loaded_contig(&nxt.iv);
+            return failed(lrc, S.load_name);
         }
     }
-    const uint32_t n_con = (uint32_t)views.size();
-    if (n_con == 0) {
-        rc = fail(CM_EINVAL, "index file holds no contig");
-        cleanup();
-        return rc;
-    }
-    // ---- GTF (gtf_parser.init / load_gtf) ----
-    {
+    // ---- phase 4: GTF (gtf_parser.init / load_gtf) ----
+    int load_annotation() {
         std::vector<uint32_t> clen(n_con);
         for (uint32_t c = 0; c < n_con; ++c) clen[c] = views[c].ref_len;
         if (gtf_thread.joinable()) gtf_thread.join();
-        if (early_rc == CM_OK && clen == clen_guess) {
-            annots = annots_early;
-            rc = CM_OK;
-        } else {                                      // .index.info and the index file disagree on the contig lengths: the file decides
+        int rc = CM_OK;
+        if (early_rc == CM_OK && clen == clen_guess) annots.swap(annots_early);
+        else {                                        // .index.info and the index file disagree on the contig lengths: the file decides
             if (early_rc == CM_OK) cm_host_free_annotation(annots_early.data(), (uint32_t)annots_early.size());
+            annots_early.clear();
             annots.resize(n_con);
             const double tg = now();
             rc = cm_host_build_annotation(a->gtf_path, chrs, n_chr, clen.data(), n_con, P.max_read_len, annots.data());
@@ -304,12 +285,11 @@ extern "C" int cm_mapping_run(const cm_mapping_args *a, cm_mapping_stats *stats,
         }
         if (rc != CM_OK) {
             annots.clear();
-            rc = fail(rc, "cm_host_build_annotation failed (%d)", rc);
-            cleanup();
-            return rc;
+            return refuse(rc, "cm_host_build_annotation failed (%d)", rc);
         }
         const double tu = now();
-        for (uint32_t c = 0; c < n_con; ++c) MAP_TRY(cm_load_annotation(cm, (int)c, &annots[c]), "cm_load_annotation");
+        for (uint32_t c = 0; c < n_con; ++c)
+            if ((rc = cm_load_annotation(cm, (int)c, &annots[c])) != CM_OK) return failed(rc, "cm_load_annotation");
         lap("annotation uploaded", tu);
         views.clear();                                              // (their arrays went back after each upload)
         // everything is in HBM: the file handle's buffers (two sets of raw records on the full-format path, ~ 19 GB for hg38)
@@ -318,125 +298,189 @@ extern "C" int cm_mapping_run(const cm_mapping_args *a, cm_mapping_stats *stats,
         free_thread = std::thread([h = idx]() { cm_host_close_index(h); });
         idx = nullptr;
         lap("load done", t0);
-    }
-    st.rounds = (int32_t)n_con;
-    st.seconds_load = now() - t0;
-
-    // ---- outputs (FilterRead::init, src/filter.cpp:34-84; SAMOutput::init) ----
-    const std::string out = a->out_prefix;
-    if (a->report) {
-        const std::string path = out + (a->report == 2 ? ".mapping.sam" : ".mapping.pam") + part;
-        MAP_TRY(cm_writer_open(path.c_str(), nullptr, chrs, n_chr, &w_map), "cm_writer_open (mapping)");
-        if (a->report == 2 && rank == 0) MAP_TRY(cm_write_sam_header(w_map), "cm_write_sam_header");      // one header: rank 0's part comes first
-    }
-    {
-        const std::string r1 = out + "_" + std::to_string(n_con) + "_remain_R1.fastq" + part, r2 = out + "_" + std::to_string(n_con) + "_remain_R2.fastq" + part;
-        MAP_TRY(cm_writer_open(r1.c_str(), r2.c_str(), chrs, n_chr, &w_rem), "cm_writer_open (remain)");
-    }
-    MAP_TRY(cm_fastq_open_shard(a->fastq1, a->fastq2, chrs, n_chr, P.max_ed, rank, world, n_threads, &fq, nullptr, nullptr), "cm_fastq_open_shard");
-    void (*const release_fn)(void *, const void *, uint64_t) = [](void *user, const void *ptr, uint64_t bytes) {
-        Pinned *pn = (Pinned *)user;
-        std::lock_guard<std::mutex> lk(pn->mu);
-        const char *lo = (const char *)ptr, *hi = lo + bytes;
-        for (auto it = pn->v.begin(); it != pn->v.end();) {
-            const char *a0 = (const char *)it->first, *a1 = a0 + it->second;
-            if (a0 < hi && a1 > lo) {                         // a registration inside the block that is going
-                (void)cm_host_unregister(pn->cm, it->first);
-                it = pn->v.erase(it);
-            } else ++it;
-        }
-    };
-    cm_fastq_set_release_hook(fq, release_fn, &pin);
-
-    // ---- batches: write k-1 (worker) | rounds of k (device, driven by this thread) | H2D + first round of k+1 | parse k+2 (worker) ----
-    const double t1 = now();
-    std::vector<int> all(n_con);
-    for (uint32_t c = 0; c < n_con; ++c) all[c] = (int)c;
-    // page-lock the parser's arrays of a batch (they are reused every fourth batch; re-registered only when one has moved or grown)
-    auto pin_batch = [&](const cm_fastq_batch &b) -> int {
-        std::lock_guard<std::mutex> lk(pin.mu);
-        const uint64_t n = b.reads.n_pairs;
-        const void *ptr[4] = {b.reads.seq1, b.reads.seq2, b.reads.off1, b.reads.off2};
-        const uint64_t bytes[4] = {b.reads.off1[n], b.reads.off2[n], (n + 1) * sizeof(uint64_t), (n + 1) * sizeof(uint64_t)};
-        for (int j = 0; j < 4; ++j) {
-            if (!bytes[j]) continue;
-            bool have = false;
-            for (auto it = pinned.begin(); it != pinned.end();) {
-                const char *lo = (const char *)it->first, *hi = lo + it->second, *p = (const char *)ptr[j];
-                if (p >= lo && p + bytes[j] <= hi) {
-                    have = true;
-                    break;
-                }
-                if (p < hi && p + bytes[j] > lo) {                    // overlaps a stale registration: drop that one
-                    (void)cm_host_unregister(cm, it->first);
-                    it = pinned.erase(it);
-                } else ++it;
-            }
-            if (have) continue;
-            // (the parser reuses its four generations of arrays, so there are 16 live ranges; if they kept moving -- batches that
-            // keep growing -- stale registrations would pile up: past 64 the copies simply go through pageable staging)
-            if (pinned.size() >= 64) continue;
-            if (cm_host_register(cm, (void *)ptr[j], bytes[j]) == CM_OK) pinned.emplace_back((void *)ptr[j], bytes[j]);
-            // (a failed registration is not an error: the copy is then a staged pageable one)
-        }
+        st.rounds = (int32_t)n_con;
+        st.seconds_load = now() - t0;
         return CM_OK;
-    };
-    // page-lock [p, p + bytes); a registration it overlaps (the same buffer, handed out at another offset) is widened to cover both
-    auto pin_range = [&](const void *p0, uint64_t bytes) {
-        std::lock_guard<std::mutex> lk(pin.mu);
-        const char *lo = (const char *)p0, *hi = lo + bytes;
-        if (!bytes) return;
-        for (auto it = pinned.begin(); it != pinned.end();) {
-            const char *a0 = (const char *)it->first, *a1 = a0 + it->second;
-            if (lo >= a0 && hi <= a1) return;
-            if (lo < a1 && hi > a0) {
-                lo = std::min(lo, a0);
-                hi = std::max(hi, a1);
-                (void)cm_host_unregister(cm, it->first);
-                it = pinned.erase(it);
-            } else ++it;
+    }
+    // ---- phase 5: outputs (FilterRead::init, src/filter.cpp:34-84; SAMOutput::init), the reader, and which of the two feeds it is ----
+    int open_reader() {
+        const int rc = cm_fastq_open_shard(a->fastq1, a->fastq2, chrs, n_chr, P.max_ed, rank, world, n_threads, &fq, nullptr, nullptr);
+        if (rc != CM_OK) return failed(rc, "cm_fastq_open_shard");
+        cm_fastq_set_release_hook(fq, [](void *user, const void *ptr, uint64_t bytes) { ((PinnedRanges *)user)->release(ptr, bytes); }, &pins);
+        return CM_OK;
+    }
+    int open_outputs_and_reader() {
+        const std::string out = a->out_prefix;
+        int rc;
+        if (a->report) {
+            const std::string path = out + (a->report == 2 ? ".mapping.sam" : ".mapping.pam") + part;
+            if ((rc = cm_writer_open(path.c_str(), nullptr, chrs, n_chr, &w_map)) != CM_OK) return failed(rc, "cm_writer_open (mapping)");
+            // one header: rank 0's part comes first
+            if (a->report == 2 && rank == 0 && (rc = cm_write_sam_header(w_map)) != CM_OK) return failed(rc, "cm_write_sam_header");
         }
-        if (pinned.size() >= 64) return;
-        if (cm_host_register(cm, (void *)lo, (uint64_t)(hi - lo)) == CM_OK) pinned.emplace_back((void *)lo, (uint64_t)(hi - lo));
-    };
-    // ---- the device-side tokeniser's path (opt-in): read k+2 (worker) | stage k+1 | rounds of k (+ its PAM rows with CM_PAM_DEVICE=1)
-    //      | write k-1 (worker) ----
-    bool text_path = false, pam_device = false;
-    {
-        const char *e = getenv("CM_FASTQ_DEVICE");
-        const char *ep = getenv("CM_PAM_DEVICE");
+        const std::string r1 = out + "_" + std::to_string(n_con) + "_remain_R1.fastq" + part, r2 = out + "_" + std::to_string(n_con) + "_remain_R2.fastq" + part;
+        if ((rc = cm_writer_open(r1.c_str(), r2.c_str(), chrs, n_chr, &w_rem)) != CM_OK) return failed(rc, "cm_writer_open (remain)");
+        if ((rc = open_reader()) != CM_OK) return rc;
+        t1 = now();
+        all.resize(n_con);
+        for (uint32_t c = 0; c < n_con; ++c) all[c] = (int)c;
+        return choose_text_path();
+    }
+    // The device-side tokeniser's path is opt-in and falls back to the host parser, for the run, where that one is needed.
+    int choose_text_path() {
+        const char *e = getenv("CM_FASTQ_DEVICE"), *ep = getenv("CM_PAM_DEVICE");
         pam_device = a->report == 1 && ep && atoi(ep) == 1;      // the rows of report 1 formatted on the device: needs the text path
         text_path = e && atoi(e) == 1 && (a->report == 0 || pam_device);
-    }
-    struct TextBlock {
-        const uint8_t *t1 = nullptr, *t2 = nullptr;
-        uint64_t l1 = 0, l2 = 0;
-        int e1 = 0, e2 = 0;
-        cm_text_batch tb{};
-        std::vector<uint64_t> rec1, rec2;
-    } tq[4];                                                    // block k in tq[k & 3]: its text is the reader's for three more reads
-    // bytes per file and block: what batch_pairs records take, first by a guess (a 150-bp record with its name and qualities is
-    // ~ 350 bytes), then by what the records of the last batch took -- a block that holds much more than a batch only grows the tail
-    uint64_t want = batch_pairs * 400 + (1u << 16);
-    bool want_fixed = false;
-    if (const char *e = getenv("CM_FASTQ_DEVICE_BLOCK")) {
-        const unsigned long long v = strtoull(e, nullptr, 10);
-        if (v >= 16) {
-            want = v;
-            want_fixed = true;
+        // bytes per file and block: what batch_pairs records take, first by a guess (a 150-bp record with its name and qualities is
+        // ~ 350 bytes), then by what the records of the last batch took -- a block that holds much more than a batch only grows the tail
+        want = batch_pairs * 400 + (1u << 16);
+        if (const char *eb = getenv("CM_FASTQ_DEVICE_BLOCK")) {
+            const unsigned long long v = strtoull(eb, nullptr, 10);
+            if (v >= 16) {
+                want = v;
+                want_fixed = true;
+            }
         }
+        if (!text_path) return CM_OK;
+        const int rc = read_block(tq[0], want);
+        if (rc != CM_OK && rc != CM_EINVAL) return failed(rc, "cm_fastq_next_text");
+        if (rc == CM_EINVAL) return text_path = false, CM_OK;    // gzip input or a pipe: the host parser's
+        // a carried state in the first R1 header (23 tokens): the host parser's, on a reader opened anew
+        const uint8_t *p = tq[0].t1, *nl = tq[0].l1 ? (const uint8_t *)memchr(p, '\n', tq[0].l1) : nullptr;
+        int nt = 0;
+        bool in = false;
+        for (const uint8_t *q = p + 1; nl && q < nl; ++q) {
+            nt += (*q != ' ' && !in) ? 1 : 0;
+            in = *q != ' ';
+        }
+        if (nt != 23) return CM_OK;
+        text_path = false;
+        cm_fastq_close(fq);
+        fq = nullptr;
+        return open_reader();
     }
-    auto read_block = [&](TextBlock &B, uint64_t bytes) { return cm_fastq_next_text(fq, bytes, &B.t1, &B.l1, &B.e1, &B.t2, &B.l2, &B.e2); };
+
+    // ---- phase 6: batches: write k-1 (worker) | rounds of k (device, driven by this thread) | H2D + first round of k+1 | parse k+2 (worker) ----
+    // The steps both feeds share.  Parser: started for batch k+2 if there is one to come, joined at the end of batch k's turn.
+    void start_parser(bool more, std::function<int()> job) {
+        parser_rc = CM_OK;
+        parse_s = 0.0;
+        if (more)
+            parser = std::thread([this, job]() {
+                const double tp = now();
+                parser_rc = job();
+                parse_s = now() - tp;
+            });
+    }
+    int join_parser(const char *name) {
+        if (parser.joinable()) parser.join();
+        st.seconds_parse += parse_s;
+        return parser_rc == CM_OK ? CM_OK : failed(parser_rc, name);
+    }
+    // the rows of batch k-1 are out (file order = batch order); those of batch k, if there is a job, go to a writer of their own
+    int hand_to_writer(std::function<int()> job) {
+        if (writer.joinable()) writer.join();
+        if (writer_rc != CM_OK) return failed(writer_rc, "writer");
+        if (job)
+            writer = std::thread([this, job]() {
+                const double tw = now();
+                writer_rc = job();
+                write_s += now() - tw;
+            });
+        return CM_OK;
+    }
+    // report 0: only the (pair, state) records of the re-queued pairs and the type histogram leave the device
+    int collect_records(Result &R, uint64_t n) {
+        int rc;
+        if (R.recs.size() < n) R.recs.resize(n);
+        if ((rc = cm_collect_records(cm, 0, n, R.recs.data(), &R.n_rec)) != CM_OK) return failed(rc, "cm_collect_records");
+        uint64_t h[14];
+        if ((rc = cm_type_histogram(cm, h)) != CM_OK) return failed(rc, "cm_type_histogram");
+        for (int t = 0; t < 14; ++t) st.by_type[t] += h[t];
+        return CM_OK;
+    }
+    // batch k's results are on the host: the staged batch becomes the resident one, and the books
+    int end_device_leg(const Result &R, uint64_t n, bool more, double td) {
+        const int rc = more ? cm_reads_swap(cm) : CM_OK;
+        if (rc != CM_OK) return failed(rc, "cm_reads_swap");
+        st.seconds_device += now() - td;
+        st.pairs += n;
+        st.bsj_pairs += R.n_rec;
+        return CM_OK;
+    }
+    // page-lock the parser's arrays of a batch (they are reused every fourth batch; re-registered only when one has moved or grown)
+    int stage_batch(const cm_fastq_batch &b) {
+        const uint64_t n = b.reads.n_pairs;
+        pins.cover(b.reads.seq1, b.reads.off1[n]);
+        pins.cover(b.reads.seq2, b.reads.off2[n]);
+        pins.cover(b.reads.off1, (n + 1) * sizeof(uint64_t));
+        pins.cover(b.reads.off2, (n + 1) * sizeof(uint64_t));
+        const int rc = cm_reads_stage(cm, &b.reads, b.prior);
+        return rc == CM_OK ? CM_OK : failed(rc, "cm_reads_stage");
+    }
+    int host_batches() {
+        int rc;
+        const double tp = now();
+        if ((rc = cm_fastq_next(fq, batch_pairs, &cur)) != CM_OK) return failed(rc, "cm_fastq_next");
+        if (cur.reads.n_pairs && (rc = cm_fastq_next(fq, batch_pairs, &nxt)) != CM_OK) return failed(rc, "cm_fastq_next");
+        st.seconds_parse += now() - tp;
+        if (cur.reads.n_pairs) {
+            if ((rc = stage_batch(cur)) != CM_OK) return rc;
+            if ((rc = cm_reads_swap(cm)) != CM_OK) return failed(rc, "cm_reads_swap");
+        }
+        for (uint64_t k = 0; cur.reads.n_pairs; ++k) {
+            const uint64_t n = cur.reads.n_pairs;
+            Result &R = res[k & 1];
+            const bool more = nxt.reads.n_pairs != 0;
+            memset(&nn, 0, sizeof nn);
+            start_parser(more, [this]() { return cm_fastq_next(fq, batch_pairs, &nn); });
+            const double td = now();
+            if (more && (rc = stage_batch(nxt)) != CM_OK) return rc;
+            if ((rc = cm_map_rounds(cm, all.data(), (int)n_con, 1)) != CM_OK) return failed(rc, "cm_map_rounds");          // round r + 1 seeds while r pairs
+            // results of batch k: rows of every pair (PAM / SAM) or just the re-queued pairs' records
+            if (a->report) {
+                R.state.resize(n);
+                R.active.resize(n);
+                if ((rc = cm_reads_download(cm, R.state.data(), nullptr, R.active.data())) != CM_OK) return failed(rc, "cm_reads_download");
+                R.sel.clear();
+                for (uint64_t i = 0; i < n; ++i) {
+                    if (R.active[i]) R.sel.push_back(i);
+                    const int t = R.state[i].type;
+                    if (t >= 0 && t < 14) ++st.by_type[t];
+                }
+                R.n_rec = R.sel.size();
+            } else if ((rc = collect_records(R, n)) != CM_OK) return rc;
+            if ((rc = end_device_leg(R, n, more, td)) != CM_OK) return rc;
+            R.batch = cur;
+            // map_reads, src/circminer.cpp:386-397: printed if (skip || last round) = every pair by now;
+            // written to the remain files if still active after the last round = CHIBSJ / CHI2BSJ
+            rc = hand_to_writer([this, &R]() {
+                int r = CM_OK;
+                if (a->report == 1) r = cm_write_pam(w_map, &R.batch, R.state.data(), nullptr, 0);
+                if (a->report == 2) r = cm_write_sam(w_map, &R.batch, R.state.data(), nullptr, 0);
+                if (r != CM_OK || !R.n_rec) return r;
+                return a->report ? cm_write_remain(w_rem, &R.batch, R.state.data(), R.sel.data(), R.sel.size())
+                                 : cm_write_remain_records(w_rem, &R.batch, R.recs.data(), R.n_rec);
+            });
+            if (rc != CM_OK || (rc = join_parser("cm_fastq_next")) != CM_OK) return rc;
+            cur = nxt;
+            nxt = nn;
+        }
+        return CM_OK;
+    }
+
+    // ---- the device-side tokeniser's feed: read k+2 (worker) | stage k+1 | rounds of k (+ its PAM rows with CM_PAM_DEVICE=1) | write k-1 (worker) ----
+    int read_block(TextBlock &B, uint64_t bytes) { return cm_fastq_next_text(fq, bytes, &B.t1, &B.l1, &B.e1, &B.t2, &B.l2, &B.e2); }
     // block -> staged batch; B.tb.n_pairs == 0: the input is at its end.  A block that holds no whole pair is read again, larger.
-    auto stage_block = [&](TextBlock &B) -> int {
+    int stage_block(TextBlock &B) {
         uint64_t bytes = want;
         for (;;) {
             memset(&B.tb, 0, sizeof B.tb);
             if (B.l1 == 0 && B.e1) return CM_OK;                 // R1 is through (what is left of R2 is surplus)
             B.rec1.resize(batch_pairs + 1);
             B.rec2.resize(batch_pairs + 1);
-            pin_range(B.t1, B.l1);
-            pin_range(B.t2, B.l2);
+            pins.cover(B.t1, B.l1);                              // (the same buffer handed out at another offset: widened to cover both)
+            pins.cover(B.t2, B.l2);
             int r = cm_reads_stage_text(cm, B.t1, B.l1, B.t2, B.l2, batch_pairs, (B.e1 ? 1u : 0u) | (B.e2 ? 2u : 0u) | (pam_device ? 4u : 0u), B.rec1.data(), B.rec2.data(), &B.tb);
             if (r != CM_OK) return r;
             if (B.tb.n_pairs) {
@@ -447,40 +491,45 @@ extern "C" int cm_mapping_run(const cm_mapping_args *a, cm_mapping_stats *stats,
             bytes *= 2;
             if ((r = cm_fastq_text_consumed(fq, 0, 0)) != CM_OK || (r = read_block(B, bytes)) != CM_OK) return r;
         }
-    };
-    if (text_path) {
-        const int r = read_block(tq[0], want);
-        if (r == CM_EINVAL) text_path = false;                   // gzip input or a pipe: the host parser's
-        else MAP_TRY(r, "cm_fastq_next_text");
     }
-    if (text_path) {                                             // a carried state in the first R1 header: the host parser's, for the run
-        const uint8_t *p = tq[0].t1, *nl = tq[0].l1 ? (const uint8_t *)memchr(p, '\n', tq[0].l1) : nullptr;
-        int nt = 0;
-        bool in = false;
-        for (const uint8_t *q = p + 1; nl && q < nl; ++q) {
-            nt += (*q != ' ' && !in) ? 1 : 0;
-            in = *q != ' ';
+    // The PAM rows of the resident batch's n pairs, in ranges: a range whose rows would not fit 32-bit offsets is halved, a buffer that
+    // is too small is replaced by one that holds what is there plus what the device asks for.
+    int format_rows(RowBuf &RB, uint64_t n) {
+        uint64_t done = 0, step = std::min<uint64_t>(n, 1ull << 22);
+        while (done < n) {
+            const uint64_t c = std::min(step, n - done);
+            uint64_t got = 0;
+            int r = cm_format_pam(cm, chrs, n_chr, done, c, RB.p ? (char *)RB.p + RB.n : nullptr, RB.cap - RB.n, &got, nullptr);
+            if (r == CM_ELIMIT && got >= (1ull << 32) && c > 1) {
+                step = c / 2;
+                continue;
+            }
+            if (r == CM_ELIMIT && got > RB.cap - RB.n) {
+                const uint64_t cap = RB.n + got + got / c * (n - done - c) + (1u << 16);
+                void *np = nullptr;
+                if ((r = cm_host_alloc(cm, cap, &np)) != CM_OK) return failed(r, "cm_host_alloc (PAM rows)");
+                if (RB.n) memcpy(np, RB.p, RB.n);
+                if (RB.p) (void)cm_host_free(cm, RB.p);
+                RB.p = np;
+                RB.cap = cap;
+                continue;
+            }
+            if (r != CM_OK) return failed(r, "cm_format_pam");
+            RB.n += got;
+            done += c;
         }
-        if (nt == 23) {
-            text_path = false;
-            cm_fastq_close(fq);
-            fq = nullptr;
-            MAP_TRY(cm_fastq_open_shard(a->fastq1, a->fastq2, chrs, n_chr, P.max_ed, rank, world, n_threads, &fq, nullptr, nullptr), "cm_fastq_open_shard");
-            cm_fastq_set_release_hook(fq, release_fn, &pin);
-        }
+        return CM_OK;
     }
-    if (text_path) {
-        double write_s = 0.0;
+    int text_batches() {
+        int rc;
         bool more = false;
-        {
-            const double td = now();
-            MAP_TRY(stage_block(tq[0]), "cm_reads_stage_text");
-            st.seconds_device += now() - td;
-        }
+        const double td0 = now();
+        if ((rc = stage_block(tq[0])) != CM_OK) return failed(rc, "cm_reads_stage_text");
+        st.seconds_device += now() - td0;
         if (tq[0].tb.n_pairs) {
-            MAP_TRY(cm_reads_swap(cm), "cm_reads_swap");
+            if ((rc = cm_reads_swap(cm)) != CM_OK) return failed(rc, "cm_reads_swap");
             const double tp = now();
-            MAP_TRY(read_block(tq[1], want), "cm_fastq_next_text");
+            if ((rc = read_block(tq[1], want)) != CM_OK) return failed(rc, "cm_fastq_next_text");
             st.seconds_parse += now() - tp;
             more = true;
         }
@@ -489,175 +538,51 @@ extern "C" int cm_mapping_run(const cm_mapping_args *a, cm_mapping_stats *stats,
             const uint64_t n = B.tb.n_pairs;
             ++st.device_parsed_batches;
             Result &R = res[k & 1];
-            double parse_s = 0.0;
-            parser_rc = CM_OK;
+            RowBuf &RB = rows[k & 1];
             const double td = now();
             if (more) {
-                MAP_TRY(stage_block(N), "cm_reads_stage_text");
+                if ((rc = stage_block(N)) != CM_OK) return failed(rc, "cm_reads_stage_text");
                 more = N.tb.n_pairs != 0;
             } else memset(&N.tb, 0, sizeof N.tb);
-            if (more)
-                parser = std::thread([&]() {
-                    const double tp = now();
-                    parser_rc = read_block(tq[(k + 2) & 3], want);
-                    parse_s = now() - tp;
-                });
-            MAP_TRY(cm_map_rounds(cm, all.data(), (int)n_con, 1), "cm_map_rounds");
-            RowBuf &RB = rows[k & 1];
+            start_parser(more, [this, k]() { return read_block(tq[(k + 2) & 3], want); });
+            if ((rc = cm_map_rounds(cm, all.data(), (int)n_con, 1)) != CM_OK) return failed(rc, "cm_map_rounds");
             RB.n = 0;
-            if (pam_device) {
-                // the rows of the batch, in ranges: a range whose rows would not fit 32-bit offsets is halved, a buffer that is too
-                // small is replaced by one that holds what is there plus what the device asks for
-                uint64_t done = 0, step = std::min<uint64_t>(n, 1ull << 22);
-                while (done < n) {
-                    const uint64_t c = std::min(step, n - done);
-                    uint64_t got = 0;
-                    const int r = cm_format_pam(cm, chrs, n_chr, done, c, RB.p ? (char *)RB.p + RB.n : nullptr, RB.cap - RB.n, &got, nullptr);
-                    if (r == CM_ELIMIT && got >= (1ull << 32) && c > 1) {
-                        step = c / 2;
-                        continue;
-                    }
-                    if (r == CM_ELIMIT && got > RB.cap - RB.n) {
-                        const uint64_t cap = RB.n + got + got / c * (n - done - c) + (1u << 16);
-                        void *np = nullptr;
-                        MAP_TRY(cm_host_alloc(cm, cap, &np), "cm_host_alloc (PAM rows)");
-                        if (RB.n) memcpy(np, RB.p, RB.n);
-                        if (RB.p) (void)cm_host_free(cm, RB.p);
-                        RB.p = np;
-                        RB.cap = cap;
-                        continue;
-                    }
-                    MAP_TRY(r, "cm_format_pam");
-                    RB.n += got;
-                    done += c;
-                }
-            }
-            uint64_t n_rec = 0;
-            if (R.recs.size() < n) R.recs.resize(n);
-            MAP_TRY(cm_collect_records(cm, 0, n, R.recs.data(), &n_rec), "cm_collect_records");
-            uint64_t h[14];
-            MAP_TRY(cm_type_histogram(cm, h), "cm_type_histogram");
-            for (int t = 0; t < 14; ++t) st.by_type[t] += h[t];
-            R.n_rec = n_rec;
-            if (more) MAP_TRY(cm_reads_swap(cm), "cm_reads_swap");
-            st.seconds_device += now() - td;
-            st.pairs += n;
-            st.bsj_pairs += n_rec;
-            if (writer.joinable()) writer.join();                    // rows of batch k-1 are out: file order = batch order
-            MAP_TRY(writer_rc, "writer");
-            writer = std::thread([&R, &B, &RB, &writer_rc, &write_s, w_map, w_rem, pam_device]() {
-                const double tw = now();
-                int r = pam_device ? cm_write_bytes(w_map, RB.p, RB.n) : CM_OK;
-                if (r == CM_OK && R.n_rec) r = cm_write_remain_text(w_rem, B.t1, B.rec1.data(), B.t2, B.rec2.data(), R.recs.data(), R.n_rec);
-                writer_rc = r;
-                write_s += now() - tw;
+            if (pam_device && (rc = format_rows(RB, n)) != CM_OK) return rc;
+            if ((rc = collect_records(R, n)) != CM_OK || (rc = end_device_leg(R, n, more, td)) != CM_OK) return rc;
+            rc = hand_to_writer([this, &R, &B, &RB]() {
+                const int r = pam_device ? cm_write_bytes(w_map, RB.p, RB.n) : CM_OK;
+                if (r != CM_OK || !R.n_rec) return r;
+                return cm_write_remain_text(w_rem, B.t1, B.rec1.data(), B.t2, B.rec2.data(), R.recs.data(), R.n_rec);
             });
-            if (parser.joinable()) parser.join();
-            st.seconds_parse += parse_s;
-            MAP_TRY(parser_rc, "cm_fastq_next_text");
+            if (rc != CM_OK || (rc = join_parser("cm_fastq_next_text")) != CM_OK) return rc;
         }
-        if (writer.joinable()) writer.join();
-        MAP_TRY(writer_rc, "writer");
-        if (w_map) MAP_TRY(cm_writer_flush(w_map), "writing the mapping file");
-        MAP_TRY(cm_writer_flush(w_rem), "writing the remain files");
+        return CM_OK;
+    }
+    // ---- phase 7: the last rows, and the books (a full disk is an error, not a short file) ----
+    int finish(cm_mapping_stats *stats) {
+        int rc;
+        if ((rc = hand_to_writer(nullptr)) != CM_OK) return rc;
+        if (w_map && (rc = cm_writer_flush(w_map)) != CM_OK) return failed(rc, "writing the mapping file");
+        if ((rc = cm_writer_flush(w_rem)) != CM_OK) return failed(rc, "writing the remain files");
         st.seconds_map = now() - t1;
         st.seconds_write = write_s;
-        cleanup();
         if (stats) *stats = st;
         return CM_OK;
     }
-    cm_fastq_batch cur, nxt, nn;
-    memset(&nxt, 0, sizeof nxt);
-    memset(&nn, 0, sizeof nn);
-    double write_s = 0.0;                                       // written by the writer thread, read after its join
-    {
-        const double tp = now();
-        MAP_TRY(cm_fastq_next(fq, batch_pairs, &cur), "cm_fastq_next");
-        if (cur.reads.n_pairs) MAP_TRY(cm_fastq_next(fq, batch_pairs, &nxt), "cm_fastq_next");
-        st.seconds_parse += now() - tp;
-    }
-    if (cur.reads.n_pairs) {
-        pin_batch(cur);
-        MAP_TRY(cm_reads_stage(cm, &cur.reads, cur.prior), "cm_reads_stage");
-        MAP_TRY(cm_reads_swap(cm), "cm_reads_swap");
-    }
-    for (uint64_t k = 0; cur.reads.n_pairs; ++k) {
-        const uint64_t n = cur.reads.n_pairs;
-        Result &R = res[k & 1];
-        double parse_s = 0.0;
-        const bool more = nxt.reads.n_pairs != 0;
-        parser_rc = CM_OK;
-        memset(&nn, 0, sizeof nn);
-        if (more)
-            parser = std::thread([&]() {
-                const double tp = now();
-                parser_rc = cm_fastq_next(fq, batch_pairs, &nn);
-                parse_s = now() - tp;
-            });
-        const double td = now();
-        if (more) {
-            pin_batch(nxt);
-            MAP_TRY(cm_reads_stage(cm, &nxt.reads, nxt.prior), "cm_reads_stage");
-        }
-        MAP_TRY(cm_map_rounds(cm, all.data(), (int)n_con, 1), "cm_map_rounds");          // round r + 1 seeds while r pairs
-        // results of batch k: rows of every pair (PAM / SAM) or just the re-queued pairs' records
-        uint64_t n_rec = 0;
-        if (a->report) {
-            R.state.resize(n);
-            R.active.resize(n);
-            MAP_TRY(cm_reads_download(cm, R.state.data(), nullptr, R.active.data()), "cm_reads_download");
-            R.sel.clear();
-            for (uint64_t i = 0; i < n; ++i) {
-                if (R.active[i]) R.sel.push_back(i);
-                const int t = R.state[i].type;
-                if (t >= 0 && t < 14) ++st.by_type[t];
-            }
-            n_rec = R.sel.size();
-        } else {
-            if (R.recs.size() < n) R.recs.resize(n);
-            MAP_TRY(cm_collect_records(cm, 0, n, R.recs.data(), &n_rec), "cm_collect_records");
-            uint64_t h[14];
-            MAP_TRY(cm_type_histogram(cm, h), "cm_type_histogram");
-            for (int t = 0; t < 14; ++t) st.by_type[t] += h[t];
-        }
-        R.n_rec = n_rec;
-        if (more) MAP_TRY(cm_reads_swap(cm), "cm_reads_swap");
-        st.seconds_device += now() - td;
-        st.pairs += n;
-        st.bsj_pairs += n_rec;
-        R.batch = cur;
-        if (writer.joinable()) writer.join();                    // rows of batch k-1 are out: file order = batch order
-        MAP_TRY(writer_rc, "writer");
-        // map_reads, src/circminer.cpp:386-397: printed if (skip || last round) = every pair by now;
-        // written to the remain files if still active after the last round = CHIBSJ / CHI2BSJ
-        writer = std::thread([&R, &writer_rc, &write_s, w_map, w_rem, report = a->report]() {
-            const double tw = now();
-            int r = CM_OK;
-            if (report == 1) r = cm_write_pam(w_map, &R.batch, R.state.data(), nullptr, 0);
-            if (report == 2) r = cm_write_sam(w_map, &R.batch, R.state.data(), nullptr, 0);
-            if (r == CM_OK && R.n_rec) {
-                if (report) r = cm_write_remain(w_rem, &R.batch, R.state.data(), R.sel.data(), R.sel.size());
-                else r = cm_write_remain_records(w_rem, &R.batch, R.recs.data(), R.n_rec);
-            }
-            writer_rc = r;
-            write_s += now() - tw;
-        });
-        if (parser.joinable()) parser.join();
-        st.seconds_parse += parse_s;
-        MAP_TRY(parser_rc, "cm_fastq_next");
-        cur = nxt;
-        nxt = nn;
-    }
-    if (writer.joinable()) writer.join();
-    MAP_TRY(writer_rc, "writer");
-    if (w_map) MAP_TRY(cm_writer_flush(w_map), "writing the mapping file");          // a full disk is an error, not a short file
-    MAP_TRY(cm_writer_flush(w_rem), "writing the remain files");
-    st.seconds_map = now() - t1;
-    st.seconds_write = write_s;
-    cleanup();
-    if (stats) *stats = st;
-    return CM_OK;
-#undef MAP_TRY
+};
+
+}  // namespace
+
+extern "C" int cm_mapping_run(const cm_mapping_args *a, cm_mapping_stats *stats, char *err, uint64_t err_cap) {
+    Run run(a, err, err_cap);
+    int rc;
+    if ((rc = run.check_args()) == CM_OK && (rc = run.open_index()) == CM_OK && (rc = run.load_contigs()) == CM_OK &&
+        (rc = run.load_annotation()) == CM_OK && (rc = run.open_outputs_and_reader()) == CM_OK &&
+        (rc = run.text_path ? run.text_batches() : run.host_batches()) == CM_OK)
+        rc = run.finish(stats);
+    // a call that failed is named here, with what the context says of it, while there still is a context; ~Run releases the rest
+    if (rc != CM_OK && run.what) run.refuse(rc, "%s failed (%d)%s%s", run.what, rc, run.cm ? ": " : "", run.cm ? cm_last_error(run.cm) : "");
+    return rc;
 }
 
 extern "C" int cm_merge_parts(const char *out_prefix, int32_t rounds, int32_t world, int32_t report) {

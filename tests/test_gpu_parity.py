@@ -518,7 +518,7 @@ def test_stage1_from_files_to_files(preset, contig_size, report, tmp_path):
     from the CPU oracle's final states through the Python restatements of the writers (tests/test_fastq_io.py)."""
     import gzip
     from circminer_amd import synth
-    from test_fastq_io import py_pam_row, py_remain_header, py_sam_rows
+    from mapping_files_util import expected_mapping_rows, expected_remain_lines
     n = 3000
     d = synth.generate(preset, n_pairs=n, seed=33)
     fa = str(tmp_path / "ref.fa")
@@ -557,23 +557,23 @@ def test_stage1_from_files_to_files(preset, contig_size, report, tmp_path):
     s2 = [d.seq2[i].tobytes().decode() for i in range(n)]
     if report == 1:
         rows = open(out + ".mapping.pam").read().split("\n")
-        assert rows[-1] == "" and rows[:-1] == [py_pam_row(names[i], want[i], chrs) for i in range(n)]
+        assert rows[-1] == "" and rows[:-1] == expected_mapping_rows(1, names, want, chrs)
     else:
         rows = open(out + ".mapping.sam").read().split("\n")
         hdr = 1 + len(chrs)
         assert rows[0].startswith("@HD") and [r.split("\t")[1] for r in rows[1:hdr]] == [f"SN:{c[0]}" for c in chrs]
-        exp = []
-        for i in range(n):
-            exp += py_sam_rows(names[i], want[i], chrs, s1[i], quals[i % 16], s2[i], quals[i % 16])
+        q = [quals[i % 16] for i in range(n)]
+        exp = expected_mapping_rows(2, names, want, chrs, s1, q, s2, q)
         assert rows[hdr:-1] == exp
     keep = np.nonzero(act)[0]
     assert set(want["type"][keep]) <= {3, 4}
     for mate, seqs in ((1, s1), (2, s2)):
         lines = open(f"{out}_{hi.n_contigs}_remain_R{mate}.fastq").read().split("\n")
+        exp = expected_remain_lines(names, want, keep, chrs, seqs, [quals[i % 16] for i in range(n)])
         assert lines[-1] == "" and len(lines) == 4 * len(keep) + 1
         for k, i in enumerate(keep):
-            assert lines[4 * k] == py_remain_header(names[i], want[i], chrs)
-            assert lines[4 * k + 1:4 * k + 4] == [seqs[i], "+", quals[i % 16]]
+            assert lines[4 * k] == exp[4 * k]
+            assert lines[4 * k + 1:4 * k + 4] == exp[4 * k + 1:4 * k + 4] == [seqs[i], "+", quals[i % 16]]
     # stage 2 on the files the device path just wrote (cm_circ_run = circ_detect): candidates.pam and circ_report equal the
     # oracle's restatement of ProcessCirc fed with the GNU-sorted remain files
     from stage2_util import gnu_sort, oracle_stage2

@@ -121,6 +121,16 @@ def test_device_allocation_list_over_malloc(tmp_path):
     assert subprocess.check_output([exe], text=True).strip() == "devlist: 0 mismatches, 0 blocks live"
 
 
+def test_pinned_ranges_over_a_fake_runtime(tmp_path):
+    """PinnedRanges (cm_pinned_ranges.h), the owner of cm_mapping_run's page-locked ranges, over a fake register / unregister that
+    keeps its own set of live ranges: growing batch arrays, widened text blocks, a block with two registrations, the cap of 64, a
+    refused registration, a failed unregistration, release from a second thread -- the program checks the invariants after every call"""
+    exe = str(tmp_path / "pinned")
+    subprocess.check_call(["g++", "-O1", "-std=c++17", "-pthread", "-I", os.path.join(ROOT, "circminer_amd", "csrc"),
+                           os.path.join(ROOT, "tests", "diag", "pinned_san_main.cpp"), "-o", exe])
+    assert subprocess.check_output([exe], text=True).strip() == "0 mismatches"
+
+
 def _write_packed(tmp_path):
     """a FASTA of two chromosomes with lower-case and IUPAC letters, packed into two contigs"""
     rng = np.random.default_rng(3)
@@ -181,6 +191,42 @@ def test_mapping_run_on_a_packed_fasta_needs_k(built, tmp_path):
     st, err = cl.MappingStats(), C.create_string_buffer(512)
     assert L.cm_mapping_run(C.byref(a), C.byref(st), err, len(err)) == -1
     assert b"packed FASTA" in err.value and b"kmer" in err.value
+
+
+def test_mapping_run_refusals_before_any_device(built, tmp_path):
+    """what cm_mapping_run refuses before it creates a context, each with its code and message, each followed by another refusal
+    in the same process (a clean-up that frees twice would show): null path, report 3, rank 2 of 2, k of the index file against
+    params.kmer, a missing index file, a missing .index.info"""
+    L = cl.load()
+    packed, info = _write_packed(tmp_path)
+    idx = cl.write_index(packed, kmer=20, n_threads=2)
+    gtf = str(tmp_path / "a.gtf")
+    open(gtf, "w").write("")
+    out = str(tmp_path / "out").encode()
+
+    def run(index=idx.encode(), index_info=None, gtf_path=gtf.encode(), kmer=0, report=1, rank=0, world=1):
+        a = cl.MappingArgs(index, index_info or (index or b"") + b".info", gtf_path, b"/nonexistent_1.fq", b"/nonexistent_2.fq", out,
+                           cl.default_params(kmer=kmer), report, 2, 0, rank, world)
+        st, err = cl.MappingStats(), C.create_string_buffer(512)
+        rc = L.cm_mapping_run(C.byref(a), C.byref(st), err, len(err))
+        return rc, err.value
+
+    k_mismatch = (-1, b"index was built for k = 20, params ask for k = 18")
+    cases = [
+        (dict(gtf_path=None), (-1, b"cm_mapping_run: null argument")),
+        (dict(kmer=18), k_mismatch),
+        (dict(report=3), (-1, b"report must be 0 (none), 1 (PAM) or 2 (SAM)")),
+        (dict(index=(idx + ".nope").encode(), index_info=(idx + ".info").encode()), (-1, b"cm_host_open_index failed (-1)")),
+        (dict(rank=2, world=2), (-1, b"rank 2 of 2")),
+        (dict(index_info=(idx + ".nope.info").encode()), (-1, b"cm_host_read_index_info failed (-1)")),
+        (dict(kmer=18), k_mismatch),
+        (dict(index=packed.encode(), index_info=info.encode()), (-1, b"is a packed FASTA, not an index file")),
+    ]
+    for kw, (rc, msg) in cases:
+        got = run(**kw)
+        assert got[0] == rc and msg in got[1], (kw, got)
+    assert L.cm_mapping_run(None, None, None, 0) == -1                  # no arguments, no room for a message
+    assert run(kmer=18) == k_mismatch
 
 
 def test_new_names_agree_between_header_library_and_binding(built):
