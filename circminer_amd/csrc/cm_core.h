@@ -2718,4 +2718,80 @@ inline long long dp_req_check(const cm_params &P, uint64_t arena_len, const cm_d
     return 0;
 }
 
+// ------------------------------------------------------------------------------------------
+// Test hook (cm_annot_batch: k_annot_probe in cm_annot_probe.hip; emu_annot_batch in tests/hostemu.cpp;
+// tests/diag/annot_san_main.cpp): one cm_annot_req through the annotation look-up its kind names (table in
+// circminer_hot.h).  tids: the request's own 64 words (kind 9).
+// ------------------------------------------------------------------------------------------
+constexpr int ANNOT_REQ_KINDS = 12;
+CM_HD inline void annot_req_run(const Core &c, const cm_annot_req &q, cm_annot_res &res, uint32_t *tids) {
+    res.ret = res.aux = 0;
+    res.u0 = res.u1 = 0;
+    switch (q.kind) {
+    case 0: res.ret = iv_find_ind(c.A, q.p0, res.aux); break;
+    case 1: res.ret = overlap_ind(c, q.p0, res.aux); break;
+    case 2: res.ret = (int32_t)upper_bound(c, q.p0, q.p1, q.p2, res.u0, res.aux); break;
+    case 3: res.ret = (int32_t)upper_bound_lookup(c, q.p0, q.p1, q.p2, res.u0, res.aux); break;
+    case 4: res.ret = check_junction(c, q.p0, q.p1, q.i0, q.i1, q.i2, res.aux) ? 1 : 0; break;
+    case 5: res.ret = chr_row(c, q.p0); break;
+    case 6:
+        res.ret = bit_at(c.A.near_border_bits, c.A.n_bits, q.p0) ? 1 : 0;
+        res.aux = bit_at(c.A.intronic_bits, c.A.n_bits, q.p0) ? 1 : 0;
+        break;
+    case 7: res.ret = same_gene_span(c, q.i0, q.p0, q.p1) ? 1 : 0; break;
+    case 8: res.ret = share_gene(c, q.i0, q.i1) ? 1 : 0; break;
+    case 9: {
+        const TidList tl = common_tids(c, q.i0, q.i1, tids);
+        res.ret = tl.n;
+        res.aux = tl.more ? 1 : 0;
+        uint32_t total = 0, fold = 2166136261u;
+        common_tids_from(c, q.i0, q.i1, 0, [&](uint32_t t) {
+            ++total;
+            fold = (fold ^ t) * 16777619u;
+            return true;
+        });
+        res.u0 = total;
+        res.u1 = fold;
+        break;
+    }
+    case 10: {
+        MM sm = mm_init(c), lm = mm_init(c);
+        sm.epos = q.p0; sm.matched_len = q.p1;
+        lm.spos = q.p2; lm.matched_len = q.p3;
+        overlap_to_epos(c, sm);
+        overlap_to_spos(c, lm);
+        if (sm.exons_epos >= 0 && lm.exons_spos >= 0) {
+            int intron_num = 0;
+            res.ret = calc_tlen(c, sm, lm, intron_num);
+            res.aux = intron_num;
+            res.u0 = 1;
+        }
+        break;
+    }
+    case 11: res.ret = (int32_t)pair_code(c, CHEnds(q.p0, q.p1), CHEnds(q.p2, q.p3), overlap(c, q.p0), overlap(c, q.p2), q.i0); break;
+    default: break;
+    }
+}
+// (host side) What is checked before a request batch runs: 0, or 1 + the index of the first bad request; -1: an annotation the
+// hook does not ask -- no interval, or a bucket table with a shift of 0 or above 31 (iv_find_ind's `b + 1` wraps at position
+// 2^32 - 1 under shift 0 and the table would be read at entry 2^32 - 1; a shift of 32 or more is no shift of a 32-bit position).
+inline long long annot_req_check(const AnnotDev &A, const cm_annot_req *req, uint32_t n_req) {
+    const uint32_t n_iv = A.n_iv;
+    if (n_iv == 0 || !A.iv) return -1;
+    if (A.iv_bucket && (A.iv_bucket_shift == 0 || A.iv_bucket_shift > 31)) return -1;
+    auto iv_ok = [&](int32_t i, int32_t lo) { return i >= lo && (long long)i < (long long)n_iv; };
+    for (uint32_t r = 0; r < n_req; ++r) {
+        const cm_annot_req &q = req[r];
+        bool ok = q.kind >= 0 && q.kind < ANNOT_REQ_KINDS;
+        if (q.kind == 2 || q.kind == 3) ok = q.p1 != 0;
+        if (q.kind == 4) ok = iv_ok(q.i0, -0x7fffffff - 1);
+        if (q.kind == 7) ok = iv_ok(q.i0, 0);
+        if (q.kind == 8) ok = iv_ok(q.i0, 0) && iv_ok(q.i1, 0);
+        if (q.kind == 9) ok = iv_ok(q.i0, -1) && iv_ok(q.i1, -1);
+        if (q.kind == 10) ok = q.p0 <= q.p2;
+        if (!ok) return 1 + (long long)r;
+    }
+    return 0;
+}
+
 }  // namespace cmc

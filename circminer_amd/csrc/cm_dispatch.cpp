@@ -48,6 +48,7 @@ CM_VARIANTS(int, cm_map_batch, (void *, int, int, const cm_reads *, const cm_map
 CM_VARIANTS(int, cm_seed_batch, (void *, int, uint32_t *, uint32_t *, uint32_t *, uint32_t, uint32_t *))
 CM_VARIANTS(int, cm_chain_batch, (void *, int, void *, int32_t *, int32_t *))
 CM_VARIANTS(int, cm_dp_batch, (void *, const cm_params *, const uint8_t *, uint64_t, const cm_dp_req *, uint32_t, int, uint32_t, int, uint32_t, cm_dp_res *))
+CM_VARIANTS(int, cm_annot_batch, (void *, int, const cm_params *, const cm_annot_req *, uint32_t, cm_annot_res *, uint32_t *))
 CM_VARIANTS(int, cm_debug_lane_clk, (void *, unsigned long long *))
 CM_VARIANTS(int, cm_debug_counters, (void *, unsigned long long *))
 CM_VARIANTS(int, cm_prof_enable, (void *, int))
@@ -134,6 +135,9 @@ int cm_chain_batch(cm_ctx *ctx, int slot, cm_chain *out, int32_t *nchain, int32_
 int cm_dp_batch(cm_ctx *ctx, const cm_params *P, const uint8_t *arena, uint64_t arena_len, const cm_dp_req *req, uint32_t n_req, int str_cap,
                 uint32_t lds_fill, int arrangement, uint32_t grid, cm_dp_res *out) {
     return ctx ? GO(cm_dp_batch, P, arena, arena_len, req, n_req, str_cap, lds_fill, arrangement, grid, out) : CM_EINVAL;      // (the DP bodies are the same in both builds)
+}
+int cm_annot_batch(cm_ctx *ctx, int slot, const cm_params *P, const cm_annot_req *req, uint32_t n_req, cm_annot_res *out, uint32_t *out_tids) {
+    return ctx ? GO(cm_annot_batch, slot, P, req, n_req, out, out_tids) : CM_EINVAL;      // (each build answers from the slot it loaded itself)
 }
 int cm_debug_lane_clk(cm_ctx *ctx, unsigned long long *out) { return ctx ? GO(cm_debug_lane_clk, out) : CM_EINVAL; }
 int cm_debug_counters(cm_ctx *ctx, unsigned long long *out) { return ctx ? GO(cm_debug_counters, out) : CM_EINVAL; }

@@ -3352,8 +3352,9 @@ int cm_load_annotation(cm_ctx *ctx, int slot, const cm_annot_view *av) {
     if ((rc = up(ctx, al, aos.tr.data(), aos.tr.size(), &A.tr))) return rc;
     if ((rc = up(ctx, al, av->t2s, (size_t)av->t2s_off[av->n_trans], &A.t2s))) return rc;
     if ((rc = up(ctx, al, aos.gene.data(), aos.gene.size(), &A.gene))) return rc;
-    if ((rc = up(ctx, al, av->near_border_bits, (size_t)(av->n_bits / 64), &A.near_border_bits))) return rc;
-    if ((rc = up(ctx, al, av->intronic_bits, (size_t)(av->n_bits / 64), &A.intronic_bits))) return rc;
+    const size_t bit_words = (size_t)((av->n_bits + 63) / 64);      // bit_at() takes any p < n_bits: the last word may be a partial one
+    if ((rc = up(ctx, al, av->near_border_bits, bit_words, &A.near_border_bits))) return rc;
+    if ((rc = up(ctx, al, av->intronic_bits, bit_words, &A.intronic_bits))) return rc;
     if ((rc = up(ctx, al, av->chr_shift, (size_t)av->n_chr, &A.chr_shift))) return rc;
     if ((rc = up(ctx, al, av->chr_id, (size_t)av->n_chr, &A.chr_id))) return rc;
     if (av->iv_bucket && av->n_iv_bucket >= 2) {
@@ -4640,6 +4641,19 @@ int cm_dp_batch(cm_ctx *ctx, const cm_params *P, const uint8_t *arena, uint64_t 
     char msg[256] = "";
     const int rc = cm_dp_probe_run(ctx->st.B, P, arena, arena_len, req, n_req, str_cap, lds_fill, arrangement, grid, out, msg, sizeof msg);
     return rc == CM_OK ? CM_OK : fail(ctx, rc, "cm_dp_batch: %s", msg);
+}
+
+// test hook: the annotation look-ups against the slot's own AnnotDev (kernel, validation and launch in cm_annot_probe.hip)
+extern "C" int cm_annot_probe_run(hipStream_t so, const cm_params *P, const void *annot, size_t annot_bytes, const cm_annot_req *req, uint32_t n_req,
+                                  cm_annot_res *out, uint32_t *out_tids, char *err, size_t err_cap);
+int cm_annot_batch(cm_ctx *ctx, int slot, const cm_params *P, const cm_annot_req *req, uint32_t n_req, cm_annot_res *out, uint32_t *out_tids) {
+    if (!ctx) return CM_EINVAL;
+    if (slot < 0 || slot >= MAX_SLOTS) return fail(ctx, CM_EINVAL, "slot %d out of range", slot);
+    if (!ctx->slots[slot].has_annot) return fail(ctx, CM_ESTATE, "annotation of slot %d not loaded", slot);      // (no index, no reads needed)
+    HIPCHK(ctx, hipSetDevice(ctx->P.device));
+    char msg[256] = "";
+    const int rc = cm_annot_probe_run(ctx->st.B, P, &ctx->slots[slot].A, sizeof(cmc::AnnotDev), req, n_req, out, out_tids, msg, sizeof msg);
+    return rc == CM_OK ? CM_OK : fail(ctx, rc, "cm_annot_batch: %s", msg);
 }
 
 /* diagnostic: per-pair k_pair lane time in 100 MHz ticks (only when CM_LANE_CLK was set at upload) */

@@ -628,7 +628,7 @@ extern "C" int cm_abi_sizes(uint32_t *out, uint32_t cap) {
                           (uint32_t)sizeof(cm_reads),        (uint32_t)sizeof(cm_record),      (uint32_t)sizeof(cm_chr_info),   (uint32_t)sizeof(cm_fastq_batch),
                           (uint32_t)sizeof(cm_mapping_args), (uint32_t)sizeof(cm_mapping_stats), (uint32_t)sizeof(cm_circ_res), (uint32_t)sizeof(cm_circ_args),
                           (uint32_t)sizeof(cm_circ_stats), (uint32_t)sizeof(cm_index_raw), (uint32_t)sizeof(cm_build_stats),
-                          (uint32_t)sizeof(cm_dp_req), (uint32_t)sizeof(cm_dp_res)};
+                          (uint32_t)sizeof(cm_dp_req), (uint32_t)sizeof(cm_dp_res), (uint32_t)sizeof(cm_annot_req), (uint32_t)sizeof(cm_annot_res)};
     const uint32_t n = (uint32_t)(sizeof v / sizeof v[0]);
     if (!out || cap < n) return CM_EINVAL;
     for (uint32_t i = 0; i < n; ++i) out[i] = v[i];

@@ -92,6 +92,20 @@ DP_RES_DTYPE = np.dtype([(n, "<i4") for n, _ in DpRes._fields_])
 assert DP_REQ_DTYPE.itemsize == C.sizeof(DpReq) == 40 and DP_RES_DTYPE.itemsize == C.sizeof(DpRes) == 20
 
 
+class AnnotReq(C.Structure):           # cm_annot_req (test hook cm_annot_batch)
+    _fields_ = [("kind", C.c_int32)] + [(n, C.c_uint32) for n in ("p0", "p1", "p2", "p3")] + [(n, C.c_int32) for n in ("i0", "i1", "i2")]
+
+
+class AnnotRes(C.Structure):           # cm_annot_res
+    _fields_ = [("ret", C.c_int32), ("aux", C.c_int32), ("u0", C.c_uint32), ("u1", C.c_uint32)]
+
+
+ANNOT_REQ_DTYPE = np.dtype([("kind", "<i4")] + [(n, "<u4") for n in ("p0", "p1", "p2", "p3")] + [(n, "<i4") for n in ("i0", "i1", "i2")])
+ANNOT_RES_DTYPE = np.dtype([("ret", "<i4"), ("aux", "<i4"), ("u0", "<u4"), ("u1", "<u4")])
+assert ANNOT_REQ_DTYPE.itemsize == C.sizeof(AnnotReq) == 32 and ANNOT_RES_DTYPE.itemsize == C.sizeof(AnnotRes) == 16
+ANNOT_TIDS = 64                        # words of out_tids per request (cmc::MAX_TID)
+
+
 class AnnotView(C.Structure):
     _fields_ = [("n_iv", C.c_uint32), ("iv_spos", u32p), ("iv_epos", u32p), ("iv_max_end", u32p), ("iv_min_end", u32p),
                 ("iv_max_next_exon", u32p), ("iv_seg_off", u32p), ("iv_seg", u32p),
@@ -233,6 +247,7 @@ def load(path: str = LIB_PATH) -> C.CDLL:
         "cm_seed_batch": (C.c_int, [vp, C.c_int, vp, vp, vp, C.c_uint32, pp(C.c_uint32)]),
         "cm_chain_batch": (C.c_int, [vp, C.c_int, vp, vp, vp]),
         "cm_dp_batch": (C.c_int, [vp, pp(Params), vp, C.c_uint64, vp, C.c_uint32, C.c_int, C.c_uint32, C.c_int, C.c_uint32, vp]),
+        "cm_annot_batch": (C.c_int, [vp, C.c_int, pp(Params), vp, C.c_uint32, vp, vp]),
         "cm_prof_enable": (C.c_int, [vp, C.c_int]),
         "cm_prof_reset": (C.c_int, [vp]),
         "cm_prof_get": (C.c_int, [vp, pp(C.c_double), pp(C.c_uint64)]),
@@ -286,7 +301,7 @@ def load(path: str = LIB_PATH) -> C.CDLL:
     got = (C.c_uint32 * 32)()
     n = L.cm_abi_sizes(got, 32)
     mine = [C.sizeof(t) for t in (Params, IndexView, AnnotView, MappedRead, Reads, C.c_uint8 * RECORD_DTYPE.itemsize, ChrInfo, FastqBatch, MappingArgs,
-                                  MappingStats, CircRes, CircArgs, CircStats, IndexRaw, BuildStats, DpReq, DpRes)]
+                                  MappingStats, CircRes, CircArgs, CircStats, IndexRaw, BuildStats, DpReq, DpRes, AnnotReq, AnnotRes)]
     if n != len(mine) or list(got[:n]) != mine:
         raise RuntimeError(f"circminer_amd.lib: struct sizes differ from {path}: library {list(got[:max(n, 0)])}, ctypes {mine}")
     _lib = L
@@ -295,7 +310,7 @@ def load(path: str = LIB_PATH) -> C.CDLL:
 
 EXPORTED_SYMBOLS = ["cm_create", "cm_destroy", "cm_last_error", "cm_load_contig", "cm_load_contig_raw", "cm_host_next_contig_raw", "cm_load_annotation",
                     "cm_unload_contig", "cm_reads_upload", "cm_reads_stage", "cm_reads_swap", "cm_map_round", "cm_map_rounds", "cm_reads_download", "cm_map_batch",
-                    "cm_sync", "cm_reads_reset", "cm_collect_active", "cm_collect_records", "cm_collect_records_device", "cm_abi_sizes", "cm_host_alloc", "cm_host_free", "cm_host_register", "cm_host_unregister", "cm_type_histogram", "cm_write_remain_records", "cm_seed_batch", "cm_chain_batch", "cm_dp_batch", "cm_prof_enable", "cm_prof_reset", "cm_prof_get",
+                    "cm_sync", "cm_reads_reset", "cm_collect_active", "cm_collect_records", "cm_collect_records_device", "cm_abi_sizes", "cm_host_alloc", "cm_host_free", "cm_host_register", "cm_host_unregister", "cm_type_histogram", "cm_write_remain_records", "cm_seed_batch", "cm_chain_batch", "cm_dp_batch", "cm_annot_batch", "cm_prof_enable", "cm_prof_reset", "cm_prof_get",
                     "cm_prof_counters", "cm_host_build_index", "cm_host_free_index", "cm_host_index_stats", "cm_host_build_annotation",
                     "cm_host_free_annotation", "cm_host_pack_genome", "cm_host_read_index_info", "cm_host_free_index_info",
                     "cm_host_write_index", "cm_host_open_index", "cm_host_next_contig", "cm_host_next_contig_genome", "cm_host_free_loaded_contig",
@@ -891,6 +906,19 @@ class HotPath:
         self._chk(self.L.cm_dp_batch(self.h, C.byref(P), arena.ctypes.data, arena.size, req.ctypes.data, len(req), int(str_cap), int(lds_fill) & 0xFFFFFFFF,
                                      int(arrangement), int(grid), out.ctypes.data), "cm_dp_batch")
         return out
+
+    def load_annotation(self, slot, av: AnnotView):
+        """the annotation alone: what cm_annot_batch needs (no index in the slot)"""
+        self._chk(self.L.cm_load_annotation(self.h, slot, C.byref(av)), "cm_load_annotation")
+
+    def annot_batch(self, slot, P, req):
+        """cm_annot_batch: the requests `req` (ANNOT_REQ_DTYPE) against the annotation of `slot` -> (results (ANNOT_RES_DTYPE),
+        kept transcript ids, ANNOT_TIDS words per request)"""
+        req = np.ascontiguousarray(req, dtype=ANNOT_REQ_DTYPE)
+        out = np.zeros(len(req), ANNOT_RES_DTYPE)
+        tids = np.zeros((len(req), ANNOT_TIDS), np.uint32)
+        self._chk(self.L.cm_annot_batch(self.h, slot, C.byref(P), req.ctypes.data, len(req), out.ctypes.data, tids.ctypes.data), "cm_annot_batch")
+        return out, tids
 
     def prof(self, on=True):
         self._chk(self.L.cm_prof_enable(self.h, int(on)), "cm_prof_enable")

@@ -110,7 +110,7 @@ typedef struct cm_annot_view {
     /* genes (gid2ginfo, src/gene_annotation.cpp:243-245) */
     uint32_t n_gene;
     const uint32_t *gene_start, *gene_end;
-    /* position bitsets (src/common.h:117-118); bit p = contig position p */
+    /* position bitsets (src/common.h:117-118); bit p = contig position p, p < n_bits; each array holds (n_bits + 63) / 64 words */
     uint64_t n_bits;
     const uint64_t *near_border_bits;
     const uint64_t *intronic_bits;
@@ -366,6 +366,38 @@ typedef struct cm_dp_res {
  * for a request that is none of the above.  Synchronous. */
 int cm_dp_batch(cm_ctx *ctx, const cm_params *P, const uint8_t *arena, uint64_t arena_len, const cm_dp_req *req, uint32_t n_req,
                 int str_cap, uint32_t lds_fill, int arrangement, uint32_t grid, cm_dp_res *out);
+/* The annotation look-ups behind every chain and every pairing decision (cm_core.h), one request per lane on the device (kernel
+ * k_annot_probe, one wave per workgroup), against the annotation resident in `slot` -- the records, the bucket table and the
+ * pair_reach that cm_load_annotation made, not a second upload.  Needs no reads and no index; CM_ESTATE without an annotation.
+ * `P` supplies max_ed and scan_level.  Fields a kind does not name are 0.
+ *   kind  call                                                          request                           result
+ *   0     iv_find_ind(pos)                                              p0 = pos                          ret, aux = ind
+ *   1     overlap_ind(pos)                                              p0 = pos                          ret, aux = ind
+ *   2     upper_bound(spos, mlen, rlen)                                 p0, p1, p2                        ret, aux = ol, u0 = max_end
+ *   3     upper_bound_lookup(spos, mlen, rlen) (no bit test)            p0, p1, p2                        ret, aux = ol, u0 = max_end
+ *   4     check_junction(s1, s2, ol, kmer, read_dist)                   p0, p1, i0, i1, i2                ret, aux = trans_dist
+ *   5     chr_row(loc)                                                  p0 = loc                          ret
+ *   6     bit_at(near_border_bits, p), bit_at(intronic_bits, p)         p0 = p                            ret, aux
+ *   7     same_gene_span(iv, s, e)                                      i0 = iv, p0 = s, p1 = e           ret
+ *   8     share_gene(a, b)                                              i0 = a, i1 = b                    ret
+ *   9     common_tids(s, r), s or r may be -1                           i0 = s, i1 = r                    ret = ids kept, aux = more,
+ *         u0 = size of the whole intersection, u1 = order-sensitive fold of all its ids (both from common_tids_from(skip = 0)),
+ *         the kept ids in out_tids[64 * request ...]
+ *   10    calc_tlen of sm (epos = p0, matched_len = p1) and lm (spos = p2, matched_len = p3), p0 <= p2, after overlap_to_epos(sm)
+ *         and overlap_to_spos(lm), called only if both hit (as concordant_explanation does)   ret, aux = intron_num, u0 = 1 if called
+ *   11    pair_code of chains [p0, p1) and [p2, p3) with the intervals of overlap(p0), overlap(p2), saved_type = i0      ret
+ * Interval indices lie in [-1, n_iv); kinds 4, 7, 8 take none below 0, except ol (kind 4).  mlen (kinds 2, 3: p1) is not 0.  Any
+ * 32-bit position is legal.  A slot whose bucket table has iv_bucket_shift 0 or above 31 is not asked.  CM_EINVAL otherwise.  out_tids: 64 words per request (zero where not written).  Synchronous. */
+typedef struct cm_annot_req {
+    int32_t kind;
+    uint32_t p0, p1, p2, p3;
+    int32_t i0, i1, i2;
+} cm_annot_req;
+typedef struct cm_annot_res {
+    int32_t ret, aux;                  /* ret: the call's return value (a uint32_t return as its bit pattern) */
+    uint32_t u0, u1;
+} cm_annot_res;
+int cm_annot_batch(cm_ctx *ctx, int slot, const cm_params *P, const cm_annot_req *req, uint32_t n_req, cm_annot_res *out, uint32_t *out_tids);
 
 /* The resident batch's read bytes and offsets copied back (what cm_reads_upload / cm_reads_swap made resident): off1 / off2 take
  * n_pairs + 1 words, seq1 / seq2 off[n_pairs] bytes (CM_ELIMIT when cap1 / cap2 is smaller).  A NULL pointer skips that array; all
@@ -663,7 +695,7 @@ int cm_circ_run(const cm_circ_args *args, cm_circ_stats *stats, char *err, uint6
 
 /* sizeof of the structs above, in this order: cm_params, cm_index_view, cm_annot_view, cm_mapped_read, cm_reads, cm_record,
  * cm_chr_info, cm_fastq_batch, cm_mapping_args, cm_mapping_stats, cm_circ_res, cm_circ_args, cm_circ_stats, cm_index_raw, cm_build_stats, cm_dp_req,
- * cm_dp_res -- for a binding to
+ * cm_dp_res, cm_annot_req, cm_annot_res -- for a binding to
  * check its mirrors of them against the library it loaded.  Returns the number of entries written (cap must hold them). */
 int cm_abi_sizes(uint32_t *out, uint32_t cap);
 

@@ -1324,6 +1324,20 @@ struct Rec { const uint8_t *seq; std::vector<uint8_t> rc; int seq_len; };
 
 struct MatePair { int type; int fi, rj; std::vector<uint32_t> common_tid; };
 
+// the predicate of pair_chains for one (i, j), filter.cpp:507-546: -1 = not paired, else MatePair::type; common_tid as
+// same_transcript leaves it
+int pair_predicate(const Ctx &c, uint32_t fs, uint32_t fe, uint32_t rs, uint32_t re, int fe_iv, int re_iv, int saved_type,
+                   std::vector<uint32_t> &common_tid) {
+    int tlen = (int)((fs < rs) ? (re - fs) : (fe - rs));
+    bool same_tr = false, same_gen = false;
+    common_tid.clear();
+    if (fe_iv >= 0 && re_iv >= 0) same_tr = same_transcript(c, fe_iv, re_iv, common_tid);
+    if (!same_tr && fe_iv >= 0 && ((c.P.scan_level == 0 && saved_type > CM_CONGEN) || (c.P.scan_level > 0 && saved_type >= CM_CONGEN)))
+        same_gen = same_gene_iv(c, fe_iv, rs, re);
+    if (!same_gen && re_iv >= 0 && saved_type >= CM_CONGEN) same_gen = same_gene_iv(c, re_iv, fs, fe);
+    if (same_tr || same_gen || ((tlen <= MAXDISCRDTLEN) && (saved_type >= CM_CONGNM))) return same_tr ? 0 : (same_gen ? 1 : 2);
+    return -1;
+}
 // FilterRead::pair_chains, filter.cpp:484-551
 void pair_chains(const Ctx &c, const ChainList &fwd, const ChainList &rev, std::vector<MatePair> &mate_pairs, std::vector<char> &fp,
                  std::vector<char> &rp, int saved_type) {
@@ -1339,18 +1353,11 @@ void pair_chains(const Ctx &c, const ChainList &fwd, const ChainList &rev, std::
             uint32_t fs = F.frags[0].rpos, rs = R.frags[0].rpos;
             uint32_t fe = F.frags[F.chain_len - 1].rpos + F.frags[F.chain_len - 1].len;
             uint32_t re = R.frags[R.chain_len - 1].rpos + R.frags[R.chain_len - 1].len;
-            int tlen = (int)((fs < rs) ? (re - fs) : (fe - rs));
             MatePair temp;
-            bool same_tr = false, same_gen = false;
-            if (fe_list[i] >= 0 && re_list[j] >= 0) same_tr = same_transcript(c, fe_list[i], re_list[j], temp.common_tid);
-            if (!same_tr && fe_list[i] >= 0 &&
-                ((c.P.scan_level == 0 && saved_type > CM_CONGEN) || (c.P.scan_level > 0 && saved_type >= CM_CONGEN)))
-                same_gen = same_gene_iv(c, fe_list[i], rs, re);
-            if (!same_gen && re_list[j] >= 0 && saved_type >= CM_CONGEN) same_gen = same_gene_iv(c, re_list[j], fs, fe);
-            if (same_tr || same_gen || ((tlen <= MAXDISCRDTLEN) && (saved_type >= CM_CONGNM))) {
+            temp.type = pair_predicate(c, fs, fe, rs, re, fe_list[i], re_list[j], saved_type, temp.common_tid);
+            if (temp.type >= 0) {
                 temp.fi = i;
                 temp.rj = j;
-                temp.type = same_tr ? 0 : (same_gen ? 1 : 2);
                 mate_pairs.push_back(temp);
                 fp[i] = 1;
                 rp[j] = 1;
@@ -2463,6 +2470,69 @@ int oracle_map_round(const cm_params *P, const cm_index_view *X, const cm_annot_
 void oracle_default_state(const cm_params *P, cm_mapped_read *state, uint8_t *active, uint64_t n) {
     Ctx c{*P, nullptr, nullptr};
     for (uint64_t i = 0; i < n; ++i) { default_mr(c, state[i]); active[i] = 1; }
+}
+
+// The annotation look-ups one request at a time: the requests and results of cm_annot_batch (include/circminer_hot.h), answered
+// by this file's own functions over the structure-of-arrays view -- plain binary search, no bucket table, no quick reject.
+int oracle_annot_batch(const cm_params *P, const cm_annot_view *A, const cm_annot_req *req, uint32_t n_req, cm_annot_res *out, uint32_t *out_tids) {
+    Ctx c{*P, nullptr, A};
+    memset(out_tids, 0, (size_t)n_req * 64 * sizeof(uint32_t));
+    for (uint32_t r = 0; r < n_req; ++r) {
+        const cm_annot_req &q = req[r];
+        cm_annot_res v{0, 0, 0, 0};
+        switch (q.kind) {
+        case 0: v.ret = iv_find_ind(A, q.p0, v.aux); break;
+        case 1: v.ret = get_location_overlap_ind(c, q.p0, v.aux); break;
+        case 2: v.ret = (int32_t)get_upper_bound(c, q.p0, q.p1, q.p2, v.u0, v.aux); break;
+        case 3: v.ret = (int32_t)get_upper_bound_lookup(c, q.p0, q.p1, q.p2, v.u0, v.aux); break;
+        case 4: v.ret = check_junction(c, q.p0, q.p1, q.i0, q.i1, q.i2, v.aux) ? 1 : 0; break;
+        case 5: v.ret = get_shift(c, q.p0); break;
+        case 6:
+            v.ret = bit(A->near_border_bits, A->n_bits, q.p0) ? 1 : 0;
+            v.aux = bit(A->intronic_bits, A->n_bits, q.p0) ? 1 : 0;
+            break;
+        case 7: v.ret = same_gene_iv(c, q.i0, q.p0, q.p1) ? 1 : 0; break;
+        case 8: {                       // the gene test of check_chimeric / bsj_tail, utils.cpp:215-231
+            for (uint32_t i = 0; i < iv_nseg(A, q.i0) && !v.ret; i++)
+                for (uint32_t j = 0; j < iv_nseg(A, q.i1); j++)
+                    if (A->seg_gene_id[iv_segid(A, q.i0, i)] == A->seg_gene_id[iv_segid(A, q.i1, j)]) { v.ret = 1; break; }
+            break;
+        }
+        case 9: {
+            std::vector<uint32_t> tids;
+            same_transcript(c, q.i0, q.i1, tids);
+            v.ret = (int32_t)std::min<size_t>(tids.size(), 64);
+            v.aux = tids.size() > 64 ? 1 : 0;
+            v.u0 = (uint32_t)tids.size();
+            v.u1 = 2166136261u;
+            for (uint32_t t : tids) v.u1 = (v.u1 ^ t) * 16777619u;
+            for (int i = 0; i < v.ret; ++i) out_tids[(size_t)r * 64 + i] = tids[i];
+            break;
+        }
+        case 10: {
+            MatchedMate sm(c), lm(c);
+            sm.epos = q.p0; sm.matched_len = q.p1;
+            lm.spos = q.p2; lm.matched_len = q.p3;
+            overlap_to_epos(c, sm);
+            overlap_to_spos(c, lm);
+            if (sm.exons_epos >= 0 && lm.exons_spos >= 0) {
+                int intron_num = 0;
+                v.ret = calc_tlen(c, sm, lm, intron_num);
+                v.aux = intron_num;
+                v.u0 = 1;
+            }
+            break;
+        }
+        case 11: {
+            std::vector<uint32_t> tids;
+            v.ret = pair_predicate(c, q.p0, q.p1, q.p2, q.p3, get_location_overlap(c, q.p0), get_location_overlap(c, q.p2), q.i0, tids) + 1;
+            break;
+        }
+        default: return CM_EINVAL;
+        }
+        out[r] = v;
+    }
+    return 0;
 }
 
 // Stand-alone DP entry points (property tests of A14).

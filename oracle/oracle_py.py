@@ -48,8 +48,21 @@ def load():
         L.oracle_drop_sc.argtypes = [pp(cl.Params), vp, C.c_int, vp, C.c_int, C.c_int, pp(C.c_int), pp(C.c_int), pp(C.c_int)]
         L.oracle_one_side.restype = C.c_int
         L.oracle_one_side.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int]
+        L.oracle_annot_batch.restype = C.c_int
+        L.oracle_annot_batch.argtypes = [pp(cl.Params), pp(cl.AnnotView), vp, C.c_uint32, vp, vp]
         _lib = L
     return _lib
+
+
+def annot_batch(params, av, req):
+    """the requests of cm_annot_batch (cl.ANNOT_REQ_DTYPE) answered by the oracle's own look-ups -> (results, kept transcript ids)"""
+    L = load()
+    req = np.ascontiguousarray(req, dtype=cl.ANNOT_REQ_DTYPE)
+    out = np.zeros(len(req), cl.ANNOT_RES_DTYPE)
+    tids = np.zeros((len(req), cl.ANNOT_TIDS), np.uint32)
+    rc = L.oracle_annot_batch(C.byref(params), C.byref(av), req.ctypes.data, len(req), out.ctypes.data, tids.ctypes.data)
+    assert rc == 0, rc
+    return out, tids
 
 
 def seeds(params, iv, batch, n_slots):

@@ -304,6 +304,32 @@ int emu_dp_batch(const cm_params *P, const uint8_t *arena, uint64_t arena_len, c
     }
     return 0;
 }
+// cm_annot_batch on the host: the same requests through the host build of cmc::annot_req_run, over the records build_annot_aos
+// makes of the caller's view (vectors of exactly n records) and the caller's own pass-through arrays.  Returns CM_EINVAL for what
+// cm_annot_batch refuses.
+int emu_annot_batch(const cm_params *P, const cm_annot_view *A, const cm_annot_req *req, uint32_t n_req, cm_annot_res *out, uint32_t *out_tids) {
+    if (!P || !A || A->n_iv == 0 || (n_req && (!req || !out || !out_tids))) return CM_EINVAL;
+    Core c{};
+    c.P = *P;
+    cmc::AnnotAosHost aos;
+    cmc::build_annot_aos(*A, aos);
+    const cmc::AnnotDev dev = cmc::annot_dev_host(*A, aos);
+    if (cmc::annot_req_check(dev, req, n_req) != 0) return CM_EINVAL;
+    c.A = cmc::to_dev(dev);
+    memset(out_tids, 0, (size_t)n_req * cmc::MAX_TID * sizeof(uint32_t));
+    for (uint32_t r = 0; r < n_req; ++r) {
+        uint32_t tids[cmc::MAX_TID];
+        cmc::annot_req_run(c, req[r], out[r], tids);
+        if (req[r].kind == 9) memcpy(out_tids + (size_t)r * cmc::MAX_TID, tids, (size_t)out[r].ret * sizeof(uint32_t));
+    }
+    return 0;
+}
+// AnnotDev::pair_reach as cm_load_annotation derives it for this view (cm_aos.h)
+uint32_t emu_annot_pair_reach(const cm_annot_view *A) {
+    cmc::AnnotAosHost aos;
+    cmc::build_annot_aos(*A, aos);
+    return aos.pair_reach;
+}
 int emu_one_side(const cm_params *P, const uint8_t *s, int n, const uint8_t *t, int m, int w) {
     Core c{};
     c.P = *P;

@@ -31,6 +31,7 @@ def test_struct_layouts_match_header():
     assert cl.CHAIN_DTYPE.itemsize == 8 + 4 * 16 * 2
     assert C.sizeof(cl.Params) == 48
     assert C.sizeof(cl.DpReq) == cl.DP_REQ_DTYPE.itemsize == 40 and C.sizeof(cl.DpRes) == cl.DP_RES_DTYPE.itemsize == 20      # cm_dp_req, cm_dp_res
+    assert C.sizeof(cl.AnnotReq) == cl.ANNOT_REQ_DTYPE.itemsize == 32 and C.sizeof(cl.AnnotRes) == cl.ANNOT_RES_DTYPE.itemsize == 16      # cm_annot_req, cm_annot_res
 
 
 def test_no_cpu_fallback_without_device():

@@ -233,16 +233,19 @@ def test_new_names_agree_between_header_library_and_binding(built):
     L = cl.load()
     hdr = open(os.path.join(ROOT, "include", "circminer_hot.h")).read()
     hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    for name in ("cm_build_contig", "cm_index_download", "cm_dp_batch"):
+    for name in ("cm_build_contig", "cm_index_download", "cm_dp_batch", "cm_annot_batch"):
         assert re.search(r"\b" + name + r"\s*\(", hdr), name
         assert hasattr(L, name) and name in cl.EXPORTED_SYMBOLS
     assert "typedef struct cm_build_stats" in hdr and "typedef struct cm_dp_req" in hdr and "typedef struct cm_dp_res" in hdr
+    assert "typedef struct cm_annot_req" in hdr and "typedef struct cm_annot_res" in hdr
     got = (C.c_uint32 * 32)()
     n = L.cm_abi_sizes(got, 32)
-    assert n == 17 and got[14] == C.sizeof(cl.BuildStats) == 48
+    assert n == 19 and got[14] == C.sizeof(cl.BuildStats) == 48
     assert got[15] == C.sizeof(cl.DpReq) == 40 and got[16] == C.sizeof(cl.DpRes) == 20
-    assert L.cm_abi_sizes(got, 16) == -1                  # (a caller with room for fewer entries is told so)
+    assert got[17] == C.sizeof(cl.AnnotReq) == 32 and got[18] == C.sizeof(cl.AnnotRes) == 16
+    assert L.cm_abi_sizes(got, 16) == -1 and L.cm_abi_sizes(got, 18) == -1                # (a caller with room for fewer entries is told so)
     # without a context both refuse, they do not crash
     assert L.cm_build_contig(None, 0, 0, None, 0, None) == -1
     assert L.cm_index_download(None, 0, None, None, None, 0, None) == -1
     assert L.cm_dp_batch(None, None, None, 0, None, 0, 144, 0, 0, 0, None) == -1
+    assert L.cm_annot_batch(None, 0, None, None, 0, None, None) == -1
