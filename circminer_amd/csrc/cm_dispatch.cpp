@@ -26,6 +26,8 @@ CM_VARIANTS(int, cm_reads_stage, (void *, const cm_reads *, const cm_mapped_read
 CM_VARIANTS(int, cm_reads_stage_text, (void *, const uint8_t *, uint64_t, const uint8_t *, uint64_t, uint64_t, uint32_t, uint64_t *, uint64_t *, cm_text_batch *))
 CM_VARIANTS(int, cm_reads_peek, (void *, uint8_t *, uint64_t, uint64_t *, uint8_t *, uint64_t, uint64_t *, uint64_t *))
 CM_VARIANTS(int, cm_format_pam, (void *, const cm_chr_info *, uint32_t, uint64_t, uint64_t, void *, uint64_t, uint64_t *, uint64_t *))
+CM_VARIANTS(int, cm_format_sam, (void *, const cm_chr_info *, uint32_t, uint64_t, uint64_t, void *, uint64_t, uint64_t *, uint64_t *))
+CM_VARIANTS(int, cm_quals_peek, (void *, uint8_t *, uint64_t, uint8_t *, uint64_t))
 CM_VARIANTS(int, cm_state_poke, (void *, const cm_mapped_read *))
 CM_VARIANTS(int, cm_reads_swap, (void *))
 CM_VARIANTS(int, cm_map_rounds, (void *, const int *, int, int))
@@ -97,6 +99,11 @@ int cm_format_pam(cm_ctx *ctx, const cm_chr_info *chrs, uint32_t n_chr, uint64_t
                   uint64_t stats[4]) {
     return ctx ? GO(cm_format_pam, chrs, n_chr, first, count, out, cap, out_bytes, stats) : CM_EINVAL;
 }
+int cm_format_sam(cm_ctx *ctx, const cm_chr_info *chrs, uint32_t n_chr, uint64_t first, uint64_t count, void *out, uint64_t cap, uint64_t *out_bytes,
+                  uint64_t stats[4]) {
+    return ctx ? GO(cm_format_sam, chrs, n_chr, first, count, out, cap, out_bytes, stats) : CM_EINVAL;
+}
+int cm_quals_peek(cm_ctx *ctx, uint8_t *qual1, uint64_t cap1, uint8_t *qual2, uint64_t cap2) { return ctx ? GO(cm_quals_peek, qual1, cap1, qual2, cap2) : CM_EINVAL; }
 int cm_state_poke(cm_ctx *ctx, const cm_mapped_read *states) { return ctx ? GO(cm_state_poke, states) : CM_EINVAL; }
 int cm_reads_swap(cm_ctx *ctx) { return ctx ? GO(cm_reads_swap) : CM_EINVAL; }
 int cm_map_rounds(cm_ctx *ctx, const int *slots, int n, int last) { return ctx ? GO(cm_map_rounds, slots, n, last) : CM_EINVAL; }

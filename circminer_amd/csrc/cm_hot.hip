@@ -29,6 +29,7 @@
 #include "cm_index_build.h"
 #include "cm_fastq_text.h"
 #include "cm_pam_text.h"
+#include "cm_sam_text.h"
 
 using cmc::Core;
 using cmc::KCore;
@@ -45,7 +46,7 @@ constexpr int BLK_CHAIN = 64;
 // Profile classes: the index of cm_ctx::ms[] / launches[], of Timer, launch() and cm_prof_get (include/circminer_hot.h).  PC_NONE:
 // a launch no class counts (index build, collect, the small housekeeping kernels).
 enum ProfClass { PC_NONE = -1, PC_SEED = 0, PC_CHAIN = 1, PC_PAIR = 2, PC_SCAN = 3, PC_HEAVY = 4, PC_ORDER = 5, PC_CHAIN_HEAVY = 6, PC_PREFETCH = 7,
-                 PC_PAM = 7 /* the same slot: PC_PREFETCH counts launches and has no time, cm_format_pam has time and counts none */, PC_COUNT = 8 };
+                 PC_PAM = 7 /* the same slot: PC_PREFETCH counts launches and has no time, the row formatters (cm_format_pam, cm_format_sam) have time and count none */, PC_COUNT = 8 };
 // The words of cm_ctx::d_counters.  0 - 6 are public (cm_prof_counters, include/circminer_hot.h); from 8 on what a diagnostic build
 // accumulates, read by the scripts of tests/diag through cm_debug_counters at these indices.  The two diagnostic builds overlap (they
 // are never one build): both write word 24.
@@ -69,7 +70,7 @@ enum Pin {
     PIN_CELLS = 8,                                   // + 2 * seed set: DP cells of the tile, + 1: of its largest problem
     PIN_RERUN_N = 12, PIN_FALL_N = 14,               // + chain-record set: length of the re-run list / of the pipeline's fall-back list
     PIN_TEXT = 16,                                   // cm_reads_stage_text: the result block of the tokeniser (cmft::RES_WORDS words)
-    PIN_PAM = 26,                                    // cm_format_pam: the bytes of the rows
+    PIN_PAM = 26,                                    // cm_format_pam / cm_format_sam: the bytes of the rows
     PIN_WORDS = 32
 };
 constexpr size_t PIN_BYTES = PIN_WORDS * sizeof(unsigned long long);        // allocated and cleared in cm_create
@@ -2119,6 +2120,12 @@ __global__ void __launch_bounds__(FT_T) k_ft_name_copy(const uint8_t *text, cons
     for (uint32_t i = (blockIdx.x * FT_T + threadIdx.x) / cmft::COPY_LANES; i < n; i += groups)
         cmft::copy_bases(names, name_off[i], text, nstart[i], name_off[i + 1] - name_off[i], (int)lane, cmft::COPY_LANES);
 }
+// flag bit 3: COPY_LANES lanes per record move its quality line (line 4 i + 3, as long as the bases) to qual[off[i] ..), word by word
+__global__ void __launch_bounds__(FT_T) k_ft_qual_copy(const uint8_t *text, const uint32_t *ls, const uint64_t *off, uint32_t n, uint8_t *qual) {
+    const uint32_t groups = gridDim.x * (FT_T / cmft::COPY_LANES), lane = threadIdx.x % cmft::COPY_LANES;
+    for (uint32_t i = (blockIdx.x * FT_T + threadIdx.x) / cmft::COPY_LANES; i < n; i += groups)
+        cmft::copy_bases(qual, off[i], text, ls[4 * (uint64_t)i + 3], (uint32_t)(off[i + 1] - off[i]), (int)lane, cmft::COPY_LANES);
+}
 // one lane per row k of the call (pair first + k): its length; item count is 0, the slot the scan leaves the total in
 __global__ void __launch_bounds__(BLK) k_pam_len(const cm_mapped_read *state, const uint32_t *name_off, cmpt::ChrTab ct, uint64_t first, uint32_t count, uint32_t *len) {
     const uint32_t k = blockIdx.x * BLK + threadIdx.x;
@@ -2165,6 +2172,67 @@ __global__ void __launch_bounds__(cmpt::SPAN_ROWS) k_pam_rows(const cm_mapped_re
         const uint32_t a = name_off[first + k];
         cmpt::format_row(out + off[k], m, names + a, name_off[first + k + 1] - a, ct);
     }
+}
+
+// ---- cm_format_sam (bodies and the plan: cm_sam_text.h) ----------------------------------------------------------------------
+// what the SAM kernels read of the resident batch: the states, the kept names, bases and kept qualities (seq: behind the slack)
+struct SamSrc {
+    const cm_mapped_read *state;
+    const uint8_t *names;
+    const uint32_t *name_off;
+    const uint8_t *seq[2], *qual[2];
+    const uint64_t *off[2];
+};
+// one lane per record q of the call (mate q & 1 of pair first + q / 2): its length; item `items` is 0, the slot the scan leaves the
+// total in.  Only a reversed record reads its bases.
+__global__ void __launch_bounds__(BLK) k_sam_len(SamSrc S, cmpt::ChrTab ct, uint64_t first, uint32_t items, uint32_t *len) {
+    const uint32_t q = blockIdx.x * BLK + threadIdx.x;
+    if (q > items) return;
+    uint32_t l = 0;
+    if (q < items) {
+        const uint64_t pair = first + q / 2;
+        const uint32_t mate = q & 1u;
+        const cm_mapped_read m = S.state[pair];
+        const uint64_t a = S.off[mate][pair];
+        l = cmst::item_len(m, mate, S.name_off[pair + 1] - S.name_off[pair], S.seq[mate], a, (uint32_t)(S.off[mate][pair + 1] - a), ct);
+    }
+    len[q] = l;
+}
+// the two steps of a span into dst (the wave's window, or the output): the ends of its records, a lane each, then the strings
+template <class Pos>
+__device__ __forceinline__ void sam_span(uint8_t *dst, cmst::Strings *desc, const SamSrc &S, const cmpt::ChrTab &ct, uint64_t first, uint32_t q0, uint32_t q1,
+                                         const uint32_t *off, uint32_t lane, Pos pos) {
+    if (lane < q1 - q0) {
+        const uint32_t q = q0 + lane, mate = q & 1u;
+        const uint64_t pair = first + q / 2;
+        const cm_mapped_read m = S.state[pair];
+        const uint32_t na = S.name_off[pair];
+        const uint64_t a = S.off[mate][pair];
+        desc[lane] = cmst::format_ends(dst, pos(off[q]), off[q + 1] - off[q], m, mate, S.names + na, S.name_off[pair + 1] - na, a, (uint32_t)(S.off[mate][pair + 1] - a), ct);
+    }
+    __syncthreads();
+    const uint32_t r = lane / cmst::REC_LANES;
+    if (r < q1 - q0) {
+        const cmst::Strings D = desc[r];
+        const uint32_t mate = D.rev_mate >> 1;
+        cmst::copy_strings(dst, D, S.seq[mate], S.qual[mate], lane % cmst::REC_LANES, cmst::REC_LANES);
+    }
+}
+// One wave (a workgroup of its own) per span of SPAN_RECS records: put together in the wave's LDS window and streamed out as words,
+// or, for a span larger than the window, stored to the output directly.  path[span] = 1 / 0 says which.
+__global__ void __launch_bounds__(cmst::WAVE) k_sam_rows(SamSrc S, cmpt::ChrTab ct, uint64_t first, uint32_t items, const uint32_t *off, uint8_t *out, uint8_t *path) {
+    __shared__ uint32_t win[cmst::WINDOW_WORDS];
+    __shared__ cmst::Strings desc[cmst::SPAN_RECS];
+    const uint32_t lane = threadIdx.x, q0 = blockIdx.x * cmst::SPAN_RECS;
+    const uint32_t q1 = items - q0 < cmst::SPAN_RECS ? items : q0 + cmst::SPAN_RECS;
+    const uint32_t s = off[q0], e = off[q1];
+    const bool staged = cmst::span_in_window(s, e);                  // (uniform)
+    if (lane == 0) path[blockIdx.x] = staged ? 1 : 0;
+    if (staged) {
+        sam_span((uint8_t *)win, desc, S, ct, first, q0, q1, off, lane, [s](uint32_t g) { return cmpt::window_at(s, g); });
+        __syncthreads();
+        cmpt::stream_span(out, (const uint8_t *)win, s, e, lane, cmst::WAVE);
+    } else sam_span(out, desc, S, ct, first, q0, q1, off, lane, [](uint32_t g) { return g; });
 }
 
 // ------------------------------------------------------------------ host side
@@ -2219,6 +2287,11 @@ struct ReadBufs {
     BatchBuf<uint32_t> name_off;
     bool has_names = false;
     uint64_t name_bytes_max = 0;                 // no more name bytes than this (the host never learns the exact number)
+    // cm_reads_stage_text with flag bit 3: the quality lines of the batch in the layout of the bases, quality of read i =
+    // qual[off[i] .. off[i + 1]) (cm_format_sam); allocated only when the bit is given
+    BatchBuf<uint8_t> qual1, qual2;
+    bool has_quals = false;
+    uint64_t bases = 0;                          // with has_quals: off1[n] + off2[n]
 };
 inline void swap(ReadBufs &a, ReadBufs &b) {
     swap(a.seq1_base, b.seq1_base);
@@ -2229,6 +2302,10 @@ inline void swap(ReadBufs &a, ReadBufs &b) {
     swap(a.name_off, b.name_off);
     std::swap(a.has_names, b.has_names);
     std::swap(a.name_bytes_max, b.name_bytes_max);
+    swap(a.qual1, b.qual1);
+    swap(a.qual2, b.qual2);
+    std::swap(a.has_quals, b.has_quals);
+    std::swap(a.bases, b.bases);
 }
 
 // What the seeding of a tile leaves for its chain stage: the seed ranges of every probe, the DP-cell offsets of every chaining
@@ -3612,7 +3689,7 @@ int cm_reads_upload(cm_ctx *ctx, const cm_reads *rd, const cm_mapped_read *prior
     int max_len = 0;
     int rc = check_reads(ctx, rd, &max_len);
     if (rc) return rc;
-    ctx->rd.has_names = false;
+    ctx->rd.has_names = ctx->rd.has_quals = false;
     if ((rc = copy_reads(ctx, rd, ctx->st.B, ctx->rd))) return rc;
     if ((rc = prepare_resident(ctx, n, max_len))) return rc;
     ctx->n_pairs = n;
@@ -3638,7 +3715,7 @@ int cm_reads_stage(cm_ctx *ctx, const cm_reads *rd, const cm_mapped_read *prior)
     HIPCHK(ctx, hipStreamSynchronize(ctx->st.C));          // an earlier staged batch that was never swapped in is dropped
     ctx->staged = false;
     ctx->pre_launched = false;
-    ctx->st_rd.has_names = false;
+    ctx->st_rd.has_names = ctx->st_rd.has_quals = false;
     if ((rc = copy_reads(ctx, rd, ctx->st.C, ctx->st_rd))) return rc;
     ctx->st_has_prior = prior != nullptr;
     if (prior) {
@@ -3680,7 +3757,7 @@ int cm_reads_stage_text(cm_ctx *ctx, const uint8_t *text1, uint64_t len1, const 
     const size_t pad = cmc::CM_STAGE_PAD;
     uint32_t n_chunks[2], ls_cap[2];
     ReadBufs &to = ctx->st_rd;
-    to.has_names = false;
+    to.has_names = to.has_quals = false;
     HIPCHK(ctx, ensure(ctx, to.seq1_base, len1 + 2 * pad));
     HIPCHK(ctx, ensure(ctx, to.seq2_base, len2 + 2 * pad));
     HIPCHK(ctx, ensure(ctx, to.off1, ((size_t)nb + 1) * sizeof(uint64_t)));
@@ -3787,6 +3864,22 @@ int cm_reads_stage_text(cm_ctx *ctx, const uint8_t *text1, uint64_t len1, const 
         HIPCHK(ctx, hipEventRecord(ctx->ev.staged, st));
         to.has_names = true;
         to.name_bytes_max = name_max;
+    }
+    if (flags & 8u) {
+        // Keep the qualities: the quality line of every staged record of both files, copied word-wise into arrays that share off1 /
+        // off2 with the bases (the stage has verified that the lines are as long).  Behind the read-back, which gives the sizes, like
+        // the names; ev.staged moves behind the copies.  A word of slack: the formatter reads whole words.
+        const uint64_t bases[2] = {R[cmft::RES_BASES1], R[cmft::RES_BASES2]};
+        HIPCHK(ctx, ensure(ctx, to.qual1, (size_t)bases[0] + 8));
+        HIPCHK(ctx, ensure(ctx, to.qual2, (size_t)bases[1] + 8));
+        const unsigned gc = (unsigned)std::min<uint64_t>((n * cmft::COPY_LANES + FT_T - 1) / FT_T, 1u << 16);
+        for (int f = 0; f < 2; ++f)
+            hipLaunchKernelGGL(k_ft_qual_copy, dim3(gc), dim3(FT_T), 0, st, (const uint8_t *)T.text[f], (const uint32_t *)T.ls[f],
+                               (const uint64_t *)(f ? to.off2 : to.off1), (uint32_t)n, (uint8_t *)(f ? to.qual2 : to.qual1));
+        HIPCHK(ctx, hipGetLastError());
+        HIPCHK(ctx, hipEventRecord(ctx->ev.staged, st));
+        to.has_quals = true;
+        to.bases = bases[0] + bases[1];
     }
     ctx->st_has_prior = false;
     ctx->st_n_pairs = n;
@@ -4426,6 +4519,31 @@ int cm_collect_records_device(cm_ctx *ctx, uint64_t index_base, uint64_t cap, vo
     return collect_records_into(ctx, index_base, cap, (cm_record *)d_out, out_n, "cm_collect_records_device");
 }
 
+// The chromosome names of a row formatter's call: uploaded when they differ from the table on the device.  *chr_max: the longest name.
+static int upload_chr_table(cm_ctx *ctx, PamRows &F, const cm_chr_info *chrs, uint32_t n_chr, hipStream_t st, uint32_t *chr_max) {
+    std::vector<uint32_t> o((size_t)n_chr + 1, 0u);
+    std::string text;
+    for (uint32_t c = 0; c < n_chr; ++c) {
+        if (chrs[c].name) text += chrs[c].name;
+        o[c + 1] = (uint32_t)text.size();
+    }
+    if (!F.chr_valid || o != F.h_chr_off || text != F.h_chr_text) {
+        F.chr_valid = false;
+        HIPCHK(ctx, hipStreamSynchronize(st));              // (rows of an earlier call are out, but be sure nothing reads the old table)
+        F.h_chr_off.swap(o);
+        F.h_chr_text.swap(text);
+        HIPCHK(ctx, ensure(ctx, F.chr_text, F.h_chr_text.size() + 4));
+        HIPCHK(ctx, ensure(ctx, F.chr_off, F.h_chr_off.size() * sizeof(uint32_t)));
+        if (!F.h_chr_text.empty()) HIPCHK(ctx, hipMemcpyAsync(F.chr_text, F.h_chr_text.data(), F.h_chr_text.size(), hipMemcpyHostToDevice, st));
+        HIPCHK(ctx, hipMemcpyAsync(F.chr_off, F.h_chr_off.data(), F.h_chr_off.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        HIPCHK(ctx, hipStreamSynchronize(st));
+        F.chr_valid = true;
+    }
+    *chr_max = 1;
+    for (uint32_t c = 0; c < n_chr; ++c) *chr_max = std::max(*chr_max, F.h_chr_off[c + 1] - F.h_chr_off[c]);
+    return CM_OK;
+}
+
 // The PAM rows of pairs [first, first + count) of the resident batch, formatted on the device (bodies and the plan: cm_pam_text.h)
 // on the mapping stream, behind everything queued for the batch.  Two waits: for the rows' total (the caller's buffer may be too
 // small, the device buffer is sized by it), then for the bytes.
@@ -4444,28 +4562,9 @@ int cm_format_pam(cm_ctx *ctx, const cm_chr_info *chrs, uint32_t n_chr, uint64_t
     if (count >= 0xffffffffull) return fail(ctx, CM_ELIMIT, "cm_format_pam: %llu rows in one call", (unsigned long long)count);
     PamRows &F = ctx->pam;
     hipStream_t st = ctx->st.B;
-    {   // the chromosome names: uploaded when they differ from the table on the device
-        std::vector<uint32_t> o((size_t)n_chr + 1, 0u);
-        std::string text;
-        for (uint32_t c = 0; c < n_chr; ++c) {
-            if (chrs[c].name) text += chrs[c].name;
-            o[c + 1] = (uint32_t)text.size();
-        }
-        if (!F.chr_valid || o != F.h_chr_off || text != F.h_chr_text) {
-            F.chr_valid = false;
-            HIPCHK(ctx, hipStreamSynchronize(st));              // (rows of an earlier call are out, but be sure nothing reads the old table)
-            F.h_chr_off.swap(o);
-            F.h_chr_text.swap(text);
-            HIPCHK(ctx, ensure(ctx, F.chr_text, F.h_chr_text.size() + 4));
-            HIPCHK(ctx, ensure(ctx, F.chr_off, F.h_chr_off.size() * sizeof(uint32_t)));
-            if (!F.h_chr_text.empty()) HIPCHK(ctx, hipMemcpyAsync(F.chr_text, F.h_chr_text.data(), F.h_chr_text.size(), hipMemcpyHostToDevice, st));
-            HIPCHK(ctx, hipMemcpyAsync(F.chr_off, F.h_chr_off.data(), F.h_chr_off.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-            HIPCHK(ctx, hipStreamSynchronize(st));
-            F.chr_valid = true;
-        }
-    }
     uint32_t chr_max = 1;
-    for (uint32_t c = 0; c < n_chr; ++c) chr_max = std::max(chr_max, F.h_chr_off[c + 1] - F.h_chr_off[c]);
+    int rc;
+    if ((rc = upload_chr_table(ctx, F, chrs, n_chr, st, &chr_max))) return rc;
     const cmpt::ChrTab ct{F.chr_text, F.chr_off, n_chr};
     const uint32_t cnt = (uint32_t)count, spans = (cnt + cmpt::SPAN_ROWS - 1) / cmpt::SPAN_ROWS;
     HIPCHK(ctx, ensure(ctx, F.off, ((size_t)cnt + 1) * sizeof(uint32_t)));
@@ -4476,7 +4575,6 @@ int cm_format_pam(cm_ctx *ctx, const cm_chr_info *chrs, uint32_t n_chr, uint64_t
     // are summed in 64 bits first
     const bool wide = ctx->rd.name_bytes_max + count * (uint64_t)(cmpt::ROW_FIXED_MAX + 2 * chr_max) >= (1ull << 32);
     unsigned long long *land = ctx->h_pin + PIN_PAM;
-    int rc;
     {
         Timer t(ctx, PC_PAM, st);
         hipLaunchKernelGGL(k_pam_len, dim3(cnt / BLK + 1), dim3(BLK), 0, st, (const cm_mapped_read *)ctx->d_state, (const uint32_t *)ctx->rd.name_off, ct, first, cnt,
@@ -4510,6 +4608,92 @@ int cm_format_pam(cm_ctx *ctx, const cm_chr_info *chrs, uint32_t n_chr, uint64_t
         stats[1] = total;
         for (uint32_t i = 0; i < spans; ++i) ++stats[F.h_path[i] ? 2 : 3];
     }
+    return CM_OK;
+}
+
+// The SAM records of pairs [first, first + count) of the resident batch, formatted on the device (bodies and the plan:
+// cm_sam_text.h): cm_format_pam's steps over 2 * count records, with the formatter's buffers.
+int cm_format_sam(cm_ctx *ctx, const cm_chr_info *chrs, uint32_t n_chr, uint64_t first, uint64_t count, void *out, uint64_t cap, uint64_t *out_bytes,
+                  uint64_t stats[4]) {
+    if (!ctx || !out_bytes || (n_chr && !chrs)) return CM_EINVAL;
+    *out_bytes = 0;
+    if (stats) stats[0] = stats[1] = stats[2] = stats[3] = 0;
+    HIPCHK(ctx, hipSetDevice(ctx->P.device));
+    if (ctx->n_pairs == 0) return fail(ctx, CM_ESTATE, "cm_format_sam: no resident batch");
+    if (!ctx->rd.has_names || !ctx->rd.has_quals)
+        return fail(ctx, CM_ESTATE, "cm_format_sam: the resident batch was not staged with cm_reads_stage_text, flag %s",
+                    ctx->rd.has_quals ? "bit 2 (no names)" : ctx->rd.has_names ? "bit 3 (no qualities)" : "bits 2 and 3 (no names, no qualities)");
+    if (first > ctx->n_pairs || count > ctx->n_pairs - first)
+        return fail(ctx, CM_EINVAL, "cm_format_sam: pairs [%llu, +%llu) of %llu", (unsigned long long)first, (unsigned long long)count, (unsigned long long)ctx->n_pairs);
+    if (!out && cap) return fail(ctx, CM_EINVAL, "cm_format_sam: null out");
+    if (count == 0) return CM_OK;
+    if (count >= 0x7fffffffull) return fail(ctx, CM_ELIMIT, "cm_format_sam: %llu pairs in one call", (unsigned long long)count);
+    PamRows &F = ctx->pam;
+    hipStream_t st = ctx->st.B;
+    uint32_t chr_max = 1;
+    int rc;
+    if ((rc = upload_chr_table(ctx, F, chrs, n_chr, st, &chr_max))) return rc;
+    const cmpt::ChrTab ct{F.chr_text, F.chr_off, n_chr};
+    const uint32_t items = 2u * (uint32_t)count, spans = (items + cmst::SPAN_RECS - 1) / cmst::SPAN_RECS;
+    HIPCHK(ctx, ensure(ctx, F.off, ((size_t)items + 1) * sizeof(uint32_t)));
+    HIPCHK(ctx, ensure(ctx, F.tmp, (size_t)(((uint64_t)items + 1) / S32_B + 2) * sizeof(uint32_t)));
+    HIPCHK(ctx, ensure(ctx, F.path, spans));
+    HIPCHK(ctx, ensure(ctx, F.total, sizeof(unsigned long long)));
+    const ReadBufs &rd = ctx->rd;
+    const SamSrc S{ctx->d_state, rd.names, rd.name_off, {rd.seq1_base + cmc::CM_STAGE_PAD, rd.seq2_base + cmc::CM_STAGE_PAD}, {rd.qual1, rd.qual2}, {rd.off1, rd.off2}};
+    // offsets are uint32: where the records could come to 2^32 bytes (every name twice, every read as SEQ and as QUAL, every number at
+    // its widest) the lengths are summed in 64 bits first
+    const bool wide = 2 * (rd.name_bytes_max + rd.bases) + (uint64_t)items * (cmst::REC_FIXED_MAX + chr_max) >= (1ull << 32);
+    unsigned long long *land = ctx->h_pin + PIN_PAM;
+    {
+        Timer t(ctx, PC_PAM, st);
+        hipLaunchKernelGGL(k_sam_len, dim3(items / BLK + 1), dim3(BLK), 0, st, S, ct, first, items, (uint32_t *)F.off);
+        if (wide) hipLaunchKernelGGL(k_pam_total, dim3(1), dim3(BLK), 0, st, (const uint32_t *)F.off, items, (unsigned long long *)F.total);
+        if ((rc = scan32_on(ctx, st, F.off, (uint64_t)items + 1, F.off, F.tmp, 0u, 0))) return rc;
+    }
+    *land = 0;
+    if (wide) HIPCHK(ctx, hipMemcpyAsync(land, F.total, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    else HIPCHK(ctx, hipMemcpyAsync(land, F.off + items, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    const uint64_t total = *land;
+    *out_bytes = total;
+    if (total >= (1ull << 32)) return fail(ctx, CM_ELIMIT, "cm_format_sam: %llu bytes of records in one call (offsets are 32 bits: format in ranges)", (unsigned long long)total);
+    if (total > cap) return fail(ctx, CM_ELIMIT, "cm_format_sam: %llu bytes of records > cap %llu", (unsigned long long)total, (unsigned long long)cap);
+    HIPCHK(ctx, ensure(ctx, F.out, (size_t)total + 4));
+    {
+        Timer t(ctx, PC_PAM, st);
+        hipLaunchKernelGGL(k_sam_rows, dim3(spans), dim3(cmst::WAVE), 0, st, S, ct, first, items, (const uint32_t *)F.off, (uint8_t *)F.out, (uint8_t *)F.path);
+    }
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipMemcpyAsync(out, F.out, (size_t)total, hipMemcpyDeviceToHost, st));
+    if (stats) {
+        F.h_path.resize(spans);
+        HIPCHK(ctx, hipMemcpyAsync(F.h_path.data(), F.path, spans, hipMemcpyDeviceToHost, st));
+    }
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    if (stats) {
+        stats[0] = items;
+        stats[1] = total;
+        for (uint32_t i = 0; i < spans; ++i) ++stats[F.h_path[i] ? 2 : 3];
+    }
+    return CM_OK;
+}
+
+// test hook: the qualities cm_reads_stage_text kept with the resident batch (flag bit 3), copied back: off1[n] / off2[n] bytes
+int cm_quals_peek(cm_ctx *ctx, uint8_t *qual1, uint64_t cap1, uint8_t *qual2, uint64_t cap2) {
+    if (!ctx) return CM_EINVAL;
+    HIPCHK(ctx, hipSetDevice(ctx->P.device));
+    if (ctx->n_pairs == 0) return fail(ctx, CM_ESTATE, "cm_quals_peek: no resident batch");
+    if (!ctx->rd.has_quals) return fail(ctx, CM_ESTATE, "cm_quals_peek: the resident batch was not staged with cm_reads_stage_text, flag bit 3 (no qualities)");
+    const uint64_t n = ctx->n_pairs;
+    uint64_t total[2] = {0, 0};
+    HIPCHK(ctx, hipMemcpyAsync(&total[0], ctx->rd.off1 + n, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->st.B));
+    HIPCHK(ctx, hipMemcpyAsync(&total[1], ctx->rd.off2 + n, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->st.B));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->st.B));
+    if ((qual1 && cap1 < total[0]) || (qual2 && cap2 < total[1])) return fail(ctx, CM_ELIMIT, "cm_quals_peek: %llu / %llu quality bytes", (unsigned long long)total[0], (unsigned long long)total[1]);
+    if (qual1 && total[0]) HIPCHK(ctx, hipMemcpyAsync(qual1, ctx->rd.qual1, total[0], hipMemcpyDeviceToHost, ctx->st.B));
+    if (qual2 && total[1]) HIPCHK(ctx, hipMemcpyAsync(qual2, ctx->rd.qual2, total[1], hipMemcpyDeviceToHost, ctx->st.B));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->st.B));
     return CM_OK;
 }
 

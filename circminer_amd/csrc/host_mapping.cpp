@@ -115,7 +115,7 @@ struct Run {
     std::vector<uint32_t> clen_guess;
     int early_rc = CM_EINVAL, writer_rc = CM_OK, parser_rc = CM_OK;
     double write_s = 0.0, parse_s = 0.0;           // read after the join
-    bool text_path = false, pam_device = false, want_fixed = false;
+    bool text_path = false, pam_device = false, sam_device = false, want_fixed = false;
     TextBlock tq[4];
     cm_fastq_batch cur{}, nxt{}, nn{};
     Run(const cm_mapping_args *args, char *e, uint64_t cap) : a(args), err(e), err_cap((size_t)cap) {
@@ -328,9 +328,10 @@ struct Run {
     }
     // The device-side tokeniser's path is opt-in and falls back to the host parser, for the run, where that one is needed.
     int choose_text_path() {
-        const char *e = getenv("CM_FASTQ_DEVICE"), *ep = getenv("CM_PAM_DEVICE");
+        const char *e = getenv("CM_FASTQ_DEVICE"), *ep = getenv("CM_PAM_DEVICE"), *es = getenv("CM_SAM_DEVICE");
         pam_device = a->report == 1 && ep && atoi(ep) == 1;      // the rows of report 1 formatted on the device: needs the text path
-        text_path = e && atoi(e) == 1 && (a->report == 0 || pam_device);
+        sam_device = a->report == 2 && es && atoi(es) == 1;      // the records of report 2 likewise
+        text_path = e && atoi(e) == 1 && (a->report == 0 || pam_device || sam_device);
         // bytes per file and block: what batch_pairs records take, first by a guess (a 150-bp record with its name and qualities is
         // ~ 350 bytes), then by what the records of the last batch took -- a block that holds much more than a batch only grows the tail
         want = batch_pairs * 400 + (1u << 16);
@@ -469,7 +470,7 @@ struct Run {
         return CM_OK;
     }
 
-    // ---- the device-side tokeniser's feed: read k+2 (worker) | stage k+1 | rounds of k (+ its PAM rows with CM_PAM_DEVICE=1) | write k-1 (worker) ----
+    // ---- the device-side tokeniser's feed: read k+2 (worker) | stage k+1 | rounds of k (+ its rows with CM_PAM_DEVICE=1 / CM_SAM_DEVICE=1) | write k-1 (worker) ----
     int read_block(TextBlock &B, uint64_t bytes) { return cm_fastq_next_text(fq, bytes, &B.t1, &B.l1, &B.e1, &B.t2, &B.l2, &B.e2); }
     // block -> staged batch; B.tb.n_pairs == 0: the input is at its end.  A block that holds no whole pair is read again, larger.
     int stage_block(TextBlock &B) {
@@ -481,7 +482,7 @@ struct Run {
             B.rec2.resize(batch_pairs + 1);
             pins.cover(B.t1, B.l1);                              // (the same buffer handed out at another offset: widened to cover both)
             pins.cover(B.t2, B.l2);
-            int r = cm_reads_stage_text(cm, B.t1, B.l1, B.t2, B.l2, batch_pairs, (B.e1 ? 1u : 0u) | (B.e2 ? 2u : 0u) | (pam_device ? 4u : 0u), B.rec1.data(), B.rec2.data(), &B.tb);
+            int r = cm_reads_stage_text(cm, B.t1, B.l1, B.t2, B.l2, batch_pairs, (B.e1 ? 1u : 0u) | (B.e2 ? 2u : 0u) | (pam_device ? 4u : 0u) | (sam_device ? 12u : 0u), B.rec1.data(), B.rec2.data(), &B.tb);
             if (r != CM_OK) return r;
             if (B.tb.n_pairs) {
                 if (!want_fixed) want = std::max(B.tb.used1, B.tb.used2) / B.tb.n_pairs * batch_pairs / 100 * 101 + (1u << 16);
@@ -492,14 +493,18 @@ struct Run {
             if ((r = cm_fastq_text_consumed(fq, 0, 0)) != CM_OK || (r = read_block(B, bytes)) != CM_OK) return r;
         }
     }
-    // The PAM rows of the resident batch's n pairs, in ranges: a range whose rows would not fit 32-bit offsets is halved, a buffer that
-    // is too small is replaced by one that holds what is there plus what the device asks for.
+    // The PAM rows or SAM records of the resident batch's n pairs, in ranges: a range whose rows would not fit 32-bit offsets is
+    // halved, a buffer that is too small is replaced by one that holds what is there plus what the device asks for.  A SAM pair is
+    // its name and its reads twice over (~ 800 bytes for 2 x 150 bp, eight PAM rows): its ranges are 2^17 pairs, which keeps the
+    // formatter's device buffer near 100 MB; the page-locked buffer holds the batch's records.
     int format_rows(RowBuf &RB, uint64_t n) {
-        uint64_t done = 0, step = std::min<uint64_t>(n, 1ull << 22);
+        const auto format = sam_device ? cm_format_sam : cm_format_pam;
+        const char *const name = sam_device ? "cm_format_sam" : "cm_format_pam";
+        uint64_t done = 0, step = std::min<uint64_t>(n, sam_device ? 1ull << 17 : 1ull << 22);
         while (done < n) {
             const uint64_t c = std::min(step, n - done);
             uint64_t got = 0;
-            int r = cm_format_pam(cm, chrs, n_chr, done, c, RB.p ? (char *)RB.p + RB.n : nullptr, RB.cap - RB.n, &got, nullptr);
+            int r = format(cm, chrs, n_chr, done, c, RB.p ? (char *)RB.p + RB.n : nullptr, RB.cap - RB.n, &got, nullptr);
             if (r == CM_ELIMIT && got >= (1ull << 32) && c > 1) {
                 step = c / 2;
                 continue;
@@ -507,14 +512,14 @@ struct Run {
             if (r == CM_ELIMIT && got > RB.cap - RB.n) {
                 const uint64_t cap = RB.n + got + got / c * (n - done - c) + (1u << 16);
                 void *np = nullptr;
-                if ((r = cm_host_alloc(cm, cap, &np)) != CM_OK) return failed(r, "cm_host_alloc (PAM rows)");
+                if ((r = cm_host_alloc(cm, cap, &np)) != CM_OK) return failed(r, "cm_host_alloc (rows)");
                 if (RB.n) memcpy(np, RB.p, RB.n);
                 if (RB.p) (void)cm_host_free(cm, RB.p);
                 RB.p = np;
                 RB.cap = cap;
                 continue;
             }
-            if (r != CM_OK) return failed(r, "cm_format_pam");
+            if (r != CM_OK) return failed(r, name);
             RB.n += got;
             done += c;
         }
@@ -547,10 +552,10 @@ struct Run {
             start_parser(more, [this, k]() { return read_block(tq[(k + 2) & 3], want); });
             if ((rc = cm_map_rounds(cm, all.data(), (int)n_con, 1)) != CM_OK) return failed(rc, "cm_map_rounds");
             RB.n = 0;
-            if (pam_device && (rc = format_rows(RB, n)) != CM_OK) return rc;
+            if ((pam_device || sam_device) && (rc = format_rows(RB, n)) != CM_OK) return rc;
             if ((rc = collect_records(R, n)) != CM_OK || (rc = end_device_leg(R, n, more, td)) != CM_OK) return rc;
             rc = hand_to_writer([this, &R, &B, &RB]() {
-                const int r = pam_device ? cm_write_bytes(w_map, RB.p, RB.n) : CM_OK;
+                const int r = (pam_device || sam_device) ? cm_write_bytes(w_map, RB.p, RB.n) : CM_OK;
                 if (r != CM_OK || !R.n_rec) return r;
                 return cm_write_remain_text(w_rem, B.t1, B.rec1.data(), B.t2, B.rec2.data(), R.recs.data(), R.n_rec);
             });

@@ -228,6 +228,8 @@ def load(path: str = LIB_PATH) -> C.CDLL:
         "cm_fastq_text_consumed": (C.c_int, [vp, C.c_uint64, C.c_uint64]),
         "cm_write_remain_text": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_uint64]),
         "cm_format_pam": (C.c_int, [vp, pp(ChrInfo), C.c_uint32, C.c_uint64, C.c_uint64, vp, C.c_uint64, pp(C.c_uint64), pp(C.c_uint64)]),
+        "cm_format_sam": (C.c_int, [vp, pp(ChrInfo), C.c_uint32, C.c_uint64, C.c_uint64, vp, C.c_uint64, pp(C.c_uint64), pp(C.c_uint64)]),
+        "cm_quals_peek": (C.c_int, [vp, vp, C.c_uint64, vp, C.c_uint64]),
         "cm_state_poke": (C.c_int, [vp, vp]),
         "cm_write_bytes": (C.c_int, [vp, vp, C.c_uint64]),
         "cm_map_round": (C.c_int, [vp, C.c_int, C.c_int]),
@@ -317,7 +319,7 @@ EXPORTED_SYMBOLS = ["cm_create", "cm_destroy", "cm_last_error", "cm_load_contig"
                     "cm_host_close_index", "cm_fastq_open", "cm_fastq_open_shard", "cm_merge_parts", "cm_fastq_next", "cm_fastq_set_release_hook", "cm_fastq_close", "cm_writer_open", "cm_write_remain",
                     "cm_write_pam", "cm_write_sam_header", "cm_write_sam", "cm_writer_flush", "cm_writer_close", "cm_mapping_run", "cm_sort_remain", "cm_circ_report", "cm_circ_call", "cm_circ_run", "cm_host_gene_overlap", "cm_regional_table_build", "cm_regional_table_free",
                     "cm_build_contig", "cm_index_download", "cm_reads_stage_text", "cm_reads_peek", "cm_fastq_next_text", "cm_fastq_text_consumed",
-                    "cm_write_remain_text", "cm_format_pam", "cm_state_poke", "cm_write_bytes"]
+                    "cm_write_remain_text", "cm_format_pam", "cm_state_poke", "cm_write_bytes", "cm_format_sam", "cm_quals_peek"]
 
 
 class HostIndex:
@@ -747,17 +749,18 @@ class HotPath:
         p = prior.ctypes.data if prior is not None else None
         self._chk(self.L.cm_reads_stage(self.h, C.byref(batch.c), p), "cm_reads_stage")
 
-    def stage_text(self, text1, text2, max_pairs, eof1=True, eof2=True, keep_names=False):
+    def stage_text(self, text1, text2, max_pairs, eof1=True, eof2=True, keep_names=False, keep_quals=False):
         """cm_reads_stage_text: the next batch staged from FASTQ text, tokenised on the device.  text1 / text2: uint8 arrays or
         bytes.  Returns (TextBatch, rec1, rec2); n_pairs == 0: nothing was staged.  keep_names (flag bit 2): the R1 names stay on
-        the device with the batch, for format_pam."""
+        the device with the batch, for format_pam; keep_quals (flag bit 3): so do the quality lines of both files, for format_sam,
+        which needs both."""
         t1 = np.frombuffer(text1, np.uint8) if isinstance(text1, (bytes, bytearray)) else np.ascontiguousarray(text1, dtype=np.uint8)
         t2 = np.frombuffer(text2, np.uint8) if isinstance(text2, (bytes, bytearray)) else np.ascontiguousarray(text2, dtype=np.uint8)
         cap = int(min(max_pairs, min(t1.size, t2.size) // 4)) + 1           # a record has four bytes at least
         rec1, rec2 = np.zeros(cap, np.uint64), np.zeros(cap, np.uint64)
         tb = TextBatch()
         self._chk(self.L.cm_reads_stage_text(self.h, t1.ctypes.data if t1.size else None, t1.size, t2.ctypes.data if t2.size else None, t2.size, int(max_pairs),
-                                             int(bool(eof1)) | int(bool(eof2)) << 1 | int(bool(keep_names)) << 2, rec1.ctypes.data, rec2.ctypes.data, C.byref(tb)), "cm_reads_stage_text")
+                                             int(bool(eof1)) | int(bool(eof2)) << 1 | int(bool(keep_names)) << 2 | int(bool(keep_quals)) << 3, rec1.ctypes.data, rec2.ctypes.data, C.byref(tb)), "cm_reads_stage_text")
         self._staged_n = int(tb.n_pairs)
         return tb, rec1[:self._staged_n + 1], rec2[:self._staged_n + 1]
 
@@ -765,19 +768,36 @@ class HotPath:
         """cm_format_pam: the PAM rows of pairs [first, first + count) of the resident batch (staged with keep_names), formatted on
         the device.  chrs: chromosome table rows (name, contig id, start, length).  Returns (bytes, stats); cap: the size of the
         buffer offered (default: what the rows need, asked for first)."""
+        return self._format_rows("cm_format_pam", chrs, first, count, cap)
+
+    def format_sam(self, chrs=(), first=0, count=None, cap=None):
+        """cm_format_sam: the SAM records (two per pair, no header) of pairs [first, first + count) of the resident batch (staged
+        with keep_names and keep_quals), formatted on the device.  Arguments and result as format_pam's; stats count records."""
+        return self._format_rows("cm_format_sam", chrs, first, count, cap)
+
+    def _format_rows(self, fn, chrs, first, count, cap):
+        call = getattr(self.L, fn)
         table = chr_array(list(chrs))
         n = self.n - first if count is None else count
         got = C.c_uint64(0)
         stats = (C.c_uint64 * 4)()
         if cap is None:
-            rc = self.L.cm_format_pam(self.h, table, len(chrs), int(first), int(n), None, 0, C.byref(got), None)
+            rc = call(self.h, table, len(chrs), int(first), int(n), None, 0, C.byref(got), None)
             if rc not in (0, -6) or (rc == -6 and got.value >= 1 << 32):        # CM_ELIMIT with the needed size is the answer here
-                self._chk(rc, "cm_format_pam")
+                self._chk(rc, fn)
             cap = got.value
         buf = np.full(int(cap) + 64, 0xA5, np.uint8)                             # (the bytes behind cap show a write past it)
-        self._chk(self.L.cm_format_pam(self.h, table, len(chrs), int(first), int(n), buf.ctypes.data, int(cap), C.byref(got), stats), "cm_format_pam")
+        self._chk(call(self.h, table, len(chrs), int(first), int(n), buf.ctypes.data, int(cap), C.byref(got), stats), fn)
         assert got.value <= cap and bool((buf[int(cap):] == 0xA5).all())
         return buf[:got.value].tobytes(), list(stats)
+
+    def peek_quals(self):
+        """cm_quals_peek (test hook): (qual1, qual2) of the resident batch as cm_reads_stage_text kept them (keep_quals), in the
+        layout of peek_reads' seq1 / seq2"""
+        _, off1, _, off2 = self.peek_reads()
+        q1, q2 = np.zeros(max(int(off1[-1]), 1), np.uint8), np.zeros(max(int(off2[-1]), 1), np.uint8)
+        self._chk(self.L.cm_quals_peek(self.h, q1.ctypes.data, q1.size, q2.ctypes.data, q2.size), "cm_quals_peek")
+        return q1[:int(off1[-1])], q2[:int(off2[-1])]
 
     def poke_states(self, states):
         """cm_state_poke (test hook): the carried states of the resident batch overwritten (MAPPED_DTYPE, n records)"""

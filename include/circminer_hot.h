@@ -249,8 +249,15 @@ int cm_reads_swap(cm_ctx *ctx);
  *     cm_fastq_next would put it into names1: token 0 of the header line (tokens are runs of bytes other than ' ' behind the
  *     '@') without a trailing "/x", up to its first NUL byte; empty for a header without a token.  The names belong to the batch:
  *     they travel with its read buffers through cm_reads_swap and stay valid while the batch is resident, also while the next
- *     cm_reads_stage_text overwrites the text.  cm_format_pam is their reader.  R2 names are not kept.  Without the bit the
- *     kernels launched, the buffers and the results are those of a stage without names. */
+ *     cm_reads_stage_text overwrites the text.  cm_format_pam and cm_format_sam are their readers.  R2 names are not kept.
+ *     Without the bit the kernels launched, the buffers and the results are those of a stage without names.
+ *   - flags bit 3 (value 8, "keep qualities"): the stage also leaves on the device the quality line of every staged record of both
+ *     files, in the layout of the bases: quality of read i = qual[off[i] .. off[i + 1]), sharing off1 / off2 (the stage has checked
+ *     that the lines are as long).  The qualities belong to the batch exactly as the names do: they travel with its read buffers
+ *     through cm_reads_swap and the cross-batch prefetch and outlive the text.  cm_format_sam is their reader (cm_quals_peek, a
+ *     test hook, copies them back).  HBM: the bytes of the bases once more, in each of the two buffer sets, allocated only when
+ *     the bit is given.  Bits 2 and 3 are independent; without bit 3 the kernels launched, the buffers and the results are those
+ *     of a stage without it. */
 typedef struct cm_text_batch {
     uint64_t n_pairs;        /* pairs staged */
     uint64_t used1, used2;   /* bytes of text1 / text2 consumed = start of the first record not staged */
@@ -404,6 +411,9 @@ int cm_annot_batch(cm_ctx *ctx, int slot, const cm_params *P, const cm_annot_req
  * four NULL return only *n_pairs. */
 int cm_reads_peek(cm_ctx *ctx, uint8_t *seq1, uint64_t cap1, uint64_t *off1, uint8_t *seq2, uint64_t cap2, uint64_t *off2,
                   uint64_t *n_pairs);
+/* test hook: the qualities kept by cm_reads_stage_text (flag bit 3) for the resident batch copied back, off1[n] / off2[n] bytes
+ * (CM_ELIMIT when cap1 / cap2 is smaller; a NULL pointer skips that array).  CM_ESTATE: no resident batch, or one without them. */
+int cm_quals_peek(cm_ctx *ctx, uint8_t *qual1, uint64_t cap1, uint8_t *qual2, uint64_t cap2);
 /* test hook, the counterpart of cm_reads_download: overwrite the carried states of the resident batch (n_pairs records), behind
  * everything queued for it.  CM_ESTATE without a resident batch.  Flags and categories are not touched. */
 int cm_state_poke(cm_ctx *ctx, const cm_mapped_read *states);
@@ -411,7 +421,8 @@ int cm_state_poke(cm_ctx *ctx, const cm_mapped_read *states);
 /* ---------------- timing hooks for bench.py (HIP events on the ctx stream) ---------------- */
 /* Milliseconds spent in each kernel class since the last cm_prof_reset(), and launch counts:
  * [0]=k_seed [1]=k_chain (light problems) [2]=k_pair (light pairs) [3]=k_scan_* [4]=k_pair_heavy
- * [5]=class / counting-sort kernels [6]=k_chain_heavy [7]=the kernels of cm_format_pam (no launch count); launches[7] = first
+ * [5]=class / counting-sort kernels [6]=k_chain_heavy [7]=the row formatters: the kernels of cm_format_pam and cm_format_sam (no
+ * launch count); launches[7] = first
  * rounds taken over from the cross-batch prefetch of cm_map_rounds.  [1] and [2] are timed up to the join with the second
  * stream, on which the heavy kernels [6] / [4] run concurrently. */
 int cm_prof_enable(cm_ctx *ctx, int on);
@@ -583,8 +594,29 @@ int cm_write_pam(cm_writer *w, const cm_fastq_batch *b, const cm_mapped_read *st
  * After cm_prof_enable(ctx, 1) the formatter's kernels are timed by HIP events into ms[7] of cm_prof_get. */
 int cm_format_pam(cm_ctx *ctx, const cm_chr_info *chrs, uint32_t n_chr, uint64_t first, uint64_t count,
                   void *out, uint64_t cap, uint64_t *out_bytes, uint64_t stats[4] /* nullable */);
-/* Appends n raw bytes to the writer's first file through its buffer (the rows cm_format_pam delivers); CM_EIO like the other
- * cm_write_* calls. */
+/* <out>.mapping.sam records (cm_write_sam / write_sam_rec_pe) of pairs [first, first + count) of the resident batch, formatted BY
+ * THE DEVICE from the states in HBM, the names (flag bit 2) and qualities (flag bit 3) kept by cm_reads_stage_text and the bases in
+ * the read buffers: the bytes cm_write_sam writes for the same pairs, in pair order, two records per pair (mate 1, then mate 2;
+ * QNAME is the R1 name in both) -- a pair is mapped for type <= CM_CHIORF || type == CM_CONGEN || type == CM_CONGNM (signed),
+ * TLEN is "%u" of the int32 with the sign by spos_r1 < spos_r2, a record with the reverse flag prints the reverse complement cut at
+ * the first byte outside ACGTNacgtn and the reversed qualities, "-" for a chr_id outside [0, n_chr).  One value differs in
+ * principle: for tlen == INT_MIN the host's negation is signed overflow; the device negates in unsigned arithmetic and prints
+ * 2147483648 for both mates.  The header is not formatted here: cm_write_sam_header.  chrs: as for cm_format_pam (one table per
+ * context, shared by both formatters).
+ * Ordering is that of cm_collect_records: the work is queued behind everything queued for the resident batch (pair stages, the
+ * re-run launch, fall-backs) and the call returns when the bytes are in out (page-locked or pageable, cap bytes); it neither
+ * waits for nor disturbs the staging stream or a cross-batch prefetch in flight.
+ * CM_ESTATE: no resident batch, or one staged without bit 2 or without bit 3 (cm_last_error names which).
+ * CM_EINVAL: first + count > n_pairs, or out == NULL with cap > 0.  CM_ELIMIT with the needed size in *out_bytes and nothing
+ * written: cap is too small; CM_ELIMIT also when the records of one call come to 2^32 bytes or more (offsets are 32 bits: format
+ * in ranges).  count == 0 is CM_OK with *out_bytes == 0.  A refusal leaves the resident batch as it was.
+ * stats (nullable): [0] records (2 count), [1] bytes, [2] / [3] spans of 16 records (one wave each) that were put together in the
+ * wave's LDS window and streamed out as whole words / that were larger than the window (long names, long reads) and stored to the
+ * output directly.  After cm_prof_enable(ctx, 1) the formatter's kernels are timed by HIP events into ms[7] of cm_prof_get. */
+int cm_format_sam(cm_ctx *ctx, const cm_chr_info *chrs, uint32_t n_chr, uint64_t first, uint64_t count,
+                  void *out, uint64_t cap, uint64_t *out_bytes, uint64_t stats[4] /* nullable */);
+/* Appends n raw bytes to the writer's first file through its buffer (the rows cm_format_pam / cm_format_sam deliver); CM_EIO like
+ * the other cm_write_* calls. */
 int cm_write_bytes(cm_writer *w, const void *p, uint64_t n);
 /* <out>.mapping.sam (--sam): header = SAMOutput::print_header (src/output.cpp:301-311, one @SQ per row of the chromosome
  * table), records = write_sam_rec_pe with set_flag_pe / set_output_pe (src/output.cpp:118-277): two lines per pair,
@@ -608,13 +640,17 @@ void cm_writer_close(cm_writer *w);
  * (cm_build_contig) while the next contig's sequence is read; params.kmer must be given then (0 is CM_EINVAL).
  * With CM_FASTQ_DEVICE=1 in the environment, report == 0 and two regular plain-text FASTQ files of fresh reads (any rank / world)
  * the batches are tokenised on the device: cm_fastq_next_text -> cm_reads_stage_text -> cm_write_remain_text, the same files
- * byte for byte; in every other case (PAM / SAM rows need every pair's name on the host; gzip, pipes and carried 23-token headers
- * need the host parser) and with the variable unset the host parser feeds the device as before.  CM_FASTQ_DEVICE_BLOCK=<bytes>
+ * byte for byte; in every other case (PAM / SAM rows without their own variable, below, need every pair's name on the host; gzip,
+ * pipes and carried 23-token headers need the host parser) and with the variable unset the host parser feeds the device as before.  CM_FASTQ_DEVICE_BLOCK=<bytes>
  * (a test knob) sets the bytes per file and block; the default is sized for batch_pairs.
  * With CM_PAM_DEVICE=1 in addition to CM_FASTQ_DEVICE=1 the device tokeniser's path also covers report == 1 (same conditions on
  * the input): the batches are staged with their names (flag bit 2), the PAM rows of a batch are formatted on the device
  * (cm_format_pam, into one of two page-locked buffers) and the writer thread appends them with cm_write_bytes -- the same
- * <out>.mapping.pam byte for byte.  report == 2 (SAM rows need bases and qualities) stays with the host parser. */
+ * <out>.mapping.pam byte for byte.
+ * With CM_SAM_DEVICE=1 in addition to CM_FASTQ_DEVICE=1 the path covers report == 2 in the same way: the batches are staged with
+ * their names and qualities (flag bits 2 | 3), the SAM records of a batch are formatted on the device (cm_format_sam, in ranges of
+ * at most 2^17 pairs, into one of two page-locked buffers that hold a batch's records) and the writer thread appends them behind
+ * the header -- the same <out>.mapping.sam byte for byte.  Without its variable a report mode stays with the host parser. */
 typedef struct cm_mapping_args {
     const char *index_path;        /* <ref>.packed.fa.index        */
     const char *index_info_path;   /* <ref>.packed.fa.index.info   */

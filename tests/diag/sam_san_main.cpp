@@ -1,0 +1,186 @@
+// Stand-alone sanitizer pass over the bodies of circminer_amd/csrc/cm_sam_text.h through the host emulation (tests/hostemu_sam.cpp):
+// directed states (every printed field at the boundaries of its format, every combination of mapped / strands / spos order) over
+// reads of every short length, reads with a byte that has no complement at the end, the start and the middle, lower-case reads and
+// a run of long names; whole batches and ranges, the window's rule, every span direct, and a small window; every argument array an
+// exact-size heap block.  The records are compared with printf's.  CPU only, no Python.  From the repository root:
+//   g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=all -I include -I circminer_amd/csrc \
+//       tests/diag/sam_san_main.cpp tests/hostemu_sam.cpp -o /tmp/sam_san && /tmp/sam_san
+#include <climits>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <random>
+#include <string>
+#include <vector>
+#include "circminer_hot.h"
+extern "C" int emu_quals(const uint8_t *, uint64_t, uint32_t, const uint64_t *, uint64_t, uint8_t *);
+extern "C" int emu_format_sam(const cm_mapped_read *, uint64_t, const uint8_t *, const uint32_t *, const uint8_t *, const uint64_t *, const uint8_t *, const uint64_t *,
+                              const uint8_t *, const uint8_t *, const cm_chr_info *, uint32_t, uint64_t, uint64_t, uint8_t *, uint64_t, uint64_t *, uint64_t *, uint64_t,
+                              uint32_t, uint32_t *, uint64_t *);
+
+static const uint32_t U32V[] = {0u, 9u, 10u, 99u, 100u, 999999999u, 1000000000u, 4294967295u};
+static const int32_t INTV[] = {0, -1, -9, -10, INT_MIN + 1, INT_MAX, 1000000000};
+static const int32_t TYPEV[] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, -1, 14, -9, -10, INT_MIN, INT_MAX, 1000000000, 100, 13};
+
+static cm_mapped_read directed(uint32_t i, int n_chr) {
+    cm_mapped_read m;
+    memset(&m, 0xee, sizeof m);
+    m.type = TYPEV[i % 23];
+    uint32_t *u[8] = {&m.spos_r1, &m.spos_r2, &m.epos_r1, &m.epos_r2, &m.qspos_r1, &m.qspos_r2, &m.qepos_r1, &m.qepos_r2};
+    for (uint32_t j = 0; j < 8; ++j) *u[j] = U32V[(i + j) % 8];
+    if (i % 5 == 0) m.spos_r2 = m.spos_r1;
+    m.ed_r1 = INTV[i % 7];
+    m.ed_r2 = INTV[(i + 2) % 7];
+    m.tlen = INTV[(i + 4) % 7];
+    m.junc_num = i % 2 ? 65535 : 0;
+    m.gm_compatible = (uint8_t)(i % 3 == 2 ? 255 : i % 3);
+    m.r1_forward = i & 1;
+    m.r2_forward = (i >> 1) & 1;
+    const int32_t ids[4] = {-1, 0, n_chr - 1, n_chr};
+    m.chr_id = ids[i % 4];
+    m.contig_num = (int32_t)(i % 5) - 1;
+    return m;
+}
+static char comp_of(unsigned char c) {
+    const char *from = "ACGTNacgtn", *to = "TGCANTGCAN";
+    for (int i = 0; from[i]; ++i)
+        if ((unsigned char)from[i] == c) return to[i];
+    return 0;
+}
+// the record of one mate, the plain way
+static std::string printf_rec(const std::string &name, const cm_mapped_read &m, int mate, const std::string &seq, const std::string &qual, const cm_chr_info *chrs, int n_chr) {
+    const bool mapped = m.type <= 2 || m.type == 5 || m.type == 7;
+    unsigned flag = 1u | (m.type == 0 ? 2u : 0u) | (mate ? 128u : 64u);
+    if (!mapped) flag |= 12u;
+    else {
+        if (!(mate ? m.r2_forward : m.r1_forward)) flag |= 16u;
+        if (!(mate ? m.r1_forward : m.r2_forward)) flag |= 32u;
+    }
+    const char *cn = m.chr_id >= 0 && m.chr_id < n_chr ? chrs[m.chr_id].name : "-";
+    const long long t = (m.spos_r1 < m.spos_r2) == (mate == 0) ? (long long)m.tlen : -(long long)m.tlen;
+    char buf[256];
+    snprintf(buf, sizeof buf, "\t%u\t%s\t%u\t255\t*\t%s\t%u\t%u\t", flag, mapped ? cn : "*", mapped ? (mate ? m.spos_r2 : m.spos_r1) : 0u, mapped ? "=" : "*",
+             mapped ? (mate ? m.spos_r1 : m.spos_r2) : 0u, mapped ? (uint32_t)t : 0u);
+    std::string r = name + buf;
+    if (flag & 16u) {
+        std::string rc, rq(qual.rbegin(), qual.rend());
+        for (size_t x = 0; x < seq.size(); ++x) {
+            const char c = comp_of((unsigned char)seq[seq.size() - 1 - x]);
+            if (!c) break;
+            rc += c;
+        }
+        r += rc + "\t" + rq;
+    } else r += seq + "\t" + qual;
+    snprintf(buf, sizeof buf, "\tAT:i:%d\tNM:i:%d\tJC:i:%d\tTC:i:%d\n", m.type, mapped ? (mate ? m.ed_r2 : m.ed_r1) : 0, mapped ? (int)m.junc_num : 0,
+             mapped ? (int)(m.gm_compatible != 0) : 0);
+    return r + buf;
+}
+template <class T> static T *exact(const std::vector<T> &v) {            // an exact-size heap copy
+    T *p = (T *)malloc(v.size() * sizeof(T) + (v.empty() ? 1 : 0));
+    if (!v.empty()) memcpy(p, v.data(), v.size() * sizeof(T));
+    return p;
+}
+
+int main() {
+    const std::string forty(40, 'x');
+    const cm_chr_info chrs[4] = {{"c", 1, 0, 1000}, {forty.c_str(), 1, 1000, 500}, {"chr2", 2, 0, 70000}, {"7", 2, 70000, 10}};
+    const char odd[] = {'.', 'R', 'U', '\r', '\0'};
+    const uint32_t short_len[] = {0, 1, 2, 3, 4, 5, 7, 8, 9};
+    std::mt19937_64 rng(13);
+    uint64_t recs_checked = 0, staged = 0, direct = 0, cut = 0;
+    for (uint32_t n : {1u, 2u, 7u, 8u, 9u, 65u, 323u}) {
+        std::vector<std::string> name(n), seq[2], qual[2];
+        std::string text[2];
+        for (int f = 0; f < 2; ++f) {
+            seq[f].resize(n);
+            qual[f].resize(n);
+            for (uint32_t i = 0; i < n; ++i) {
+                uint32_t len = 30 + rng() % 121;
+                if ((i + 3 * f) % 11 < 9 && i % 2 == (uint32_t)f) len = short_len[(i + 3 * f) % 11];
+                std::string s, q;
+                for (uint32_t k = 0; k < len; ++k) {
+                    s += (i % 13 == 5 ? "acgtn" : "ACGTNacgtn")[rng() % (i % 13 == 5 ? 5 : 10)];
+                    q += (char)(33 + rng() % 41);
+                }
+                if (len > 12 && i % 3 == 1) s[(i / 3) % 3 == 0 ? len - 1 : (i / 3) % 3 == 1 ? 0 : len / 2] = odd[(i / 9) % 5];
+                seq[f][i] = s;
+                qual[f][i] = q;
+                if (f == 0) {
+                    const size_t nl = (n >= 64 && i >= n / 2 && i < n / 2 + 40) ? 300 + rng() % 101 : rng() % 30;
+                    for (size_t k = 0; k < nl; ++k) name[i] += (char)('a' + rng() % 26);
+                }
+                text[f] += "@" + name[i] + "/" + (f ? "2" : "1") + "\n" + s + "\n+\n" + q + "\n";
+            }
+        }
+        std::vector<uint8_t> names, s1, s2;
+        std::vector<uint32_t> name_off{0u};
+        std::vector<uint64_t> off1{0ull}, off2{0ull};
+        for (uint32_t i = 0; i < n; ++i) {
+            names.insert(names.end(), name[i].begin(), name[i].end());
+            name_off.push_back((uint32_t)names.size());
+            s1.insert(s1.end(), seq[0][i].begin(), seq[0][i].end());
+            off1.push_back(s1.size());
+            s2.insert(s2.end(), seq[1][i].begin(), seq[1][i].end());
+            off2.push_back(s2.size());
+        }
+        uint8_t *p_names = exact(names), *p_s1 = exact(s1), *p_s2 = exact(s2);
+        uint32_t *p_noff = exact(name_off);
+        uint64_t *p_off1 = exact(off1), *p_off2 = exact(off2);
+        // the qualities through the copy's body, out of the text
+        uint8_t *p_q[2];
+        for (int f = 0; f < 2; ++f) {
+            const std::vector<uint8_t> t(text[f].begin(), text[f].end());
+            uint8_t *pt = exact(t);
+            const std::vector<uint64_t> &off = f ? off2 : off1;
+            p_q[f] = (uint8_t *)malloc(off[n] ? off[n] : 1);
+            if (emu_quals(pt, t.size(), n, f ? p_off2 : p_off1, n + f, p_q[f]) != CM_OK) { printf("emu_quals failed at n = %u\n", n); return 1; }
+            for (uint32_t i = 0; i < n; ++i)
+                if (memcmp(p_q[f] + off[i], qual[f][i].data(), qual[f][i].size()) != 0) { printf("quality %u of file %d, n = %u differs\n", i, f + 1, n); return 1; }
+            free(pt);
+        }
+        std::vector<cm_mapped_read> stv(n);
+        for (uint32_t i = 0; i < n; ++i) stv[i] = directed(i, 4);
+        cm_mapped_read *st = exact(stv);
+        const uint64_t ranges[][2] = {{0, n}, {n / 3, n - n / 3}, {7 % n, (uint64_t)(n - 7 % n < 2 ? n - 7 % n : 2)}, {n, 0}, {n - 1, 1}};
+        for (const auto &r : ranges)
+            for (int n_chr : {4, 0})
+                for (uint32_t window : {0u, 1u, 3000u}) {
+                    std::string ref;
+                    for (uint64_t i = r[0]; i < r[0] + r[1]; ++i)
+                        for (int mate = 0; mate < 2; ++mate) {
+                            const std::string rec = printf_rec(name[i], st[i], mate, seq[mate][i], qual[mate][i], chrs, n_chr);
+                            cut += rec.size() < printf_rec(name[i], st[i], mate, std::string(seq[mate][i].size(), 'A'), qual[mate][i], chrs, n_chr).size();
+                            ref += rec;
+                        }
+                    uint64_t got = 0, stats[4], writes[3] = {0, 0, 0};
+                    const int rc0 = emu_format_sam(st, n, p_names, p_noff, p_s1, p_off1, p_s2, p_off2, p_q[0], p_q[1], chrs, (uint32_t)n_chr, r[0], r[1], nullptr, 0, &got,
+                                                   nullptr, 5, window, nullptr, nullptr);
+                    if (got != ref.size() || rc0 != (ref.empty() ? CM_OK : CM_ELIMIT)) { printf("size of range [%llu, +%llu) of %u differs\n", (unsigned long long)r[0], (unsigned long long)r[1], n); return 1; }
+                    uint8_t *out = (uint8_t *)malloc(ref.size() ? ref.size() : 1);
+                    const int rc = emu_format_sam(st, n, p_names, p_noff, p_s1, p_off1, p_s2, p_off2, p_q[0], p_q[1], chrs, (uint32_t)n_chr, r[0], r[1], out, ref.size(), &got,
+                                                  stats, n + r[0], window, nullptr, writes);
+                    if (rc != CM_OK || memcmp(out, ref.data(), ref.size()) != 0) {
+                        printf("records of range [%llu, +%llu) of %u differ (rc %d, window %u)\n", (unsigned long long)r[0], (unsigned long long)r[1], n, rc, window);
+                        return 1;
+                    }
+                    if (r[1] && (writes[0] != 1 || writes[1] != 1 || writes[2] != 0)) { printf("a byte written %llu .. %llu times, %llu records of another length\n", (unsigned long long)writes[0], (unsigned long long)writes[1], (unsigned long long)writes[2]); return 1; }
+                    recs_checked += 2 * r[1];
+                    staged += stats[2];
+                    direct += stats[3];
+                    free(out);
+                }
+        free(st);
+        free(p_q[0]);
+        free(p_q[1]);
+        free(p_off1);
+        free(p_off2);
+        free(p_noff);
+        free(p_names);
+        free(p_s1);
+        free(p_s2);
+    }
+    if (!staged || !direct || !cut) { printf("a path was never taken (%llu staged, %llu direct, %llu cut)\n", (unsigned long long)staged, (unsigned long long)direct, (unsigned long long)cut); return 1; }
+    printf("sanitizer pass: %llu records equal printf's, %llu spans staged, %llu direct, %llu reversed records cut short\n", (unsigned long long)recs_checked,
+           (unsigned long long)staged, (unsigned long long)direct, (unsigned long long)cut);
+    return 0;
+}
