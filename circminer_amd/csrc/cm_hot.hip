@@ -46,7 +46,7 @@ constexpr int BLK_CHAIN = 64;
 // Profile classes: the index of cm_ctx::ms[] / launches[], of Timer, launch() and cm_prof_get (include/circminer_hot.h).  PC_NONE:
 // a launch no class counts (index build, collect, the small housekeeping kernels).
 enum ProfClass { PC_NONE = -1, PC_SEED = 0, PC_CHAIN = 1, PC_PAIR = 2, PC_SCAN = 3, PC_HEAVY = 4, PC_ORDER = 5, PC_CHAIN_HEAVY = 6, PC_PREFETCH = 7,
-                 PC_PAM = 7 /* the same slot: PC_PREFETCH counts launches and has no time, the row formatters (cm_format_pam, cm_format_sam) have time and count none */, PC_COUNT = 8 };
+                 PC_ROWS = 7 /* the same slot: PC_PREFETCH counts launches and has no time, the row formatters (cm_format_pam, cm_format_sam) have time and count none */, PC_COUNT = 8 };
 // The words of cm_ctx::d_counters.  0 - 6 are public (cm_prof_counters, include/circminer_hot.h); from 8 on what a diagnostic build
 // accumulates, read by the scripts of tests/diag through cm_debug_counters at these indices.  The two diagnostic builds overlap (they
 // are never one build): both write word 24.
@@ -70,11 +70,11 @@ enum Pin {
     PIN_CELLS = 8,                                   // + 2 * seed set: DP cells of the tile, + 1: of its largest problem
     PIN_RERUN_N = 12, PIN_FALL_N = 14,               // + chain-record set: length of the re-run list / of the pipeline's fall-back list
     PIN_TEXT = 16,                                   // cm_reads_stage_text: the result block of the tokeniser (cmft::RES_WORDS words)
-    PIN_PAM = 26,                                    // cm_format_pam / cm_format_sam: the bytes of the rows
+    PIN_ROWS = 26,                                    // cm_format_pam / cm_format_sam: the bytes of the rows
     PIN_WORDS = 32
 };
 constexpr size_t PIN_BYTES = PIN_WORDS * sizeof(unsigned long long);        // allocated and cleared in cm_create
-static_assert(PIN_BYTES == 256 && PIN_FALL_N + 1 < PIN_TEXT && PIN_CELLS + 3 < PIN_RERUN_N && PIN_TEXT + cmft::RES_WORDS <= PIN_PAM && PIN_PAM < PIN_WORDS,
+static_assert(PIN_BYTES == 256 && PIN_FALL_N + 1 < PIN_TEXT && PIN_CELLS + 3 < PIN_RERUN_N && PIN_TEXT + cmft::RES_WORDS <= PIN_ROWS && PIN_ROWS < PIN_WORDS,
               "the landing zone has 32 words");
 struct ReadsDev {
     const uint8_t *seq1, *seq2;
@@ -2100,7 +2100,7 @@ __global__ void k_ft_finish(FtShape sh, const uint64_t *off1, const uint64_t *of
     res[cmft::RES_USED2] = rec2[n];
 }
 
-// ---- the names cm_reads_stage_text keeps (flag bit 2) and cm_format_pam (bodies and the plan: cm_pam_text.h) ----------------
+// ---- the names (flag bit 2, the rule: cm_pam_text.h) and the qualities (flag bit 3) cm_reads_stage_text keeps -----------------
 // one lane per record of file 1: where its name starts in the text and how long it is; item n is 0, the slot the scan leaves the total in
 __global__ void __launch_bounds__(FT_T) k_ft_name_len(const uint8_t *text, const uint32_t *ls, uint32_t n, uint32_t *nstart, uint32_t *nlen) {
     const uint32_t i = blockIdx.x * FT_T + threadIdx.x;
@@ -2126,19 +2126,15 @@ __global__ void __launch_bounds__(FT_T) k_ft_qual_copy(const uint8_t *text, cons
     for (uint32_t i = (blockIdx.x * FT_T + threadIdx.x) / cmft::COPY_LANES; i < n; i += groups)
         cmft::copy_bases(qual, off[i], text, ls[4 * (uint64_t)i + 3], (uint32_t)(off[i + 1] - off[i]), (int)lane, cmft::COPY_LANES);
 }
-// one lane per row k of the call (pair first + k): its length; item count is 0, the slot the scan leaves the total in
-__global__ void __launch_bounds__(BLK) k_pam_len(const cm_mapped_read *state, const uint32_t *name_off, cmpt::ChrTab ct, uint64_t first, uint32_t count, uint32_t *len) {
-    const uint32_t k = blockIdx.x * BLK + threadIdx.x;
-    if (k > count) return;
-    uint32_t l = 0;
-    if (k < count) {
-        const cm_mapped_read m = state[first + k];
-        l = cmpt::row_len(m, name_off[first + k + 1] - name_off[first + k], ct);
-    }
-    len[k] = l;
+
+// ---- the row formatters cm_format_pam / cm_format_sam (the plan: cm_rows_text.h; the formats: cm_pam_text.h, cm_sam_text.h) ----
+// one lane per item q of the call: its length; item `items` is 0, the slot the scan leaves the total in
+template <class F>
+__device__ __forceinline__ void rows_len(const typename F::Src &S, const cmrt::ChrTab &ct, uint64_t first, uint32_t items, uint32_t *len) {
+    cmrt::item_length<F>(S, ct, first, items, blockIdx.x * BLK + threadIdx.x, len);
 }
-// the 64-bit sum of the lengths (one workgroup; launched only where the rows of a call could reach 2^32 bytes)
-__global__ void __launch_bounds__(BLK) k_pam_total(const uint32_t *len, uint32_t count, unsigned long long *total) {
+// the 64-bit sum of the lengths (one workgroup; launched only where the items of a call could reach 2^32 bytes)
+__global__ void __launch_bounds__(BLK) k_rows_total(const uint32_t *len, uint32_t count, unsigned long long *total) {
     __shared__ unsigned long long part[BLK];
     unsigned long long t = 0;
     for (uint32_t k = threadIdx.x; k < count; k += BLK) t += len[k];
@@ -2149,90 +2145,33 @@ __global__ void __launch_bounds__(BLK) k_pam_total(const uint32_t *len, uint32_t
         *total = t;
     }
 }
-// One wave (a workgroup of its own) per span of SPAN_ROWS rows: formatted in the wave's LDS window and streamed out as words, or,
-// for a span larger than the window, stored by every lane itself.  path[span] = 1 / 0 says which.
-__global__ void __launch_bounds__(cmpt::SPAN_ROWS) k_pam_rows(const cm_mapped_read *state, const uint8_t *names, const uint32_t *name_off, cmpt::ChrTab ct,
-                                                              uint64_t first, uint32_t count, const uint32_t *off, uint8_t *out, uint8_t *path) {
-    __shared__ uint32_t win[cmpt::WINDOW_WORDS];
-    const uint32_t lane = threadIdx.x, k0 = blockIdx.x * cmpt::SPAN_ROWS, k = k0 + lane;
-    const uint32_t k1 = count - k0 < cmpt::SPAN_ROWS ? count : k0 + cmpt::SPAN_ROWS;
-    const uint32_t s = off[k0], e = off[k1];
-    const bool staged = cmpt::span_in_window(s, e);                  // (uniform)
-    if (lane == 0) path[blockIdx.x] = staged ? 1 : 0;
-    if (staged) {
-        if (k < count) {
-            const cm_mapped_read m = state[first + k];
-            const uint32_t a = name_off[first + k];
-            cmpt::format_row((uint8_t *)win + cmpt::window_at(s, off[k]), m, names + a, name_off[first + k + 1] - a, ct);
-        }
-        __syncthreads();
-        cmpt::stream_span(out, (const uint8_t *)win, s, e, lane, cmpt::SPAN_ROWS);
-    } else if (k < count) {
-        const cm_mapped_read m = state[first + k];
-        const uint32_t a = name_off[first + k];
-        cmpt::format_row(out + off[k], m, names + a, name_off[first + k + 1] - a, ct);
-    }
-}
-
-// ---- cm_format_sam (bodies and the plan: cm_sam_text.h) ----------------------------------------------------------------------
-// what the SAM kernels read of the resident batch: the states, the kept names, bases and kept qualities (seq: behind the slack)
-struct SamSrc {
-    const cm_mapped_read *state;
-    const uint8_t *names;
-    const uint32_t *name_off;
-    const uint8_t *seq[2], *qual[2];
-    const uint64_t *off[2];
+// a lane of the wave that runs cmrt::format_span: every step once, for itself
+struct WaveLane {
+    uint8_t *win, *out;
+    template <class Fn>
+    __device__ __forceinline__ void in_window(uint32_t, uint32_t, Fn f) { f(threadIdx.x, win); }
+    template <class Fn>
+    __device__ __forceinline__ void in_output(uint32_t, uint32_t, Fn f) { f(threadIdx.x, out); }
+    __device__ __forceinline__ void sync() { __syncthreads(); }
+    __device__ __forceinline__ const uint8_t *window() const { return win; }
+    __device__ __forceinline__ bool first_lane() const { return threadIdx.x == 0; }
 };
-// one lane per record q of the call (mate q & 1 of pair first + q / 2): its length; item `items` is 0, the slot the scan leaves the
-// total in.  Only a reversed record reads its bases.
-__global__ void __launch_bounds__(BLK) k_sam_len(SamSrc S, cmpt::ChrTab ct, uint64_t first, uint32_t items, uint32_t *len) {
-    const uint32_t q = blockIdx.x * BLK + threadIdx.x;
-    if (q > items) return;
-    uint32_t l = 0;
-    if (q < items) {
-        const uint64_t pair = first + q / 2;
-        const uint32_t mate = q & 1u;
-        const cm_mapped_read m = S.state[pair];
-        const uint64_t a = S.off[mate][pair];
-        l = cmst::item_len(m, mate, S.name_off[pair + 1] - S.name_off[pair], S.seq[mate], a, (uint32_t)(S.off[mate][pair + 1] - a), ct);
-    }
-    len[q] = l;
+// One wave (a workgroup of its own) per span of F::SPAN_ITEMS items: cmrt::format_span with the wave's LDS window.
+template <class F>
+__device__ __forceinline__ void rows_span(const typename F::Src &S, const cmrt::ChrTab &ct, uint64_t first, uint32_t items, const uint32_t *off, uint8_t *out, uint8_t *path) {
+    __shared__ uint32_t win[cmrt::WINDOW_WORDS];
+    __shared__ typename F::Scratch scratch;
+    WaveLane ex{(uint8_t *)win, out};
+    cmrt::format_span<F>(ex, S, ct, first, items, off, blockIdx.x, cmrt::WINDOW, scratch, path);
 }
-// the two steps of a span into dst (the wave's window, or the output): the ends of its records, a lane each, then the strings
-template <class Pos>
-__device__ __forceinline__ void sam_span(uint8_t *dst, cmst::Strings *desc, const SamSrc &S, const cmpt::ChrTab &ct, uint64_t first, uint32_t q0, uint32_t q1,
-                                         const uint32_t *off, uint32_t lane, Pos pos) {
-    if (lane < q1 - q0) {
-        const uint32_t q = q0 + lane, mate = q & 1u;
-        const uint64_t pair = first + q / 2;
-        const cm_mapped_read m = S.state[pair];
-        const uint32_t na = S.name_off[pair];
-        const uint64_t a = S.off[mate][pair];
-        desc[lane] = cmst::format_ends(dst, pos(off[q]), off[q + 1] - off[q], m, mate, S.names + na, S.name_off[pair + 1] - na, a, (uint32_t)(S.off[mate][pair + 1] - a), ct);
-    }
-    __syncthreads();
-    const uint32_t r = lane / cmst::REC_LANES;
-    if (r < q1 - q0) {
-        const cmst::Strings D = desc[r];
-        const uint32_t mate = D.rev_mate >> 1;
-        cmst::copy_strings(dst, D, S.seq[mate], S.qual[mate], lane % cmst::REC_LANES, cmst::REC_LANES);
-    }
+// the kernels under a name per format (profiles of both stay comparable)
+__global__ void __launch_bounds__(BLK) k_pam_len(cmpt::Format::Src S, cmrt::ChrTab ct, uint64_t first, uint32_t items, uint32_t *len) { rows_len<cmpt::Format>(S, ct, first, items, len); }
+__global__ void __launch_bounds__(BLK) k_sam_len(cmst::Format::Src S, cmrt::ChrTab ct, uint64_t first, uint32_t items, uint32_t *len) { rows_len<cmst::Format>(S, ct, first, items, len); }
+__global__ void __launch_bounds__(cmrt::WAVE) k_pam_rows(cmpt::Format::Src S, cmrt::ChrTab ct, uint64_t first, uint32_t items, const uint32_t *off, uint8_t *out, uint8_t *path) {
+    rows_span<cmpt::Format>(S, ct, first, items, off, out, path);
 }
-// One wave (a workgroup of its own) per span of SPAN_RECS records: put together in the wave's LDS window and streamed out as words,
-// or, for a span larger than the window, stored to the output directly.  path[span] = 1 / 0 says which.
-__global__ void __launch_bounds__(cmst::WAVE) k_sam_rows(SamSrc S, cmpt::ChrTab ct, uint64_t first, uint32_t items, const uint32_t *off, uint8_t *out, uint8_t *path) {
-    __shared__ uint32_t win[cmst::WINDOW_WORDS];
-    __shared__ cmst::Strings desc[cmst::SPAN_RECS];
-    const uint32_t lane = threadIdx.x, q0 = blockIdx.x * cmst::SPAN_RECS;
-    const uint32_t q1 = items - q0 < cmst::SPAN_RECS ? items : q0 + cmst::SPAN_RECS;
-    const uint32_t s = off[q0], e = off[q1];
-    const bool staged = cmst::span_in_window(s, e);                  // (uniform)
-    if (lane == 0) path[blockIdx.x] = staged ? 1 : 0;
-    if (staged) {
-        sam_span((uint8_t *)win, desc, S, ct, first, q0, q1, off, lane, [s](uint32_t g) { return cmpt::window_at(s, g); });
-        __syncthreads();
-        cmpt::stream_span(out, (const uint8_t *)win, s, e, lane, cmst::WAVE);
-    } else sam_span(out, desc, S, ct, first, q0, q1, off, lane, [](uint32_t g) { return g; });
+__global__ void __launch_bounds__(cmrt::WAVE) k_sam_rows(cmst::Format::Src S, cmrt::ChrTab ct, uint64_t first, uint32_t items, const uint32_t *off, uint8_t *out, uint8_t *path) {
+    rows_span<cmst::Format>(S, ct, first, items, off, out, path);
 }
 
 // ------------------------------------------------------------------ host side
@@ -2399,9 +2338,10 @@ struct TextStage {
     BatchBuf<unsigned long long> res;
     BatchBuf<uint32_t> nstart;                   // flag bit 2 only: where each R1 name starts in text[0]
 };
-// cm_format_pam: the chromosome names last uploaded (host copy: the table is compared, not uploaded, when it is the same), the rows'
-// lengths scanned in place into offsets, the scan's block totals, the rows, the path every span took
-struct PamRows {
+// The row formatters' buffers, shared by cm_format_pam and cm_format_sam: the chromosome names last uploaded (host copy: the table
+// is compared, not uploaded, when it is the same), the items' lengths scanned in place into offsets, the scan's block totals, the
+// rows or records, the path every span took
+struct RowsBufs {
     std::vector<uint32_t> h_chr_off;
     std::string h_chr_text;
     bool chr_valid = false;
@@ -2512,7 +2452,7 @@ struct cm_ctx {
     bool st_has_prior = false;
     int st_max_len = 0;
     TextStage ft;                             // cm_reads_stage_text
-    PamRows pam;                              // cm_format_pam
+    RowsBufs rows;                            // cm_format_pam, cm_format_sam
     // workspace of one tile
     uint32_t tile = 0;
     SeedSet seed[2];                          // item i + 1 is seeded into one while the chain stage of item i reads the other
@@ -4520,7 +4460,7 @@ int cm_collect_records_device(cm_ctx *ctx, uint64_t index_base, uint64_t cap, vo
 }
 
 // The chromosome names of a row formatter's call: uploaded when they differ from the table on the device.  *chr_max: the longest name.
-static int upload_chr_table(cm_ctx *ctx, PamRows &F, const cm_chr_info *chrs, uint32_t n_chr, hipStream_t st, uint32_t *chr_max) {
+static int upload_chr_table(cm_ctx *ctx, RowsBufs &F, const cm_chr_info *chrs, uint32_t n_chr, hipStream_t st, uint32_t *chr_max) {
     std::vector<uint32_t> o((size_t)n_chr + 1, 0u);
     std::string text;
     for (uint32_t c = 0; c < n_chr; ++c) {
@@ -4544,139 +4484,105 @@ static int upload_chr_table(cm_ctx *ctx, PamRows &F, const cm_chr_info *chrs, ui
     return CM_OK;
 }
 
-// The PAM rows of pairs [first, first + count) of the resident batch, formatted on the device (bodies and the plan: cm_pam_text.h)
-// on the mapping stream, behind everything queued for the batch.  Two waits: for the rows' total (the caller's buffer may be too
-// small, the device buffer is sized by it), then for the bytes.
-int cm_format_pam(cm_ctx *ctx, const cm_chr_info *chrs, uint32_t n_chr, uint64_t first, uint64_t count, void *out, uint64_t cap, uint64_t *out_bytes,
-                  uint64_t stats[4]) {
-    if (!ctx || !out_bytes || (n_chr && !chrs)) return CM_EINVAL;
+// What a row formatter's call says of itself: its name and nouns for the messages, the refusal for missing staging bits (null: the
+// batch has what the format needs), what the format reads, the bytes of names and strings all items print at most, and the kernels.
+extern "C++" {
+template <class F>
+struct RowsCall {
+    const char *fn, *limit_unit, *noun, *missing;
+    typename F::Src src;
+    uint64_t strings_max;
+    void (*k_len)(typename F::Src, cmrt::ChrTab, uint64_t, uint32_t, uint32_t *);
+    void (*k_rows)(typename F::Src, cmrt::ChrTab, uint64_t, uint32_t, const uint32_t *, uint8_t *, uint8_t *);
+};
+// The items (PAM rows, SAM records) of pairs [first, first + count) of the resident batch, formatted on the device (the plan:
+// cm_rows_text.h) on the mapping stream, behind everything queued for the batch.  Two waits: for the items' total (the caller's
+// buffer may be too small, the device buffer is sized by it), then for the bytes.
+template <class F>
+static int format_rows(cm_ctx *ctx, const RowsCall<F> &c, const cm_chr_info *chrs, uint32_t n_chr, uint64_t first, uint64_t count, void *out, uint64_t cap,
+                       uint64_t *out_bytes, uint64_t stats[4]) {
+    if (!out_bytes || (n_chr && !chrs)) return CM_EINVAL;
     *out_bytes = 0;
     if (stats) stats[0] = stats[1] = stats[2] = stats[3] = 0;
     HIPCHK(ctx, hipSetDevice(ctx->P.device));
-    if (ctx->n_pairs == 0) return fail(ctx, CM_ESTATE, "cm_format_pam: no resident batch");
-    if (!ctx->rd.has_names) return fail(ctx, CM_ESTATE, "cm_format_pam: the resident batch was not staged with cm_reads_stage_text, flag bit 2 (no names)");
+    if (ctx->n_pairs == 0) return fail(ctx, CM_ESTATE, "%s: no resident batch", c.fn);
+    if (c.missing) return fail(ctx, CM_ESTATE, "%s: the resident batch was not staged with cm_reads_stage_text, flag %s", c.fn, c.missing);
     if (first > ctx->n_pairs || count > ctx->n_pairs - first)
-        return fail(ctx, CM_EINVAL, "cm_format_pam: pairs [%llu, +%llu) of %llu", (unsigned long long)first, (unsigned long long)count, (unsigned long long)ctx->n_pairs);
-    if (!out && cap) return fail(ctx, CM_EINVAL, "cm_format_pam: null out");
+        return fail(ctx, CM_EINVAL, "%s: pairs [%llu, +%llu) of %llu", c.fn, (unsigned long long)first, (unsigned long long)count, (unsigned long long)ctx->n_pairs);
+    if (!out && cap) return fail(ctx, CM_EINVAL, "%s: null out", c.fn);
     if (count == 0) return CM_OK;
-    if (count >= 0xffffffffull) return fail(ctx, CM_ELIMIT, "cm_format_pam: %llu rows in one call", (unsigned long long)count);
-    PamRows &F = ctx->pam;
+    if (count >= F::PAIR_LIMIT) return fail(ctx, CM_ELIMIT, "%s: %llu %s in one call", c.fn, (unsigned long long)count, c.limit_unit);
+    RowsBufs &R = ctx->rows;
     hipStream_t st = ctx->st.B;
     uint32_t chr_max = 1;
     int rc;
-    if ((rc = upload_chr_table(ctx, F, chrs, n_chr, st, &chr_max))) return rc;
-    const cmpt::ChrTab ct{F.chr_text, F.chr_off, n_chr};
-    const uint32_t cnt = (uint32_t)count, spans = (cnt + cmpt::SPAN_ROWS - 1) / cmpt::SPAN_ROWS;
-    HIPCHK(ctx, ensure(ctx, F.off, ((size_t)cnt + 1) * sizeof(uint32_t)));
-    HIPCHK(ctx, ensure(ctx, F.tmp, (size_t)(((uint64_t)cnt + 1) / S32_B + 2) * sizeof(uint32_t)));
-    HIPCHK(ctx, ensure(ctx, F.path, spans));
-    HIPCHK(ctx, ensure(ctx, F.total, sizeof(unsigned long long)));
-    // offsets are uint32: where the rows could come to 2^32 bytes (the names at their most, every field at its widest) the lengths
-    // are summed in 64 bits first
-    const bool wide = ctx->rd.name_bytes_max + count * (uint64_t)(cmpt::ROW_FIXED_MAX + 2 * chr_max) >= (1ull << 32);
-    unsigned long long *land = ctx->h_pin + PIN_PAM;
+    if ((rc = upload_chr_table(ctx, R, chrs, n_chr, st, &chr_max))) return rc;
+    const cmrt::ChrTab ct{R.chr_text, R.chr_off, n_chr};
+    const uint32_t items = F::PAIR_ITEMS * (uint32_t)count, spans = (items + F::SPAN_ITEMS - 1) / F::SPAN_ITEMS;
+    HIPCHK(ctx, ensure(ctx, R.off, ((size_t)items + 1) * sizeof(uint32_t)));
+    HIPCHK(ctx, ensure(ctx, R.tmp, (size_t)(((uint64_t)items + 1) / S32_B + 2) * sizeof(uint32_t)));
+    HIPCHK(ctx, ensure(ctx, R.path, spans));
+    HIPCHK(ctx, ensure(ctx, R.total, sizeof(unsigned long long)));
+    // offsets are uint32: where the items could come to 2^32 bytes (the names and strings at their most, every number at its
+    // widest) the lengths are summed in 64 bits first
+    const bool wide = c.strings_max + (uint64_t)items * (F::ITEM_FIXED_MAX + F::ITEM_CHRS * chr_max) >= (1ull << 32);
+    unsigned long long *land = ctx->h_pin + PIN_ROWS;
     {
-        Timer t(ctx, PC_PAM, st);
-        hipLaunchKernelGGL(k_pam_len, dim3(cnt / BLK + 1), dim3(BLK), 0, st, (const cm_mapped_read *)ctx->d_state, (const uint32_t *)ctx->rd.name_off, ct, first, cnt,
-                           (uint32_t *)F.off);
-        if (wide) hipLaunchKernelGGL(k_pam_total, dim3(1), dim3(BLK), 0, st, (const uint32_t *)F.off, cnt, (unsigned long long *)F.total);
-        if ((rc = scan32_on(ctx, st, F.off, (uint64_t)cnt + 1, F.off, F.tmp, 0u, 0))) return rc;
+        Timer t(ctx, PC_ROWS, st);
+        hipLaunchKernelGGL(c.k_len, dim3(items / BLK + 1), dim3(BLK), 0, st, c.src, ct, first, items, (uint32_t *)R.off);
+        if (wide) hipLaunchKernelGGL(k_rows_total, dim3(1), dim3(BLK), 0, st, (const uint32_t *)R.off, items, (unsigned long long *)R.total);
+        if ((rc = scan32_on(ctx, st, R.off, (uint64_t)items + 1, R.off, R.tmp, 0u, 0))) return rc;
     }
     *land = 0;
-    if (wide) HIPCHK(ctx, hipMemcpyAsync(land, F.total, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    else HIPCHK(ctx, hipMemcpyAsync(land, F.off + cnt, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    if (wide) HIPCHK(ctx, hipMemcpyAsync(land, R.total, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    else HIPCHK(ctx, hipMemcpyAsync(land, R.off + items, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipStreamSynchronize(st));
     const uint64_t total = *land;
     *out_bytes = total;
-    if (total >= (1ull << 32)) return fail(ctx, CM_ELIMIT, "cm_format_pam: %llu bytes of rows in one call (offsets are 32 bits: format in ranges)", (unsigned long long)total);
-    if (total > cap) return fail(ctx, CM_ELIMIT, "cm_format_pam: %llu bytes of rows > cap %llu", (unsigned long long)total, (unsigned long long)cap);
-    HIPCHK(ctx, ensure(ctx, F.out, (size_t)total + 4));
+    if (total >= (1ull << 32))
+        return fail(ctx, CM_ELIMIT, "%s: %llu bytes of %s in one call (offsets are 32 bits: format in ranges)", c.fn, (unsigned long long)total, c.noun);
+    if (total > cap) return fail(ctx, CM_ELIMIT, "%s: %llu bytes of %s > cap %llu", c.fn, (unsigned long long)total, c.noun, (unsigned long long)cap);
+    HIPCHK(ctx, ensure(ctx, R.out, (size_t)total + 4));
     {
-        Timer t(ctx, PC_PAM, st);
-        hipLaunchKernelGGL(k_pam_rows, dim3(spans), dim3(cmpt::SPAN_ROWS), 0, st, (const cm_mapped_read *)ctx->d_state, (const uint8_t *)ctx->rd.names,
-                           (const uint32_t *)ctx->rd.name_off, ct, first, cnt, (const uint32_t *)F.off, (uint8_t *)F.out, (uint8_t *)F.path);
+        Timer t(ctx, PC_ROWS, st);
+        hipLaunchKernelGGL(c.k_rows, dim3(spans), dim3(cmrt::WAVE), 0, st, c.src, ct, first, items, (const uint32_t *)R.off, (uint8_t *)R.out, (uint8_t *)R.path);
     }
     HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipMemcpyAsync(out, F.out, (size_t)total, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipMemcpyAsync(out, R.out, (size_t)total, hipMemcpyDeviceToHost, st));
     if (stats) {
-        F.h_path.resize(spans);
-        HIPCHK(ctx, hipMemcpyAsync(F.h_path.data(), F.path, spans, hipMemcpyDeviceToHost, st));
-    }
-    HIPCHK(ctx, hipStreamSynchronize(st));
-    if (stats) {
-        stats[0] = count;
-        stats[1] = total;
-        for (uint32_t i = 0; i < spans; ++i) ++stats[F.h_path[i] ? 2 : 3];
-    }
-    return CM_OK;
-}
-
-// The SAM records of pairs [first, first + count) of the resident batch, formatted on the device (bodies and the plan:
-// cm_sam_text.h): cm_format_pam's steps over 2 * count records, with the formatter's buffers.
-int cm_format_sam(cm_ctx *ctx, const cm_chr_info *chrs, uint32_t n_chr, uint64_t first, uint64_t count, void *out, uint64_t cap, uint64_t *out_bytes,
-                  uint64_t stats[4]) {
-    if (!ctx || !out_bytes || (n_chr && !chrs)) return CM_EINVAL;
-    *out_bytes = 0;
-    if (stats) stats[0] = stats[1] = stats[2] = stats[3] = 0;
-    HIPCHK(ctx, hipSetDevice(ctx->P.device));
-    if (ctx->n_pairs == 0) return fail(ctx, CM_ESTATE, "cm_format_sam: no resident batch");
-    if (!ctx->rd.has_names || !ctx->rd.has_quals)
-        return fail(ctx, CM_ESTATE, "cm_format_sam: the resident batch was not staged with cm_reads_stage_text, flag %s",
-                    ctx->rd.has_quals ? "bit 2 (no names)" : ctx->rd.has_names ? "bit 3 (no qualities)" : "bits 2 and 3 (no names, no qualities)");
-    if (first > ctx->n_pairs || count > ctx->n_pairs - first)
-        return fail(ctx, CM_EINVAL, "cm_format_sam: pairs [%llu, +%llu) of %llu", (unsigned long long)first, (unsigned long long)count, (unsigned long long)ctx->n_pairs);
-    if (!out && cap) return fail(ctx, CM_EINVAL, "cm_format_sam: null out");
-    if (count == 0) return CM_OK;
-    if (count >= 0x7fffffffull) return fail(ctx, CM_ELIMIT, "cm_format_sam: %llu pairs in one call", (unsigned long long)count);
-    PamRows &F = ctx->pam;
-    hipStream_t st = ctx->st.B;
-    uint32_t chr_max = 1;
-    int rc;
-    if ((rc = upload_chr_table(ctx, F, chrs, n_chr, st, &chr_max))) return rc;
-    const cmpt::ChrTab ct{F.chr_text, F.chr_off, n_chr};
-    const uint32_t items = 2u * (uint32_t)count, spans = (items + cmst::SPAN_RECS - 1) / cmst::SPAN_RECS;
-    HIPCHK(ctx, ensure(ctx, F.off, ((size_t)items + 1) * sizeof(uint32_t)));
-    HIPCHK(ctx, ensure(ctx, F.tmp, (size_t)(((uint64_t)items + 1) / S32_B + 2) * sizeof(uint32_t)));
-    HIPCHK(ctx, ensure(ctx, F.path, spans));
-    HIPCHK(ctx, ensure(ctx, F.total, sizeof(unsigned long long)));
-    const ReadBufs &rd = ctx->rd;
-    const SamSrc S{ctx->d_state, rd.names, rd.name_off, {rd.seq1_base + cmc::CM_STAGE_PAD, rd.seq2_base + cmc::CM_STAGE_PAD}, {rd.qual1, rd.qual2}, {rd.off1, rd.off2}};
-    // offsets are uint32: where the records could come to 2^32 bytes (every name twice, every read as SEQ and as QUAL, every number at
-    // its widest) the lengths are summed in 64 bits first
-    const bool wide = 2 * (rd.name_bytes_max + rd.bases) + (uint64_t)items * (cmst::REC_FIXED_MAX + chr_max) >= (1ull << 32);
-    unsigned long long *land = ctx->h_pin + PIN_PAM;
-    {
-        Timer t(ctx, PC_PAM, st);
-        hipLaunchKernelGGL(k_sam_len, dim3(items / BLK + 1), dim3(BLK), 0, st, S, ct, first, items, (uint32_t *)F.off);
-        if (wide) hipLaunchKernelGGL(k_pam_total, dim3(1), dim3(BLK), 0, st, (const uint32_t *)F.off, items, (unsigned long long *)F.total);
-        if ((rc = scan32_on(ctx, st, F.off, (uint64_t)items + 1, F.off, F.tmp, 0u, 0))) return rc;
-    }
-    *land = 0;
-    if (wide) HIPCHK(ctx, hipMemcpyAsync(land, F.total, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    else HIPCHK(ctx, hipMemcpyAsync(land, F.off + items, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipStreamSynchronize(st));
-    const uint64_t total = *land;
-    *out_bytes = total;
-    if (total >= (1ull << 32)) return fail(ctx, CM_ELIMIT, "cm_format_sam: %llu bytes of records in one call (offsets are 32 bits: format in ranges)", (unsigned long long)total);
-    if (total > cap) return fail(ctx, CM_ELIMIT, "cm_format_sam: %llu bytes of records > cap %llu", (unsigned long long)total, (unsigned long long)cap);
-    HIPCHK(ctx, ensure(ctx, F.out, (size_t)total + 4));
-    {
-        Timer t(ctx, PC_PAM, st);
-        hipLaunchKernelGGL(k_sam_rows, dim3(spans), dim3(cmst::WAVE), 0, st, S, ct, first, items, (const uint32_t *)F.off, (uint8_t *)F.out, (uint8_t *)F.path);
-    }
-    HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipMemcpyAsync(out, F.out, (size_t)total, hipMemcpyDeviceToHost, st));
-    if (stats) {
-        F.h_path.resize(spans);
-        HIPCHK(ctx, hipMemcpyAsync(F.h_path.data(), F.path, spans, hipMemcpyDeviceToHost, st));
+        R.h_path.resize(spans);
+        HIPCHK(ctx, hipMemcpyAsync(R.h_path.data(), R.path, spans, hipMemcpyDeviceToHost, st));
     }
     HIPCHK(ctx, hipStreamSynchronize(st));
     if (stats) {
         stats[0] = items;
         stats[1] = total;
-        for (uint32_t i = 0; i < spans; ++i) ++stats[F.h_path[i] ? 2 : 3];
+        for (uint32_t i = 0; i < spans; ++i) ++stats[R.h_path[i] ? 2 : 3];
     }
     return CM_OK;
+}
+}  // extern "C++"
+
+// PAM rows: one per pair; needs the kept names.  At most: every name once.
+int cm_format_pam(cm_ctx *ctx, const cm_chr_info *chrs, uint32_t n_chr, uint64_t first, uint64_t count, void *out, uint64_t cap, uint64_t *out_bytes,
+                  uint64_t stats[4]) {
+    if (!ctx) return CM_EINVAL;
+    const ReadBufs &rd = ctx->rd;
+    const RowsCall<cmpt::Format> c{"cm_format_pam", "rows", "rows", rd.has_names ? nullptr : "bit 2 (no names)",
+                                   {ctx->d_state, rd.names, rd.name_off}, rd.name_bytes_max, k_pam_len, k_pam_rows};
+    return format_rows(ctx, c, chrs, n_chr, first, count, out, cap, out_bytes, stats);
+}
+
+// SAM records: two per pair; needs the kept names and qualities.  At most: every name twice, every read as SEQ and as QUAL.
+int cm_format_sam(cm_ctx *ctx, const cm_chr_info *chrs, uint32_t n_chr, uint64_t first, uint64_t count, void *out, uint64_t cap, uint64_t *out_bytes,
+                  uint64_t stats[4]) {
+    if (!ctx) return CM_EINVAL;
+    const ReadBufs &rd = ctx->rd;
+    const char *missing = rd.has_names && rd.has_quals ? nullptr : rd.has_quals ? "bit 2 (no names)" : rd.has_names ? "bit 3 (no qualities)" : "bits 2 and 3 (no names, no qualities)";
+    const RowsCall<cmst::Format> c{"cm_format_sam", "pairs", "records", missing,
+                                   {ctx->d_state, rd.names, rd.name_off, {rd.seq1_base + cmc::CM_STAGE_PAD, rd.seq2_base + cmc::CM_STAGE_PAD}, {rd.qual1, rd.qual2}, {rd.off1, rd.off2}},
+                                   2 * (rd.name_bytes_max + rd.bases), k_sam_len, k_sam_rows};
+    return format_rows(ctx, c, chrs, n_chr, first, count, out, cap, out_bytes, stats);
 }
 
 // test hook: the qualities cm_reads_stage_text kept with the resident batch (flag bit 3), copied back: off1[n] / off2[n] bytes

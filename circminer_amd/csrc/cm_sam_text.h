@@ -1,8 +1,9 @@
-// cm_sam_text.h — the bodies of the device-side SAM formatter (cm_format_sam).
+// cm_sam_text.h — the SAM record format of the device-side formatter (cm_format_sam).
 //
 // Shared by the HIP kernels (cm_hot.hip: k_sam_len, k_sam_rows) and by a host emulation (tests/hostemu_sam.cpp) that g++ compiles,
-// the way cm_pam_text.h is shared; the number formats, the chromosome table and the window's addressing are that header's.  The
-// rules are those of cm_write_sam, sam_flag and comp_of in host_fastq.cpp:
+// the way cm_fastq_text.h is shared.  The number formats, the chromosome table, the window and the plan of a call are
+// cm_rows_text.h's; Format below is what this format plugs into that plan.  The rules are those of cm_write_sam, sam_flag and
+// comp_of in host_fastq.cpp:
 //   * a pair makes two records, mate 1 then mate 2 ("items" 2 p and 2 p + 1 of a call); QNAME of both is the kept R1 name;
 //   * a pair is mapped for type <= CM_CHIORF || type == CM_CONGEN || type == CM_CONGNM (signed: negative types are mapped; this is
 //     not cmpt::mapped_type); any other pair has RUNMAP | MUNMAP in both flags, RNAME "*", POS 0, RNEXT "*", PNEXT 0, TLEN 0 and
@@ -16,16 +17,14 @@
 //   * a record with RREVER prints the reverse complement: the complement maps ACGTNacgtn to TGCANTGCAN and every other byte to
 //     NUL, and SEQ ends in front of the first NUL ("%s"), i.e. at the first byte, counted from the read's end, that is outside
 //     the ten (rc_cut); QUAL is reversed at full length.  Every other record prints SEQ and QUAL raw, NUL bytes included.
-// The plan of a call: one lane per item computes the record's length (item_len; only a record with RREVER looks at its read, from
-// the end, a word at a time) -> exclusive scan = the record's offset in the output -> a wave takes SPAN_RECS consecutive records,
-// which are one contiguous span [s, e) of the output.  A record is mostly two byte strings, so the work of a span is split by
-// kind: lane r < SPAN_RECS writes the "ends" of record r -- the name and the numbers in front of SEQ, the tab between SEQ and
+// The length of a record (item_len): only a record with RREVER looks at its read, from the end, a word at a time.  A span is
+// SPAN_RECS records.  A record is mostly two byte strings, so the work of a span is split by kind into two steps:
+// lane r < SPAN_RECS writes the "ends" of record r -- the name and the numbers in front of SEQ, the tab between SEQ and
 // QUAL, the tags behind QUAL (format_ends) -- and leaves a descriptor of the two strings (Strings); then REC_LANES lanes per
 // record, all 64 together, move SEQ and QUAL (copy_strings): whole destination words as words, each put together from two
 // aligned words of the source (reversed: byte-swapped, SEQ complemented by compares), single bytes only for the up to three bytes
-// on either side of a field, whose words the neighbouring field shares.  A span of at most WINDOW bytes is put together in the
-// wave's LDS window and streamed out as whole aligned words (cmpt::stream_span); a larger span (long names, 250 - 300-bp reads)
-// is stored to global memory directly, by the same split.
+// on either side of a field, whose words the neighbouring field shares.  Both steps write the window or, on the direct path,
+// global memory, by the same split.
 // The sources: bases and qualities of read i are seq[off[i] .. off[i + 1]) / qual[off[i] .. off[i + 1]) of 4-byte aligned arrays
 // that are readable for a whole word past their last byte.
 #ifndef CM_SAM_TEXT_H
@@ -35,26 +34,16 @@
 
 #include "circminer_hot.h"
 #include "cm_fastq_text.h"
-#include "cm_pam_text.h"
+#include "cm_rows_text.h"
 
-#if defined(__HIPCC__)
-#define CMST_HD __host__ __device__ inline
-#else
-#define CMST_HD inline
-#endif
+#define CMST_HD CMRT_HD
 
 namespace cmst {
 
-using cmpt::ChrTab;
+using namespace cmrt;
 
-constexpr uint32_t WAVE = 64;
 constexpr uint32_t SPAN_RECS = 16;                   // records of one span (8 pairs)
 constexpr uint32_t REC_LANES = WAVE / SPAN_RECS;     // lanes that move one record's SEQ and QUAL
-// Bytes of a wave's LDS window.  A record of a 150-bp read is its name + 2 x 150 + about 60 - 90 bytes of numbers and tags: 16 of
-// them with names of up to ~ 60 bytes fit 8 KB.  8 KB per one-wave workgroup lets 20 waves share the 160 KB of a compute unit (5
-// per SIMD), as in k_pam_rows; 32 records per wave would need 16 KB (10 waves per unit) for the same share of staged spans.
-constexpr uint32_t WINDOW = 8192;
-constexpr uint32_t WINDOW_WORDS = WINDOW / 4 + 1;    // the span lies in the window at its offset inside its first global word
 // what a record can take at most without its name, its chromosome name and its two strings: 14 tabs and the line feed, FLAG (3),
 // POS / PNEXT / TLEN (10 each), "255", "*", RNEXT (1), four tags of 5 bytes with 11 + 11 + 5 + 1 bytes of numbers
 constexpr uint32_t REC_FIXED_MAX = 15 + 3 + 30 + 3 + 1 + 1 + 20 + 28;
@@ -129,12 +118,12 @@ CMST_HD Fields fields_of(const cm_mapped_read &m, uint32_t mate) {
 }
 // QNAME .. TLEN with the tab behind it
 CMST_HD uint32_t head_len(const Fields &f, const cm_mapped_read &m, uint32_t name_len, const ChrTab &ct) {
-    const uint32_t rname = (f.flag & RUNMAP) ? 1u : cmpt::chr_len(ct, m.chr_id);
-    return name_len + 1u + cmpt::dec_len(f.flag) + 1u + rname + 1u + cmpt::dec_len(f.pos) + 7u + 1u + 1u + cmpt::dec_len(f.pnext) + 1u + cmpt::dec_len(f.tlen) + 1u;
+    const uint32_t rname = (f.flag & RUNMAP) ? 1u : chr_len(ct, m.chr_id);
+    return name_len + 1u + dec_len(f.flag) + 1u + rname + 1u + dec_len(f.pos) + 7u + 1u + 1u + dec_len(f.pnext) + 1u + dec_len(f.tlen) + 1u;
 }
 // the four tags and the line feed
 CMST_HD uint32_t tail_len(const Fields &f, const cm_mapped_read &m) {
-    return 4u * 6u + cmpt::int_len(m.type) + cmpt::int_len(f.nm) + cmpt::int_len(f.jc) + cmpt::int_len(f.tc) + 1u;
+    return 4u * 6u + int_len(m.type) + int_len(f.nm) + int_len(f.jc) + int_len(f.tc) + 1u;
 }
 // bytes of the record of mate `mate` of state m: the name, the read seq[s .. s + len) (looked at only when the record is reversed)
 CMST_HD uint32_t item_len(const cm_mapped_read &m, uint32_t mate, uint32_t name_len, const uint8_t *seq, uint64_t s, uint32_t len, const ChrTab &ct) {
@@ -150,35 +139,31 @@ struct Strings {
     uint32_t cut, len;       // bytes of SEQ, bytes of the read (= bytes of QUAL)
     uint32_t rev_mate;       // bit 0: reversed, bit 1: mate 2
 };
-CMST_HD uint8_t *put_lit(uint8_t *p, const char *s, uint32_t n) {
-    for (uint32_t i = 0; i < n; ++i) p[i] = (uint8_t)s[i];
-    return p + n;
-}
 // The ends of the record of `total` bytes at dst[d ..): everything but SEQ and QUAL.  `total` is the record's length from the scan;
 // the length of SEQ follows from it, so the read is not looked at here.
 CMST_HD Strings format_ends(uint8_t *dst, uint64_t d, uint32_t total, const cm_mapped_read &m, uint32_t mate, const uint8_t *name, uint32_t name_len, uint64_t src,
                             uint32_t len, const ChrTab &ct) {
     const Fields f = fields_of(m, mate);
     const bool un = (f.flag & RUNMAP) != 0;
-    uint8_t *p = cmpt::put_bytes(dst + d, name, name_len);
-    *p++ = '\t'; p = cmpt::put_u32(p, f.flag);
+    uint8_t *p = put_bytes(dst + d, name, name_len);
+    *p++ = '\t'; p = put_u32(p, f.flag);
     *p++ = '\t';
     if (un) *p++ = '*';
-    else p = cmpt::put_chr(p, ct, m.chr_id);
-    *p++ = '\t'; p = cmpt::put_u32(p, f.pos);
+    else p = put_chr(p, ct, m.chr_id);
+    *p++ = '\t'; p = put_u32(p, f.pos);
     p = put_lit(p, "\t255\t*\t", 7);
     *p++ = un ? '*' : '=';
-    *p++ = '\t'; p = cmpt::put_u32(p, f.pnext);
-    *p++ = '\t'; p = cmpt::put_u32(p, f.tlen);
+    *p++ = '\t'; p = put_u32(p, f.pnext);
+    *p++ = '\t'; p = put_u32(p, f.tlen);
     *p++ = '\t';
     const uint32_t hl = (uint32_t)(p - (dst + d)), cut = total - hl - 1u - len - tail_len(f, m);
     p += cut;
     *p++ = '\t';
     p += len;
-    p = put_lit(p, "\tAT:i:", 6); p = cmpt::put_i32(p, m.type);
-    p = put_lit(p, "\tNM:i:", 6); p = cmpt::put_i32(p, f.nm);
-    p = put_lit(p, "\tJC:i:", 6); p = cmpt::put_i32(p, f.jc);
-    p = put_lit(p, "\tTC:i:", 6); p = cmpt::put_i32(p, f.tc);
+    p = put_lit(p, "\tAT:i:", 6); p = put_i32(p, m.type);
+    p = put_lit(p, "\tNM:i:", 6); p = put_i32(p, f.nm);
+    p = put_lit(p, "\tJC:i:", 6); p = put_i32(p, f.jc);
+    p = put_lit(p, "\tTC:i:", 6); p = put_i32(p, f.tc);
     *p = '\n';
     Strings S;
     S.src = src;
@@ -204,15 +189,57 @@ CMST_HD void put_field(uint8_t *dst, uint64_t d, uint32_t n, const uint8_t *src,
     for (uint64_t w = w0 + lane; w < w1; w += lanes) dw[w] = field_word(src, s, len, (uint32_t)(4 * w - d), rev, cmp);
 }
 // SEQ and QUAL of the record S describes, into the dst format_ends wrote its ends to (word 0 of dst is a word of the output: see
-// cmpt::window_at)
+// cmrt::window_at)
 CMST_HD void copy_strings(uint8_t *dst, const Strings &S, const uint8_t *seq, const uint8_t *qual, uint32_t lane, uint32_t lanes) {
     const bool rev = (S.rev_mate & 1u) != 0;
     put_field(dst, S.at, S.cut, seq, S.src, S.len, rev, rev, lane, lanes);
     put_field(dst, (uint64_t)S.at + S.cut + 1u, S.len, qual, S.src, S.len, rev, false, lane, lanes);
 }
 
-// the span [s, e) of the output takes the LDS-staged path
-CMST_HD bool span_in_window(uint64_t s, uint64_t e) { return e - s <= WINDOW; }
+// the format as the plan of cm_rows_text.h takes it
+struct Format {
+    static constexpr uint32_t PAIR_ITEMS = 2, SPAN_ITEMS = SPAN_RECS, STEPS = 2;
+    static constexpr uint64_t PAIR_LIMIT = 0x7fffffffull;
+    static constexpr uint32_t ITEM_FIXED_MAX = REC_FIXED_MAX, ITEM_CHRS = 1;
+    // the states, the kept names, the bases and the kept qualities of the resident batch
+    struct Src {
+        const cm_mapped_read *state;
+        const uint8_t *names;
+        const uint32_t *name_off;
+        const uint8_t *seq[2], *qual[2];
+        const uint64_t *off[2];
+    };
+    struct Scratch {
+        Strings desc[SPAN_RECS];
+    };
+    // record q of the call is mate q & 1 of pair first + q / 2
+    static CMRT_PLAN uint32_t item_len(const Src &S, const ChrTab &ct, uint64_t first, uint32_t q) {
+        const uint64_t pair = first + q / 2;
+        const uint32_t mate = q & 1u;
+        const cm_mapped_read m = S.state[pair];
+        const uint64_t a = S.off[mate][pair];
+        return cmst::item_len(m, mate, S.name_off[pair + 1] - S.name_off[pair], S.seq[mate], a, (uint32_t)(S.off[mate][pair + 1] - a), ct);
+    }
+    // step 0: the ends of the span's records, a lane each; step 1: their strings
+    static CMRT_PLAN void step(uint32_t i, uint8_t *dst, uint32_t shift, Scratch &sc, const Src &S, const ChrTab &ct, uint64_t first, uint32_t q0, uint32_t n,
+                               const uint32_t *off, uint32_t lane) {
+        if (i == 0) {
+            if (lane >= n) return;
+            const uint32_t q = q0 + lane, mate = q & 1u;
+            const uint64_t pair = first + q / 2;
+            const cm_mapped_read m = S.state[pair];
+            const uint32_t na = S.name_off[pair];
+            const uint64_t a = S.off[mate][pair];
+            sc.desc[lane] = format_ends(dst, off[q] - shift, off[q + 1] - off[q], m, mate, S.names + na, S.name_off[pair + 1] - na, a, (uint32_t)(S.off[mate][pair + 1] - a), ct);
+        } else {
+            const uint32_t r = lane / REC_LANES;
+            if (r >= n) return;
+            const Strings D = sc.desc[r];
+            const uint32_t mate = D.rev_mate >> 1;
+            copy_strings(dst, D, S.seq[mate], S.qual[mate], lane % REC_LANES, REC_LANES);
+        }
+    }
+};
 
 }  // namespace cmst
 #endif /* CM_SAM_TEXT_H */

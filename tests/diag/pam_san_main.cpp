@@ -1,46 +1,14 @@
-// Stand-alone sanitizer pass over the bodies of circminer_amd/csrc/cm_pam_text.h through the host emulation (tests/hostemu_pam.cpp):
-// the directed states of tests/pam_text_util.py (every printed field at the boundaries of its format) over names that cover the
-// parser's rules and a run of long names, whole batches and ranges, every argument array an exact-size heap block; the rows are
-// also compared with printf's.  CPU only, no Python.  From the repository root:
-//   g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=all -I include -I circminer_amd/csrc \
+// Stand-alone sanitizer pass over the bodies of circminer_amd/csrc/cm_pam_text.h and the plan of cm_rows_text.h through the host
+// emulation (tests/hostemu_pam.cpp, tests/hostemu_rows.h): the directed states of tests/pam_text_util.py (every printed field at the
+// boundaries of its format) over names that cover the parser's rules and a run of long names, whole batches and ranges, the
+// window's rule, every span direct, and a small window; every argument array an exact-size heap block; the rows are also compared
+// with printf's.  CPU only, no Python.  From the repository root:
+//   g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=all -I include -I circminer_amd/csrc -I tests \
 //       tests/diag/pam_san_main.cpp tests/hostemu_pam.cpp -o /tmp/pam_san && /tmp/pam_san
-#include <climits>
 #include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <random>
 #include <string>
-#include <vector>
-#include "circminer_hot.h"
-extern "C" int emu_names(const uint8_t *, uint64_t, uint32_t, uint64_t, uint8_t *, uint32_t *);
-extern "C" int emu_format_pam(const cm_mapped_read *, uint64_t, const uint8_t *, const uint32_t *, const cm_chr_info *, uint32_t, uint64_t, uint64_t, uint8_t *,
-                              uint64_t, uint64_t *, uint64_t *, uint64_t);
+#include "hostemu_rows.h"
 
-static const uint32_t U32V[] = {0u, 9u, 10u, 99u, 100u, 999999999u, 1000000000u, 4294967295u};
-static const uint32_t MLENV[] = {0u, 9u, 10u, 99u, 100u, 999999999u, 1000000000u, 4294967295u, 2147483648u};
-static const int32_t INTV[] = {0, -1, -9, -10, INT_MIN, INT_MAX, 1000000000};
-static const int32_t TYPEV[] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, -1, 14, -9, -10, INT_MIN, INT_MAX, 1000000000, 100, 13};
-
-static cm_mapped_read directed(uint32_t i, int n_chr) {
-    cm_mapped_read m;
-    memset(&m, 0xee, sizeof m);
-    m.type = TYPEV[i % 23];
-    uint32_t *u[8] = {&m.spos_r1, &m.spos_r2, &m.epos_r1, &m.epos_r2, &m.qspos_r1, &m.qspos_r2, &m.qepos_r1, &m.qepos_r2};
-    for (uint32_t j = 0; j < 8; ++j) *u[j] = U32V[(i + j) % 8];
-    m.mlen_r1 = MLENV[i % 9];
-    m.mlen_r2 = MLENV[(i + 4) % 9];
-    m.ed_r1 = INTV[i % 7];
-    m.ed_r2 = INTV[(i + 2) % 7];
-    m.tlen = INTV[(i + 4) % 7];
-    m.junc_num = i % 2 ? 65535 : 0;
-    m.gm_compatible = (uint8_t)(i % 3 == 2 ? 255 : i % 3);
-    m.r1_forward = i & 1;
-    m.r2_forward = (i >> 1) & 1;
-    const int32_t ids[4] = {-1, 0, n_chr - 1, n_chr};
-    m.chr_id = ids[i % 4];
-    m.contig_num = (int32_t)(i % 5) - 1;
-    return m;
-}
 static bool mapped(int t) { return t == 0 || t == 1 || t == 2 || t == 3 || t == 4 || t == 5 || t == 7; }
 static std::string printf_row(const std::string &name, const cm_mapped_read &m, const cm_chr_info *chrs, int n_chr) {
     char buf[1024];
@@ -94,26 +62,28 @@ int main() {
         for (uint32_t i = 0; i < n; ++i)
             if (std::string((const char *)names + off[i], off[i + 1] - off[i]) != want[i]) { printf("name %u of %u differs\n", i, n); return 1; }
         cm_mapped_read *st = (cm_mapped_read *)malloc(n * sizeof(cm_mapped_read));
-        for (uint32_t i = 0; i < n; ++i) st[i] = directed(i, 4);
+        for (uint32_t i = 0; i < n; ++i) st[i] = emu::directed_state(i, 4, false);
         const uint64_t ranges[][2] = {{0, n}, {n / 3, n - n / 3}, {63 % n, (uint64_t)(n - 63 % n < 2 ? n - 63 % n : 2)}, {n, 0}, {n - 1, 1}};
         for (const auto &r : ranges)
-            for (int n_chr : {4, 0}) {
-                std::string ref;
-                for (uint64_t i = r[0]; i < r[0] + r[1]; ++i) ref += printf_row(want[i], st[i], chrs, n_chr);
-                uint64_t got = 0, stats[4];
-                const int rc0 = emu_format_pam(st, n, names, off, chrs, (uint32_t)n_chr, r[0], r[1], nullptr, 0, &got, nullptr, 5);
-                if (got != ref.size() || rc0 != (ref.empty() ? CM_OK : CM_ELIMIT)) { printf("size of range [%llu, +%llu) of %u differs\n", (unsigned long long)r[0], (unsigned long long)r[1], n); return 1; }
-                uint8_t *out = (uint8_t *)malloc(ref.size() ? ref.size() : 1);
-                if (emu_format_pam(st, n, names, off, chrs, (uint32_t)n_chr, r[0], r[1], out, ref.size(), &got, stats, n + r[0]) != CM_OK ||
-                    memcmp(out, ref.data(), ref.size()) != 0) {
-                    printf("rows of range [%llu, +%llu) of %u differ\n", (unsigned long long)r[0], (unsigned long long)r[1], n);
-                    return 1;
+            for (int n_chr : {4, 0})
+                for (uint32_t window : {0u, 1u, 3000u}) {
+                    std::string ref;
+                    for (uint64_t i = r[0]; i < r[0] + r[1]; ++i) ref += printf_row(want[i], st[i], chrs, n_chr);
+                    uint64_t got = 0, stats[4], writes[3] = {0, 0, 0};
+                    const int rc0 = emu_format_pam(st, n, names, off, chrs, (uint32_t)n_chr, r[0], r[1], nullptr, 0, &got, nullptr, 5, window, nullptr, nullptr);
+                    if (got != ref.size() || rc0 != (ref.empty() ? CM_OK : CM_ELIMIT)) { printf("size of range [%llu, +%llu) of %u differs\n", (unsigned long long)r[0], (unsigned long long)r[1], n); return 1; }
+                    uint8_t *out = (uint8_t *)malloc(ref.size() ? ref.size() : 1);
+                    const int rc = emu_format_pam(st, n, names, off, chrs, (uint32_t)n_chr, r[0], r[1], out, ref.size(), &got, stats, n + r[0], window, nullptr, writes);
+                    if (rc != CM_OK || memcmp(out, ref.data(), ref.size()) != 0) {
+                        printf("rows of range [%llu, +%llu) of %u differ (rc %d, window %u)\n", (unsigned long long)r[0], (unsigned long long)r[1], n, rc, window);
+                        return 1;
+                    }
+                    if (r[1] && (writes[0] != 1 || writes[1] != 1 || writes[2] != 0)) { printf("a byte written %llu .. %llu times, %llu rows of another length\n", (unsigned long long)writes[0], (unsigned long long)writes[1], (unsigned long long)writes[2]); return 1; }
+                    rows_checked += r[1];
+                    staged += stats[2];
+                    direct += stats[3];
+                    free(out);
                 }
-                rows_checked += r[1];
-                staged += stats[2];
-                direct += stats[3];
-                free(out);
-            }
         free(st);
         free(off);
         free(names);

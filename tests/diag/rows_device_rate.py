@@ -1,18 +1,20 @@
-"""The device-side SAM formatter against the host writer on the bench's workload, in ONE process on ONE box (numbers of different
-boxes do not compare, see ab_multi.py); modelled on pam_device_rate.py.  Not run by the suite.
-  (a) per batch, alternating: cm_reads_download + cm_write_sam into TMPFS against cm_format_sam (in ranges of RANGE pairs, into a
-      page-locked buffer) + cm_write_bytes; the kernels' own time by HIP events (ms[7] of cm_prof_get under cm_prof_enable) next
-      to the time the record bytes take over PCIe, and the bytes per pair that go in (FASTQ text) and come out (records).  No
-      contig is loaded for this leg: the batches are staged from the FASTQ text and given states of the usual mix through
-      cm_state_poke (90 % concordant pairs with positions below 2.5e8 and opposite strands, 10 % unmapped), so only the writers
-      are timed;
-  (b) cm_mapping_run (report 2) from the FASTQ files to .mapping.sam and the remain files, host path against CM_FASTQ_DEVICE=1
-      CM_SAM_DEVICE=1, alternating, REPS times each, with the three legs of cm_mapping_stats; the files of both must be the same
-      bytes.  The host path of this leg is also what the parent commit's report = 2 run does.
+"""A device-side row formatter (--format pam | sam) against the host writer on the bench's workload, in ONE process on ONE box
+(numbers of different boxes do not compare, see ab_multi.py).  Not run by the suite.
+  (a) per batch, alternating: cm_reads_download + cm_write_pam / cm_write_sam into TMPFS against cm_format_pam / cm_format_sam (in
+      ranges of RANGE pairs, into a page-locked buffer) + cm_write_bytes; the kernels' own time by HIP events (ms[7] of cm_prof_get
+      under cm_prof_enable) next to the time the row bytes take over PCIe; for sam also the bytes per pair that go in (FASTQ text)
+      and come out (records).  No contig is loaded for this leg: the batches are staged from the FASTQ text and given states of
+      the usual mix through cm_state_poke (90 % concordant pairs with positions below 2.5e8 and opposite strands, 10 % unmapped),
+      so only the writers are timed;
+  (b) cm_mapping_run (report 1 / 2) from the FASTQ files to .mapping.pam / .mapping.sam and the remain files, host path against
+      CM_FASTQ_DEVICE=1 CM_PAM_DEVICE=1 / CM_SAM_DEVICE=1, alternating, REPS times each, with the three legs of cm_mapping_stats;
+      the files of both must be the same bytes.
 The contigs come from the packed FASTA (tables built on the device: no index file to write); that time is seconds_load, outside
-the rates.  Writes OUT after every leg, with the device's name and the commit.
-env: WORKLOAD (hg38like), PAIRS (4194304), BATCH (1048576), RANGE (131072), REPS (2), THREADS (16), TMPFS (/dev/shm),
-OUT (profiles/sam_device.json), COMMIT (the commit to record where the tree has no git metadata)"""
+the rates.  Writes OUT after every leg.  The keys of OUT are those of the recorded profiles/pam_device.json / sam_device.json.
+env: WORKLOAD (hg38like), PAIRS (4194304), BATCH (1048576), RANGE (pam: the batch; sam: 131072), REPS (2), THREADS (16),
+TMPFS (/dev/shm), OUT (profiles/<format>_device.json), COMMIT (sam: the commit to record where the tree has no git metadata)"""
+import argparse
+import ctypes as C
 import hashlib
 import json
 import os
@@ -28,20 +30,31 @@ import numpy as np
 import bench
 from circminer_amd import lib as cl, synth
 
+# what the two formats differ in: the host writer, the C call, cm_mapping_run's report and variable, the bits to stage with, the
+# default range, and whether OUT also says the range, the commit, the kernels' time per 2^20 pairs and the PCIe bytes per pair
+FORMATS = {"pam": dict(write="write_pam", call="cm_format_pam", report=1, var="CM_PAM_DEVICE", quals=False, range=None, extras=False),
+           "sam": dict(write="write_sam", call="cm_format_sam", report=2, var="CM_SAM_DEVICE", quals=True, range=1 << 17, extras=True)}
+ap = argparse.ArgumentParser()
+ap.add_argument("--format", choices=sorted(FORMATS), required=True)
+fmt = ap.parse_args().format
+F = FORMATS[fmt]
+
 wl = os.environ.get("WORKLOAD", "hg38like")
 n_pairs = int(os.environ.get("PAIRS", 1 << 22))
 batch = int(os.environ.get("BATCH", 1 << 20))
 reps = int(os.environ.get("REPS", "2"))
 threads = int(os.environ.get("THREADS", "16"))
 tmpfs = os.environ.get("TMPFS", "/dev/shm")
-rng_pairs = int(os.environ.get("RANGE", 1 << 17))
-out_path = os.environ.get("OUT", os.path.join(ROOT, "profiles", "sam_device.json"))
+rng_pairs = int(os.environ.get("RANGE", F["range"] or batch))
+out_path = os.environ.get("OUT", os.path.join(ROOT, "profiles", f"{fmt}_device.json"))
 os.makedirs(os.path.dirname(out_path), exist_ok=True)
-res = {"workload": wl, "pairs": n_pairs, "batch_pairs": batch, "range_pairs": rng_pairs, "threads": threads, "date": time.strftime("%Y-%m-%d")}
-try:
-    res["commit"] = subprocess.run(["git", "-C", ROOT, "rev-parse", "HEAD"], capture_output=True, text=True).stdout.strip() or os.environ.get("COMMIT")
-except OSError:
-    res["commit"] = None
+res = {"workload": wl, "pairs": n_pairs, "batch_pairs": batch, "threads": threads, "date": time.strftime("%Y-%m-%d")}
+if F["extras"]:
+    res["range_pairs"] = rng_pairs
+    try:
+        res["commit"] = subprocess.run(["git", "-C", ROOT, "rev-parse", "HEAD"], capture_output=True, text=True).stdout.strip() or os.environ.get("COMMIT")
+    except OSError:
+        res["commit"] = None
 
 
 def save():
@@ -52,7 +65,7 @@ def save():
 t = time.perf_counter()
 d = synth.generate(wl, n_pairs=min(n_pairs, 1 << 21), seed=38)
 print(f"{wl}: generated in {time.perf_counter() - t:.1f} s", flush=True)
-base = os.path.join(tmpfs, f"cm_samdev_{os.getpid()}")
+base = os.path.join(tmpfs, f"cm_{fmt}dev_{os.getpid()}")
 shutil.rmtree(base, ignore_errors=True)
 os.makedirs(base)
 try:
@@ -92,8 +105,10 @@ try:
     rd_host = cl.FastqReader(fq[0], fq[1], chrs, P.max_ed, n_threads=threads)
     want = int(res["fastq_bytes"] / n_pairs / 2 * batch * 1.02) + (1 << 16)
     rows_pin = None
-    legs = {"host": {"download_s": 0.0, "write_sam_s": 0.0}, "device": {"format_s": 0.0, "write_bytes_s": 0.0, "kernels_s": 0.0, "row_bytes": 0}}
+    write_s = F["write"] + "_s"
+    legs = {"host": {"download_s": 0.0, write_s: 0.0}, "device": {"format_s": 0.0, "write_bytes_s": 0.0, "kernels_s": 0.0, "row_bytes": 0}}
     sha = {"host": hashlib.sha1(), "device": hashlib.sha1()}
+    call, table = getattr(hp.L, F["call"]), cl.chr_array(chrs)
     got = 0
     k = 0
     bases_total = 0
@@ -101,7 +116,7 @@ try:
         b1, e1, b2, e2 = rd_text.next_text(want)
         if len(b1) == 0 and e1:
             break
-        tb, _, _ = hp.stage_text(b1, b2, batch, eof1=e1, eof2=e2, keep_names=True, keep_quals=True)
+        tb, _, _ = hp.stage_text(b1, b2, batch, eof1=e1, eof2=e2, keep_names=True, keep_quals=F["quals"])
         assert tb.n_pairs > 0
         rd_text.consumed(tb.used1, tb.used2)
         hb = rd_host.next_batch(int(tb.n_pairs))
@@ -126,29 +141,27 @@ try:
         st["type"] = np.where(rng.random(m) < 0.9, 0, 13)
         hp.poke_states(st)
         for leg in (("host", "device") if k % 2 == 0 else ("device", "host")):
-            path = os.path.join(base, f"rows_{leg}.sam")
+            path = os.path.join(base, f"rows_{leg}.{fmt}")
             w = cl.RecordWriter(path, None, chrs)
             if leg == "host":
                 t0 = time.perf_counter()
                 st = hp.download()[0]
                 t1 = time.perf_counter()
-                w.write_sam(hb, st)
+                getattr(w, F["write"])(hb, st)
                 w.close()
                 legs[leg]["download_s"] += t1 - t0
-                legs[leg]["write_sam_s"] += time.perf_counter() - t1
+                legs[leg][write_s] += time.perf_counter() - t1
             else:
                 hp.prof_reset()
-                L, table = hp.L, cl.chr_array(chrs)
-                import ctypes as C
                 nb = C.c_uint64(0)
                 if rows_pin is None:                                  # sized once, outside the timing: a range's bytes scaled to the batch
-                    L.cm_format_sam(hp.h, table, len(chrs), 0, min(hp.n, rng_pairs), None, 0, C.byref(nb), None)
+                    call(hp.h, table, len(chrs), 0, min(hp.n, rng_pairs), None, 0, C.byref(nb), None)
                     rows_pin = hp.host_array(int(nb.value / min(hp.n, rng_pairs) * batch * 1.2) + (1 << 20), np.uint8)
                 t0 = time.perf_counter()
                 filled = 0
                 for a in range(0, hp.n, rng_pairs):
-                    rc = L.cm_format_sam(hp.h, table, len(chrs), a, min(rng_pairs, hp.n - a), rows_pin.ctypes.data + filled, rows_pin.size - filled, C.byref(nb), None)
-                    assert rc == 0, (rc, hp.last_error() if hasattr(hp, "last_error") else "")
+                    rc = call(hp.h, table, len(chrs), a, min(rng_pairs, hp.n - a), rows_pin.ctypes.data + filled, rows_pin.size - filled, C.byref(nb), None)
+                    assert rc == 0, rc
                     filled += int(nb.value)
                 t1 = time.perf_counter()
                 w.write_bytes(rows_pin[:filled])
@@ -165,12 +178,13 @@ try:
     hp.close()
     assert got == n_pairs
     for leg, v in legs.items():
-        total = sum(x for key, x in v.items() if key in ("download_s", "write_sam_s", "format_s", "write_bytes_s"))
+        total = sum(x for key, x in v.items() if key in ("download_s", write_s, "format_s", "write_bytes_s"))
         v["pairs_per_s"] = got / total
     legs["rows_identical"] = sha["host"].hexdigest() == sha["device"].hexdigest()
-    legs["device"]["kernels_ms_per_2_20_pairs"] = legs["device"]["kernels_s"] * 1e3 / got * (1 << 20)
-    legs["pcie_bytes_per_pair"] = {"host_in_bases_and_offsets": bases_total / got + 16, "host_out_states_and_flags": 72 + 1,
-                                   "device_in_text": res["fastq_bytes"] / got, "device_out_records": legs["device"]["row_bytes"] / got}
+    if F["extras"]:
+        legs["device"]["kernels_ms_per_2_20_pairs"] = legs["device"]["kernels_s"] * 1e3 / got * (1 << 20)
+        legs["pcie_bytes_per_pair"] = {"host_in_bases_and_offsets": bases_total / got + 16, "host_out_states_and_flags": 72 + 1,
+                                       "device_in_text": res["fastq_bytes"] / got, "device_out_records": legs["device"]["row_bytes"] / got}
     res["rows_per_batch"] = legs
     print(json.dumps(legs), flush=True)
     save()
@@ -180,13 +194,13 @@ try:
     runs, files = [], {}
     for rep in range(reps):
         for dev in (0, 1):
-            for var in ("CM_FASTQ_DEVICE", "CM_SAM_DEVICE"):
+            for var in ("CM_FASTQ_DEVICE", F["var"]):
                 if dev:
                     os.environ[var] = "1"
                 else:
                     os.environ.pop(var, None)
             out = os.path.join(base, f"run{dev}")
-            st = cl.run_mapping(packed, gtf, fq[0], fq[1], out, cl.default_params(kmer=20), report=2, n_threads=threads, batch_pairs=batch,
+            st = cl.run_mapping(packed, gtf, fq[0], fq[1], out, cl.default_params(kmer=20), report=F["report"], n_threads=threads, batch_pairs=batch,
                                 index_info=packed + ".index.info")
             row = {"rep": rep, "device_rows": dev, "pairs": int(st.pairs), "bsj_pairs": int(st.bsj_pairs), "device_parsed_batches": int(st.device_parsed_batches),
                    "load_s": st.seconds_load, "map_s": st.seconds_map, "pairs_per_s": st.pairs / st.seconds_map,
@@ -196,10 +210,10 @@ try:
             print(json.dumps(row), flush=True)
             if rep == 0:
                 files[dev] = [hashlib.sha1(open(p, "rb").read()).hexdigest()
-                              for p in (out + ".mapping.sam", f"{out}_{st.rounds}_remain_R1.fastq", f"{out}_{st.rounds}_remain_R2.fastq")]
+                              for p in (out + f".mapping.{fmt}", f"{out}_{st.rounds}_remain_R1.fastq", f"{out}_{st.rounds}_remain_R2.fastq")]
             res["file_to_file"] = runs
             save()
-    for var in ("CM_FASTQ_DEVICE", "CM_SAM_DEVICE"):
+    for var in ("CM_FASTQ_DEVICE", F["var"]):
         os.environ.pop(var, None)
     res["files_identical"] = files[0] == files[1]
     for dev, key in ((0, "host"), (1, "device")):

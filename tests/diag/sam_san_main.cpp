@@ -1,46 +1,16 @@
-// Stand-alone sanitizer pass over the bodies of circminer_amd/csrc/cm_sam_text.h through the host emulation (tests/hostemu_sam.cpp):
+// Stand-alone sanitizer pass over the bodies of circminer_amd/csrc/cm_sam_text.h and the plan of cm_rows_text.h through the host
+// emulation (tests/hostemu_sam.cpp, tests/hostemu_rows.h):
 // directed states (every printed field at the boundaries of its format, every combination of mapped / strands / spos order) over
 // reads of every short length, reads with a byte that has no complement at the end, the start and the middle, lower-case reads and
 // a run of long names; whole batches and ranges, the window's rule, every span direct, and a small window; every argument array an
 // exact-size heap block.  The records are compared with printf's.  CPU only, no Python.  From the repository root:
-//   g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=all -I include -I circminer_amd/csrc \
+//   g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=all -I include -I circminer_amd/csrc -I tests \
 //       tests/diag/sam_san_main.cpp tests/hostemu_sam.cpp -o /tmp/sam_san && /tmp/sam_san
-#include <climits>
 #include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <random>
 #include <string>
-#include <vector>
-#include "circminer_hot.h"
-extern "C" int emu_quals(const uint8_t *, uint64_t, uint32_t, const uint64_t *, uint64_t, uint8_t *);
-extern "C" int emu_format_sam(const cm_mapped_read *, uint64_t, const uint8_t *, const uint32_t *, const uint8_t *, const uint64_t *, const uint8_t *, const uint64_t *,
-                              const uint8_t *, const uint8_t *, const cm_chr_info *, uint32_t, uint64_t, uint64_t, uint8_t *, uint64_t, uint64_t *, uint64_t *, uint64_t,
-                              uint32_t, uint32_t *, uint64_t *);
+#include "hostemu_rows.h"
+using emu::exact;
 
-static const uint32_t U32V[] = {0u, 9u, 10u, 99u, 100u, 999999999u, 1000000000u, 4294967295u};
-static const int32_t INTV[] = {0, -1, -9, -10, INT_MIN + 1, INT_MAX, 1000000000};
-static const int32_t TYPEV[] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, -1, 14, -9, -10, INT_MIN, INT_MAX, 1000000000, 100, 13};
-
-static cm_mapped_read directed(uint32_t i, int n_chr) {
-    cm_mapped_read m;
-    memset(&m, 0xee, sizeof m);
-    m.type = TYPEV[i % 23];
-    uint32_t *u[8] = {&m.spos_r1, &m.spos_r2, &m.epos_r1, &m.epos_r2, &m.qspos_r1, &m.qspos_r2, &m.qepos_r1, &m.qepos_r2};
-    for (uint32_t j = 0; j < 8; ++j) *u[j] = U32V[(i + j) % 8];
-    if (i % 5 == 0) m.spos_r2 = m.spos_r1;
-    m.ed_r1 = INTV[i % 7];
-    m.ed_r2 = INTV[(i + 2) % 7];
-    m.tlen = INTV[(i + 4) % 7];
-    m.junc_num = i % 2 ? 65535 : 0;
-    m.gm_compatible = (uint8_t)(i % 3 == 2 ? 255 : i % 3);
-    m.r1_forward = i & 1;
-    m.r2_forward = (i >> 1) & 1;
-    const int32_t ids[4] = {-1, 0, n_chr - 1, n_chr};
-    m.chr_id = ids[i % 4];
-    m.contig_num = (int32_t)(i % 5) - 1;
-    return m;
-}
 static char comp_of(unsigned char c) {
     const char *from = "ACGTNacgtn", *to = "TGCANTGCAN";
     for (int i = 0; from[i]; ++i)
@@ -75,12 +45,6 @@ static std::string printf_rec(const std::string &name, const cm_mapped_read &m, 
              mapped ? (int)(m.gm_compatible != 0) : 0);
     return r + buf;
 }
-template <class T> static T *exact(const std::vector<T> &v) {            // an exact-size heap copy
-    T *p = (T *)malloc(v.size() * sizeof(T) + (v.empty() ? 1 : 0));
-    if (!v.empty()) memcpy(p, v.data(), v.size() * sizeof(T));
-    return p;
-}
-
 int main() {
     const std::string forty(40, 'x');
     const cm_chr_info chrs[4] = {{"c", 1, 0, 1000}, {forty.c_str(), 1, 1000, 500}, {"chr2", 2, 0, 70000}, {"7", 2, 70000, 10}};
@@ -139,7 +103,7 @@ int main() {
             free(pt);
         }
         std::vector<cm_mapped_read> stv(n);
-        for (uint32_t i = 0; i < n; ++i) stv[i] = directed(i, 4);
+        for (uint32_t i = 0; i < n; ++i) stv[i] = emu::directed_state(i, 4, true);
         cm_mapped_read *st = exact(stv);
         const uint64_t ranges[][2] = {{0, n}, {n / 3, n - n / 3}, {7 % n, (uint64_t)(n - 7 % n < 2 ? n - 7 % n : 2)}, {n, 0}, {n - 1, 1}};
         for (const auto &r : ranges)

@@ -1,6 +1,7 @@
 """Helpers of the device-side PAM formatter's tests (test_pam_text_cpu.py, test_gpu_pam_text.py): states at every boundary of the
 row's number formats, FASTQ records whose names cover the rules of the host parser, and the project's own host writer as the
 checker -- cm_fastq_next on files holding the same bytes, then cm_write_pam with the same states."""
+import ctypes as C
 import os
 
 import numpy as np
@@ -61,10 +62,11 @@ def name_records(rng, n, long_run=None, mate=1):
 
 
 class HostRows:
-    """the checker: cm_fastq_next on files with the bytes t1 / t2, then cm_write_pam / the parser's names"""
+    """the checker: cm_fastq_next on files with the bytes t1 / t2, then the host writer `write` ("write_pam": cm_write_pam;
+    "write_sam": cm_write_sam without a header) / the parser's names and arrays"""
 
-    def __init__(self, tmpdir, t1: bytes, t2: bytes, n, tag="pam", chrs=CHRS):
-        self.dir, self.tag, self.chrs = str(tmpdir), tag, chrs
+    def __init__(self, tmpdir, t1: bytes, t2: bytes, n, tag="pam", chrs=CHRS, write="write_pam"):
+        self.dir, self.tag, self.chrs, self.write = str(tmpdir), tag, chrs, write
         p1, p2 = os.path.join(self.dir, f"{tag}_1.fq"), os.path.join(self.dir, f"{tag}_2.fq")
         open(p1, "wb").write(t1)
         open(p2, "wb").write(t2)
@@ -74,23 +76,31 @@ class HostRows:
         assert self.batch is not None and self.batch.n == n
         self._k = 0
 
+    def arrays(self):
+        """(seq1, off1, seq2, off2, qual1, qual2) of the parsed batch, copies"""
+        fb, n = self.batch.fb, self.batch.n
+        off1 = np.ctypeslib.as_array(fb.reads.off1, (n + 1,)).copy()
+        off2 = np.ctypeslib.as_array(fb.reads.off2, (n + 1,)).copy()
+
+        def take(p, ln):
+            return np.ctypeslib.as_array(p, (ln,)).copy() if ln else np.zeros(0, np.uint8)
+        return (take(fb.reads.seq1, int(off1[n])), off1, take(fb.reads.seq2, int(off2[n])), off2, take(fb.qual1, int(off1[n])), take(fb.qual2, int(off2[n])))
+
     def names(self):
-        """(bytes of all names without their NULs as the writer prints them, offsets)"""
-        import ctypes as C
+        """the names as the writer prints them: without their NULs"""
         fb, n = self.batch.fb, self.batch.n
         off = np.ctypeslib.as_array(fb.name_off1, (n + 1,))
         raw = C.string_at(fb.names1, int(off[n])) if int(off[n]) else b""
-        out = [raw[int(off[i]):int(off[i + 1])].split(b"\0")[0] for i in range(n)]
-        return out
+        return [raw[int(off[i]):int(off[i + 1])].split(b"\0")[0] for i in range(n)]
 
-    def rows(self, states, first=0, count=None):
+    def rows(self, states, first=0, count=None, chrs=None):
         n = self.batch.n
         count = n - first if count is None else count
         self._k += 1
-        path = os.path.join(self.dir, f"{self.tag}_{self._k}.pam")
-        w = cl.RecordWriter(path, None, self.chrs)
+        path = os.path.join(self.dir, f"{self.tag}_{self._k}.{self.write[-3:]}")
+        w = cl.RecordWriter(path, None, self.chrs if chrs is None else chrs)
         if count:
-            w.write_pam(self.batch, np.ascontiguousarray(states), np.arange(first, first + count, dtype=np.uint64))
+            getattr(w, self.write)(self.batch, np.ascontiguousarray(states), np.arange(first, first + count, dtype=np.uint64))
         w.close()
         return open(path, "rb").read()
 

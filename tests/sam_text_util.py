@@ -3,16 +3,12 @@ pam_text_util with every combination the SAM rules branch on among the first 64,
 (every word edge of the cooperative copy, one byte outside ACGTNacgtn on reversed and on unreversed records, lower case), and the
 project's own host writer as the checker -- cm_fastq_next on files holding the same bytes, then cm_write_sam with the same states.
 Without a header it gives the rows alone."""
-import ctypes as C
-import os
-
 import numpy as np
 
-from circminer_amd import lib as cl
 from fastq_text_util import records, text_of
-from pam_text_util import CHRS, INT_MAX, INT_MIN, directed_states, name_records
+from pam_text_util import CHRS, INT_MAX, INT_MIN, HostRows, directed_states, name_records
 
-SPAN_RECS, WINDOW = 16, 8192                                            # cmst::SPAN_RECS, cmst::WINDOW
+SPAN_RECS, WINDOW = 16, 8192                                            # cmst::SPAN_RECS, cmrt::WINDOW
 SPAN_PAIRS = SPAN_RECS // 2
 SAM_MAPPED = (0, 1, 2, 5, 7, -1, INT_MIN, -9)                           # type <= CHIORF || CONGEN || CONGNM, as a signed compare
 SAM_UNMAPPED = (3, 4, 6, 8, 13, 14, INT_MAX, 100)
@@ -110,47 +106,6 @@ def sam_pair_text(rng, n, st, long_run=None, hi=150):
     return text_of(r1), text_of(r2), placed
 
 
-class HostSam:
-    """the checker: cm_fastq_next on files with the bytes t1 / t2, then cm_write_sam without a header"""
-
-    def __init__(self, tmpdir, t1: bytes, t2: bytes, n, tag="sam", chrs=CHRS):
-        self.dir, self.tag, self.chrs = str(tmpdir), tag, chrs
-        p1, p2 = os.path.join(self.dir, f"{tag}_1.fq"), os.path.join(self.dir, f"{tag}_2.fq")
-        open(p1, "wb").write(t1)
-        open(p2, "wb").write(t2)
-        self.paths = (p1, p2)
-        self.rd = cl.FastqReader(p1, p2, chrs, 4)
-        self.batch = self.rd.next_batch(n)
-        assert self.batch is not None and self.batch.n == n
-        self._k = 0
-
-    def arrays(self):
-        """(seq1, off1, seq2, off2, qual1, qual2) of the parsed batch, copies"""
-        fb, n = self.batch.fb, self.batch.n
-        off1 = np.ctypeslib.as_array(fb.reads.off1, (n + 1,)).copy()
-        off2 = np.ctypeslib.as_array(fb.reads.off2, (n + 1,)).copy()
-
-        def take(p, ln):
-            return np.ctypeslib.as_array(p, (ln,)).copy() if ln else np.zeros(0, np.uint8)
-        return (take(fb.reads.seq1, int(off1[n])), off1, take(fb.reads.seq2, int(off2[n])), off2, take(fb.qual1, int(off1[n])), take(fb.qual2, int(off2[n])))
-
-    def names(self):
-        """the names as the writer prints them"""
-        fb, n = self.batch.fb, self.batch.n
-        off = np.ctypeslib.as_array(fb.name_off1, (n + 1,))
-        raw = C.string_at(fb.names1, int(off[n])) if int(off[n]) else b""
-        return [raw[int(off[i]):int(off[i + 1])].split(b"\0")[0] for i in range(n)]
-
-    def rows(self, states, first=0, count=None, chrs=None):
-        n = self.batch.n
-        count = n - first if count is None else count
-        self._k += 1
-        path = os.path.join(self.dir, f"{self.tag}_{self._k}.sam")
-        w = cl.RecordWriter(path, None, self.chrs if chrs is None else chrs)
-        if count:
-            w.write_sam(self.batch, np.ascontiguousarray(states), np.arange(first, first + count, dtype=np.uint64))
-        w.close()
-        return open(path, "rb").read()
-
-    def close(self):
-        self.rd.close()
+def HostSam(tmpdir, t1: bytes, t2: bytes, n, tag="sam", chrs=CHRS):
+    """the checker: pam_text_util.HostRows with cm_write_sam (without a header) as the writer"""
+    return HostRows(tmpdir, t1, t2, n, tag=tag, chrs=chrs, write="write_sam")

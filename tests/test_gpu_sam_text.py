@@ -18,7 +18,7 @@ import pytest
 
 from circminer_amd import lib as cl
 from fastq_text_util import HostParse, check_against_host, whole_records
-from pam_text_util import CHRS
+from pam_text_util import CHRS, HostRows
 from sam_text_util import SPAN_PAIRS, SPAN_RECS, HostSam, sam_mapped, sam_pair_text, sam_states
 
 pytestmark = pytest.mark.gpu
@@ -129,6 +129,27 @@ def test_directed_states(hp_plain, hp_wide, texts, n, wide):
     rows, _ = hp.format_sam([])                                   # another chromosome table (none): every mapped RNAME is "-"
     assert rows == hsam.rows(st, chrs=[])
     assert hp.format_sam(CHRS)[0] == want                         # ... and the first table again
+
+
+@pytest.mark.parametrize("wide", [False, True])
+def test_the_two_formatters_alternate_on_one_context(hp_plain, hp_wide, texts, wide):
+    """cm_format_pam and cm_format_sam share the driver, the device buffers and the cached chromosome table: PAM, SAM with another
+    table (none), PAM, a SAM range that cuts a span, on one context; 65 pairs are one full PAM span + 1 row and eight full SAM
+    spans + 2 records"""
+    hp = hp_wide if wide else hp_plain
+    n = 65
+    t1, t2, _, hsam, st = texts(n)
+    hpam = HostRows(hsam.dir, t1, t2, n, tag=f"alt{int(wide)}")
+    try:
+        assert Dev(hp, t1, t2, n, True, True).n == n
+        hp.poke_states(st)
+        pam = hpam.rows(st)
+        assert hp.format_pam(CHRS)[0] == pam
+        assert hp.format_sam(())[0] == hsam.rows(st, chrs=[])
+        assert hp.format_pam(CHRS)[0] == pam
+        assert hp.format_sam(CHRS, first=3, count=9)[0] == hsam.rows(st, 3, 9)
+    finally:
+        hpam.close()
 
 
 def test_refusals_leave_the_batch_intact(built, texts):

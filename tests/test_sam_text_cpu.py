@@ -1,5 +1,5 @@
-"""The device-side SAM formatter without a device: the bodies of circminer_amd/csrc/cm_sam_text.h run by a host emulation
-(tests/hostemu_sam.cpp: shuffled items, spans and lanes, every write of every call caught in shadow buffers and counted) against the
+"""The device-side SAM formatter without a device: the bodies of circminer_amd/csrc/cm_sam_text.h and the plan of cm_rows_text.h run
+by a host emulation (tests/hostemu_sam.cpp, tests/hostemu_rows.h: shuffled items, spans and lanes, every write of every call caught in shadow buffers and counted) against the
 project's own host writer -- cm_fastq_next on files holding the same bytes, then cm_write_sam with the same states."""
 import ctypes as C
 import os
@@ -23,10 +23,11 @@ def emu_sam(built):
     os.makedirs(out_dir, exist_ok=True)
     so = os.path.join(out_dir, "libcmemu_sam.so")
     csrc = os.path.join(ROOT, "circminer_amd", "csrc")
-    srcs = [os.path.join(ROOT, "tests", "hostemu_sam.cpp"), os.path.join(csrc, "cm_sam_text.h"), os.path.join(csrc, "cm_pam_text.h"),
-            os.path.join(csrc, "cm_fastq_text.h"), os.path.join(ROOT, "include", "circminer_hot.h")]
+    srcs = [os.path.join(ROOT, "tests", "hostemu_sam.cpp"), os.path.join(ROOT, "tests", "hostemu_rows.h"), os.path.join(csrc, "cm_sam_text.h"),
+            os.path.join(csrc, "cm_rows_text.h"), os.path.join(csrc, "cm_fastq_text.h"), os.path.join(ROOT, "include", "circminer_hot.h")]
     if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(s) for s in srcs):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-I", os.path.join(ROOT, "include"), "-I", csrc, srcs[0], "-o", so])
+        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-I", os.path.join(ROOT, "include"), "-I", csrc, "-I", os.path.join(ROOT, "tests"),
+                               srcs[0], "-o", so])
     E = C.CDLL(so)
     vp = C.c_void_p
     E.emu_quals.argtypes = [vp, C.c_uint64, C.c_uint32, vp, C.c_uint64, vp]
@@ -148,5 +149,6 @@ def test_emulated_records_without_a_chromosome_table(emu_sam, tmp_path):
 
 
 def test_the_window_constants_are_the_headers():
-    hdr = open(os.path.join(ROOT, "circminer_amd", "csrc", "cm_sam_text.h")).read()
-    assert f"SPAN_RECS = {SPAN_RECS};" in hdr and f"WINDOW = {WINDOW};" in hdr
+    csrc = os.path.join(ROOT, "circminer_amd", "csrc")
+    assert f"SPAN_RECS = {SPAN_RECS};" in open(os.path.join(csrc, "cm_sam_text.h")).read()
+    assert f"WINDOW = {WINDOW};" in open(os.path.join(csrc, "cm_rows_text.h")).read()
