@@ -7,6 +7,7 @@ order is part of the result (reference src/chain.cpp:189).
 from __future__ import annotations
 
 import os
+import re
 import subprocess
 import sys
 
@@ -16,9 +17,27 @@ INC = os.path.join(HERE, "..", "include")
 OUT = os.path.join(CSRC, "libcmhot.so")
 SOURCES = ["cm_hot.hip", "cm_dp_probe.hip", "cm_annot_probe.hip", "cm_dispatch.cpp", "host_index.cpp", "host_annot.cpp", "host_index_io.cpp", "host_fastq.cpp", "host_mapping.cpp", "host_circ.cpp",
            "host_circ_call.cpp"]
-DEPS = SOURCES + sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join("..", "..", "include", "circminer_hot.h")]
-# cm_hot.hip is compiled twice (reads of <= 16 seeds / <= 24 seeds, see cm_dispatch.cpp): its exported names get a suffix
-KERNEL_EXPORTS = ['cm_create', 'cm_destroy', 'cm_last_error', 'cm_load_contig', 'cm_load_contig_raw', 'cm_build_contig', 'cm_index_download', 'cm_load_annotation', 'cm_unload_contig', 'cm_reads_upload', 'cm_reads_stage', 'cm_reads_stage_text', 'cm_reads_peek', 'cm_format_pam', 'cm_format_sam', 'cm_quals_peek', 'cm_state_poke', 'cm_reads_swap', 'cm_map_rounds', 'cm_map_round', 'cm_sync', 'cm_reads_reset', 'cm_collect_active', 'cm_collect_records', 'cm_collect_records_device', 'cm_host_alloc', 'cm_host_free', 'cm_host_register', 'cm_host_unregister', 'cm_type_histogram', 'cm_reads_download', 'cm_map_batch', 'cm_seed_batch', 'cm_chain_batch', 'cm_dp_batch', 'cm_annot_batch', 'cm_debug_lane_clk', 'cm_debug_counters', 'cm_prof_enable', 'cm_prof_reset', 'cm_prof_get', 'cm_prof_counters', 'cm_ctx', 'cm_chain']
+ABI_DEF = "cm_device_abi.def"
+DEPS = SOURCES + sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + [ABI_DEF, os.path.join("..", "..", "include", "circminer_hot.h")]
+# cm_hot.hip is compiled twice (reads of <= 16 seeds / <= 24 seeds, see cm_dispatch.cpp): the names it exports get a suffix.  The
+# entry points are the lines of the table; the context struct, the chain record and the kernel bodies' namespace are no entry points
+# but differ in size between the builds, so they are renamed with them.
+RENAMED_TYPES = ["cm_ctx", "cm_chain", "cmc"]
+_ABI_LINE = re.compile(r"(CM_DEV|CM_DEV_OWN)\((.+?), (cm_\w+), \(([^()]*)\)(?:, \(([^()]*)\))?\)")
+
+
+def device_abi(path: str = os.path.join(CSRC, ABI_DEF)):
+    """The lines of the table as (macro, return type, name, parameters, arguments or None)."""
+    rows = []
+    for line in open(path):
+        if line.startswith("CM_DEV"):
+            m = _ABI_LINE.fullmatch(line.rstrip())
+            if not m or (m.group(1) == "CM_DEV") != (m.group(5) is not None):
+                raise RuntimeError(f"{ABI_DEF}: cannot read {line.rstrip()!r}")
+            rows.append(m.groups())
+    return rows
+
+
 VARIANTS = (("k16", []), ("k24", ["-DCM_MAX_CHAIN_FRAGS=24"]))
 HIP_ONCE = ["cm_dp_probe.hip", "cm_annot_probe.hip"]      # device code that does not depend on CM_MAX_CHAIN_FRAGS: one build, its own names (the test hooks behind cm_dp_batch / cm_annot_batch)
 
@@ -39,6 +58,7 @@ def build(force: bool = False, verbose: bool = False, tag: str = "", flags=()) -
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     extra = os.environ.get("CM_EXTRA_FLAGS", "").split() + list(flags)
     sfx = ("_" + tag) if tag else ""
+    renamed = [row[2] for row in device_abi()] + RENAMED_TYPES
     objs = []
     jobs = []
     for s in SOURCES:
@@ -52,13 +72,15 @@ def build(force: bool = False, verbose: bool = False, tag: str = "", flags=()) -
                 continue
             for vtag, vflags in VARIANTS:
                 o = os.path.join(CSRC, s.rsplit(".", 1)[0] + "_" + vtag + sfx + ".o")
-                ren = [f"-D{n}={n}_{vtag}" for n in KERNEL_EXPORTS + ["cmc"]]      # cmc: the kernel bodies' namespace (their structs differ in size)
+                ren = [f"-D{n}={n}_{vtag}" for n in renamed]
                 jobs.append((s + " [" + vtag + "]", [base[0]] + arch + base[1:] + vflags + ren + [os.path.join(CSRC, s), "-o", o]))
                 objs.append(o)
         else:
             o = os.path.join(CSRC, s.rsplit(".", 1)[0] + sfx + ".o")
             jobs.append((s, [base[0], "-x", "c++"] + base[1:] + [os.path.join(CSRC, s), "-o", o]))   # host-only sources: plain C++
             objs.append(o)
+    if verbose:
+        sys.stderr.write("".join(" ".join(cmd) + "\n" for _, cmd in jobs))
     procs = [(name, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)) for name, cmd in jobs]   # in parallel
     failed = []
     for name, pr in procs:

@@ -197,6 +197,101 @@ _lib = None
 RELEASE_HOOK = C.CFUNCTYPE(None, C.c_void_p, C.c_void_p, C.c_uint64)      # cm_fastq_set_release_hook: (user, ptr, bytes)
 
 
+vp = C.c_void_p
+pp = C.POINTER
+# Every prototype of include/circminer_hot.h: (result, arguments).  This dict is the list of what the library must export.
+SIGNATURES = {
+    "cm_create": (C.c_int, [pp(Params), pp(vp)]),
+    "cm_destroy": (None, [vp]),
+    "cm_last_error": (C.c_char_p, [vp]),
+    "cm_load_contig": (C.c_int, [vp, C.c_int, pp(IndexView)]),
+    "cm_load_annotation": (C.c_int, [vp, C.c_int, pp(AnnotView)]),
+    "cm_load_contig_raw": (C.c_int, [vp, C.c_int, pp(IndexRaw)]),
+    "cm_host_next_contig_raw": (C.c_int, [vp, C.c_int, pp(IndexRaw), pp(C.c_int)]),
+    "cm_build_contig": (C.c_int, [vp, C.c_int, C.c_int32, u8p, C.c_uint32, pp(BuildStats)]),
+    "cm_index_download": (C.c_int, [vp, C.c_int, vp, vp, vp, C.c_uint64, pp(C.c_uint64)]),
+    "cm_unload_contig": (C.c_int, [vp, C.c_int]),
+    "cm_reads_upload": (C.c_int, [vp, pp(Reads), vp]),
+    "cm_reads_stage": (C.c_int, [vp, pp(Reads), vp]),
+    "cm_reads_swap": (C.c_int, [vp]),
+    "cm_reads_stage_text": (C.c_int, [vp, vp, C.c_uint64, vp, C.c_uint64, C.c_uint64, C.c_uint32, vp, vp, pp(TextBatch)]),
+    "cm_reads_peek": (C.c_int, [vp, vp, C.c_uint64, vp, vp, C.c_uint64, vp, pp(C.c_uint64)]),
+    "cm_fastq_next_text": (C.c_int, [vp, C.c_uint64, pp(vp), pp(C.c_uint64), pp(C.c_int), pp(vp), pp(C.c_uint64), pp(C.c_int)]),
+    "cm_fastq_text_consumed": (C.c_int, [vp, C.c_uint64, C.c_uint64]),
+    "cm_write_remain_text": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_uint64]),
+    "cm_format_pam": (C.c_int, [vp, pp(ChrInfo), C.c_uint32, C.c_uint64, C.c_uint64, vp, C.c_uint64, pp(C.c_uint64), pp(C.c_uint64)]),
+    "cm_format_sam": (C.c_int, [vp, pp(ChrInfo), C.c_uint32, C.c_uint64, C.c_uint64, vp, C.c_uint64, pp(C.c_uint64), pp(C.c_uint64)]),
+    "cm_quals_peek": (C.c_int, [vp, vp, C.c_uint64, vp, C.c_uint64]),
+    "cm_state_poke": (C.c_int, [vp, vp]),
+    "cm_debug_lane_clk": (C.c_int, [vp, vp]),
+    "cm_debug_counters": (C.c_int, [vp, vp]),
+    "cm_write_bytes": (C.c_int, [vp, vp, C.c_uint64]),
+    "cm_map_round": (C.c_int, [vp, C.c_int, C.c_int]),
+    "cm_map_rounds": (C.c_int, [vp, i32p, C.c_int, C.c_int]),
+    "cm_reads_download": (C.c_int, [vp, vp, vp, vp]),
+    "cm_map_batch": (C.c_int, [vp, C.c_int, C.c_int, pp(Reads), vp, vp, vp]),
+    "cm_sync": (C.c_int, [vp]),
+    "cm_reads_reset": (C.c_int, [vp]),
+    "cm_collect_active": (C.c_int, [vp, C.c_uint64, vp, vp, pp(C.c_uint64)]),
+    "cm_collect_records": (C.c_int, [vp, C.c_uint64, C.c_uint64, vp, pp(C.c_uint64)]),
+    "cm_collect_records_device": (C.c_int, [vp, C.c_uint64, C.c_uint64, vp, pp(C.c_uint64)]),
+    "cm_host_alloc": (C.c_int, [vp, C.c_uint64, pp(vp)]),
+    "cm_host_free": (C.c_int, [vp, vp]),
+    "cm_host_register": (C.c_int, [vp, vp, C.c_uint64]),
+    "cm_host_unregister": (C.c_int, [vp, vp]),
+    "cm_type_histogram": (C.c_int, [vp, pp(C.c_uint64)]),
+    "cm_seed_batch": (C.c_int, [vp, C.c_int, vp, vp, vp, C.c_uint32, pp(C.c_uint32)]),
+    "cm_chain_batch": (C.c_int, [vp, C.c_int, vp, vp, vp]),
+    "cm_dp_batch": (C.c_int, [vp, pp(Params), vp, C.c_uint64, vp, C.c_uint32, C.c_int, C.c_uint32, C.c_int, C.c_uint32, vp]),
+    "cm_annot_batch": (C.c_int, [vp, C.c_int, pp(Params), vp, C.c_uint32, vp, vp]),
+    "cm_prof_enable": (C.c_int, [vp, C.c_int]),
+    "cm_prof_reset": (C.c_int, [vp]),
+    "cm_prof_get": (C.c_int, [vp, pp(C.c_double), pp(C.c_uint64)]),
+    "cm_prof_counters": (C.c_int, [vp, pp(C.c_uint64)]),
+    "cm_host_build_index": (C.c_int, [u8p, C.c_uint32, C.c_int32, C.c_int32, C.c_int, pp(IndexView)]),
+    "cm_host_free_index": (None, [pp(IndexView)]),
+    "cm_host_index_stats": (C.c_int, [pp(IndexView), C.c_int32, C.c_int, pp(C.c_uint64)]),
+    "cm_host_build_annotation": (C.c_int, [C.c_char_p, pp(ChrInfo), C.c_uint32, u32p, C.c_uint32, C.c_int32,
+                                           pp(AnnotView)]),
+    "cm_host_free_annotation": (None, [pp(AnnotView), C.c_uint32]),
+    "cm_host_pack_genome": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32]),
+    "cm_host_read_index_info": (C.c_int, [C.c_char_p, pp(pp(ChrInfo)), pp(C.c_uint32)]),
+    "cm_host_free_index_info": (None, [pp(ChrInfo), C.c_uint32]),
+    "cm_host_write_index": (C.c_int, [C.c_char_p, C.c_char_p, C.c_int32, C.c_int, C.c_int]),
+    "cm_host_open_index": (C.c_int, [C.c_char_p, pp(vp), pp(C.c_int32), pp(C.c_int32), pp(C.c_uint32)]),
+    "cm_host_next_contig": (C.c_int, [vp, C.c_int, pp(IndexView), pp(C.c_int)]),
+    "cm_host_next_contig_genome": (C.c_int, [vp, pp(IndexView), pp(C.c_int)]),
+    "cm_host_free_loaded_contig": (None, [pp(IndexView)]),
+    "cm_host_close_index": (None, [vp]),
+    "cm_fastq_open": (C.c_int, [C.c_char_p, C.c_char_p, pp(ChrInfo), C.c_uint32, C.c_int32, pp(vp)]),
+    "cm_fastq_open_shard": (C.c_int, [C.c_char_p, C.c_char_p, pp(ChrInfo), C.c_uint32, C.c_int32, C.c_int32, C.c_int32, C.c_int, pp(vp),
+                                      pp(C.c_uint64), pp(C.c_uint64)]),
+    "cm_merge_parts": (C.c_int, [C.c_char_p, C.c_int32, C.c_int32, C.c_int32]),
+    "cm_fastq_next": (C.c_int, [vp, C.c_uint64, pp(FastqBatch)]),
+    "cm_fastq_close": (None, [vp]),
+    "cm_fastq_set_release_hook": (None, [vp, RELEASE_HOOK, vp]),
+    "cm_writer_open": (C.c_int, [C.c_char_p, C.c_char_p, pp(ChrInfo), C.c_uint32, pp(vp)]),
+    "cm_write_remain": (C.c_int, [vp, pp(FastqBatch), vp, vp, C.c_uint64]),
+    "cm_write_remain_records": (C.c_int, [vp, pp(FastqBatch), vp, C.c_uint64]),
+    "cm_write_pam": (C.c_int, [vp, pp(FastqBatch), vp, vp, C.c_uint64]),
+    "cm_host_gene_overlap": (C.c_int, [pp(AnnotView), C.c_uint32, pp(u32p), pp(C.c_uint32)]),
+    "cm_sort_remain": (C.c_int, [C.c_char_p, C.c_char_p]),
+    "cm_regional_table_build": (C.c_int, [vp, C.c_uint32, C.c_int32, C.c_int32, pp(u32p), pp(u32p)]),
+    "cm_regional_table_free": (None, [u32p, u32p]),
+    "cm_circ_report": (C.c_int, [pp(CircRes), C.c_uint64, C.c_char_p]),
+    "cm_mapping_run": (C.c_int, [pp(MappingArgs), pp(MappingStats), C.c_char_p, C.c_uint64]),
+    "cm_circ_call": (C.c_int, [pp(Params), C.c_int32, C.c_uint32, pp(IndexView), pp(AnnotView), pp(ChrInfo), C.c_uint32, pp(FastqBatch),
+                               C.c_char_p, C.c_char_p, pp(CircStats)]),
+    "cm_circ_run": (C.c_int, [pp(CircArgs), pp(CircStats), C.c_char_p, C.c_uint64]),
+    "cm_write_sam_header": (C.c_int, [vp]),
+    "cm_write_sam": (C.c_int, [vp, pp(FastqBatch), vp, vp, C.c_uint64]),
+    "cm_writer_flush": (C.c_int, [vp]),
+    "cm_writer_close": (None, [vp]),
+    "cm_abi_sizes": (C.c_int, [pp(C.c_uint32), C.c_uint32]),
+}
+EXPORTED_SYMBOLS = sorted(SIGNATURES)
+
+
 def load(path: str = LIB_PATH) -> C.CDLL:
     """Load libcmhot.so and declare every prototype of include/circminer_hot.h."""
     global _lib
@@ -206,96 +301,7 @@ def load(path: str = LIB_PATH) -> C.CDLL:
         raise RuntimeError(f"{path} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
                            "(the hot path is HIP-only; there is no CPU fallback)")
     L = C.CDLL(path)
-    vp = C.c_void_p
-    pp = C.POINTER
-    sigs = {
-        "cm_create": (C.c_int, [pp(Params), pp(vp)]),
-        "cm_destroy": (None, [vp]),
-        "cm_last_error": (C.c_char_p, [vp]),
-        "cm_load_contig": (C.c_int, [vp, C.c_int, pp(IndexView)]),
-        "cm_load_annotation": (C.c_int, [vp, C.c_int, pp(AnnotView)]),
-        "cm_load_contig_raw": (C.c_int, [vp, C.c_int, pp(IndexRaw)]),
-        "cm_host_next_contig_raw": (C.c_int, [vp, C.c_int, pp(IndexRaw), pp(C.c_int)]),
-        "cm_build_contig": (C.c_int, [vp, C.c_int, C.c_int32, u8p, C.c_uint32, pp(BuildStats)]),
-        "cm_index_download": (C.c_int, [vp, C.c_int, vp, vp, vp, C.c_uint64, pp(C.c_uint64)]),
-        "cm_unload_contig": (C.c_int, [vp, C.c_int]),
-        "cm_reads_upload": (C.c_int, [vp, pp(Reads), vp]),
-        "cm_reads_stage": (C.c_int, [vp, pp(Reads), vp]),
-        "cm_reads_swap": (C.c_int, [vp]),
-        "cm_reads_stage_text": (C.c_int, [vp, vp, C.c_uint64, vp, C.c_uint64, C.c_uint64, C.c_uint32, vp, vp, pp(TextBatch)]),
-        "cm_reads_peek": (C.c_int, [vp, vp, C.c_uint64, vp, vp, C.c_uint64, vp, pp(C.c_uint64)]),
-        "cm_fastq_next_text": (C.c_int, [vp, C.c_uint64, pp(vp), pp(C.c_uint64), pp(C.c_int), pp(vp), pp(C.c_uint64), pp(C.c_int)]),
-        "cm_fastq_text_consumed": (C.c_int, [vp, C.c_uint64, C.c_uint64]),
-        "cm_write_remain_text": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_uint64]),
-        "cm_format_pam": (C.c_int, [vp, pp(ChrInfo), C.c_uint32, C.c_uint64, C.c_uint64, vp, C.c_uint64, pp(C.c_uint64), pp(C.c_uint64)]),
-        "cm_format_sam": (C.c_int, [vp, pp(ChrInfo), C.c_uint32, C.c_uint64, C.c_uint64, vp, C.c_uint64, pp(C.c_uint64), pp(C.c_uint64)]),
-        "cm_quals_peek": (C.c_int, [vp, vp, C.c_uint64, vp, C.c_uint64]),
-        "cm_state_poke": (C.c_int, [vp, vp]),
-        "cm_write_bytes": (C.c_int, [vp, vp, C.c_uint64]),
-        "cm_map_round": (C.c_int, [vp, C.c_int, C.c_int]),
-        "cm_map_rounds": (C.c_int, [vp, i32p, C.c_int, C.c_int]),
-        "cm_reads_download": (C.c_int, [vp, vp, vp, vp]),
-        "cm_map_batch": (C.c_int, [vp, C.c_int, C.c_int, pp(Reads), vp, vp, vp]),
-        "cm_sync": (C.c_int, [vp]),
-        "cm_reads_reset": (C.c_int, [vp]),
-        "cm_collect_active": (C.c_int, [vp, C.c_uint64, vp, vp, pp(C.c_uint64)]),
-        "cm_collect_records": (C.c_int, [vp, C.c_uint64, C.c_uint64, vp, pp(C.c_uint64)]),
-        "cm_collect_records_device": (C.c_int, [vp, C.c_uint64, C.c_uint64, vp, pp(C.c_uint64)]),
-        "cm_host_alloc": (C.c_int, [vp, C.c_uint64, pp(vp)]),
-        "cm_host_free": (C.c_int, [vp, vp]),
-        "cm_host_register": (C.c_int, [vp, vp, C.c_uint64]),
-        "cm_host_unregister": (C.c_int, [vp, vp]),
-        "cm_type_histogram": (C.c_int, [vp, pp(C.c_uint64)]),
-        "cm_seed_batch": (C.c_int, [vp, C.c_int, vp, vp, vp, C.c_uint32, pp(C.c_uint32)]),
-        "cm_chain_batch": (C.c_int, [vp, C.c_int, vp, vp, vp]),
-        "cm_dp_batch": (C.c_int, [vp, pp(Params), vp, C.c_uint64, vp, C.c_uint32, C.c_int, C.c_uint32, C.c_int, C.c_uint32, vp]),
-        "cm_annot_batch": (C.c_int, [vp, C.c_int, pp(Params), vp, C.c_uint32, vp, vp]),
-        "cm_prof_enable": (C.c_int, [vp, C.c_int]),
-        "cm_prof_reset": (C.c_int, [vp]),
-        "cm_prof_get": (C.c_int, [vp, pp(C.c_double), pp(C.c_uint64)]),
-        "cm_prof_counters": (C.c_int, [vp, pp(C.c_uint64)]),
-        "cm_host_build_index": (C.c_int, [u8p, C.c_uint32, C.c_int32, C.c_int32, C.c_int, pp(IndexView)]),
-        "cm_host_free_index": (None, [pp(IndexView)]),
-        "cm_host_index_stats": (C.c_int, [pp(IndexView), C.c_int32, C.c_int, pp(C.c_uint64)]),
-        "cm_host_build_annotation": (C.c_int, [C.c_char_p, pp(ChrInfo), C.c_uint32, u32p, C.c_uint32, C.c_int32,
-                                               pp(AnnotView)]),
-        "cm_host_free_annotation": (None, [pp(AnnotView), C.c_uint32]),
-        "cm_host_pack_genome": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32]),
-        "cm_host_read_index_info": (C.c_int, [C.c_char_p, pp(pp(ChrInfo)), pp(C.c_uint32)]),
-        "cm_host_free_index_info": (None, [pp(ChrInfo), C.c_uint32]),
-        "cm_host_write_index": (C.c_int, [C.c_char_p, C.c_char_p, C.c_int32, C.c_int, C.c_int]),
-        "cm_host_open_index": (C.c_int, [C.c_char_p, pp(vp), pp(C.c_int32), pp(C.c_int32), pp(C.c_uint32)]),
-        "cm_host_next_contig": (C.c_int, [vp, C.c_int, pp(IndexView), pp(C.c_int)]),
-        "cm_host_next_contig_genome": (C.c_int, [vp, pp(IndexView), pp(C.c_int)]),
-        "cm_host_free_loaded_contig": (None, [pp(IndexView)]),
-        "cm_host_close_index": (None, [vp]),
-        "cm_fastq_open": (C.c_int, [C.c_char_p, C.c_char_p, pp(ChrInfo), C.c_uint32, C.c_int32, pp(vp)]),
-        "cm_fastq_open_shard": (C.c_int, [C.c_char_p, C.c_char_p, pp(ChrInfo), C.c_uint32, C.c_int32, C.c_int32, C.c_int32, C.c_int, pp(vp),
-                                          pp(C.c_uint64), pp(C.c_uint64)]),
-        "cm_merge_parts": (C.c_int, [C.c_char_p, C.c_int32, C.c_int32, C.c_int32]),
-        "cm_fastq_next": (C.c_int, [vp, C.c_uint64, pp(FastqBatch)]),
-        "cm_fastq_close": (None, [vp]),
-        "cm_fastq_set_release_hook": (None, [vp, RELEASE_HOOK, vp]),
-        "cm_writer_open": (C.c_int, [C.c_char_p, C.c_char_p, pp(ChrInfo), C.c_uint32, pp(vp)]),
-        "cm_write_remain": (C.c_int, [vp, pp(FastqBatch), vp, vp, C.c_uint64]),
-        "cm_write_remain_records": (C.c_int, [vp, pp(FastqBatch), vp, C.c_uint64]),
-        "cm_write_pam": (C.c_int, [vp, pp(FastqBatch), vp, vp, C.c_uint64]),
-        "cm_host_gene_overlap": (C.c_int, [pp(AnnotView), C.c_uint32, pp(u32p), pp(C.c_uint32)]),
-        "cm_sort_remain": (C.c_int, [C.c_char_p, C.c_char_p]),
-        "cm_regional_table_build": (C.c_int, [vp, C.c_uint32, C.c_int32, C.c_int32, pp(u32p), pp(u32p)]),
-        "cm_regional_table_free": (None, [u32p, u32p]),
-        "cm_circ_report": (C.c_int, [pp(CircRes), C.c_uint64, C.c_char_p]),
-        "cm_mapping_run": (C.c_int, [pp(MappingArgs), pp(MappingStats), C.c_char_p, C.c_uint64]),
-        "cm_circ_call": (C.c_int, [pp(Params), C.c_int32, C.c_uint32, pp(IndexView), pp(AnnotView), pp(ChrInfo), C.c_uint32, pp(FastqBatch),
-                                   C.c_char_p, C.c_char_p, pp(CircStats)]),
-        "cm_circ_run": (C.c_int, [pp(CircArgs), pp(CircStats), C.c_char_p, C.c_uint64]),
-        "cm_write_sam_header": (C.c_int, [vp]),
-        "cm_write_sam": (C.c_int, [vp, pp(FastqBatch), vp, vp, C.c_uint64]),
-        "cm_writer_flush": (C.c_int, [vp]),
-        "cm_writer_close": (None, [vp]),
-    }
-    sigs["cm_abi_sizes"] = (C.c_int, [pp(C.c_uint32), C.c_uint32])
-    for name, (res, args) in sigs.items():
+    for name, (res, args) in SIGNATURES.items():
         fn = getattr(L, name)  # AttributeError if the library does not export a declared symbol
         fn.restype = res
         fn.argtypes = args
@@ -308,18 +314,6 @@ def load(path: str = LIB_PATH) -> C.CDLL:
         raise RuntimeError(f"circminer_amd.lib: struct sizes differ from {path}: library {list(got[:max(n, 0)])}, ctypes {mine}")
     _lib = L
     return L
-
-
-EXPORTED_SYMBOLS = ["cm_create", "cm_destroy", "cm_last_error", "cm_load_contig", "cm_load_contig_raw", "cm_host_next_contig_raw", "cm_load_annotation",
-                    "cm_unload_contig", "cm_reads_upload", "cm_reads_stage", "cm_reads_swap", "cm_map_round", "cm_map_rounds", "cm_reads_download", "cm_map_batch",
-                    "cm_sync", "cm_reads_reset", "cm_collect_active", "cm_collect_records", "cm_collect_records_device", "cm_abi_sizes", "cm_host_alloc", "cm_host_free", "cm_host_register", "cm_host_unregister", "cm_type_histogram", "cm_write_remain_records", "cm_seed_batch", "cm_chain_batch", "cm_dp_batch", "cm_annot_batch", "cm_prof_enable", "cm_prof_reset", "cm_prof_get",
-                    "cm_prof_counters", "cm_host_build_index", "cm_host_free_index", "cm_host_index_stats", "cm_host_build_annotation",
-                    "cm_host_free_annotation", "cm_host_pack_genome", "cm_host_read_index_info", "cm_host_free_index_info",
-                    "cm_host_write_index", "cm_host_open_index", "cm_host_next_contig", "cm_host_next_contig_genome", "cm_host_free_loaded_contig",
-                    "cm_host_close_index", "cm_fastq_open", "cm_fastq_open_shard", "cm_merge_parts", "cm_fastq_next", "cm_fastq_set_release_hook", "cm_fastq_close", "cm_writer_open", "cm_write_remain",
-                    "cm_write_pam", "cm_write_sam_header", "cm_write_sam", "cm_writer_flush", "cm_writer_close", "cm_mapping_run", "cm_sort_remain", "cm_circ_report", "cm_circ_call", "cm_circ_run", "cm_host_gene_overlap", "cm_regional_table_build", "cm_regional_table_free",
-                    "cm_build_contig", "cm_index_download", "cm_reads_stage_text", "cm_reads_peek", "cm_fastq_next_text", "cm_fastq_text_consumed",
-                    "cm_write_remain_text", "cm_format_pam", "cm_state_poke", "cm_write_bytes", "cm_format_sam", "cm_quals_peek"]
 
 
 class HostIndex:

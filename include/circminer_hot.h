@@ -417,6 +417,13 @@ int cm_quals_peek(cm_ctx *ctx, uint8_t *qual1, uint64_t cap1, uint8_t *qual2, ui
 /* test hook, the counterpart of cm_reads_download: overwrite the carried states of the resident batch (n_pairs records), behind
  * everything queued for it.  CM_ESTATE without a resident batch.  Flags and categories are not touched. */
 int cm_state_poke(cm_ctx *ctx, const cm_mapped_read *states);
+/* test hook for the scripts of tests/diag: the pair kernels' lane times in 100 MHz ticks, recorded for a batch uploaded with
+ * CM_LANE_CLK in the environment: n_pairs words, 33 n_pairs in a -DCM_DIAG build of the library (the scripts name the rows);
+ * CM_EINVAL when nothing was recorded. */
+int cm_debug_lane_clk(cm_ctx *ctx, unsigned long long *out);
+/* test hook for the scripts of tests/diag: the 32 raw counter words of which cm_prof_counters returns the first 8; from word 8 on
+ * what a diagnostic build (-DCM_CHAIN_DIAG, -DCM_DIAG_CNT) accumulates there. */
+int cm_debug_counters(cm_ctx *ctx, unsigned long long *out);
 
 /* ---------------- timing hooks for bench.py (HIP events on the ctx stream) ---------------- */
 /* Milliseconds spent in each kernel class since the last cm_prof_reset(), and launch counts:

@@ -24,7 +24,6 @@ ms, nl, cnt = hp.prof_get()
 print("stage ms:", [round(x, 2) for x in ms], "launches", nl)
 import ctypes as C
 raw = (C.c_ulonglong * 32)()
-hp.L.cm_debug_counters.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong)]
 hp.L.cm_debug_counters(hp.h, raw)
 t = [raw[k] / 1e5 for k in (13, 14, 15)]          # ms of wave time
 print(f"k_chain_heavy wave-ms: load+init {t[0]:.0f}, DP {t[1]:.0f}, back-tracking {t[2]:.0f}  (sum {sum(t):.0f}; "

@@ -23,7 +23,6 @@ hp.prof(True); hp.prof_reset()
 hp.map_rounds(slots, True); hp.sync()
 ms, nl, _ = hp.prof_get()
 raw = (C.c_ulonglong * 32)()
-hp.L.cm_debug_counters.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong)]
 hp.L.cm_debug_counters(hp.h, raw)
 t = [raw[k] / 1e5 for k in (13, 14, 15)]          # ms of wave time
 np_ = max(raw[22], 1)

@@ -20,7 +20,6 @@ hp.upload(b)
 hp.prof(True); hp.prof_reset()
 hp.map_rounds([0, 1, 2], True); hp.sync()
 raw = (C.c_ulonglong * 32)()
-hp.L.cm_debug_counters.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong)]
 hp.L.cm_debug_counters(hp.h, raw)
 for a in range(2):
     o = [raw[8 + 8 * a + k] for k in range(6)]

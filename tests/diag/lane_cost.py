@@ -14,7 +14,6 @@ d = synth.generate(os.environ.get('PRESET', 'chr21'), n_pairs=N, seed=int(os.env
 open('/tmp/c.gtf', 'w').write(d.gtf_text)
 hi = cl.HostIndex(d.contigs[:1], [t for t in d.chr_table if t[1] == 1], '/tmp/c.gtf', n_threads=16)
 P = cl.default_params(); hp = cl.HotPath(P); hp.load_contig(0, hi.views[0], hi.annots[0])
-hp.L.cm_debug_lane_clk.argtypes = [C.c_void_p, C.c_void_p]
 b = cl.ReadBatch(d.seq1, d.seq2); hp.upload(b)
 hp.reset(); hp.map_round(0, True); hp.sync()
 clk = np.zeros(b.n, np.uint64); assert hp.L.cm_debug_lane_clk(hp.h, clk.ctypes.data) == 0

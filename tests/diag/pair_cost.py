@@ -9,7 +9,6 @@ d = synth.generate('chr21', n_pairs=N, seed=21)
 open('/tmp/c.gtf', 'w').write(d.gtf_text)
 hi = cl.HostIndex(d.contigs, d.chr_table, '/tmp/c.gtf')
 P = cl.default_params(); hp = cl.HotPath(P); hp.load_contig(0, hi.views[0], hi.annots[0])
-hp.L.cm_debug_lane_clk.argtypes = [C.c_void_p, C.c_void_p]
 b = cl.ReadBatch(d.seq1, d.seq2); hp.upload(b); ch, nc, hh = hp.chains(0); nc = nc.reshape(-1, 4)
 ch = ch.reshape(-1, 4, 30)
 cost = nc[:, 0] * nc[:, 3] + nc[:, 2] * nc[:, 1] + nc.sum(1)

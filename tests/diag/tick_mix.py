@@ -9,7 +9,6 @@ d = synth.generate('chr21', n_pairs=N, seed=21)
 open('/tmp/c.gtf', 'w').write(d.gtf_text)
 hi = cl.HostIndex(d.contigs, d.chr_table, '/tmp/c.gtf')
 P = cl.default_params(); hp = cl.HotPath(P); hp.load_contig(0, hi.views[0], hi.annots[0])
-hp.L.cm_debug_lane_clk.argtypes = [C.c_void_p, C.c_void_p]
 b = cl.ReadBatch(d.seq1, d.seq2); hp.upload(b); ch, nc, hh = hp.chains(0); nc = nc.reshape(-1, 4)
 hp.reset(); hp.map_round(0, True); hp.sync()
 clk = np.zeros(b.n * 16, np.uint64); assert hp.L.cm_debug_lane_clk(hp.h, clk.ctypes.data) == 0

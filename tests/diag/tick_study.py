@@ -8,7 +8,6 @@ d = synth.generate('chr21', n_pairs=100000, seed=21)
 open('/tmp/c.gtf', 'w').write(d.gtf_text)
 hi = cl.HostIndex(d.contigs, d.chr_table, '/tmp/c.gtf')
 P = cl.default_params(); hp = cl.HotPath(P); hp.load_contig(0, hi.views[0], hi.annots[0])
-hp.L.cm_debug_lane_clk.argtypes = [C.c_void_p, C.c_void_p]
 def run(idx):
     b = cl.ReadBatch(d.seq1[idx], d.seq2[idx]); hp.upload(b); hp.map_round(0, True); hp.sync()
     clk = np.zeros(b.n * 16, np.uint64); assert hp.L.cm_debug_lane_clk(hp.h, clk.ctypes.data) == 0

@@ -10,7 +10,6 @@ d = synth.generate(os.environ.get('PRESET', 'chr21'), n_pairs=N, seed=21)
 open('/tmp/c.gtf', 'w').write(d.gtf_text)
 hi = cl.HostIndex(d.contigs[:1], [t for t in d.chr_table if t[1] == 1], '/tmp/c.gtf', n_threads=16)
 P = cl.default_params(); hp = cl.HotPath(P); hp.load_contig(0, hi.views[0], hi.annots[0])
-hp.L.cm_debug_lane_clk.argtypes = [C.c_void_p, C.c_void_p]
 
 def run(s1, s2, label):
     b = cl.ReadBatch(s1, s2); hp.upload(b)
