@@ -53,6 +53,7 @@ enum ProfClass { PC_NONE = -1, PC_SEED = 0, PC_CHAIN = 1, PC_PAIR = 2, PC_SCAN =
 enum Counter {
     CN_PROBES = 0 /* + 1: touches, + 2: hits (k_seed) */, CN_PAIR_ROUNDS = 3, CN_RERUN = 4 /* ... mapped by the re-run launch */,
     CN_FALL = 5, CN_FALL_2ND = 6,                    // pairs the pipeline handed to its fall-back list; those of the second attempt
+    CN_DEAD_CHAINS = 7,                              // chaining problems with hits that were not chained (k_chain_cls, quad_dead): read through cm_debug_counters
     // -DCM_CHAIN_DIAG (k_chain_heavy): lane sums [5], wave time per phase [3], wave time per DP step [4], shape of the back-tracking
     CN_CD_LANE = 8, CN_CD_PHASE = 13, CN_CD_WAVE = 16, CN_CD_EVENTS = 20, CN_CD_LEVELS = 21, CN_CD_PROBLEMS = 22, CN_CD_PASSES = 23, CN_CD_CELLS = 24,
     CN_CD_REGLOG = 25, CN_CD_BATCHES = 26, CN_CD_PRE_USED = 27, CN_CD_PRE_UNUSED = 28,      // problems whose log fits registers, candidate batches, scores asked for ahead
@@ -153,8 +154,23 @@ __global__ void __launch_bounds__(BLK) k_seed(KCore kc, ReadsDev rd, const uint8
 // k_scan_c: adds the block base.  out[n] = grand total.
 constexpr int SCAN_T = 256;
 constexpr int SCAN_ELEMS = 1024;       // 4 per thread
+// A chaining problem whose chains nobody reads: it has retained hits (cells > 0), the other mate of its pair has none in either
+// orientation.  process_read (cm_core.h) settles such a pair as CM_OEANCH from "has this mate a chain" alone, and a problem has a
+// chain exactly when it has a retained hit (chain_kbest returns 0 only for kc <= 0; the back-tracking always emits the first event
+// of the best group; max_chain_len >= 1, cm_create).  So the answer is in the seed counts, and the problem is not chained at all.
+// The four problems of a pair (r = 4 t + 2 mate + orientation) are a quad of consecutive lanes: `cells` of the caller's own problem,
+// all four lanes of the quad in the same state of execution.
+constexpr int CHAIN_CLS_NONE = -2;      // class of a problem without a retained hit: no chain, no kernel visits it
+constexpr int CHAIN_CLS_DEAD = -3;      // class of a dead problem: hits, but not chained; the pair stage sees the marker nchain = 1
+__device__ inline bool quad_dead(uint32_t cells) {
+    const uint32_t mate = cells + (uint32_t)__shfl_xor((int)cells, 1);         // both orientations of this problem's mate
+    const uint32_t other = (uint32_t)__shfl_xor((int)mate, 2);                 // ... of the other mate
+    return cells > 0 && other == 0;
+}
+static_assert(SCAN_T % 4 == 0 && SCAN_ELEMS % SCAN_T == 0 && BLK % 4 == 0, "a pair's four problems are one aligned quad of lanes in k_scan_a and k_chain_cls");
+// skip_dead: a dead problem counts 0 cells (no DP workspace, not the tile's largest problem)
 __global__ void __launch_bounds__(SCAN_T) k_scan_a(const uint32_t *scnt, int S, uint32_t n, unsigned long long *out, unsigned long long *bsum,
-                                                   unsigned int *bmax) {
+                                                   unsigned int *bmax, int skip_dead) {
     // element k * SCAN_T + t of the block belongs to thread t: consecutive lanes read consecutive problems
     // (28-byte stride, the S loads of a lane reuse its sectors) instead of four problems per lane
     __shared__ unsigned long long sh[SCAN_T];
@@ -169,6 +185,7 @@ __global__ void __launch_bounds__(SCAN_T) k_scan_a(const uint32_t *scnt, int S, 
         uint32_t c = 0;
         if (r < n)
             for (int s = 0; s < S; ++s) c += scnt[(uint64_t)r * S + s];
+        if (skip_dead && quad_dead(c)) c = 0;           // (n is a multiple of 4: a quad is inside the tile or outside)
         my_max = c > my_max ? c : my_max;
         sh[threadIdx.x] = c;
         __syncthreads();
@@ -246,15 +263,17 @@ __global__ void __launch_bounds__(BLK_CHAIN, CM_CHAIN_WAVES) k_chain(KCore kc, R
                                                      const unsigned long long *celloff, unsigned long long cellbase, double *dp_score,
                                                      int32_t *dp_prev, uint8_t *pool, unsigned long long pool_bytes,
                                                      unsigned long long *pool_cursor, cm_chain *chains, int32_t *nchain, int32_t *high, int *err,
-                                                     uint16_t *resid, const uint32_t *perm, const unsigned int *perm_lo, const unsigned int *perm_hi) {
-    // perm == null: problems r0..r1 in index order;
+                                                     uint16_t *resid, const uint32_t *perm, const unsigned int *perm_lo, const unsigned int *perm_hi,
+                                                     const int8_t *cls) {
+    // perm == null: problems r0..r1 in index order, but for the dead ones (cls, may be null: none is dead), whose three fields
+    //               k_chain_cls / k_chain_apply have written and which have no DP cells;
     // perm != null: the light problems perm[*perm_lo .. *perm_hi), grouped by work class so that the lanes of a wave carry similar DPs
     uint32_t r = r0 + blockIdx.x * BLK_CHAIN + threadIdx.x;
     if (perm) {
         r += *perm_lo;
         if (r >= *perm_hi) return;
         r = perm[r];
-    } else if (r >= r1) return;
+    } else if (r >= r1 || (cls && cls[r] == CHAIN_CLS_DEAD)) return;
     const Core c = cmc::to_core(kc);
     const uint64_t p = pair0 + (r >> 2);
     int n = 0, hh = 0, rs = 0;
@@ -1137,6 +1156,9 @@ __device__ inline int pair_class(const Core &c, const cm_chain *chains, const ui
         }
         return HEAVY_CLS;
     }
+    // chains on one mate only, or on neither: settled from the chain counts (CM_OEANCH, NOPROC_*).  The cheapest light class, and no
+    // look into chains[]: the records of an unchained problem (nchain is the marker 1, see ChainRecs) are not there to be read
+    if ((a + b) <= 0 || (cc + d) <= 0) return 0;
     const uint16_t *q = resid4 + 4 * (uint64_t)t;
     int resid = 0;
     for (int x = 0; x < 4; ++x) resid += (q[x] & 0xff) + (q[x] >> 8);
@@ -1238,51 +1260,72 @@ __global__ void __launch_bounds__(BLK) k_pair_cls(KCore kc, const cm_chain *chai
     }
 }
 // work class of one chaining problem: number of (hit, later hit) pairs the DP may have to examine
+// skip_dead: a dead problem (quad_dead) gets the class CHAIN_CLS_DEAD, which no kernel visits, and what the pair stage reads of it:
+// nchain = 1 (the marker "has hits, not chained", see ChainRecs), resid = 0, and chain_len = 0 in its first chain record, so that
+// a record left from an earlier item cannot pass for a chain.  counters[CN_DEAD_CHAINS] counts them.
 __global__ void __launch_bounds__(BLK) k_chain_cls(const uint32_t *scnt, const uint32_t *sraw, int S, uint32_t n_prob, int8_t *cls, int32_t *high,
                                                   unsigned long long light_w, unsigned int light_cells, int32_t *nchain, uint16_t *resid,
-                                                  const uint8_t *active, uint64_t pair0) {
+                                                  cm_chain *chains, const uint8_t *active, uint64_t pair0, int skip_dead,
+                                                  unsigned long long *counters) {
+    __shared__ unsigned int n_dead;
     const uint32_t r = blockIdx.x * BLK + threadIdx.x;
-    if (r >= n_prob) return;
+    if (threadIdx.x == 0) n_dead = 0;
+    __syncthreads();
     // nchain == null: the chain records are still being read by an earlier pair stage; `high` is a scratch array of the seed set and
-    // k_chain_apply carries the three fields over when the records are free (the class -2 stands for "no chain, no kernel visits it")
-    if (!active[pair0 + (r >> 2)]) {    // seeded under older flags (a superset), retired since: no chains wanted
+    // k_chain_apply carries the fields over when the records are free (the class -2 stands for "no chain, no kernel visits it")
+    const bool on = r < n_prob && active[pair0 + (r >> 2)];
+    if (r < n_prob && !on) {            // seeded under older flags (a superset), retired since: no chains wanted
         high[r] = 0;
         if (nchain) {
             nchain[r] = 0;
             resid[r] = 0;
         }
-        cls[r] = -2;
-        return;
+        cls[r] = CHAIN_CLS_NONE;
     }
     unsigned long long w = 0, suffix = 0;
     int hh = 0;
-    for (int s = S - 1; s >= 0; --s) {
-        const unsigned long long c = scnt[(uint64_t)r * S + s];
-        w += c * suffix;
-        suffix += c;
-        if (sraw[(uint64_t)r * S + s] > 0 && c == 0) ++hh;       // get_best_chains high_hits (also for problems k_chain skips)
+    if (on)
+        for (int s = S - 1; s >= 0; --s) {
+            const unsigned long long c = scnt[(uint64_t)r * S + s];
+            w += c * suffix;
+            suffix += c;
+            if (sraw[(uint64_t)r * S + s] > 0 && c == 0) ++hh;       // get_best_chains high_hits (also for problems k_chain skips)
+        }
+    // (n_prob is a multiple of 4 and the four problems of a pair share its flag: a quad is on or off as a whole; off counts no cell)
+    const bool dead = skip_dead && quad_dead((uint32_t)suffix);
+    if (skip_dead) {                    // the count: one add per wave in LDS, one per workgroup in memory
+        const unsigned long long md = __ballot(dead);
+        if ((threadIdx.x & 63) == 0 && md) atomicAdd(&n_dead, (unsigned int)__popcll(md));
+        __syncthreads();
+        if (threadIdx.x == 0 && n_dead) atomicAdd(&counters[CN_DEAD_CHAINS], (unsigned long long)n_dead);
     }
+    if (!on) return;
     high[r] = hh;
-    if (suffix == 0 && nchain) {        // no retained hit: no chain, and no kernel visits this problem
-        nchain[r] = 0;
+    if ((suffix == 0 || dead) && nchain) {        // no retained hit: no chain; dead: the marker.  No kernel visits either.
+        nchain[r] = dead ? 1 : 0;
         resid[r] = 0;
+        if (dead) chains[(uint64_t)r * CM_BESTCHAINLIM].chain_len = 0;
     }
     // classes 0..11 = light (one lane each, k_chain; grouped so the lanes of a wave carry similar DPs),
     // 12..15 = heavy (one wave each, k_chain_heavy, heaviest class first)
     const bool light = w <= light_w && suffix <= light_cells;
     const unsigned int n = (unsigned int)suffix;
-    cls[r] = (int8_t)(suffix == 0 ? -2
+    cls[r] = (int8_t)(suffix == 0 ? CHAIN_CLS_NONE
+                      : dead ? CHAIN_CLS_DEAD
                       : light ? (n <= 3 ? 0 : n <= 6 ? 1 : n <= 7 ? 2 : n <= 9 ? 3 : n <= 12 ? 4 : n <= 16 ? 5 : n <= 24 ? 6 : n <= 32 ? 7 : n <= 48 ? 8 : n <= 64 ? 9
                                  : n <= 96 ? 10 : 11)
                       : w <= 4096 ? 12 : w <= 65536 ? 13 : w <= 1048576 ? 14 : 15);
 }
-__global__ void __launch_bounds__(BLK) k_chain_apply(uint32_t n_prob, const int8_t *cls, const int32_t *thigh, int32_t *high, int32_t *nchain, uint16_t *resid) {
+__global__ void __launch_bounds__(BLK) k_chain_apply(uint32_t n_prob, const int8_t *cls, const int32_t *thigh, int32_t *high, int32_t *nchain, uint16_t *resid,
+                                                    cm_chain *chains) {
     const uint32_t r = blockIdx.x * BLK + threadIdx.x;
     if (r >= n_prob) return;
     high[r] = thigh[r];
-    if (cls[r] == -2) {
-        nchain[r] = 0;
+    const int k = cls[r];
+    if (k == CHAIN_CLS_NONE || k == CHAIN_CLS_DEAD) {
+        nchain[r] = k == CHAIN_CLS_DEAD ? 1 : 0;
         resid[r] = 0;
+        if (k == CHAIN_CLS_DEAD) chains[(uint64_t)r * CM_BESTCHAINLIM].chain_len = 0;
     }
 }
 // `order` (optional): visit the elements in this order (second pass of an LSD radix sort: order = the permutation of the
@@ -2262,8 +2305,13 @@ struct SeedSet {
     BatchBuf<uint32_t> perm4;
     BatchBuf<int32_t> thigh;                     // high_hits per problem while the chain records are not free yet (k_chain_apply)
     bool cls_deferred = false;                   // classes made before the chain records were free, k_chain_apply still to run
+    bool skip_dead = false;                      // the cell offsets (and the classes, once made) leave the dead problems out (run_seed_tile)
 };
 // The chain records of a round.  Two sets: the pair stage of round r reads set r & 1 while the chaining of round r + 1 fills the other.
+// nchain[r] is the number of chains in the problem's records -- except for a problem the round pipeline did not chain because nobody
+// reads its chains (quad_dead: the pair's other mate has no hit): there nchain[r] = 1 is a marker, "this mate has hits", resid[r] = 0
+// and the first record has chain_len = 0.  Such a pair has nchain = 0 on all of the other mate, so every reader that looks at records
+// of two-sided pairs only (process_read, pair_class, k_pair_cost, the heavy pairs' kernels) never meets the marker as a count.
 struct ChainRecs {
     BatchBuf<cm_chain> chains;
     BatchBuf<int32_t> nchain, high;
@@ -2664,17 +2712,24 @@ static unsigned int chain_light_cells() {
     return v;
 }
 
+// The round pipeline leaves unchained the problems whose chains nobody reads (quad_dead).  The rule rests on "a retained hit makes a
+// chain", which needs room for one chain: max_chain_len >= 1, all cm_create admits.
+static bool skip_dead_chains(const cm_ctx *ctx) { return ctx->P.max_chain_len >= 1; }
+
 // seeds of one tile into seed set s, on stream st: k_seed, the scan of the problems' DP cells, the two totals to the host; with
 // rb (the chain records the tile's chain stage will fill: their per-problem counters are initialised here) also the work
 // classes + sorted lists of the chaining problems and the zeroed cursors.  ev.seed[s] is recorded behind them.
 // The second half of run_seed_tile: the work classes + sorted lists of the chaining problems of seed set s, the per-problem counters of
 // the chain records rb and the zeroed cursors.  (On its own when the seeds were computed before the chain records were free: the
 // cross-batch prefetch.)
-static int seed_classes(cm_ctx *ctx, uint64_t pair0, uint32_t n_tile, const uint8_t *act, int s, hipStream_t st, const ChainRecs *rb, bool defer = false) {
+// skip_dead: as the seeds' scan was told (run_seed_tile).
+static int seed_classes(cm_ctx *ctx, uint64_t pair0, uint32_t n_tile, const uint8_t *act, int s, hipStream_t st, const ChainRecs *rb, bool skip_dead,
+                        bool defer = false) {
     const int S = ctx->n_seeds;
     const uint32_t n_prob = n_tile * 4u;
     if ((uint64_t)n_prob * (uint64_t)S == 0) return CM_OK;
     const SeedSet &sb = ctx->seed[s];
+    if (sb.skip_dead != skip_dead) return fail(ctx, CM_ESTATE, "seed set %d: cell offsets and classes disagree about unchained problems", s);
     // Light problems: one lane each, index order.  Heavy problems (many hits): one wave each (k_chain_heavy), heaviest class
     // first.  (Used by run_chain_tile when it takes the split path; computed here because these five small launches, queued
     // behind the persistent pair kernels of the previous item, took 6 ms of the chain stage's critical path.)
@@ -2682,7 +2737,8 @@ static int seed_classes(cm_ctx *ctx, uint64_t pair0, uint32_t n_tile, const uint
     // defer: the chain records rb are still read by an earlier pair stage -- nothing is written into them here, run_chain_tile does that
     // (k_chain_apply) when it is ordered behind that stage
     launch(ctx, PC_ORDER, k_chain_cls, dim3((n_prob + BLK - 1) / BLK), dim3(BLK), 0, st, sb.scnt, sb.sraw, S, n_prob, sb.cls4, defer ? sb.thigh : rb->high,
-           chain_light_w(), chain_light_cells(), defer ? (int32_t *)nullptr : rb->nchain, defer ? (uint16_t *)nullptr : rb->resid, act, pair0);
+           chain_light_w(), chain_light_cells(), defer ? (int32_t *)nullptr : rb->nchain, defer ? (uint16_t *)nullptr : rb->resid,
+           defer ? (cm_chain *)nullptr : rb->chains, act, pair0, skip_dead ? 1 : 0, ctx->d_counters);
     ctx->seed[s].cls_deferred = defer;
     counting_sort(ctx, PC_ORDER, {st, sb.cls4, n_prob, sb.cblk, (n_prob + CLS_T - 1) / CLS_T, sb.cctr, sb.perm4});
     HIPCHK(ctx, hipMemsetAsync(ctx->pool_cursor(s), 0, sizeof(unsigned long long), st));
@@ -2690,8 +2746,10 @@ static int seed_classes(cm_ctx *ctx, uint64_t pair0, uint32_t n_tile, const uint
     HIPCHK(ctx, hipGetLastError());
     return CM_OK;
 }
+// skip_dead: the round pipeline's rule -- a problem whose chains nobody reads (quad_dead) gets no DP cells, no class and no chains.
+// Off for the test hooks (cm_seed_batch, cm_chain_batch), which chain everything.
 int run_seed_tile(cm_ctx *ctx, const KCore &core, const ReadsDev &rd, uint64_t pair0, uint32_t n_tile, const uint8_t *act, int s, hipStream_t st,
-                  const ChainRecs *rb, bool defer_rb = false) {
+                  const ChainRecs *rb, bool skip_dead, bool defer_rb = false) {
     const int S = ctx->n_seeds;
     const uint64_t total = (uint64_t)n_tile * 4u * (uint64_t)S;
     if (total == 0) return CM_OK;
@@ -2705,13 +2763,14 @@ int run_seed_tile(cm_ctx *ctx, const KCore &core, const ReadsDev &rd, uint64_t p
     {
         Timer t(ctx, PC_SCAN, st);
         const uint32_t nb = (n_prob + SCAN_ELEMS - 1) / SCAN_ELEMS;
-        launch(ctx, PC_SCAN, k_scan_a, dim3(nb), dim3(SCAN_T), 0, st, sb.scnt, S, n_prob, sb.celloff, sb.bsum, sb.bmax);
+        launch(ctx, PC_SCAN, k_scan_a, dim3(nb), dim3(SCAN_T), 0, st, sb.scnt, S, n_prob, sb.celloff, sb.bsum, sb.bmax, skip_dead ? 1 : 0);
+        ctx->seed[s].skip_dead = skip_dead;
         launch(ctx, PC_SCAN, k_scan_mid<unsigned long long, true>, dim3(1), dim3(1024), 0, st, sb.bsum, nb, sb.celloff + n_prob, sb.bmax);
         launch(ctx, PC_SCAN, k_scan_c, dim3((n_prob + SCAN_T - 1) / SCAN_T), dim3(SCAN_T), 0, st, sb.celloff, sb.bsum, n_prob);
     }
     HIPCHK(ctx, hipMemcpyAsync(ctx->h_pin + PIN_CELLS + 2 * s, sb.celloff + n_prob, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
     if (rb) {
-        const int rc = seed_classes(ctx, pair0, n_tile, act, s, st, rb, defer_rb);
+        const int rc = seed_classes(ctx, pair0, n_tile, act, s, st, rb, skip_dead, defer_rb);
         if (rc) return rc;
     }
     HIPCHK(ctx, hipEventRecord(ctx->ev.seed[s], st));
@@ -2731,7 +2790,7 @@ int run_chain_tile(cm_ctx *ctx, const KCore &core, const ReadsDev &rd, uint64_t 
     HIPCHK(ctx, hipEventSynchronize(ctx->ev.seed[s]));
     if (ctx->seed[s].cls_deferred) {           // classes made while the chain records were in use (the caller has ordered this stream behind that)
         hipLaunchKernelGGL(k_chain_apply, dim3((n_prob + BLK - 1) / BLK), dim3(BLK), 0, ctx->st.B, n_prob, (const int8_t *)sb.cls4, (const int32_t *)sb.thigh,
-                           rb.high, rb.nchain, rb.resid);
+                           rb.high, rb.nchain, rb.resid, rb.chains);
         ctx->seed[s].cls_deferred = false;
     }
     const unsigned long long total = ctx->h_pin[PIN_CELLS + 2 * s];
@@ -2803,7 +2862,8 @@ int run_chain_tile(cm_ctx *ctx, const KCore &core, const ReadsDev &rd, uint64_t 
         Timer t(ctx, PC_CHAIN);
         launch(ctx, PC_CHAIN, k_chain, dim3((n + BLK_CHAIN - 1) / BLK_CHAIN), dim3(BLK_CHAIN), 0, ctx->st.B, core, rd, act, pair0, a, b, S, sb.sstart, sb.scnt,
                sb.sraw, sb.celloff, base, ctx->dp.score, ctx->dp.prev, ctx->dp.pool, ctx->dp.pool_bytes, ctx->pool_cursor(s), rb.chains, rb.nchain, rb.high,
-               ctx->d_err, rb.resid, use_split ? sb.perm4 : (const uint32_t *)nullptr, sb.cctr + CTR_BASE + CHAIN_LIGHT_CLS - 1, sb.cctr + CTR_SUM);
+               ctx->d_err, rb.resid, use_split ? sb.perm4 : (const uint32_t *)nullptr, sb.cctr + CTR_BASE + CHAIN_LIGHT_CLS - 1, sb.cctr + CTR_SUM,
+               sb.skip_dead ? (const int8_t *)sb.cls4 : (const int8_t *)nullptr);
         if (use_split) HIPCHK(ctx, hipStreamWaitEvent(ctx->st.B, ctx->ev.join, 0));       // timed with the light kernel: the stage ends here
         HIPCHK(ctx, hipGetLastError());
         return CM_OK;
@@ -4193,7 +4253,7 @@ static int map_rounds_issue(cm_ctx *ctx, const int *slots, int n_rounds, int las
         // the whole seed stage: the classes too, into scratch of the seed set (the chain records they belong in are still being read;
         // run_chain_tile carries them over).  Under superset flags a pair the late launches retire gets chains nobody looks at.
         const ChainRecs &rbe = ctx->rec[(ctx->item_base + i) & 1];
-        const int e = run_seed_tile(ctx, make_core(ctx, ctx->slots[slots[items[i].r]]), rd_cur, items[i].p0, items[i].nt, prep_flags(i), i & 1, ctx->st.S, &rbe, true);
+        const int e = run_seed_tile(ctx, make_core(ctx, ctx->slots[slots[items[i].r]]), rd_cur, items[i].p0, items[i].nt, prep_flags(i), i & 1, ctx->st.S, &rbe, skip_dead_chains(ctx), true);
         seeded[(size_t)i] = 1;
         return e;
     };
@@ -4205,7 +4265,7 @@ static int map_rounds_issue(cm_ctx *ctx, const int *slots, int n_rounds, int las
         if ((e = settle_pair(ctx, b))) return e;
         if (ctx->pair_pending[b]) HIPCHK(ctx, hipStreamWaitEvent(st, ctx->ev.pair[b], 0));
         const ChainRecs &rbi = ctx->rec[b];
-        e = run_seed_tile(ctx, make_core(ctx, ctx->slots[slots[items[i].r]]), rd_cur, items[i].p0, items[i].nt, prep_flags(i), i & 1, st, &rbi);
+        e = run_seed_tile(ctx, make_core(ctx, ctx->slots[slots[items[i].r]]), rd_cur, items[i].p0, items[i].nt, prep_flags(i), i & 1, st, &rbi, skip_dead_chains(ctx));
         seeded[(size_t)i] = 1;
         return e;
     };
@@ -4239,7 +4299,7 @@ static int map_rounds_issue(cm_ctx *ctx, const int *slots, int n_rounds, int las
             const uint32_t nt0 = tile_for(ctx->st_n_pairs);                     // = that batch's first tile (<= this batch's: it has no more pairs)
             const ReadsDev rd_next = reads_dev(ctx->st_rd);
             HIPCHK(ctx, hipStreamWaitEvent(ctx->st.S, ctx->ev.staged, 0));
-            if ((rc = run_seed_tile(ctx, make_core(ctx, sl0), rd_next, 0, nt0, ctx->d_ones, n_items & 1, ctx->st.S, nullptr))) return rc;
+            if ((rc = run_seed_tile(ctx, make_core(ctx, sl0), rd_next, 0, nt0, ctx->d_ones, n_items & 1, ctx->st.S, nullptr, skip_dead_chains(ctx)))) return rc;
             pre_seeded = true;
         }
         if (use_pre && i == 0) {                                          // set b holds this item's chains, ev.prep[b] is recorded
@@ -4287,8 +4347,8 @@ static int map_rounds_issue(cm_ctx *ctx, const int *slots, int n_rounds, int las
         const ReadsDev rd_next = reads_dev(ctx->st_rd);
         if (pre_seeded) {                                      // seeds are there (or on their way): the classes, into the records now free
             HIPCHK(ctx, hipStreamWaitEvent(ctx->st.B, ctx->ev.seed[n_items & 1], 0));
-            if ((rc = seed_classes(ctx, 0, nt, ctx->d_ones, n_items & 1, ctx->st.B, &rbn))) return rc;
-        } else if ((rc = run_seed_tile(ctx, core, rd_next, 0, nt, ctx->d_ones, n_items & 1, ctx->st.B, &rbn))) return rc;
+            if ((rc = seed_classes(ctx, 0, nt, ctx->d_ones, n_items & 1, ctx->st.B, &rbn, skip_dead_chains(ctx)))) return rc;
+        } else if ((rc = run_seed_tile(ctx, core, rd_next, 0, nt, ctx->d_ones, n_items & 1, ctx->st.B, &rbn, skip_dead_chains(ctx)))) return rc;
         if ((rc = run_chain_tile(ctx, core, rd_next, 0, nt, sl.chain_parallel_ok, ctx->d_ones, rbn, n_items & 1))) return rc;
         HIPCHK(ctx, hipEventRecord(ctx->ev.prep[b], ctx->st.B));
         ctx->pre_launched = true;
@@ -4688,7 +4748,7 @@ int cm_seed_batch(cm_ctx *ctx, int slot, uint32_t *out_start, uint32_t *out_cnt,
     const KCore core = make_core(ctx, ctx->slots[slot]);
     for (uint64_t p0 = 0; p0 < ctx->n_pairs; p0 += ctx->tile) {
         const uint32_t nt = (uint32_t)((ctx->n_pairs - p0 < ctx->tile) ? ctx->n_pairs - p0 : ctx->tile);
-        if ((rc = run_seed_tile(ctx, core, current_reads(ctx), p0, nt, ctx->d_active, 0, ctx->st.B, nullptr))) return rc;
+        if ((rc = run_seed_tile(ctx, core, current_reads(ctx), p0, nt, ctx->d_active, 0, ctx->st.B, nullptr, false))) return rc;
         const size_t cnt = (size_t)nt * 4 * ctx->n_seeds, o = (size_t)p0 * 4 * ctx->n_seeds;
         HIPCHK(ctx, hipMemcpyAsync(out_start + o, ctx->seed[0].sstart, cnt * 4, hipMemcpyDeviceToHost, ctx->st.B));
         HIPCHK(ctx, hipMemcpyAsync(out_cnt + o, ctx->seed[0].scnt, cnt * 4, hipMemcpyDeviceToHost, ctx->st.B));
@@ -4708,7 +4768,7 @@ int cm_chain_batch(cm_ctx *ctx, int slot, cm_chain *out_chains, int32_t *out_nch
         const uint32_t nt = (uint32_t)((ctx->n_pairs - p0 < ctx->tile) ? ctx->n_pairs - p0 : ctx->tile);
         HIPCHK(ctx, hipMemsetAsync(ctx->rec[0].chains, 0, (size_t)nt * 4 * CM_BESTCHAINLIM * sizeof(cm_chain), ctx->st.B));
         const ChainRecs &rb0 = ctx->rec[0];
-        if ((rc = run_seed_tile(ctx, core, current_reads(ctx), p0, nt, ctx->d_active, 0, ctx->st.B, &rb0))) return rc;
+        if ((rc = run_seed_tile(ctx, core, current_reads(ctx), p0, nt, ctx->d_active, 0, ctx->st.B, &rb0, false))) return rc;
         if ((rc = run_chain_tile(ctx, core, current_reads(ctx), p0, nt, ctx->slots[slot].chain_parallel_ok, ctx->d_active, rb0, 0))) return rc;
         const size_t np = (size_t)nt * 4, o = (size_t)p0 * 4;
         HIPCHK(ctx, hipMemcpyAsync(out_chains + o * CM_BESTCHAINLIM, ctx->rec[0].chains, np * CM_BESTCHAINLIM * sizeof(cm_chain), hipMemcpyDeviceToHost,
@@ -4815,6 +4875,7 @@ int cm_prof_counters(cm_ctx *ctx, uint64_t c[8]) {
     HIPCHK(ctx, hipMemcpyAsync(h, ctx->d_counters, sizeof h, hipMemcpyDeviceToHost, ctx->st.B));
     HIPCHK(ctx, hipStreamSynchronize(ctx->st.B));
     for (int i = 0; i < 8; ++i) c[i] = h[i];
+    c[CN_DEAD_CHAINS] = 0;          // the public words are 0 - 6, [7] is reserved (0): the device's word 7 is read through cm_debug_counters
     return CM_OK;
 }
 

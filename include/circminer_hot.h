@@ -422,7 +422,8 @@ int cm_state_poke(cm_ctx *ctx, const cm_mapped_read *states);
  * CM_EINVAL when nothing was recorded. */
 int cm_debug_lane_clk(cm_ctx *ctx, unsigned long long *out);
 /* test hook for the scripts of tests/diag: the 32 raw counter words of which cm_prof_counters returns the first 8; from word 8 on
- * what a diagnostic build (-DCM_CHAIN_DIAG, -DCM_DIAG_CNT) accumulates there. */
+ * what a diagnostic build (-DCM_CHAIN_DIAG, -DCM_DIAG_CNT) accumulates there.  Word 7 (every build): chaining problems with hits
+ * that cm_map_rounds left unchained because the pair's other mate has no hit, since the last cm_prof_reset(). */
 int cm_debug_counters(cm_ctx *ctx, unsigned long long *out);
 
 /* ---------------- timing hooks for bench.py (HIP events on the ctx stream) ---------------- */
