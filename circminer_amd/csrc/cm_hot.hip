@@ -29,6 +29,7 @@
 #include "cm_index_build.h"
 #include "cm_fastq_text.h"
 #include "cm_pam_text.h"
+#include "cm_remain_text.h"
 #include "cm_sam_text.h"
 
 using cmc::Core;
@@ -71,11 +72,11 @@ enum Pin {
     PIN_CELLS = 8,                                   // + 2 * seed set: DP cells of the tile, + 1: of its largest problem
     PIN_RERUN_N = 12, PIN_FALL_N = 14,               // + chain-record set: length of the re-run list / of the pipeline's fall-back list
     PIN_TEXT = 16,                                   // cm_reads_stage_text: the result block of the tokeniser (cmft::RES_WORDS words)
-    PIN_ROWS = 26,                                    // cm_format_pam / cm_format_sam: the bytes of the rows
+    PIN_ROWS = 26,                                    // cm_format_pam / cm_format_sam: the bytes of the rows; cm_format_remain: + 1, of the second file
     PIN_WORDS = 32
 };
 constexpr size_t PIN_BYTES = PIN_WORDS * sizeof(unsigned long long);        // allocated and cleared in cm_create
-static_assert(PIN_BYTES == 256 && PIN_FALL_N + 1 < PIN_TEXT && PIN_CELLS + 3 < PIN_RERUN_N && PIN_TEXT + cmft::RES_WORDS <= PIN_ROWS && PIN_ROWS < PIN_WORDS,
+static_assert(PIN_BYTES == 256 && PIN_FALL_N + 1 < PIN_TEXT && PIN_CELLS + 3 < PIN_RERUN_N && PIN_TEXT + cmft::RES_WORDS <= PIN_ROWS && PIN_ROWS + 1 < PIN_WORDS,
               "the landing zone has 32 words");
 struct ReadsDev {
     const uint8_t *seq1, *seq2;
@@ -2217,6 +2218,16 @@ __global__ void __launch_bounds__(cmrt::WAVE) k_sam_rows(cmst::Format::Src S, cm
     rows_span<cmst::Format>(S, ct, first, items, off, out, path);
 }
 
+// the remain records of one mate file (cm_format_remain): the same plan over the selection list
+template <uint32_t MATE>
+__global__ void __launch_bounds__(BLK) k_remain_len(cmrm::Src S, cmrt::ChrTab ct, uint64_t first, uint32_t items, uint32_t *len) {
+    rows_len<cmrm::Format<MATE>>(S, ct, first, items, len);
+}
+template <uint32_t MATE>
+__global__ void __launch_bounds__(cmrt::WAVE) k_remain_rows(cmrm::Src S, cmrt::ChrTab ct, uint64_t first, uint32_t items, const uint32_t *off, uint8_t *out, uint8_t *path) {
+    rows_span<cmrm::Format<MATE>>(S, ct, first, items, off, out, path);
+}
+
 // ------------------------------------------------------------------ host side
 struct Slot {
     bool loaded = false, has_annot = false;
@@ -2274,6 +2285,12 @@ struct ReadBufs {
     BatchBuf<uint8_t> qual1, qual2;
     bool has_quals = false;
     uint64_t bases = 0;                          // with has_quals: off1[n] + off2[n]
+    // cm_reads_stage_text with flag bit 4: the R2 names of the batch, laid out as the R1 names are (cm_format_remain); allocated
+    // only when the bit is given
+    BatchBuf<uint8_t> names2;
+    BatchBuf<uint32_t> name_off2;
+    bool has_names2 = false;
+    uint64_t name2_bytes_max = 0;
 };
 inline void swap(ReadBufs &a, ReadBufs &b) {
     swap(a.seq1_base, b.seq1_base);
@@ -2288,6 +2305,10 @@ inline void swap(ReadBufs &a, ReadBufs &b) {
     swap(a.qual2, b.qual2);
     std::swap(a.has_quals, b.has_quals);
     std::swap(a.bases, b.bases);
+    swap(a.names2, b.names2);
+    swap(a.name_off2, b.name_off2);
+    std::swap(a.has_names2, b.has_names2);
+    std::swap(a.name2_bytes_max, b.name2_bytes_max);
 }
 
 // What the seeding of a tile leaves for its chain stage: the seed ranges of every probe, the DP-cell offsets of every chaining
@@ -2384,7 +2405,7 @@ struct TextStage {
     BatchBuf<uint64_t> rec[2];
     BatchBuf<uint32_t> tmp;
     BatchBuf<unsigned long long> res;
-    BatchBuf<uint32_t> nstart;                   // flag bit 2 only: where each R1 name starts in text[0]
+    BatchBuf<uint32_t> nstart;                   // flag bits 2 and 4 only: where each name starts in its text (R1's, then R2's: one stream)
 };
 // The row formatters' buffers, shared by cm_format_pam and cm_format_sam: the chromosome names last uploaded (host copy: the table
 // is compared, not uploaded, when it is the same), the items' lengths scanned in place into offsets, the scan's block totals, the
@@ -2399,6 +2420,14 @@ struct RowsBufs {
     BatchBuf<uint32_t> off, tmp;
     BatchBuf<uint8_t> out, path;
     std::vector<uint8_t> h_path;
+    // cm_format_remain only: the chromosome shifts (cm_chr_info.start_pos) beside the names, uploaded by the same rule; the second
+    // file's offsets, records and paths (both files are sized before either is written); the sort keys
+    std::vector<uint32_t> h_chr_shift;
+    bool shift_valid = false;
+    CtxBuf<uint32_t> chr_shift;
+    BatchBuf<uint32_t> off2;
+    BatchBuf<uint8_t> out2, path2;
+    BatchBuf<int64_t> keys;
 };
 
 // The streams of a context, under the letters of DESIGN §4.  STREAMS lists them in creation order, which decides the hardware
@@ -3689,7 +3718,7 @@ int cm_reads_upload(cm_ctx *ctx, const cm_reads *rd, const cm_mapped_read *prior
     int max_len = 0;
     int rc = check_reads(ctx, rd, &max_len);
     if (rc) return rc;
-    ctx->rd.has_names = ctx->rd.has_quals = false;
+    ctx->rd.has_names = ctx->rd.has_quals = ctx->rd.has_names2 = false;
     if ((rc = copy_reads(ctx, rd, ctx->st.B, ctx->rd))) return rc;
     if ((rc = prepare_resident(ctx, n, max_len))) return rc;
     ctx->n_pairs = n;
@@ -3715,7 +3744,7 @@ int cm_reads_stage(cm_ctx *ctx, const cm_reads *rd, const cm_mapped_read *prior)
     HIPCHK(ctx, hipStreamSynchronize(ctx->st.C));          // an earlier staged batch that was never swapped in is dropped
     ctx->staged = false;
     ctx->pre_launched = false;
-    ctx->st_rd.has_names = ctx->st_rd.has_quals = false;
+    ctx->st_rd.has_names = ctx->st_rd.has_quals = ctx->st_rd.has_names2 = false;
     if ((rc = copy_reads(ctx, rd, ctx->st.C, ctx->st_rd))) return rc;
     ctx->st_has_prior = prior != nullptr;
     if (prior) {
@@ -3757,7 +3786,7 @@ int cm_reads_stage_text(cm_ctx *ctx, const uint8_t *text1, uint64_t len1, const 
     const size_t pad = cmc::CM_STAGE_PAD;
     uint32_t n_chunks[2], ls_cap[2];
     ReadBufs &to = ctx->st_rd;
-    to.has_names = to.has_quals = false;
+    to.has_names = to.has_quals = to.has_names2 = false;
     HIPCHK(ctx, ensure(ctx, to.seq1_base, len1 + 2 * pad));
     HIPCHK(ctx, ensure(ctx, to.seq2_base, len2 + 2 * pad));
     HIPCHK(ctx, ensure(ctx, to.off1, ((size_t)nb + 1) * sizeof(uint64_t)));
@@ -3880,6 +3909,25 @@ int cm_reads_stage_text(cm_ctx *ctx, const uint8_t *text1, uint64_t len1, const 
         HIPCHK(ctx, hipEventRecord(ctx->ev.staged, st));
         to.has_quals = true;
         to.bases = bases[0] + bases[1];
+    }
+    if (flags & 16u) {
+        // Keep the R2 names: what bit 2 does for file 1, for file 2, into arrays of their own.  The name starts share T.nstart with
+        // bit 2 (n + 1 words either way, so the buffer does not move): the staging stream runs the two one after the other.
+        const uint64_t name_max = R[cmft::RES_USED2] - std::min<uint64_t>(R[cmft::RES_USED2], 2 * R[cmft::RES_BASES2]);
+        HIPCHK(ctx, ensure(ctx, to.names2, (size_t)name_max + 4));
+        HIPCHK(ctx, ensure(ctx, to.name_off2, ((size_t)n + 1) * sizeof(uint32_t)));
+        HIPCHK(ctx, ensure(ctx, T.nstart, ((size_t)n + 1) * sizeof(uint32_t)));
+        const unsigned gn = (unsigned)(n / FT_T + 1);            // covers i = 0 .. n
+        hipLaunchKernelGGL(k_ft_name_len, dim3(gn), dim3(FT_T), 0, st, (const uint8_t *)T.text[1], (const uint32_t *)T.ls[1], (uint32_t)n, (uint32_t *)T.nstart,
+                           (uint32_t *)to.name_off2);
+        if ((rc = scan32_on(ctx, st, to.name_off2, n + 1, to.name_off2, T.tmp, 0u, 0))) return rc;
+        const unsigned gc = (unsigned)std::min<uint64_t>((n * cmft::COPY_LANES + FT_T - 1) / FT_T, 1u << 16);
+        hipLaunchKernelGGL(k_ft_name_copy, dim3(gc), dim3(FT_T), 0, st, (const uint8_t *)T.text[1], (const uint32_t *)T.nstart, (const uint32_t *)to.name_off2,
+                           (uint32_t)n, (uint8_t *)to.names2);
+        HIPCHK(ctx, hipGetLastError());
+        HIPCHK(ctx, hipEventRecord(ctx->ev.staged, st));
+        to.has_names2 = true;
+        to.name2_bytes_max = name_max;
     }
     ctx->st_has_prior = false;
     ctx->st_n_pairs = n;
@@ -4643,6 +4691,122 @@ int cm_format_sam(cm_ctx *ctx, const cm_chr_info *chrs, uint32_t n_chr, uint64_t
                                    {ctx->d_state, rd.names, rd.name_off, {rd.seq1_base + cmc::CM_STAGE_PAD, rd.seq2_base + cmc::CM_STAGE_PAD}, {rd.qual1, rd.qual2}, {rd.off1, rd.off2}},
                                    2 * (rd.name_bytes_max + rd.bases), k_sam_len, k_sam_rows};
     return format_rows(ctx, c, chrs, n_chr, first, count, out, cap, out_bytes, stats);
+}
+
+// Remain records: one per mate file of every record [first, first + count) of the active set, the set and order of
+// cm_collect_records (compact_active's list is the formats' selection).  The plan runs once per mate: both length passes first --
+// either file may be refused for its size, and then neither is written --, then both span passes.  Needs the kept names of both
+// files and the kept qualities.  Three waits: for the size of the active set, for the two totals, for the bytes.
+int cm_format_remain(cm_ctx *ctx, const cm_chr_info *chrs, uint32_t n_chr, uint64_t first, uint64_t count, void *out1, uint64_t cap1, void *out2, uint64_t cap2,
+                     uint64_t out_bytes[2], int64_t *out_keys, uint64_t *n_records, uint64_t stats[4]) {
+    static const char *const fn = "cm_format_remain";
+    if (!ctx || !out_bytes || (n_chr && !chrs)) return CM_EINVAL;
+    out_bytes[0] = out_bytes[1] = 0;
+    if (n_records) *n_records = 0;
+    if (stats) stats[0] = stats[1] = stats[2] = stats[3] = 0;
+    HIPCHK(ctx, hipSetDevice(ctx->P.device));
+    if (ctx->n_pairs == 0) return fail(ctx, CM_ESTATE, "%s: no resident batch", fn);
+    int rc;
+    unsigned int active = 0;
+    if ((rc = compact_active(ctx)) || (rc = read_count(ctx, ~0ull, &active, fn))) return rc;
+    if (n_records) *n_records = active;
+    const ReadBufs &rd = ctx->rd;
+    if (!rd.has_names || !rd.has_quals || !rd.has_names2) {
+        std::string bits, what;
+        const struct { bool has; const char *bit, *what; } need[3] = {{rd.has_names, "2", "R1 names"}, {rd.has_quals, "3", "qualities"}, {rd.has_names2, "4", "R2 names"}};
+        int missing = 0;
+        for (const auto &b : need)
+            if (!b.has) {
+                bits += (missing ? ", " : "") + std::string(b.bit);
+                what += (missing++ ? ", no " : "no ") + std::string(b.what);
+            }
+        return fail(ctx, CM_ESTATE, "%s: the resident batch was not staged with cm_reads_stage_text, flag bit%s %s (%s)", fn, missing > 1 ? "s" : "", bits.c_str(), what.c_str());
+    }
+    if (count == ~0ull && first <= active) count = active - first;
+    if (first > active || count > active - first)
+        return fail(ctx, CM_EINVAL, "%s: records [%llu, +%llu) of %u", fn, (unsigned long long)first, (unsigned long long)count, active);
+    if ((!out1 && cap1) || (!out2 && cap2)) return fail(ctx, CM_EINVAL, "%s: null out", fn);
+    if (count == 0) return CM_OK;
+    RowsBufs &R = ctx->rows;
+    hipStream_t st = ctx->st.B;
+    uint32_t chr_max = 1;
+    if ((rc = upload_chr_table(ctx, R, chrs, n_chr, st, &chr_max))) return rc;
+    {   // the shifts, beside the names and by their rule: uploaded when they differ from the table on the device
+        std::vector<uint32_t> sh(n_chr);
+        for (uint32_t c = 0; c < n_chr; ++c) sh[c] = chrs[c].start_pos;
+        if (!R.shift_valid || sh != R.h_chr_shift) {
+            R.shift_valid = false;
+            HIPCHK(ctx, hipStreamSynchronize(st));
+            R.h_chr_shift.swap(sh);
+            HIPCHK(ctx, ensure(ctx, R.chr_shift, (R.h_chr_shift.size() + 1) * sizeof(uint32_t)));
+            if (n_chr) HIPCHK(ctx, hipMemcpyAsync(R.chr_shift, R.h_chr_shift.data(), (size_t)n_chr * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+            HIPCHK(ctx, hipStreamSynchronize(st));
+            R.shift_valid = true;
+        }
+    }
+    const cmrt::ChrTab ct{R.chr_text, R.chr_off, n_chr};
+    const uint32_t items = (uint32_t)count, spans = (items + cmrm::SPAN_RECS - 1) / cmrm::SPAN_RECS;
+    HIPCHK(ctx, ensure(ctx, R.off, ((size_t)items + 1) * sizeof(uint32_t)));
+    HIPCHK(ctx, ensure(ctx, R.off2, ((size_t)items + 1) * sizeof(uint32_t)));
+    HIPCHK(ctx, ensure(ctx, R.tmp, (size_t)(((uint64_t)items + 1) / S32_B + 2) * sizeof(uint32_t)));
+    HIPCHK(ctx, ensure(ctx, R.path, spans));
+    HIPCHK(ctx, ensure(ctx, R.path2, spans));
+    HIPCHK(ctx, ensure(ctx, R.total, 2 * sizeof(unsigned long long)));
+    if (out_keys) HIPCHK(ctx, ensure(ctx, R.keys, (size_t)items * sizeof(int64_t)));
+    const cmrm::Src S{ctx->col.perm, ctx->d_state, {rd.names, rd.names2}, {rd.name_off, rd.name_off2},
+                      {rd.seq1_base + cmc::CM_STAGE_PAD, rd.seq2_base + cmc::CM_STAGE_PAD}, {rd.qual1, rd.qual2}, {rd.off1, rd.off2},
+                      R.chr_shift, out_keys ? (int64_t *)R.keys : nullptr};
+    uint32_t *const off[2] = {R.off, R.off2};
+    uint8_t *const path[2] = {R.path, R.path2};
+    // offsets are uint32: where a file's records could come to 2^32 bytes the lengths are summed in 64 bits first (format_rows)
+    const bool wide = std::max(rd.name_bytes_max, rd.name2_bytes_max) + 2 * rd.bases + (uint64_t)items * (cmrm::REC_FIXED_MAX + 2 * chr_max) >= (1ull << 32);
+    unsigned long long *land = ctx->h_pin + PIN_ROWS;
+    {
+        Timer t(ctx, PC_ROWS, st);
+        for (int m = 0; m < 2; ++m) {
+            hipLaunchKernelGGL((m ? k_remain_len<1> : k_remain_len<0>), dim3(items / BLK + 1), dim3(BLK), 0, st, S, ct, first, items, off[m]);
+            if (wide) hipLaunchKernelGGL(k_rows_total, dim3(1), dim3(BLK), 0, st, (const uint32_t *)off[m], items, (unsigned long long *)R.total + m);
+            if ((rc = scan32_on(ctx, st, off[m], (uint64_t)items + 1, off[m], R.tmp, 0u, 0))) return rc;
+        }
+    }
+    land[0] = land[1] = 0;
+    for (int m = 0; m < 2; ++m) {
+        if (wide) HIPCHK(ctx, hipMemcpyAsync(land + m, R.total + m, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+        else HIPCHK(ctx, hipMemcpyAsync(land + m, off[m] + items, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    }
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    const uint64_t total[2] = {land[0], land[1]}, cap[2] = {cap1, cap2};
+    out_bytes[0] = total[0];
+    out_bytes[1] = total[1];
+    for (int m = 0; m < 2; ++m)
+        if (total[m] >= (1ull << 32))
+            return fail(ctx, CM_ELIMIT, "%s: %llu bytes of records of file %d in one call (offsets are 32 bits: format in ranges)", fn, (unsigned long long)total[m], m + 1);
+    for (int m = 0; m < 2; ++m)
+        if (total[m] > cap[m])
+            return fail(ctx, CM_ELIMIT, "%s: %llu bytes of records of file %d > cap %llu", fn, (unsigned long long)total[m], m + 1, (unsigned long long)cap[m]);
+    HIPCHK(ctx, ensure(ctx, R.out, (size_t)total[0] + 4));
+    HIPCHK(ctx, ensure(ctx, R.out2, (size_t)total[1] + 4));
+    uint8_t *const d_out[2] = {R.out, R.out2};
+    void *const h_out[2] = {out1, out2};
+    {
+        Timer t(ctx, PC_ROWS, st);
+        for (int m = 0; m < 2; ++m)
+            hipLaunchKernelGGL((m ? k_remain_rows<1> : k_remain_rows<0>), dim3(spans), dim3(cmrt::WAVE), 0, st, S, ct, first, items, (const uint32_t *)off[m], d_out[m], path[m]);
+    }
+    HIPCHK(ctx, hipGetLastError());
+    for (int m = 0; m < 2; ++m) HIPCHK(ctx, hipMemcpyAsync(h_out[m], d_out[m], (size_t)total[m], hipMemcpyDeviceToHost, st));
+    if (out_keys) HIPCHK(ctx, hipMemcpyAsync(out_keys, R.keys, (size_t)items * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    if (stats) {
+        R.h_path.resize(2 * (size_t)spans);
+        for (int m = 0; m < 2; ++m) HIPCHK(ctx, hipMemcpyAsync(R.h_path.data() + (size_t)m * spans, path[m], spans, hipMemcpyDeviceToHost, st));
+    }
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    if (stats) {
+        stats[0] = 2ull * items;
+        stats[1] = total[0] + total[1];
+        for (size_t i = 0; i < 2 * (size_t)spans; ++i) ++stats[R.h_path[i] ? 2 : 3];
+    }
+    return CM_OK;
 }
 
 // test hook: the qualities cm_reads_stage_text kept with the resident batch (flag bit 3), copied back: off1[n] / off2[n] bytes

@@ -1,8 +1,9 @@
-// cm_rows_text.h — what the device-side row formatters (cm_format_pam, cm_format_sam) share: everything that is not a row format.
+// cm_rows_text.h — what the device-side row formatters (cm_format_pam, cm_format_sam, cm_format_remain) share: everything that is
+// not a row format.
 //
-// Shared by the HIP kernels (cm_hot.hip: k_pam_len / k_sam_len, k_pam_rows / k_sam_rows) and by the host emulation
-// (tests/hostemu_rows.h) that g++ compiles, the way cm_fastq_text.h is shared.  The two formats are cm_pam_text.h and
-// cm_sam_text.h; each plugs into the plan below as a policy type.
+// Shared by the HIP kernels (cm_hot.hip: k_pam_len / k_sam_len / k_remain_len, k_pam_rows / k_sam_rows / k_remain_rows) and by the
+// host emulation (tests/hostemu_rows.h) that g++ compiles, the way cm_fastq_text.h is shared.  The formats are cm_pam_text.h,
+// cm_sam_text.h and cm_remain_text.h; each plugs into the plan below as a policy type.
 // The plan of a call: one lane per item (a PAM row, a SAM record) computes the item's length (item_length) -> exclusive scan = the
 // item's offset in the output -> a wave takes F::SPAN_ITEMS consecutive items, which are one contiguous span [s, e) of the output
 // (format_span).  A span of at most WINDOW bytes is put together in the wave's LDS window, every byte at window_at() of its place
@@ -44,7 +45,7 @@ struct ChrTab {
 };
 
 // Numbers are written into their place from the last digit backwards: the length is known beforehand (dec_len: compares, no
-// division loop), so nothing is reversed, and every field fits 32 bits.
+// division loop), so nothing is reversed, and every field of a PAM row and of a SAM record fits 32 bits.
 // decimal digits of v
 CMRT_HD uint32_t dec_len(uint32_t v) {
     return 1u + (v >= 10u) + (v >= 100u) + (v >= 1000u) + (v >= 10000u) + (v >= 100000u) + (v >= 1000000u) + (v >= 10000000u) + (v >= 100000000u) +
@@ -66,6 +67,29 @@ CMRT_HD uint8_t *put_i32(uint8_t *p, int32_t v) {
     if (v >= 0) return put_u32(p, (uint32_t)v);
     *p++ = '-';
     return put_u32(p, 0u - (uint32_t)v);
+}
+// The one field that does not fit 32 bits: the sort key of a remain record (cm_remain_text.h), a 64-bit signed decimal.
+// decimal digits of v
+CMRT_HD uint32_t dec_len64(uint64_t v) {
+    if (v <= 0xffffffffull) return dec_len((uint32_t)v);
+    uint32_t k = 10;
+    for (uint64_t p = 10000000000ull; k < 20u && v >= p; p *= 10u) ++k;      // (p = 10^19 is the last power below 2^64)
+    return k;
+}
+CMRT_HD uint32_t int_len64(int64_t v) { return v < 0 ? 1u + dec_len64(0ull - (uint64_t)v) : dec_len64((uint64_t)v); }
+CMRT_HD uint8_t *put_u64(uint8_t *p, uint64_t v) {
+    if (v <= 0xffffffffull) return put_u32(p, (uint32_t)v);
+    const uint32_t k = dec_len64(v);
+    for (uint32_t i = k; i-- > 0;) {
+        p[i] = (uint8_t)('0' + (uint32_t)(v % 10u));
+        v /= 10u;
+    }
+    return p + k;
+}
+CMRT_HD uint8_t *put_i64(uint8_t *p, int64_t v) {
+    if (v >= 0) return put_u64(p, (uint64_t)v);
+    *p++ = '-';
+    return put_u64(p, 0ull - (uint64_t)v);
 }
 CMRT_HD uint8_t *put_bytes(uint8_t *p, const uint8_t *from, uint32_t n) {
     for (uint32_t i = 0; i < n; ++i) p[i] = from[i];

@@ -1328,9 +1328,7 @@ int cm_write_pam(cm_writer *w, const cm_fastq_batch *b, const cm_mapped_read *st
 
 // rows somebody else formatted (cm_format_pam): small pieces go through the buffer, a piece the buffer cannot hold goes to the file
 // behind what the buffer holds
-int cm_write_bytes(cm_writer *w, const void *p, uint64_t n) {
-    if (!w || (n && !p)) return CM_EINVAL;
-    Out &o = w->o1;
+static int write_bytes_to(Out &o, const void *p, uint64_t n) {
     if (n <= o.buf.size()) {
         if (n) o.raw(p, (size_t)n);
     } else {
@@ -1338,6 +1336,15 @@ int cm_write_bytes(cm_writer *w, const void *p, uint64_t n) {
         if (o.f && fwrite(p, 1, (size_t)n, o.f) != n) o.failed = true;
     }
     return o.failed ? CM_EIO : CM_OK;
+}
+int cm_write_bytes(cm_writer *w, const void *p, uint64_t n) {
+    if (!w || (n && !p)) return CM_EINVAL;
+    return write_bytes_to(w->o1, p, n);
+}
+// ... for the writer's second file (the R2 records cm_format_remain delivers)
+int cm_write_bytes2(cm_writer *w, const void *p, uint64_t n) {
+    if (!w || !w->f2 || (n && !p)) return CM_EINVAL;
+    return write_bytes_to(w->o2, p, n);
 }
 
 // SAMOutput::print_header (src/output.cpp:301-311)

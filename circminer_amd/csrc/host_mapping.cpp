@@ -22,7 +22,9 @@
 //
 // With CM_FASTQ_DEVICE=1 and report 0 the parser thread only reads: raw text blocks (cm_fastq_next_text) are tokenised by the device
 // (cm_reads_stage_text) and the remain rows of the re-queued pairs are sliced from the text (cm_write_remain_text); same pipeline,
-// same files.  Opt-in: see DESIGN.md §7 for what it costs and gains.
+// same files.  Opt-in: see DESIGN.md §7 for what it costs and gains.  With CM_REMAIN_DEVICE=1 beside it those rows are formatted by
+// the device as well (cm_format_remain into two of four page-locked buffers, appended with cm_write_bytes / cm_write_bytes2): once a
+// batch is staged the host needs none of its read text.  The text blocks still live as long as before; that is a later change.
 //
 // One process per GPU: rank r of w maps the r-th contiguous block of pairs (cm_fastq_open_shard) and writes .part<r> files;
 // cm_merge_parts on rank 0 concatenates them in rank order -- the bytes one process would have written.
@@ -107,6 +109,7 @@ struct Run {
     std::vector<cm_annot_view> annots, annots_early;             // _early: the GTF thread's, until load_annotation() takes or frees them
     Result res[2];
     RowBuf rows[2];
+    RowBuf rem_rows[2][2];                         // CM_REMAIN_DEVICE=1: the remain records of batch k, file 1 and file 2, in set k & 1
     // parser arrays and text blocks registered with the runtime.  The parser tells us (release hook, on its own thread) before one of
     // them is freed -- a generation's array that has to grow is allocated anew -- so that no registration outlives its block.
     PinnedRanges pins;
@@ -115,7 +118,7 @@ struct Run {
     std::vector<uint32_t> clen_guess;
     int early_rc = CM_EINVAL, writer_rc = CM_OK, parser_rc = CM_OK;
     double write_s = 0.0, parse_s = 0.0;           // read after the join
-    bool text_path = false, pam_device = false, sam_device = false, want_fixed = false;
+    bool text_path = false, pam_device = false, sam_device = false, remain_device = false, want_fixed = false;
     TextBlock tq[4];
     cm_fastq_batch cur{}, nxt{}, nn{};
     Run(const cm_mapping_args *args, char *e, uint64_t cap) : a(args), err(e), err_cap((size_t)cap) {
@@ -138,8 +141,8 @@ struct Run {
         if (writer.joinable()) writer.join();
         if (w_map) cm_writer_close(w_map);
         if (w_rem) cm_writer_close(w_rem);
-        for (RowBuf &rb : rows)
-            if (rb.p) (void)cm_host_free(cm, rb.p);
+        for (RowBuf *rb : {&rows[0], &rows[1], &rem_rows[0][0], &rem_rows[0][1], &rem_rows[1][0], &rem_rows[1][1]})
+            if (rb->p) (void)cm_host_free(cm, rb->p);
         if (cm) (void)cm_sync(cm);
         pins.clear();
         if (pins.failed)
@@ -328,10 +331,11 @@ struct Run {
     }
     // The device-side tokeniser's path is opt-in and falls back to the host parser, for the run, where that one is needed.
     int choose_text_path() {
-        const char *e = getenv("CM_FASTQ_DEVICE"), *ep = getenv("CM_PAM_DEVICE"), *es = getenv("CM_SAM_DEVICE");
+        const char *e = getenv("CM_FASTQ_DEVICE"), *ep = getenv("CM_PAM_DEVICE"), *es = getenv("CM_SAM_DEVICE"), *er = getenv("CM_REMAIN_DEVICE");
         pam_device = a->report == 1 && ep && atoi(ep) == 1;      // the rows of report 1 formatted on the device: needs the text path
         sam_device = a->report == 2 && es && atoi(es) == 1;      // the records of report 2 likewise
         text_path = e && atoi(e) == 1 && (a->report == 0 || pam_device || sam_device);
+        remain_device = er && atoi(er) == 1;                     // the remain records formatted on the device: on the text path, in any report mode it covers
         // bytes per file and block: what batch_pairs records take, first by a guess (a 150-bp record with its name and qualities is
         // ~ 350 bytes), then by what the records of the last batch took -- a block that holds much more than a batch only grows the tail
         want = batch_pairs * 400 + (1u << 16);
@@ -482,7 +486,7 @@ struct Run {
             B.rec2.resize(batch_pairs + 1);
             pins.cover(B.t1, B.l1);                              // (the same buffer handed out at another offset: widened to cover both)
             pins.cover(B.t2, B.l2);
-            int r = cm_reads_stage_text(cm, B.t1, B.l1, B.t2, B.l2, batch_pairs, (B.e1 ? 1u : 0u) | (B.e2 ? 2u : 0u) | (pam_device ? 4u : 0u) | (sam_device ? 12u : 0u), B.rec1.data(), B.rec2.data(), &B.tb);
+            int r = cm_reads_stage_text(cm, B.t1, B.l1, B.t2, B.l2, batch_pairs, (B.e1 ? 1u : 0u) | (B.e2 ? 2u : 0u) | (pam_device ? 4u : 0u) | (sam_device ? 12u : 0u) | (remain_device ? 28u : 0u), B.rec1.data(), B.rec2.data(), &B.tb);
             if (r != CM_OK) return r;
             if (B.tb.n_pairs) {
                 if (!want_fixed) want = std::max(B.tb.used1, B.tb.used2) / B.tb.n_pairs * batch_pairs / 100 * 101 + (1u << 16);
@@ -492,6 +496,17 @@ struct Run {
             bytes *= 2;
             if ((r = cm_fastq_text_consumed(fq, 0, 0)) != CM_OK || (r = read_block(B, bytes)) != CM_OK) return r;
         }
+    }
+    // a larger page-locked buffer with what the old one holds
+    int grow_rows(RowBuf &RB, uint64_t cap) {
+        void *np = nullptr;
+        const int r = cm_host_alloc(cm, cap, &np);
+        if (r != CM_OK) return failed(r, "cm_host_alloc (rows)");
+        if (RB.n) memcpy(np, RB.p, RB.n);
+        if (RB.p) (void)cm_host_free(cm, RB.p);
+        RB.p = np;
+        RB.cap = cap;
+        return CM_OK;
     }
     // The PAM rows or SAM records of the resident batch's n pairs, in ranges: a range whose rows would not fit 32-bit offsets is
     // halved, a buffer that is too small is replaced by one that holds what is there plus what the device asks for.  A SAM pair is
@@ -510,19 +525,52 @@ struct Run {
                 continue;
             }
             if (r == CM_ELIMIT && got > RB.cap - RB.n) {
-                const uint64_t cap = RB.n + got + got / c * (n - done - c) + (1u << 16);
-                void *np = nullptr;
-                if ((r = cm_host_alloc(cm, cap, &np)) != CM_OK) return failed(r, "cm_host_alloc (rows)");
-                if (RB.n) memcpy(np, RB.p, RB.n);
-                if (RB.p) (void)cm_host_free(cm, RB.p);
-                RB.p = np;
-                RB.cap = cap;
+                if ((r = grow_rows(RB, RB.n + got + got / c * (n - done - c) + (1u << 16))) != CM_OK) return r;
                 continue;
             }
             if (r != CM_OK) return failed(r, name);
             RB.n += got;
             done += c;
         }
+        return CM_OK;
+    }
+    // CM_REMAIN_DEVICE=1: the remain records of the resident batch's active set, formatted on the device into the two page-locked
+    // buffers of a set (file 1, file 2) -- to the end of the set in one call; where a file's records would not fit 32-bit offsets,
+    // in ranges that are halved until they do.  *n_rec: the size of the set (the run's bsj_pairs).
+    int format_remain(RowBuf RM[2], uint64_t *n_rec) {
+        uint64_t done = 0, total = 0, step = ~0ull;
+        RM[0].n = RM[1].n = 0;
+        for (;;) {
+            const uint64_t count = step == ~0ull ? ~0ull : std::min(step, total - done);
+            uint64_t got[2] = {0, 0};
+            int r = cm_format_remain(cm, chrs, n_chr, done, count, RM[0].p ? (char *)RM[0].p + RM[0].n : nullptr, RM[0].cap - RM[0].n,
+                                     RM[1].p ? (char *)RM[1].p + RM[1].n : nullptr, RM[1].cap - RM[1].n, got, nullptr, &total, nullptr);
+            const uint64_t c = count == ~0ull ? total - done : count;
+            if (r == CM_ELIMIT && std::max(got[0], got[1]) >= (1ull << 32) && c > 1) {
+                step = c / 2;
+                continue;
+            }
+            if (r == CM_ELIMIT && c && (got[0] > RM[0].cap - RM[0].n || got[1] > RM[1].cap - RM[1].n)) {
+                for (int m = 0; m < 2; ++m)
+                    if (got[m] > RM[m].cap - RM[m].n && (r = grow_rows(RM[m], RM[m].n + got[m] + got[m] / c * (total - done - c) + (1u << 16))) != CM_OK) return r;
+                continue;
+            }
+            if (r != CM_OK) return failed(r, "cm_format_remain");
+            RM[0].n += got[0];
+            RM[1].n += got[1];
+            done += c;
+            if (done >= total) break;
+        }
+        *n_rec = total;
+        return CM_OK;
+    }
+    // ... and the type histogram, which collect_records delivers on the other path
+    int remain_records(Result &R, RowBuf RM[2]) {
+        int rc;
+        if ((rc = format_remain(RM, &R.n_rec)) != CM_OK) return rc;
+        uint64_t h[14];
+        if ((rc = cm_type_histogram(cm, h)) != CM_OK) return failed(rc, "cm_type_histogram");
+        for (int t = 0; t < 14; ++t) st.by_type[t] += h[t];
         return CM_OK;
     }
     int text_batches() {
@@ -553,11 +601,13 @@ struct Run {
             if ((rc = cm_map_rounds(cm, all.data(), (int)n_con, 1)) != CM_OK) return failed(rc, "cm_map_rounds");
             RB.n = 0;
             if ((pam_device || sam_device) && (rc = format_rows(RB, n)) != CM_OK) return rc;
-            if ((rc = collect_records(R, n)) != CM_OK || (rc = end_device_leg(R, n, more, td)) != CM_OK) return rc;
-            rc = hand_to_writer([this, &R, &B, &RB]() {
-                const int r = (pam_device || sam_device) ? cm_write_bytes(w_map, RB.p, RB.n) : CM_OK;
+            RowBuf *const RM = rem_rows[k & 1];
+            if ((rc = remain_device ? remain_records(R, RM) : collect_records(R, n)) != CM_OK || (rc = end_device_leg(R, n, more, td)) != CM_OK) return rc;
+            rc = hand_to_writer([this, &R, &B, &RB, RM]() {
+                int r = (pam_device || sam_device) ? cm_write_bytes(w_map, RB.p, RB.n) : CM_OK;
                 if (r != CM_OK || !R.n_rec) return r;
-                return cm_write_remain_text(w_rem, B.t1, B.rec1.data(), B.t2, B.rec2.data(), R.recs.data(), R.n_rec);
+                if (!remain_device) return cm_write_remain_text(w_rem, B.t1, B.rec1.data(), B.t2, B.rec2.data(), R.recs.data(), R.n_rec);
+                return (r = cm_write_bytes(w_rem, RM[0].p, RM[0].n)) != CM_OK ? r : cm_write_bytes2(w_rem, RM[1].p, RM[1].n);
             });
             if (rc != CM_OK || (rc = join_parser("cm_fastq_next_text")) != CM_OK) return rc;
         }

@@ -221,6 +221,8 @@ SIGNATURES = {
     "cm_write_remain_text": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_uint64]),
     "cm_format_pam": (C.c_int, [vp, pp(ChrInfo), C.c_uint32, C.c_uint64, C.c_uint64, vp, C.c_uint64, pp(C.c_uint64), pp(C.c_uint64)]),
     "cm_format_sam": (C.c_int, [vp, pp(ChrInfo), C.c_uint32, C.c_uint64, C.c_uint64, vp, C.c_uint64, pp(C.c_uint64), pp(C.c_uint64)]),
+    "cm_format_remain": (C.c_int, [vp, pp(ChrInfo), C.c_uint32, C.c_uint64, C.c_uint64, vp, C.c_uint64, vp, C.c_uint64, pp(C.c_uint64), vp, pp(C.c_uint64),
+                                   pp(C.c_uint64)]),
     "cm_quals_peek": (C.c_int, [vp, vp, C.c_uint64, vp, C.c_uint64]),
     "cm_state_poke": (C.c_int, [vp, vp]),
     "cm_debug_lane_clk": (C.c_int, [vp, vp]),
@@ -290,6 +292,8 @@ SIGNATURES = {
     "cm_abi_sizes": (C.c_int, [pp(C.c_uint32), C.c_uint32]),
 }
 EXPORTED_SYMBOLS = sorted(SIGNATURES)
+# Declared beside the table: EXPORTED_SYMBOLS is held against the header's names of letters and underscores, and this one ends in a digit.
+SIGNATURES_NUMBERED = {"cm_write_bytes2": (C.c_int, [vp, vp, C.c_uint64])}
 
 
 def load(path: str = LIB_PATH) -> C.CDLL:
@@ -301,7 +305,7 @@ def load(path: str = LIB_PATH) -> C.CDLL:
         raise RuntimeError(f"{path} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
                            "(the hot path is HIP-only; there is no CPU fallback)")
     L = C.CDLL(path)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_NUMBERED.items()):
         fn = getattr(L, name)  # AttributeError if the library does not export a declared symbol
         fn.restype = res
         fn.argtypes = args
@@ -668,6 +672,14 @@ class RecordWriter:
         if rc != 0:
             raise RuntimeError(f"writer failed ({rc})")
 
+    def write_bytes2(self, data):
+        """cm_write_bytes2: raw bytes (the second file's records of HotPath.format_remain) appended to the second file; refused
+        (CM_EINVAL) by a writer opened without one"""
+        a = np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray)) else np.ascontiguousarray(data, dtype=np.uint8)
+        rc = self.L.cm_write_bytes2(self.h, a.ctypes.data if a.size else None, a.size)
+        if rc != 0:
+            raise RuntimeError(f"writer failed ({rc})")
+
     def write_sam_header(self):
         if self.L.cm_write_sam_header(self.h) != 0:
             raise RuntimeError("cm_write_sam_header failed")
@@ -743,18 +755,18 @@ class HotPath:
         p = prior.ctypes.data if prior is not None else None
         self._chk(self.L.cm_reads_stage(self.h, C.byref(batch.c), p), "cm_reads_stage")
 
-    def stage_text(self, text1, text2, max_pairs, eof1=True, eof2=True, keep_names=False, keep_quals=False):
+    def stage_text(self, text1, text2, max_pairs, eof1=True, eof2=True, keep_names=False, keep_quals=False, keep_names2=False):
         """cm_reads_stage_text: the next batch staged from FASTQ text, tokenised on the device.  text1 / text2: uint8 arrays or
         bytes.  Returns (TextBatch, rec1, rec2); n_pairs == 0: nothing was staged.  keep_names (flag bit 2): the R1 names stay on
         the device with the batch, for format_pam; keep_quals (flag bit 3): so do the quality lines of both files, for format_sam,
-        which needs both."""
+        which needs both; keep_names2 (flag bit 4): so do the R2 names, for format_remain, which needs all three."""
         t1 = np.frombuffer(text1, np.uint8) if isinstance(text1, (bytes, bytearray)) else np.ascontiguousarray(text1, dtype=np.uint8)
         t2 = np.frombuffer(text2, np.uint8) if isinstance(text2, (bytes, bytearray)) else np.ascontiguousarray(text2, dtype=np.uint8)
         cap = int(min(max_pairs, min(t1.size, t2.size) // 4)) + 1           # a record has four bytes at least
         rec1, rec2 = np.zeros(cap, np.uint64), np.zeros(cap, np.uint64)
         tb = TextBatch()
         self._chk(self.L.cm_reads_stage_text(self.h, t1.ctypes.data if t1.size else None, t1.size, t2.ctypes.data if t2.size else None, t2.size, int(max_pairs),
-                                             int(bool(eof1)) | int(bool(eof2)) << 1 | int(bool(keep_names)) << 2 | int(bool(keep_quals)) << 3, rec1.ctypes.data, rec2.ctypes.data, C.byref(tb)), "cm_reads_stage_text")
+                                             int(bool(eof1)) | int(bool(eof2)) << 1 | int(bool(keep_names)) << 2 | int(bool(keep_quals)) << 3 | int(bool(keep_names2)) << 4, rec1.ctypes.data, rec2.ctypes.data, C.byref(tb)), "cm_reads_stage_text")
         self._staged_n = int(tb.n_pairs)
         return tb, rec1[:self._staged_n + 1], rec2[:self._staged_n + 1]
 
@@ -784,6 +796,33 @@ class HotPath:
         self._chk(call(self.h, table, len(chrs), int(first), int(n), buf.ctypes.data, int(cap), C.byref(got), stats), fn)
         assert got.value <= cap and bool((buf[int(cap):] == 0xA5).all())
         return buf[:got.value].tobytes(), list(stats)
+
+    def format_remain(self, chrs=(), first=0, count=None, caps=None, keys=False):
+        """cm_format_remain: the remain-FASTQ records of records [first, first + count) of the resident batch's active set (the
+        pairs of collect_records, ascending; count None: to the end), formatted on the device from a batch staged with
+        keep_names, keep_quals and keep_names2.  chrs: chromosome table rows (name, contig id, start, length).  Returns
+        (bytes of file 1, bytes of file 2, keys or None, size of the active set, stats); caps: the sizes (cap1, cap2) of the
+        buffers offered (default: what the records need, asked for first); keys: also the int64 sort key of every record."""
+        table = chr_array(list(chrs))
+        cnt = (1 << 64) - 1 if count is None else int(count)
+        got, n_rec, stats = (C.c_uint64 * 2)(), C.c_uint64(0), (C.c_uint64 * 4)()
+
+        def call(b1, c1, b2, c2, kp, sp):
+            return self.L.cm_format_remain(self.h, table, len(chrs), int(first), cnt, b1, c1, b2, c2, got, kp, C.byref(n_rec), sp)
+        if caps is None:
+            rc = call(None, 0, None, 0, None, None)
+            if rc not in (0, -6) or (rc == -6 and max(got) >= 1 << 32):         # CM_ELIMIT with the needed sizes is the answer here
+                self._chk(rc, "cm_format_remain")
+            caps = (got[0], got[1])
+        elif count is None and keys:                                            # (the size of the set, for the keys' array)
+            self._chk(self.L.cm_format_remain(self.h, table, len(chrs), 0, 0, None, 0, None, 0, got, None, C.byref(n_rec), None), "cm_format_remain")
+        n = max(int(n_rec.value) - int(first), 0) if count is None else int(count)
+        bufs = [np.full(int(c) + 64, 0xA5, np.uint8) for c in caps]             # (the bytes behind a cap show a write past it)
+        kk = np.full(n + 1, -0x5A5A5A5A5A5A5A5A, np.int64) if keys else None
+        self._chk(call(bufs[0].ctypes.data, int(caps[0]), bufs[1].ctypes.data, int(caps[1]), kk.ctypes.data if keys else None, stats), "cm_format_remain")
+        assert all(got[m] <= caps[m] and bool((bufs[m][int(caps[m]):] == 0xA5).all()) for m in (0, 1))
+        assert kk is None or kk[-1] == -0x5A5A5A5A5A5A5A5A
+        return bufs[0][:got[0]].tobytes(), bufs[1][:got[1]].tobytes(), (kk[:-1] if keys else None), int(n_rec.value), list(stats)
 
     def peek_quals(self):
         """cm_quals_peek (test hook): (qual1, qual2) of the resident batch as cm_reads_stage_text kept them (keep_quals), in the

@@ -249,7 +249,7 @@ int cm_reads_swap(cm_ctx *ctx);
  *     cm_fastq_next would put it into names1: token 0 of the header line (tokens are runs of bytes other than ' ' behind the
  *     '@') without a trailing "/x", up to its first NUL byte; empty for a header without a token.  The names belong to the batch:
  *     they travel with its read buffers through cm_reads_swap and stay valid while the batch is resident, also while the next
- *     cm_reads_stage_text overwrites the text.  cm_format_pam and cm_format_sam are their readers.  R2 names are not kept.
+ *     cm_reads_stage_text overwrites the text.  cm_format_pam, cm_format_sam and cm_format_remain are their readers.  R2 names: bit 4.
  *     Without the bit the kernels launched, the buffers and the results are those of a stage without names.
  *   - flags bit 3 (value 8, "keep qualities"): the stage also leaves on the device the quality line of every staged record of both
  *     files, in the layout of the bases: quality of read i = qual[off[i] .. off[i + 1]), sharing off1 / off2 (the stage has checked
@@ -257,7 +257,13 @@ int cm_reads_swap(cm_ctx *ctx);
  *     through cm_reads_swap and the cross-batch prefetch and outlive the text.  cm_format_sam is their reader (cm_quals_peek, a
  *     test hook, copies them back).  HBM: the bytes of the bases once more, in each of the two buffer sets, allocated only when
  *     the bit is given.  Bits 2 and 3 are independent; without bit 3 the kernels launched, the buffers and the results are those
- *     of a stage without it. */
+ *     of a stage without it.
+ *   - flags bit 4 (value 16, "keep R2 names"): the stage also leaves on the device the R2 name of each staged pair, by the rule of
+ *     bit 2 applied to file 2's header lines, in arrays of their own.  They belong to the batch exactly as the R1 names do (through
+ *     cm_reads_swap and the cross-batch prefetch, outliving the text).  cm_format_remain, which needs bits 2, 3 and 4, is their
+ *     reader.  HBM: the bytes of the names and a word per pair, in each of the two buffer sets, allocated only when the bit is
+ *     given.  Bit 4 is independent of bits 2 and 3; without it the kernels launched, the buffers and the results are those of a
+ *     stage without it. */
 typedef struct cm_text_batch {
     uint64_t n_pairs;        /* pairs staged */
     uint64_t used1, used2;   /* bytes of text1 / text2 consumed = start of the first record not staged */
@@ -429,7 +435,7 @@ int cm_debug_counters(cm_ctx *ctx, unsigned long long *out);
 /* ---------------- timing hooks for bench.py (HIP events on the ctx stream) ---------------- */
 /* Milliseconds spent in each kernel class since the last cm_prof_reset(), and launch counts:
  * [0]=k_seed [1]=k_chain (light problems) [2]=k_pair (light pairs) [3]=k_scan_* [4]=k_pair_heavy
- * [5]=class / counting-sort kernels [6]=k_chain_heavy [7]=the row formatters: the kernels of cm_format_pam and cm_format_sam (no
+ * [5]=class / counting-sort kernels [6]=k_chain_heavy [7]=the row formatters: the kernels of cm_format_pam, cm_format_sam and cm_format_remain (no
  * launch count); launches[7] = first
  * rounds taken over from the cross-batch prefetch of cm_map_rounds.  [1] and [2] are timed up to the join with the second
  * stream, on which the heavy kernels [6] / [4] run concurrently. */
@@ -623,9 +629,41 @@ int cm_format_pam(cm_ctx *ctx, const cm_chr_info *chrs, uint32_t n_chr, uint64_t
  * output directly.  After cm_prof_enable(ctx, 1) the formatter's kernels are timed by HIP events into ms[7] of cm_prof_get. */
 int cm_format_sam(cm_ctx *ctx, const cm_chr_info *chrs, uint32_t n_chr, uint64_t first, uint64_t count,
                   void *out, uint64_t cap, uint64_t *out_bytes, uint64_t stats[4] /* nullable */);
-/* Appends n raw bytes to the writer's first file through its buffer (the rows cm_format_pam / cm_format_sam deliver); CM_EIO like
- * the other cm_write_* calls. */
+/* <out>_<R>_remain_R1.fastq / _R2.fastq records (cm_write_remain_records / write_read_category, src/filter.cpp:413-455) of
+ * records [first, first + count) of the resident batch's ACTIVE SET -- the pairs cm_collect_records delivers, in ascending pair
+ * index --, formatted BY THE DEVICE from the states in HBM, the R1 names (flag bit 2), the qualities (bit 3) and the R2 names
+ * (bit 4) kept by cm_reads_stage_text and the bases in the read buffers: into out1 the bytes cm_write_remain_records writes to the
+ * first file for the same records, into out2 those of the second.  A record is '@', the mate's name, the header fields (the same
+ * in both files), '\n', the bases, "\n+\n", the qualities, '\n'.  The fields of a type among CONCRD, DISCRD, CHIORF, CHIBSJ,
+ * CHI2BSJ, CONGNM, CONGEN: " %lld %d %s %u %u %d %u %u %c %d %s %u %u %d %u %u %c %d %d %d %d %d" with
+ * gspos = (uint64)(int64)contig_num * CM_CONTIG_SIZE + (uint32)(spos_r1 + shift) printed signed, shift = start_pos of chr_id inside
+ * [0, n_chr) and 0 outside (where the chromosome prints "-"), mlen_* through (int), junc_num a uint16, gm_compatible as != 0; of
+ * every other type " * <type>" and 20 times " *".  The names end at their first NUL byte, as those of a host-parsed batch do
+ * (cm_write_remain_text does not cut there: the one input on which the two writers of the device tokeniser's path differ).
+ * count == ~0ull: to the end of the set.  chrs: names and start_pos are used (one table per context, shared with cm_format_pam and
+ * cm_format_sam).  n_records (nullable) receives the size of the active set: also for count == 0 and on every refusal for which a
+ * resident batch exists.  out_keys (nullable, count words): out_keys[k] is what `sort -k2,2n` orders record first + k by (key_of
+ * in stage 2): gspos for a type that prints its fields, 0 for the star form -- the value, not a parse: for a name that holds a
+ * blank the text's second field is something else.
+ * Ordering is that of cm_collect_records: the work is queued behind everything queued for the resident batch and the call returns
+ * when the bytes are in out1 / out2 (page-locked or pageable); it neither waits for nor disturbs the staging stream or a
+ * cross-batch prefetch in flight.
+ * CM_ESTATE: no resident batch, or one staged without bit 2, 3 or 4 (cm_last_error names which).  CM_EINVAL: first + count beyond
+ * the set, or out1 / out2 == NULL with a cap > 0.  CM_ELIMIT with the needed sizes in out_bytes[0] / [1] and nothing written:
+ * either cap is too small; CM_ELIMIT also when a file's records of one call come to 2^32 bytes or more (format in ranges).
+ * count == 0 is CM_OK with out_bytes == {0, 0}.  A refusal leaves the resident batch as it was.
+ * stats (nullable): [0] records of both files (2 count), [1] bytes of both, [2] / [3] spans of 16 records (one wave each, both
+ * files) that were put together in the wave's LDS window and streamed out as whole words / that were larger than the window (long
+ * names, reads of 250 - 300 bases) and stored to the output directly.  After cm_prof_enable(ctx, 1) the formatter's kernels are
+ * timed by HIP events into ms[7] of cm_prof_get. */
+int cm_format_remain(cm_ctx *ctx, const cm_chr_info *chrs, uint32_t n_chr, uint64_t first, uint64_t count,
+                     void *out1, uint64_t cap1, void *out2, uint64_t cap2, uint64_t out_bytes[2], int64_t *out_keys,
+                     uint64_t *n_records, uint64_t stats[4] /* out_keys, n_records, stats: nullable */);
+/* Appends n raw bytes to the writer's first file through its buffer (the rows cm_format_pam / cm_format_sam deliver, the first
+ * file's records of cm_format_remain); CM_EIO like the other cm_write_* calls. */
 int cm_write_bytes(cm_writer *w, const void *p, uint64_t n);
+/* ... to the writer's second file; CM_EINVAL for a writer opened without one. */
+int cm_write_bytes2(cm_writer *w, const void *p, uint64_t n);
 /* <out>.mapping.sam (--sam): header = SAMOutput::print_header (src/output.cpp:301-311, one @SQ per row of the chromosome
  * table), records = write_sam_rec_pe with set_flag_pe / set_output_pe (src/output.cpp:118-277): two lines per pair,
  * CIGAR "*", MAPQ 255, tags AT / NM / JC / TC; TLEN is printed with %u like the reference does. */
@@ -658,7 +696,13 @@ void cm_writer_close(cm_writer *w);
  * With CM_SAM_DEVICE=1 in addition to CM_FASTQ_DEVICE=1 the path covers report == 2 in the same way: the batches are staged with
  * their names and qualities (flag bits 2 | 3), the SAM records of a batch are formatted on the device (cm_format_sam, in ranges of
  * at most 2^17 pairs, into one of two page-locked buffers that hold a batch's records) and the writer thread appends them behind
- * the header -- the same <out>.mapping.sam byte for byte.  Without its variable a report mode stays with the host parser. */
+ * the header -- the same <out>.mapping.sam byte for byte.  Without its variable a report mode stays with the host parser.
+ * With CM_REMAIN_DEVICE=1 in addition to CM_FASTQ_DEVICE=1 the remain records of the path are formatted on the device too, in every
+ * report mode the path covers: the batches are staged with flag bits 2 | 3 | 4 on top of what the report mode asks for, after a
+ * batch's last round cm_format_remain puts the records of the pairs still active into two of four page-locked buffers (two sets of
+ * two) and the writer thread appends them with cm_write_bytes / cm_write_bytes2 in place of cm_write_remain_text -- the same remain
+ * files byte for byte (names with a NUL byte excepted, see cm_format_remain), the same statistics, for one process and for rank /
+ * world part files.  Where the host parser's path is taken the variable has no effect. */
 typedef struct cm_mapping_args {
     const char *index_path;        /* <ref>.packed.fa.index        */
     const char *index_info_path;   /* <ref>.packed.fa.index.info   */
