@@ -29,6 +29,7 @@
 #include "cm_index_build.h"
 #include "cm_fastq_text.h"
 #include "cm_pam_text.h"
+#include "cm_remain_order.h"
 #include "cm_remain_text.h"
 #include "cm_sam_text.h"
 
@@ -73,10 +74,11 @@ enum Pin {
     PIN_RERUN_N = 12, PIN_FALL_N = 14,               // + chain-record set: length of the re-run list / of the pipeline's fall-back list
     PIN_TEXT = 16,                                   // cm_reads_stage_text: the result block of the tokeniser (cmft::RES_WORDS words)
     PIN_ROWS = 26,                                    // cm_format_pam / cm_format_sam: the bytes of the rows; cm_format_remain: + 1, of the second file
+    PIN_TIES = 28,                                    // cm_format_remain_sorted: the tie groups' counters (three 32-bit words)
     PIN_WORDS = 32
 };
 constexpr size_t PIN_BYTES = PIN_WORDS * sizeof(unsigned long long);        // allocated and cleared in cm_create
-static_assert(PIN_BYTES == 256 && PIN_FALL_N + 1 < PIN_TEXT && PIN_CELLS + 3 < PIN_RERUN_N && PIN_TEXT + cmft::RES_WORDS <= PIN_ROWS && PIN_ROWS + 1 < PIN_WORDS,
+static_assert(PIN_BYTES == 256 && PIN_FALL_N + 1 < PIN_TEXT && PIN_CELLS + 3 < PIN_RERUN_N && PIN_TEXT + cmft::RES_WORDS <= PIN_ROWS && PIN_ROWS + 1 < PIN_TIES && PIN_TIES + 1 < PIN_WORDS,
               "the landing zone has 32 words");
 struct ReadsDev {
     const uint8_t *seq1, *seq2;
@@ -2228,6 +2230,37 @@ __global__ void __launch_bounds__(cmrt::WAVE) k_remain_rows(cmrm::Src S, cmrt::C
     rows_span<cmrm::Format<MATE>>(S, ct, first, items, off, out, path);
 }
 
+// the order of the sorted remain records (cm_format_remain_sorted; the bodies and the plan: cm_remain_order.h), a lane per entry
+__global__ void __launch_bounds__(BLK) k_remain_keys(cmrm::Src S, uint32_t n_chr, uint32_t n, uint64_t *rkey, uint32_t *pair) {
+    const uint32_t q = blockIdx.x * BLK + threadIdx.x;
+    if (q < n) cmro::entry_key(S, n_chr, q, rkey, pair);
+}
+__global__ void __launch_bounds__(BLK) k_remain_heads(const uint64_t *rkey, uint32_t n, uint32_t *head) { cmro::group_head(rkey, n, blockIdx.x * BLK + threadIdx.x, head); }
+__global__ void __launch_bounds__(BLK) k_remain_gstart(const uint32_t *ex, uint32_t n, uint32_t *gstart) { cmro::group_start(ex, n, blockIdx.x * BLK + threadIdx.x, gstart); }
+// a lane per group: ctr[0] the largest group, ctr[1] the groups of two or more members, ctr[2] their members (a workgroup's share
+// through LDS, one atomic per counter and workgroup that has any)
+__global__ void __launch_bounds__(BLK) k_remain_gsizes(const uint32_t *gstart, const uint32_t *n_groups, unsigned int *ctr) {
+    __shared__ unsigned int part[3];
+    if (threadIdx.x < 3) part[threadIdx.x] = 0u;
+    __syncthreads();
+    const uint32_t sz = cmro::group_size(gstart, *n_groups, blockIdx.x * BLK + threadIdx.x);
+    if (sz >= 2u) {
+        atomicMax(&part[0], sz);
+        atomicAdd(&part[1], 1u);
+        atomicAdd(&part[2], sz);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0 && part[1]) {
+        atomicMax(&ctr[0], part[0]);
+        atomicAdd(&ctr[1], part[1]);
+        atomicAdd(&ctr[2], part[2]);
+    }
+}
+template <uint32_t MATE>
+__global__ void __launch_bounds__(BLK) k_remain_rank(cmrm::Src S, cmrt::ChrTab ct, const uint32_t *by_key, const uint32_t *ex, const uint32_t *gstart, uint32_t n, uint32_t *list) {
+    cmro::rank_in_group<MATE>(S, ct, by_key, ex, gstart, n, blockIdx.x * BLK + threadIdx.x, list);
+}
+
 // ------------------------------------------------------------------ host side
 struct Slot {
     bool loaded = false, has_annot = false;
@@ -2428,6 +2461,12 @@ struct RowsBufs {
     BatchBuf<uint32_t> off2;
     BatchBuf<uint8_t> out2, path2;
     BatchBuf<int64_t> keys;
+    // cm_format_remain_sorted only: the radix keys and pairs before and behind the sort, its workspace, the heads scanned into group
+    // numbers, the groups' starts and counters, the selection list of either mate file
+    BatchBuf<uint64_t> rkey0, rkey1;
+    BatchBuf<uint32_t> pair0, by_key, heads, gstart, list1, list2;
+    BatchBuf<uint8_t> sort_ws;
+    CtxBuf<unsigned int> ties;
 };
 
 // The streams of a context, under the letters of DESIGN §4.  STREAMS lists them in creation order, which decides the hardware
@@ -4693,13 +4732,66 @@ int cm_format_sam(cm_ctx *ctx, const cm_chr_info *chrs, uint32_t n_chr, uint64_t
     return format_rows(ctx, c, chrs, n_chr, first, count, out, cap, out_bytes, stats);
 }
 
+// Either mate file's order of the n entries of the active set (S.sel = compact_active's list) into rows.list1 / list2: the plan of
+// cm_remain_order.h on the mapping stream.  One wait, for the tie groups' counters: a group above the cap is refused before any
+// lane ranks (CM_ELIMIT), and without a group of two the key order is both files' order.
+static int sort_remain(cm_ctx *ctx, const char *fn, const cmrm::Src &S, const cmrt::ChrTab &ct, uint32_t n) {
+    RowsBufs &R = ctx->rows;
+    hipStream_t st = ctx->st.B;
+    uint32_t cap = cmro::TIE_CAP;
+    if (const char *e = getenv("CM_REMAIN_TIE_CAP")) cap = (uint32_t)std::min<long>(cmro::TIE_CAP, std::max<long>(1, atol(e)));     // (a test knob: the boundary at small sizes)
+    HIPCHK(ctx, ensure(ctx, R.rkey0, (size_t)n * sizeof(uint64_t)));
+    HIPCHK(ctx, ensure(ctx, R.rkey1, (size_t)n * sizeof(uint64_t)));
+    HIPCHK(ctx, ensure(ctx, R.pair0, (size_t)n * sizeof(uint32_t)));
+    HIPCHK(ctx, ensure(ctx, R.by_key, (size_t)n * sizeof(uint32_t)));
+    HIPCHK(ctx, ensure(ctx, R.heads, ((size_t)n + 1) * sizeof(uint32_t)));
+    HIPCHK(ctx, ensure(ctx, R.gstart, ((size_t)n + 1) * sizeof(uint32_t)));
+    HIPCHK(ctx, ensure(ctx, R.list1, (size_t)n * sizeof(uint32_t)));
+    HIPCHK(ctx, ensure(ctx, R.list2, (size_t)n * sizeof(uint32_t)));
+    HIPCHK(ctx, ensure(ctx, R.tmp, (size_t)(((uint64_t)n + 1) / S32_B + 2) * sizeof(uint32_t)));
+    HIPCHK(ctx, ensure(ctx, R.ties, 4 * sizeof(unsigned int)));
+    size_t ws = 0;
+    HIPCHK(ctx, rocprim::radix_sort_pairs(nullptr, ws, (uint64_t *)R.rkey0, (uint64_t *)R.rkey1, (uint32_t *)R.pair0, (uint32_t *)R.by_key, (size_t)n, 0u, 64u, st));
+    HIPCHK(ctx, ensure(ctx, R.sort_ws, ws));
+    const dim3 grid(n / BLK + 1), block(BLK);
+    int rc;
+    unsigned int *land = (unsigned int *)(ctx->h_pin + PIN_TIES);
+    {
+        Timer t(ctx, PC_ROWS, st);
+        hipLaunchKernelGGL(k_remain_keys, grid, block, 0, st, S, ct.n, n, (uint64_t *)R.rkey0, (uint32_t *)R.pair0);
+        HIPCHK(ctx, rocprim::radix_sort_pairs((void *)R.sort_ws, ws, (uint64_t *)R.rkey0, (uint64_t *)R.rkey1, (uint32_t *)R.pair0, (uint32_t *)R.by_key, (size_t)n, 0u, 64u, st));
+        hipLaunchKernelGGL(k_remain_heads, grid, block, 0, st, (const uint64_t *)R.rkey1, n, (uint32_t *)R.heads);
+        if ((rc = scan32_on(ctx, st, R.heads, (uint64_t)n + 1, R.heads, R.tmp, 0u, 0))) return rc;
+        HIPCHK(ctx, hipMemsetAsync(R.ties, 0, 4 * sizeof(unsigned int), st));
+        hipLaunchKernelGGL(k_remain_gstart, grid, block, 0, st, (const uint32_t *)R.heads, n, (uint32_t *)R.gstart);
+        hipLaunchKernelGGL(k_remain_gsizes, grid, block, 0, st, (const uint32_t *)R.gstart, (const uint32_t *)R.heads + n, (unsigned int *)R.ties);
+    }
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipMemcpyAsync(land, R.ties, 4 * sizeof(unsigned int), hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    if (land[0] > cap) return fail(ctx, CM_ELIMIT, "%s: a tie group of %u records > cap %u (order the batch on the host)", fn, land[0], cap);
+    if (land[1] == 0) {                                   // every key once
+        HIPCHK(ctx, hipMemcpyAsync(R.list1, R.by_key, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+        HIPCHK(ctx, hipMemcpyAsync(R.list2, R.by_key, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+        return CM_OK;
+    }
+    {
+        Timer t(ctx, PC_ROWS, st);
+        hipLaunchKernelGGL(k_remain_rank<0>, grid, block, 0, st, S, ct, (const uint32_t *)R.by_key, (const uint32_t *)R.heads, (const uint32_t *)R.gstart, n, (uint32_t *)R.list1);
+        hipLaunchKernelGGL(k_remain_rank<1>, grid, block, 0, st, S, ct, (const uint32_t *)R.by_key, (const uint32_t *)R.heads, (const uint32_t *)R.gstart, n, (uint32_t *)R.list2);
+    }
+    HIPCHK(ctx, hipGetLastError());
+    return CM_OK;
+}
+
 // Remain records: one per mate file of every record [first, first + count) of the active set, the set and order of
 // cm_collect_records (compact_active's list is the formats' selection).  The plan runs once per mate: both length passes first --
 // either file may be refused for its size, and then neither is written --, then both span passes.  Needs the kept names of both
 // files and the kept qualities.  Three waits: for the size of the active set, for the two totals, for the bytes.
-int cm_format_remain(cm_ctx *ctx, const cm_chr_info *chrs, uint32_t n_chr, uint64_t first, uint64_t count, void *out1, uint64_t cap1, void *out2, uint64_t cap2,
-                     uint64_t out_bytes[2], int64_t *out_keys, uint64_t *n_records, uint64_t stats[4]) {
-    static const char *const fn = "cm_format_remain";
+// sorted: the order of cm_remain_order.h in place of the active set's (cm_format_remain_sorted, below); out_off (nullable): the
+// records' offsets in either file, count + 1 words each.
+static int format_remain(cm_ctx *ctx, const char *fn, bool sorted, const cm_chr_info *chrs, uint32_t n_chr, uint64_t first, uint64_t count, void *out1, uint64_t cap1,
+                         void *out2, uint64_t cap2, uint64_t out_bytes[2], int64_t *out_keys, uint32_t *const out_off[2], uint64_t *n_records, uint64_t stats[4]) {
     if (!ctx || !out_bytes || (n_chr && !chrs)) return CM_EINVAL;
     out_bytes[0] = out_bytes[1] = 0;
     if (n_records) *n_records = 0;
@@ -4756,6 +4848,13 @@ int cm_format_remain(cm_ctx *ctx, const cm_chr_info *chrs, uint32_t n_chr, uint6
     const cmrm::Src S{ctx->col.perm, ctx->d_state, {rd.names, rd.names2}, {rd.name_off, rd.name_off2},
                       {rd.seq1_base + cmc::CM_STAGE_PAD, rd.seq2_base + cmc::CM_STAGE_PAD}, {rd.qual1, rd.qual2}, {rd.off1, rd.off2},
                       R.chr_shift, out_keys ? (int64_t *)R.keys : nullptr};
+    // either file's selection list: the active set, or the file's own order of it
+    cmrm::Src Sm[2] = {S, S};
+    if (sorted) {
+        if ((rc = sort_remain(ctx, fn, S, ct, active))) return rc;
+        Sm[0].sel = R.list1;
+        Sm[1].sel = R.list2;
+    }
     uint32_t *const off[2] = {R.off, R.off2};
     uint8_t *const path[2] = {R.path, R.path2};
     // offsets are uint32: where a file's records could come to 2^32 bytes the lengths are summed in 64 bits first (format_rows)
@@ -4764,7 +4863,7 @@ int cm_format_remain(cm_ctx *ctx, const cm_chr_info *chrs, uint32_t n_chr, uint6
     {
         Timer t(ctx, PC_ROWS, st);
         for (int m = 0; m < 2; ++m) {
-            hipLaunchKernelGGL((m ? k_remain_len<1> : k_remain_len<0>), dim3(items / BLK + 1), dim3(BLK), 0, st, S, ct, first, items, off[m]);
+            hipLaunchKernelGGL((m ? k_remain_len<1> : k_remain_len<0>), dim3(items / BLK + 1), dim3(BLK), 0, st, Sm[m], ct, first, items, off[m]);
             if (wide) hipLaunchKernelGGL(k_rows_total, dim3(1), dim3(BLK), 0, st, (const uint32_t *)off[m], items, (unsigned long long *)R.total + m);
             if ((rc = scan32_on(ctx, st, off[m], (uint64_t)items + 1, off[m], R.tmp, 0u, 0))) return rc;
         }
@@ -4791,11 +4890,13 @@ int cm_format_remain(cm_ctx *ctx, const cm_chr_info *chrs, uint32_t n_chr, uint6
     {
         Timer t(ctx, PC_ROWS, st);
         for (int m = 0; m < 2; ++m)
-            hipLaunchKernelGGL((m ? k_remain_rows<1> : k_remain_rows<0>), dim3(spans), dim3(cmrt::WAVE), 0, st, S, ct, first, items, (const uint32_t *)off[m], d_out[m], path[m]);
+            hipLaunchKernelGGL((m ? k_remain_rows<1> : k_remain_rows<0>), dim3(spans), dim3(cmrt::WAVE), 0, st, Sm[m], ct, first, items, (const uint32_t *)off[m], d_out[m], path[m]);
     }
     HIPCHK(ctx, hipGetLastError());
     for (int m = 0; m < 2; ++m) HIPCHK(ctx, hipMemcpyAsync(h_out[m], d_out[m], (size_t)total[m], hipMemcpyDeviceToHost, st));
     if (out_keys) HIPCHK(ctx, hipMemcpyAsync(out_keys, R.keys, (size_t)items * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    for (int m = 0; m < 2; ++m)
+        if (out_off && out_off[m]) HIPCHK(ctx, hipMemcpyAsync(out_off[m], off[m], ((size_t)items + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     if (stats) {
         R.h_path.resize(2 * (size_t)spans);
         for (int m = 0; m < 2; ++m) HIPCHK(ctx, hipMemcpyAsync(R.h_path.data() + (size_t)m * spans, path[m], spans, hipMemcpyDeviceToHost, st));
@@ -4807,6 +4908,18 @@ int cm_format_remain(cm_ctx *ctx, const cm_chr_info *chrs, uint32_t n_chr, uint6
         for (size_t i = 0; i < 2 * (size_t)spans; ++i) ++stats[R.h_path[i] ? 2 : 3];
     }
     return CM_OK;
+}
+
+int cm_format_remain(cm_ctx *ctx, const cm_chr_info *chrs, uint32_t n_chr, uint64_t first, uint64_t count, void *out1, uint64_t cap1, void *out2, uint64_t cap2,
+                     uint64_t out_bytes[2], int64_t *out_keys, uint64_t *n_records, uint64_t stats[4]) {
+    return format_remain(ctx, "cm_format_remain", false, chrs, n_chr, first, count, out1, cap1, out2, cap2, out_bytes, out_keys, nullptr, n_records, stats);
+}
+// ... in the order of cm_sort_remain: records [first, first + count) of either file's own order of the active set (sort_remain
+// above: one more wait, for the tie groups' counters).  The sort is redone by every call.
+int cm_format_remain_sorted(cm_ctx *ctx, const cm_chr_info *chrs, uint32_t n_chr, uint64_t first, uint64_t count, void *out1, uint64_t cap1, void *out2, uint64_t cap2,
+                            uint64_t out_bytes[2], int64_t *out_keys, uint32_t *out_off1, uint32_t *out_off2, uint64_t *n_records, uint64_t stats[4]) {
+    uint32_t *const out_off[2] = {out_off1, out_off2};
+    return format_remain(ctx, "cm_format_remain_sorted", true, chrs, n_chr, first, count, out1, cap1, out2, cap2, out_bytes, out_keys, out_off, n_records, stats);
 }
 
 // test hook: the qualities cm_reads_stage_text kept with the resident batch (flag bit 3), copied back: off1[n] / off2[n] bytes

@@ -18,6 +18,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <new>
 #include <string>
 #include <vector>
 
@@ -200,18 +201,10 @@ struct RemainFile {
     std::vector<size_t> start;      // start[r] = offset of record r; start[n] = end of the last record's bytes (incl. its newline if present)
     std::vector<uint8_t> lines;     // lines actually present in record r (4, except an incomplete last group)
 };
-// byte of the pasted form of record r at position k (line ends become TABs; a missing trailing line contributes its TAB, no bytes)
-inline int pasted_cmp(const RemainFile &F, uint32_t a, uint32_t b) {
-    auto len_of = [&](uint32_t r) {
-        size_t e = F.start[r + 1];
-        size_t n = e - F.start[r];
-        if (n && F.buf[e - 1] == '\n') --n;            // the 4th line's newline is not part of the pasted line
-        return n + (size_t)(4 - F.lines[r]);            // paste pads an incomplete group with empty fields: one TAB each
-    };
-    const size_t la = len_of(a), lb = len_of(b);
+// Two pasted lines compared as GNU sort's last resort does: pa[0 .. ra) / pb[0 .. rb) are the bytes present, la / lb the lengths of
+// the pasted lines (line ends become TABs; a missing trailing line contributes its TAB, no bytes)
+inline int pasted_cmp_bytes(const char *pa, size_t ra, size_t la, const char *pb, size_t rb, size_t lb) {
     const size_t m = la < lb ? la : lb;
-    const char *pa = F.buf.data() + F.start[a], *pb = F.buf.data() + F.start[b];
-    const size_t ra = F.start[a + 1] - F.start[a], rb = F.start[b + 1] - F.start[b];
     for (size_t k = 0; k < m; ++k) {
         unsigned char ca = k < ra ? (unsigned char)pa[k] : (unsigned char)'\t', cb = k < rb ? (unsigned char)pb[k] : (unsigned char)'\t';
         if (ca == '\n') ca = '\t';
@@ -220,21 +213,18 @@ inline int pasted_cmp(const RemainFile &F, uint32_t a, uint32_t b) {
     }
     return la < lb ? -1 : (la > lb ? 1 : 0);
 }
-}  // namespace
-
-extern "C" int cm_sort_remain(const char *in_path, const char *out_path) {
-    if (!in_path || !out_path) return CM_EINVAL;
-    FILE *in = fopen(in_path, "rb");
-    if (!in) return CM_EINVAL;
-    RemainFile F;
-    {
-        if (fseek(in, 0, SEEK_END) != 0) { fclose(in); return CM_EIO; }
-        const long sz = ftell(in);
-        if (sz < 0 || fseek(in, 0, SEEK_SET) != 0) { fclose(in); return CM_EIO; }
-        F.buf.resize((size_t)sz);
-        if (sz && fread(F.buf.data(), 1, (size_t)sz, in) != (size_t)sz) { fclose(in); return CM_EIO; }
-        fclose(in);
-    }
+inline int pasted_cmp(const RemainFile &F, uint32_t a, uint32_t b) {
+    auto len_of = [&](uint32_t r) {
+        size_t e = F.start[r + 1];
+        size_t n = e - F.start[r];
+        if (n && F.buf[e - 1] == '\n') --n;            // the 4th line's newline is not part of the pasted line
+        return n + (size_t)(4 - F.lines[r]);            // paste pads an incomplete group with empty fields: one TAB each
+    };
+    return pasted_cmp_bytes(F.buf.data() + F.start[a], F.start[a + 1] - F.start[a], len_of(a), F.buf.data() + F.start[b], F.start[b + 1] - F.start[b], len_of(b));
+}
+// The in-memory part of cm_sort_remain: the records of F.buf located and keyed, recs in the sorted order.  Shared by the file
+// version below and by the runs' fall-back (cm_remain_runs_add_unsorted).
+int order_records(RemainFile &F, std::vector<SortRec> &recs) {
     const size_t n_bytes = F.buf.size();
     {   // record boundaries: every fourth line end
         size_t pos = 0;
@@ -256,7 +246,7 @@ extern "C" int cm_sort_remain(const char *in_path, const char *out_path) {
     }
     const size_t n_rec = F.lines.size();
     if (n_rec > 0xfffffff0ull) return CM_ELIMIT;
-    std::vector<SortRec> recs(n_rec);
+    recs.assign(n_rec, SortRec{0, 0, 0, 0});
     auto blank = [](char c) { return c == ' ' || c == '\t'; };
     for (size_t r = 0; r < n_rec; ++r) {               // key_of() on the first line (the pasted line's field 2 lies inside it unless it has one field:
         const char *p = F.buf.data() + F.start[r];     // then field 2 begins at the TAB that replaces the line end, i.e. with the second line)
@@ -302,6 +292,26 @@ extern "C" int cm_sort_remain(const char *in_path, const char *out_path) {
             return pasted_cmp(F, a.idx, b.idx) < 0;                    // GNU sort's last resort: the whole line, C locale
         });
     }
+    return CM_OK;
+}
+}  // namespace
+
+extern "C" int cm_sort_remain(const char *in_path, const char *out_path) {
+    if (!in_path || !out_path) return CM_EINVAL;
+    FILE *in = fopen(in_path, "rb");
+    if (!in) return CM_EINVAL;
+    RemainFile F;
+    {
+        if (fseek(in, 0, SEEK_END) != 0) { fclose(in); return CM_EIO; }
+        const long sz = ftell(in);
+        if (sz < 0 || fseek(in, 0, SEEK_SET) != 0) { fclose(in); return CM_EIO; }
+        F.buf.resize((size_t)sz);
+        if (sz && fread(F.buf.data(), 1, (size_t)sz, in) != (size_t)sz) { fclose(in); return CM_EIO; }
+        fclose(in);
+    }
+    std::vector<SortRec> recs;
+    const int rc = order_records(F, recs);
+    if (rc != CM_OK) return rc;
     FILE *out = fopen(out_path, "wb");
     if (!out) return CM_EINVAL;
     std::vector<char> ob;
@@ -325,6 +335,170 @@ extern "C" int cm_sort_remain(const char *in_path, const char *out_path) {
     if (fclose(out) != 0 || bad) return CM_EIO;
     return CM_OK;
 }
+
+// ---- the same order from sorted runs (cm_remain_runs, see circminer_hot.h) ----------------------------------------------------
+// A run of one mate file: records of four lines each, in cm_sort_remain's order, with the signed key of each.  The merge orders by
+// key, then by the pasted line (pasted_cmp_bytes: the comparator of cm_sort_remain), then by run number; records are gathered into
+// the output as they are.
+namespace {
+struct Run {
+    std::vector<char> bytes;
+    std::vector<uint64_t> off;        // records + 1
+    std::vector<int64_t> key;
+};
+// key_of() on a record's first line as a signed 64-bit value (saturating; what a key printed from 64 bits parses back to)
+int64_t parsed_key(const char *p, size_t n) {
+    auto blank = [](char c) { return c == ' ' || c == '\t' || c == '\n'; };       // (the line end is paste's TAB)
+    size_t i = 0;
+    while (i < n && blank(p[i])) ++i;
+    while (i < n && !blank(p[i])) ++i;
+    while (i < n && blank(p[i])) ++i;
+    bool neg = false;
+    if (i < n && p[i] == '-') neg = true, ++i;
+    uint64_t v = 0;
+    bool sat = false;
+    for (; i < n && p[i] >= '0' && p[i] <= '9'; ++i) {
+        const uint64_t d = (uint64_t)(p[i] - '0');
+        if (v > (0x8000000000000000ull - d) / 10) sat = true;
+        else v = v * 10 + d;
+    }
+    if (sat) v = 0x8000000000000000ull;
+    if (neg) return v >= 0x8000000000000000ull ? INT64_MIN : -(int64_t)v;
+    return v >= 0x7fffffffffffffffull ? INT64_MAX : (int64_t)v;
+}
+}  // namespace
+struct cm_remain_runs {
+    std::string path[2];
+    std::vector<Run> runs[2];
+};
+
+extern "C" int cm_remain_runs_open(const char *srt_path1, const char *srt_path2, cm_remain_runs **out) {
+    if (!srt_path1 || !srt_path2 || !out) return CM_EINVAL;
+    *out = nullptr;
+    try {
+        cm_remain_runs *r = new cm_remain_runs;
+        *out = r;
+        r->path[0] = srt_path1;
+        r->path[1] = srt_path2;
+    } catch (const std::bad_alloc &) {
+        delete *out;
+        *out = nullptr;
+        return CM_ENOMEM;
+    }
+    return CM_OK;
+}
+extern "C" int cm_remain_runs_add(cm_remain_runs *r, const void *bytes1, const uint32_t *off1, const void *bytes2, const uint32_t *off2, const int64_t *keys,
+                                  uint64_t n_records) {
+    if (!r || (n_records && (!bytes1 || !off1 || !bytes2 || !off2 || !keys))) return CM_EINVAL;
+    const void *bytes[2] = {bytes1, bytes2};
+    const uint32_t *off[2] = {off1, off2};
+    for (int m = 0; m < 2; ++m)
+        for (uint64_t i = 0; i < n_records; ++i)
+            if (off[m][i + 1] <= off[m][i] || ((const char *)bytes[m])[off[m][i + 1] - 1] != '\n') return CM_EINVAL;     // a record ends with its line feed
+    for (uint64_t i = 1; i < n_records; ++i)
+        if (keys[i] < keys[i - 1]) return CM_EINVAL;
+    try {
+    for (int m = 0; m < 2; ++m) {
+        Run run;
+        if (n_records) {
+            run.bytes.assign((const char *)bytes[m] + off[m][0], (const char *)bytes[m] + off[m][n_records]);
+            run.off.resize(n_records + 1);
+            for (uint64_t i = 0; i <= n_records; ++i) run.off[i] = off[m][i] - off[m][0];
+            run.key.assign(keys, keys + n_records);
+        } else run.off.assign(1, 0);
+        r->runs[m].push_back(std::move(run));
+    }
+    } catch (const std::bad_alloc &) {          // (a run added to file 1 only is dropped again: the two files keep the same runs)
+        if (r->runs[0].size() > r->runs[1].size()) r->runs[0].pop_back();
+        return CM_ENOMEM;
+    }
+    return CM_OK;
+}
+extern "C" int cm_remain_runs_add_unsorted(cm_remain_runs *r, const void *bytes1, uint64_t n1, const void *bytes2, uint64_t n2) {
+    if (!r || (n1 && !bytes1) || (n2 && !bytes2)) return CM_EINVAL;
+    const void *bytes[2] = {bytes1, bytes2};
+    const uint64_t n[2] = {n1, n2};
+    try {
+    Run made[2];
+    for (int m = 0; m < 2; ++m) {
+        RemainFile F;
+        F.buf.assign((const char *)bytes[m], (const char *)bytes[m] + n[m]);
+        std::vector<SortRec> recs;
+        const int rc = order_records(F, recs);
+        if (rc != CM_OK) return rc;
+        Run &run = made[m];
+        run.bytes.reserve(F.buf.size() + 4);
+        run.off.push_back(0);
+        for (const SortRec &k : recs) {
+            const char *p = F.buf.data() + F.start[k.idx];
+            size_t len = F.start[k.idx + 1] - F.start[k.idx];
+            if (len && p[len - 1] == '\n') --len;
+            run.key.push_back(parsed_key(p, len));
+            run.bytes.insert(run.bytes.end(), p, p + len);
+            for (int x = F.lines[k.idx]; x < 4; ++x) run.bytes.push_back('\n');      // (as cm_sort_remain writes an incomplete group)
+            run.bytes.push_back('\n');
+            run.off.push_back(run.bytes.size());
+        }
+    }
+    r->runs[0].reserve(r->runs[0].size() + 1);
+    r->runs[1].reserve(r->runs[1].size() + 1);
+    for (int m = 0; m < 2; ++m) r->runs[m].push_back(std::move(made[m]));
+    } catch (const std::bad_alloc &) {
+        return CM_ENOMEM;
+    }
+    return CM_OK;
+}
+extern "C" int cm_remain_runs_finish(cm_remain_runs *r) {
+    if (!r) return CM_EINVAL;
+    struct Head {
+        uint32_t run;
+        uint64_t rec;
+    };
+    try {
+    for (int m = 0; m < 2; ++m) {
+        const std::vector<Run> &runs = r->runs[m];
+        // a > b: a comes out later (std::*_heap keep the largest on top, so the comparator is the order reversed)
+        auto later = [&](const Head &a, const Head &b) {
+            const Run &A = runs[a.run], &B = runs[b.run];
+            if (A.key[a.rec] != B.key[b.rec]) return A.key[a.rec] > B.key[b.rec];
+            const size_t la = (size_t)(A.off[a.rec + 1] - A.off[a.rec]) - 1, lb = (size_t)(B.off[b.rec + 1] - B.off[b.rec]) - 1;
+            const int c = pasted_cmp_bytes(A.bytes.data() + A.off[a.rec], la, la, B.bytes.data() + B.off[b.rec], lb, lb);
+            if (c) return c > 0;
+            return a.run > b.run;
+        };
+        std::vector<Head> heap;
+        for (uint32_t k = 0; k < runs.size(); ++k)
+            if (!runs[k].key.empty()) heap.push_back(Head{k, 0});
+        std::make_heap(heap.begin(), heap.end(), later);
+        FILE *out = fopen(r->path[m].c_str(), "wb");
+        if (!out) return CM_EIO;
+        std::vector<char> ob;
+        ob.reserve(8u << 20);
+        bool bad = false;
+        auto flush = [&]() {
+            if (!ob.empty() && fwrite(ob.data(), 1, ob.size(), out) != ob.size()) bad = true;
+            ob.clear();
+        };
+        while (!heap.empty()) {
+            std::pop_heap(heap.begin(), heap.end(), later);
+            Head h = heap.back();
+            const Run &R = runs[h.run];
+            ob.insert(ob.end(), R.bytes.data() + R.off[h.rec], R.bytes.data() + R.off[h.rec + 1]);
+            if (ob.size() > (8u << 20) - 4096) flush();
+            if (++h.rec < R.key.size()) {
+                heap.back() = h;
+                std::push_heap(heap.begin(), heap.end(), later);
+            } else heap.pop_back();
+        }
+        flush();
+        if (fclose(out) != 0 || bad) return CM_EIO;
+    }
+    } catch (const std::bad_alloc &) {
+        return CM_ENOMEM;
+    }
+    return CM_OK;
+}
+extern "C" void cm_remain_runs_close(cm_remain_runs *r) { delete r; }
 
 extern "C" int cm_circ_report(const cm_circ_res *res, uint64_t n, const char *report_path) {
     if (!report_path || (n && !res)) return CM_EINVAL;

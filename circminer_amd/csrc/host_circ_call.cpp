@@ -1083,8 +1083,17 @@ extern "C" int cm_circ_run(const cm_circ_args *a, cm_circ_stats *stats, char *er
     const std::string s1 = std::string(r1) + ".srt", s2 = std::string(r2) + ".srt";
     // three things that do not depend on one another run side by side: the two sorts, the genome out of the index file, the GTF
     int rc_s1 = CM_OK, rc_s2 = CM_OK;
-    std::thread t_s1([&]() { rc_s1 = cm_sort_remain(r1, s1.c_str()); });
-    std::thread t_s2([&]() { rc_s2 = cm_sort_remain(r2, s2.c_str()); });
+    // CM_CIRC_PRESORTED=1: the .srt files are there already (cm_mapping_run with CM_REMAIN_SORTED=1) and are taken as they are
+    const char *pre_env = getenv("CM_CIRC_PRESORTED");
+    const bool presorted = pre_env && atoi(pre_env) != 0;
+    if (presorted)
+        for (const std::string *s : {&s1, &s2}) {
+            FILE *f = fopen(s->c_str(), "rb");
+            if (!f) return fail(CM_EIO, "cm_circ_run: CM_CIRC_PRESORTED=1 and %s cannot be opened", s->c_str());
+            fclose(f);
+        }
+    std::thread t_s1([&]() { if (!presorted) rc_s1 = cm_sort_remain(r1, s1.c_str()); });
+    std::thread t_s2([&]() { if (!presorted) rc_s2 = cm_sort_remain(r2, s2.c_str()); });
     struct Join2 {
         std::thread &a, &b;
         ~Join2() {

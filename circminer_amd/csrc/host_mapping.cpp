@@ -110,6 +110,13 @@ struct Run {
     Result res[2];
     RowBuf rows[2];
     RowBuf rem_rows[2][2];                         // CM_REMAIN_DEVICE=1: the remain records of batch k, file 1 and file 2, in set k & 1
+    // CM_REMAIN_SORTED=1 beside it: the same records in cm_sort_remain's order (cm_format_remain_sorted), their offsets and keys; the
+    // batches' sorted runs, merged into the .srt files after the last batch
+    RowBuf srt_rows[2];
+    std::vector<uint32_t> srt_off[2];
+    std::vector<int64_t> srt_keys;
+    cm_remain_runs *srt_runs = nullptr;
+    uint64_t srt_batches = 0, srt_host_batches = 0, srt_records = 0;
     // parser arrays and text blocks registered with the runtime.  The parser tells us (release hook, on its own thread) before one of
     // them is freed -- a generation's array that has to grow is allocated anew -- so that no registration outlives its block.
     PinnedRanges pins;
@@ -118,7 +125,7 @@ struct Run {
     std::vector<uint32_t> clen_guess;
     int early_rc = CM_EINVAL, writer_rc = CM_OK, parser_rc = CM_OK;
     double write_s = 0.0, parse_s = 0.0;           // read after the join
-    bool text_path = false, pam_device = false, sam_device = false, remain_device = false, want_fixed = false;
+    bool text_path = false, pam_device = false, sam_device = false, remain_device = false, remain_sorted = false, want_fixed = false;
     TextBlock tq[4];
     cm_fastq_batch cur{}, nxt{}, nn{};
     Run(const cm_mapping_args *args, char *e, uint64_t cap) : a(args), err(e), err_cap((size_t)cap) {
@@ -141,8 +148,9 @@ struct Run {
         if (writer.joinable()) writer.join();
         if (w_map) cm_writer_close(w_map);
         if (w_rem) cm_writer_close(w_rem);
-        for (RowBuf *rb : {&rows[0], &rows[1], &rem_rows[0][0], &rem_rows[0][1], &rem_rows[1][0], &rem_rows[1][1]})
+        for (RowBuf *rb : {&rows[0], &rows[1], &rem_rows[0][0], &rem_rows[0][1], &rem_rows[1][0], &rem_rows[1][1], &srt_rows[0], &srt_rows[1]})
             if (rb->p) (void)cm_host_free(cm, rb->p);
+        if (srt_runs) cm_remain_runs_close(srt_runs);
         if (cm) (void)cm_sync(cm);
         pins.clear();
         if (pins.failed)
@@ -347,6 +355,9 @@ struct Run {
             }
         }
         if (!text_path) return CM_OK;
+        // the sorted runs beside the remain files: one process only (the ranks' part files are not merged into one order)
+        const char *eo = getenv("CM_REMAIN_SORTED");
+        remain_sorted = remain_device && world <= 1 && eo && atoi(eo) == 1;
         const int rc = read_block(tq[0], want);
         if (rc != CM_OK && rc != CM_EINVAL) return failed(rc, "cm_fastq_next_text");
         if (rc == CM_EINVAL) return text_path = false, CM_OK;    // gzip input or a pipe: the host parser's
@@ -564,10 +575,48 @@ struct Run {
         *n_rec = total;
         return CM_OK;
     }
+    // CM_REMAIN_SORTED=1: the batch's records once more, in cm_sort_remain's order, as a run of srt_runs -- in ranges where a file's
+    // records would not fit 32-bit offsets (consecutive ranges of one order are runs like any other).  A batch the device refuses
+    // for a tie group is ordered here, from the unsorted records RM holds.
+    int sorted_run(RowBuf RM[2], uint64_t n_rec) {
+        int r;
+        ++srt_batches;
+        srt_records += n_rec;
+        if (!n_rec) return CM_OK;
+        for (int m = 0; m < 2; ++m) {
+            srt_rows[m].n = 0;
+            if (srt_rows[m].cap < RM[m].n && (r = grow_rows(srt_rows[m], RM[m].n + (1u << 16))) != CM_OK) return r;
+        }
+        uint64_t done = 0, step = n_rec;
+        while (done < n_rec) {
+            const uint64_t c = std::min(step, n_rec - done);
+            uint64_t got[2] = {0, 0}, total = 0;
+            srt_off[0].resize(c + 1);
+            srt_off[1].resize(c + 1);
+            srt_keys.resize(c);
+            r = cm_format_remain_sorted(cm, chrs, n_chr, done, c, srt_rows[0].p, srt_rows[0].cap, srt_rows[1].p, srt_rows[1].cap, got, srt_keys.data(), srt_off[0].data(),
+                                        srt_off[1].data(), &total, nullptr);
+            if (r == CM_ELIMIT && std::max(got[0], got[1]) >= (1ull << 32) && c > 1) {
+                step = c / 2;
+                continue;
+            }
+            if (r == CM_ELIMIT && got[0] == 0 && got[1] == 0 && done == 0) {          // a tie group above the cap
+                ++srt_host_batches;
+                if ((r = cm_remain_runs_add_unsorted(srt_runs, RM[0].p, RM[0].n, RM[1].p, RM[1].n)) != CM_OK) return failed(r, "cm_remain_runs_add_unsorted");
+                return CM_OK;
+            }
+            if (r != CM_OK) return failed(r, "cm_format_remain_sorted");
+            if ((r = cm_remain_runs_add(srt_runs, srt_rows[0].p, srt_off[0].data(), srt_rows[1].p, srt_off[1].data(), srt_keys.data(), c)) != CM_OK)
+                return failed(r, "cm_remain_runs_add");
+            done += c;
+        }
+        return CM_OK;
+    }
     // ... and the type histogram, which collect_records delivers on the other path
     int remain_records(Result &R, RowBuf RM[2]) {
         int rc;
         if ((rc = format_remain(RM, &R.n_rec)) != CM_OK) return rc;
+        if (remain_sorted && (rc = sorted_run(RM, R.n_rec)) != CM_OK) return rc;
         uint64_t h[14];
         if ((rc = cm_type_histogram(cm, h)) != CM_OK) return failed(rc, "cm_type_histogram");
         for (int t = 0; t < 14; ++t) st.by_type[t] += h[t];
@@ -579,6 +628,10 @@ struct Run {
         const double td0 = now();
         if ((rc = stage_block(tq[0])) != CM_OK) return failed(rc, "cm_reads_stage_text");
         st.seconds_device += now() - td0;
+        if (remain_sorted) {
+            const std::string base = std::string(a->out_prefix) + "_" + std::to_string(n_con) + "_remain_R";
+            if ((rc = cm_remain_runs_open((base + "1.fastq.srt").c_str(), (base + "2.fastq.srt").c_str(), &srt_runs)) != CM_OK) return failed(rc, "cm_remain_runs_open");
+        }
         if (tq[0].tb.n_pairs) {
             if ((rc = cm_reads_swap(cm)) != CM_OK) return failed(rc, "cm_reads_swap");
             const double tp = now();
@@ -619,6 +672,13 @@ struct Run {
         if ((rc = hand_to_writer(nullptr)) != CM_OK) return rc;
         if (w_map && (rc = cm_writer_flush(w_map)) != CM_OK) return failed(rc, "writing the mapping file");
         if ((rc = cm_writer_flush(w_rem)) != CM_OK) return failed(rc, "writing the remain files");
+        if (srt_runs) {
+            const double tm = now();
+            if ((rc = cm_remain_runs_finish(srt_runs)) != CM_OK) return failed(rc, "cm_remain_runs_finish (the .srt files)");
+            if (getenv("CM_REMAIN_TRACE"))
+                fprintf(stderr, "[remain] sorted runs: %llu batches, %llu sorted on the host, %llu records, merge %.3f s\n", (unsigned long long)srt_batches,
+                        (unsigned long long)srt_host_batches, (unsigned long long)srt_records, now() - tm);
+        }
         st.seconds_map = now() - t1;
         st.seconds_write = write_s;
         if (stats) *stats = st;

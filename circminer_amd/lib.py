@@ -223,6 +223,8 @@ SIGNATURES = {
     "cm_format_sam": (C.c_int, [vp, pp(ChrInfo), C.c_uint32, C.c_uint64, C.c_uint64, vp, C.c_uint64, pp(C.c_uint64), pp(C.c_uint64)]),
     "cm_format_remain": (C.c_int, [vp, pp(ChrInfo), C.c_uint32, C.c_uint64, C.c_uint64, vp, C.c_uint64, vp, C.c_uint64, pp(C.c_uint64), vp, pp(C.c_uint64),
                                    pp(C.c_uint64)]),
+    "cm_format_remain_sorted": (C.c_int, [vp, pp(ChrInfo), C.c_uint32, C.c_uint64, C.c_uint64, vp, C.c_uint64, vp, C.c_uint64, pp(C.c_uint64), vp, vp, vp,
+                                          pp(C.c_uint64), pp(C.c_uint64)]),
     "cm_quals_peek": (C.c_int, [vp, vp, C.c_uint64, vp, C.c_uint64]),
     "cm_state_poke": (C.c_int, [vp, vp]),
     "cm_debug_lane_clk": (C.c_int, [vp, vp]),
@@ -278,6 +280,11 @@ SIGNATURES = {
     "cm_write_pam": (C.c_int, [vp, pp(FastqBatch), vp, vp, C.c_uint64]),
     "cm_host_gene_overlap": (C.c_int, [pp(AnnotView), C.c_uint32, pp(u32p), pp(C.c_uint32)]),
     "cm_sort_remain": (C.c_int, [C.c_char_p, C.c_char_p]),
+    "cm_remain_runs_open": (C.c_int, [C.c_char_p, C.c_char_p, pp(vp)]),
+    "cm_remain_runs_add": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_uint64]),
+    "cm_remain_runs_add_unsorted": (C.c_int, [vp, vp, C.c_uint64, vp, C.c_uint64]),
+    "cm_remain_runs_finish": (C.c_int, [vp]),
+    "cm_remain_runs_close": (None, [vp]),
     "cm_regional_table_build": (C.c_int, [vp, C.c_uint32, C.c_int32, C.c_int32, pp(u32p), pp(u32p)]),
     "cm_regional_table_free": (None, [u32p, u32p]),
     "cm_circ_report": (C.c_int, [pp(CircRes), C.c_uint64, C.c_char_p]),
@@ -507,6 +514,38 @@ class ParsedBatch:
     def qual(self, i: int, mate: int = 1) -> bytes:
         q, o = (self.fb.qual1, self.c.off1) if mate == 1 else (self.fb.qual2, self.c.off2)
         return bytes(np.ctypeslib.as_array(q, (int(o[self.n]),))[int(o[i]):int(o[i + 1])])
+
+
+class RemainRuns:
+    """cm_remain_runs: sorted runs of remain records, merged into the two .srt files by finish()"""
+
+    def __init__(self, srt1: str, srt2: str):
+        self.L, self.h = load(), C.c_void_p()
+        rc = self.L.cm_remain_runs_open(srt1.encode(), srt2.encode(), C.byref(self.h))
+        if rc != 0:
+            raise RuntimeError(f"cm_remain_runs_open failed ({rc})")
+
+    def add(self, bytes1: bytes, off1, bytes2: bytes, off2, keys):
+        """a run in cm_sort_remain's order: the records of either file, their offsets (records + 1) and their keys"""
+        o1, o2, kk = np.ascontiguousarray(off1, np.uint32), np.ascontiguousarray(off2, np.uint32), np.ascontiguousarray(keys, np.int64)
+        assert len(o1) == len(o2) == len(kk) + 1
+        rc = self.L.cm_remain_runs_add(self.h, bytes1, o1.ctypes.data, bytes2, o2.ctypes.data, kk.ctypes.data if len(kk) else None, len(kk))
+        if rc != 0:
+            raise RuntimeError(f"cm_remain_runs_add failed ({rc})")
+
+    def add_unsorted(self, bytes1: bytes, bytes2: bytes):
+        """a run made here from records in any order (the fall-back for a batch the device refuses)"""
+        rc = self.L.cm_remain_runs_add_unsorted(self.h, bytes1, len(bytes1), bytes2, len(bytes2))
+        if rc != 0:
+            raise RuntimeError(f"cm_remain_runs_add_unsorted failed ({rc})")
+
+    def finish(self) -> int:
+        return self.L.cm_remain_runs_finish(self.h)
+
+    def close(self):
+        if self.h:
+            self.L.cm_remain_runs_close(self.h)
+            self.h = C.c_void_p()
 
 
 def sort_remain(path: str, out: str = None) -> str:
@@ -823,6 +862,35 @@ class HotPath:
         assert all(got[m] <= caps[m] and bool((bufs[m][int(caps[m]):] == 0xA5).all()) for m in (0, 1))
         assert kk is None or kk[-1] == -0x5A5A5A5A5A5A5A5A
         return bufs[0][:got[0]].tobytes(), bufs[1][:got[1]].tobytes(), (kk[:-1] if keys else None), int(n_rec.value), list(stats)
+
+    def format_remain_sorted(self, chrs=(), first=0, count=None, caps=None):
+        """cm_format_remain_sorted: format_remain with the records in cm_sort_remain's order (by key, ties per file by the pasted
+        line).  Returns (bytes of file 1, bytes of file 2, keys, (offsets of file 1, offsets of file 2), size of the active set,
+        stats); a refusal (a tie group above the cap among them) raises with the library's message."""
+        table = chr_array(list(chrs))
+        cnt = (1 << 64) - 1 if count is None else int(count)
+        got, n_rec, stats = (C.c_uint64 * 2)(), C.c_uint64(0), (C.c_uint64 * 4)()
+
+        def call(b1, c1, b2, c2, kp, o1, o2, sp):
+            return self.L.cm_format_remain_sorted(self.h, table, len(chrs), int(first), cnt, b1, c1, b2, c2, got, kp, o1, o2, C.byref(n_rec), sp)
+        if caps is None:
+            rc = call(None, 0, None, 0, None, None, None, None)
+            if rc not in (0, -6) or (rc == -6 and (max(got) >= 1 << 32 or max(got) == 0)):   # CM_ELIMIT with the needed sizes is the answer here
+                self._chk(rc, "cm_format_remain_sorted")
+            caps = (got[0], got[1])
+        elif count is None:                                                     # (the size of the set, for the arrays)
+            self._chk(self.L.cm_format_remain(self.h, table, len(chrs), 0, 0, None, 0, None, 0, got, None, C.byref(n_rec), None), "cm_format_remain")
+        n = max(int(n_rec.value) - int(first), 0) if count is None else int(count)
+        bufs = [np.full(int(c) + 64, 0xA5, np.uint8) for c in caps]             # (the bytes behind a cap show a write past it)
+        kk = np.full(n + 1, -0x5A5A5A5A5A5A5A5A, np.int64)
+        oo = [np.full(n + 2, 0xA5A5A5A5, np.uint32) for _ in (0, 1)]
+        self._chk(call(bufs[0].ctypes.data, int(caps[0]), bufs[1].ctypes.data, int(caps[1]), kk.ctypes.data, oo[0].ctypes.data, oo[1].ctypes.data, stats),
+                  "cm_format_remain_sorted")
+        assert all(got[m] <= caps[m] and bool((bufs[m][int(caps[m]):] == 0xA5).all()) for m in (0, 1))
+        assert kk[-1] == -0x5A5A5A5A5A5A5A5A and all(o[-1] == 0xA5A5A5A5 for o in oo)
+        if n == 0:
+            oo = [np.zeros(2, np.uint32) for _ in (0, 1)]                       # (count == 0 writes nothing: no offsets either)
+        return bufs[0][:got[0]].tobytes(), bufs[1][:got[1]].tobytes(), kk[:-1], (oo[0][:-1], oo[1][:-1]), int(n_rec.value), list(stats)
 
     def peek_quals(self):
         """cm_quals_peek (test hook): (qual1, qual2) of the resident batch as cm_reads_stage_text kept them (keep_quals), in the

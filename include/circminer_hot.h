@@ -659,6 +659,24 @@ int cm_format_sam(cm_ctx *ctx, const cm_chr_info *chrs, uint32_t n_chr, uint64_t
 int cm_format_remain(cm_ctx *ctx, const cm_chr_info *chrs, uint32_t n_chr, uint64_t first, uint64_t count,
                      void *out1, uint64_t cap1, void *out2, uint64_t cap2, uint64_t out_bytes[2], int64_t *out_keys,
                      uint64_t *n_records, uint64_t stats[4] /* out_keys, n_records, stats: nullable */);
+/* cm_format_remain with the records in the order cm_sort_remain gives the files it writes: records [first, first + count) of the
+ * active set ordered by key (out_keys' value, ascending, signed) and, among equal keys, per file by the bytes of the record as
+ * `paste - - - -` joins it (the first three line feeds read as TAB, the last left out; unsigned bytes, a proper prefix first;
+ * identical lines in the order of the active set).  Inside a group of equal keys file 1 and file 2 may therefore hold the pairs in
+ * different orders, as two separately sorted files do; a range that cuts such a group holds each file's own members of it.  The
+ * key's VALUE orders, where cm_sort_remain parses the text's second field: for a name that holds a TAB the two differ (see
+ * out_keys above), and such names are outside this call's promise.
+ * Everything else is cm_format_remain's contract -- arguments, refusals, count == ~0ull, n_records, the stream, "a refusal leaves
+ * the resident batch as it was" -- with these additions: out_keys is non-decreasing and serves both files; out_off1 / out_off2
+ * (nullable, count + 1 words each) receive the byte offset of every record in out1 / out2 and the files' sizes in their last word;
+ * CM_ELIMIT with nothing written and out_bytes == {0, 0} when more than 4096 records share a key (the ranking inside a group is
+ * quadratic; cm_last_error names the group's size and the cap; CM_REMAIN_TIE_CAP=<n> in the environment, a test knob read by every
+ * call, lowers the cap): the caller orders such a batch on the host.  The set is sorted again by every call, so a caller that
+ * formats in ranges (32-bit offsets) pays the sort per range.  ms[7] of cm_prof_get covers the sort's kernels too. */
+int cm_format_remain_sorted(cm_ctx *ctx, const cm_chr_info *chrs, uint32_t n_chr, uint64_t first, uint64_t count,
+                            void *out1, uint64_t cap1, void *out2, uint64_t cap2, uint64_t out_bytes[2], int64_t *out_keys,
+                            uint32_t *out_off1, uint32_t *out_off2, uint64_t *n_records,
+                            uint64_t stats[4] /* out_keys, out_off1, out_off2, n_records, stats: nullable */);
 /* Appends n raw bytes to the writer's first file through its buffer (the rows cm_format_pam / cm_format_sam deliver, the first
  * file's records of cm_format_remain); CM_EIO like the other cm_write_* calls. */
 int cm_write_bytes(cm_writer *w, const void *p, uint64_t n);
@@ -702,7 +720,14 @@ void cm_writer_close(cm_writer *w);
  * batch's last round cm_format_remain puts the records of the pairs still active into two of four page-locked buffers (two sets of
  * two) and the writer thread appends them with cm_write_bytes / cm_write_bytes2 in place of cm_write_remain_text -- the same remain
  * files byte for byte (names with a NUL byte excepted, see cm_format_remain), the same statistics, for one process and for rank /
- * world part files.  Where the host parser's path is taken the variable has no effect. */
+ * world part files.  Where the host parser's path is taken the variable has no effect.
+ * With CM_REMAIN_SORTED=1 beside CM_FASTQ_DEVICE=1 CM_REMAIN_DEVICE=1 and world <= 1 the run also leaves
+ * <out>_<R>_remain_R{1,2}.fastq.srt, the files cm_sort_remain makes of the remain files (which are written exactly as without the
+ * variable): every batch's active set goes through cm_format_remain_sorted into page-locked buffers and into a cm_remain_runs, a
+ * batch the device refuses for a tie group is ordered on the host from its unsorted records (cm_remain_runs_add_unsorted), and
+ * cm_remain_runs_finish writes both files after the last batch.  CM_REMAIN_TRACE=1 prints one line to stderr: batches, batches
+ * ordered on the host, records, seconds of the merge.  With world > 1, or off the device tokeniser's path, the variable has no
+ * effect. */
 typedef struct cm_mapping_args {
     const char *index_path;        /* <ref>.packed.fa.index        */
     const char *index_info_path;   /* <ref>.packed.fa.index.info   */
@@ -740,6 +765,24 @@ int cm_merge_parts(const char *out_prefix, int32_t rounds, int32_t world, int32_
 /* ProcessCirc::sort_fq (src/process_circ.cpp:179-193): the remain FASTQ of the last round ordered like
  * `paste - - - - | sort -k2,2n | tr "\t" "\n"` does in the C locale (key = genome_spos, ties by the whole pasted line). */
 int cm_sort_remain(const char *in_path, const char *out_path);
+/* The same order made from sorted runs: every run is the records of one cm_format_remain_sorted call (or any records in
+ * cm_sort_remain's order with their keys), `finish` merges the runs of file 1 into srt_path1 and, independently, those of file 2
+ * into srt_path2 -- by key, then by the pasted line (cm_sort_remain's comparator), then by run number -- so that the two files
+ * are what cm_sort_remain makes of the concatenated runs.  bytes1 / bytes2: the records of the run, off1 / off2: n_records + 1
+ * byte offsets (the last is the run's size), keys: n_records values serving both files.  `add` copies; n_records == 0 is fine.
+ * The runs stay in host memory until `finish` (the remain records of the whole run: about 5 % of the pairs at about 820 bytes a
+ * pair); spilling them to disk is not built.  CM_EIO: a file cannot be opened or a write came up short.  `close` frees; it does
+ * not write. */
+typedef struct cm_remain_runs cm_remain_runs;
+int cm_remain_runs_open(const char *srt_path1, const char *srt_path2, cm_remain_runs **out);
+int cm_remain_runs_add(cm_remain_runs *r, const void *bytes1, const uint32_t *off1, const void *bytes2, const uint32_t *off2,
+                       const int64_t *keys, uint64_t n_records);
+int cm_remain_runs_finish(cm_remain_runs *r);
+void cm_remain_runs_close(cm_remain_runs *r);
+/* A run made on the host from UNSORTED records (the fall-back for a batch cm_format_remain_sorted refuses): the two files' bytes
+ * as cm_format_remain delivers them are ordered by the in-memory body of cm_sort_remain -- the key parsed from the text -- and
+ * added as one run. */
+int cm_remain_runs_add_unsorted(cm_remain_runs *r, const void *bytes1, uint64_t n1, const void *bytes2, uint64_t n2);
 /* RegionalHashTable::create_table (src/hash_table.cpp:58-78) flattened: the window_size-mers of a gene region, bucket hv =
  * loc[off[hv] .. off[hv+1]) ascending, location = start + offset in seq; buckets above MAXHIT = 1000 are emptied. */
 int cm_regional_table_build(const uint8_t *seq, uint32_t start, int32_t len, int32_t window_size, uint32_t **off, uint32_t **loc);
@@ -771,7 +814,9 @@ int cm_circ_call(const cm_params *p, int32_t window_size, uint32_t n_contigs, co
                  const char *report_path, cm_circ_stats *stats);
 /* circ_detect() of the reference (src/circminer.cpp:347-352) from files to files: sorts <out>_<last_round>_remain_R{1,2}.fastq
  * (-> .srt), loads the packed genome from the index file and the GTF, calls the junctions, writes <out>.candidates.pam and
- * <out>.circ_report.  params.kmer == 0 takes the index file's k.  index_path may be the packed FASTA (stage 2 needs the sequence only). */
+ * <out>.circ_report.  params.kmer == 0 takes the index file's k.  index_path may be the packed FASTA (stage 2 needs the sequence only).
+ * With CM_CIRC_PRESORTED=1 in the environment the two .srt files are taken as they are (cm_mapping_run with CM_REMAIN_SORTED=1
+ * leaves them) and cm_sort_remain is not called; a .srt file that cannot be opened is CM_EIO, and err names it. */
 typedef struct cm_circ_args {
     const char *index_path, *index_info_path, *gtf_path, *out_prefix;
     cm_params params;
