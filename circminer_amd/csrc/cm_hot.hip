@@ -2440,27 +2440,31 @@ struct TextStage {
     BatchBuf<unsigned long long> res;
     BatchBuf<uint32_t> nstart;                   // flag bits 2 and 4 only: where each name starts in its text (R1's, then R2's: one stream)
 };
-// The row formatters' buffers, shared by cm_format_pam and cm_format_sam: the chromosome names last uploaded (host copy: the table
-// is compared, not uploaded, when it is the same), the items' lengths scanned in place into offsets, the scan's block totals, the
-// rows or records, the path every span took
-struct RowsBufs {
-    std::vector<uint32_t> h_chr_off;
-    std::string h_chr_text;
-    bool chr_valid = false;
-    CtxBuf<uint8_t> chr_text;
-    CtxBuf<uint32_t> chr_off;
-    CtxBuf<unsigned long long> total;
-    BatchBuf<uint32_t> off, tmp;
+// A column of the chromosome table on the device with its host mirror: a call compares its table with the mirror and uploads only
+// a column that differs (RowsRun::prepare).
+template <class T>
+struct ChrColumn {
+    std::vector<T> host;
+    bool valid = false;
+    CtxBuf<T> dev;
+    bool holds(const std::vector<T> &now) const { return valid && now == host; }
+};
+// One output file of a row formatter's call: the items' lengths scanned in place into offsets, the rows or records, every span's path.
+struct RowsFileBufs {
+    BatchBuf<uint32_t> off;
     BatchBuf<uint8_t> out, path;
+};
+// The row formatters' buffers, shared by cm_format_pam, cm_format_sam (one file) and cm_format_remain, cm_format_remain_sorted (two:
+// both are sized before either is written).  The chromosome table in columns -- the names' text and offsets, and for the remain
+// records the shifts (cm_chr_info.start_pos) --, the 64-bit totals of the files, the scan's block totals, the files' own buffers.
+struct RowsBufs {
+    ChrColumn<uint8_t> chr_text;
+    ChrColumn<uint32_t> chr_off, chr_shift;
+    CtxBuf<unsigned long long> total;
+    BatchBuf<uint32_t> tmp;
+    RowsFileBufs file[2];
     std::vector<uint8_t> h_path;
-    // cm_format_remain only: the chromosome shifts (cm_chr_info.start_pos) beside the names, uploaded by the same rule; the second
-    // file's offsets, records and paths (both files are sized before either is written); the sort keys
-    std::vector<uint32_t> h_chr_shift;
-    bool shift_valid = false;
-    CtxBuf<uint32_t> chr_shift;
-    BatchBuf<uint32_t> off2;
-    BatchBuf<uint8_t> out2, path2;
-    BatchBuf<int64_t> keys;
+    BatchBuf<int64_t> keys;                      // the remain records' sort keys
     // cm_format_remain_sorted only: the radix keys and pairs before and behind the sort, its workspace, the heads scanned into group
     // numbers, the groups' starts and counters, the selection list of either mate file
     BatchBuf<uint64_t> rkey0, rkey1;
@@ -4606,130 +4610,214 @@ int cm_collect_records_device(cm_ctx *ctx, uint64_t index_base, uint64_t cap, vo
     return collect_records_into(ctx, index_base, cap, (cm_record *)d_out, out_n, "cm_collect_records_device");
 }
 
-// The chromosome names of a row formatter's call: uploaded when they differ from the table on the device.  *chr_max: the longest name.
-static int upload_chr_table(cm_ctx *ctx, RowsBufs &F, const cm_chr_info *chrs, uint32_t n_chr, hipStream_t st, uint32_t *chr_max) {
-    std::vector<uint32_t> o((size_t)n_chr + 1, 0u);
-    std::string text;
-    for (uint32_t c = 0; c < n_chr; ++c) {
-        if (chrs[c].name) text += chrs[c].name;
-        o[c + 1] = (uint32_t)text.size();
-    }
-    if (!F.chr_valid || o != F.h_chr_off || text != F.h_chr_text) {
-        F.chr_valid = false;
-        HIPCHK(ctx, hipStreamSynchronize(st));              // (rows of an earlier call are out, but be sure nothing reads the old table)
-        F.h_chr_off.swap(o);
-        F.h_chr_text.swap(text);
-        HIPCHK(ctx, ensure(ctx, F.chr_text, F.h_chr_text.size() + 4));
-        HIPCHK(ctx, ensure(ctx, F.chr_off, F.h_chr_off.size() * sizeof(uint32_t)));
-        if (!F.h_chr_text.empty()) HIPCHK(ctx, hipMemcpyAsync(F.chr_text, F.h_chr_text.data(), F.h_chr_text.size(), hipMemcpyHostToDevice, st));
-        HIPCHK(ctx, hipMemcpyAsync(F.chr_off, F.h_chr_off.data(), F.h_chr_off.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-        HIPCHK(ctx, hipStreamSynchronize(st));
-        F.chr_valid = true;
-    }
-    *chr_max = 1;
-    for (uint32_t c = 0; c < n_chr; ++c) *chr_max = std::max(*chr_max, F.h_chr_off[c + 1] - F.h_chr_off[c]);
+// "... was not staged with cm_reads_stage_text, flag bit(s) ...": the refusal of a call that needs what the resident batch does not
+// keep, composed from what the call needs; CM_OK where it is all there.
+struct StagedBit { bool has; const char *bit, *noun; };
+static int not_staged(cm_ctx *ctx, const char *fn, std::initializer_list<StagedBit> need) {
+    std::string bits, what;
+    int missing = 0;
+    for (const StagedBit &b : need)
+        if (!b.has) {
+            bits += (missing ? ", " : "") + std::string(b.bit);
+            what += (missing++ ? ", no " : "no ") + std::string(b.noun);
+        }
+    if (!missing) return CM_OK;
+    return fail(ctx, CM_ESTATE, "%s: the resident batch was not staged with cm_reads_stage_text, flag bit%s %s (%s)", fn, missing > 1 ? "s" : "", bits.c_str(), what.c_str());
+}
+
+extern "C++" {
+// One column of a call's chromosome table, queued for upload when it differs from the column on the device (`now` is used up then;
+// `pad` elements more are allocated than it holds).  The waits around the uploads of a call, and `valid` behind them, are prepare()'s.
+template <class T>
+static int upload_chr_column(cm_ctx *ctx, hipStream_t st, ChrColumn<T> &col, std::vector<T> &now, size_t pad) {
+    if (col.holds(now)) return CM_OK;
+    col.valid = false;
+    col.host.swap(now);
+    HIPCHK(ctx, ensure(ctx, col.dev, (col.host.size() + pad) * sizeof(T)));
+    if (!col.host.empty()) HIPCHK(ctx, hipMemcpyAsync(col.dev, col.host.data(), col.host.size() * sizeof(T), hipMemcpyHostToDevice, st));
     return CM_OK;
 }
 
-// What a row formatter's call says of itself: its name and nouns for the messages, the refusal for missing staging bits (null: the
-// batch has what the format needs), what the format reads, the bytes of names and strings all items print at most, and the kernels.
-extern "C++" {
-template <class F>
+// What a row formatter's call says of itself: its name and nouns for the messages, the constants of its format (cm_rows_text.h),
+// and the bytes of names and strings all items of a file print at most.
 struct RowsCall {
-    const char *fn, *limit_unit, *noun, *missing;
-    typename F::Src src;
-    uint64_t strings_max;
-    void (*k_len)(typename F::Src, cmrt::ChrTab, uint64_t, uint32_t, uint32_t *);
-    void (*k_rows)(typename F::Src, cmrt::ChrTab, uint64_t, uint32_t, const uint32_t *, uint8_t *, uint8_t *);
+    const char *fn, *range_unit, *limit_unit, *noun;
+    uint32_t pair_items, span_items, item_fixed_max, item_chrs;
+    uint64_t pair_limit, strings_max;
 };
-// The items (PAM rows, SAM records) of pairs [first, first + count) of the resident batch, formatted on the device (the plan:
-// cm_rows_text.h) on the mapping stream, behind everything queued for the batch.  Two waits: for the items' total (the caller's
-// buffer may be too small, the device buffer is sized by it), then for the bytes.
 template <class F>
-static int format_rows(cm_ctx *ctx, const RowsCall<F> &c, const cm_chr_info *chrs, uint32_t n_chr, uint64_t first, uint64_t count, void *out, uint64_t cap,
-                       uint64_t *out_bytes, uint64_t stats[4]) {
-    if (!out_bytes || (n_chr && !chrs)) return CM_EINVAL;
-    *out_bytes = 0;
+static RowsCall rows_call(const char *fn, const char *range_unit, const char *limit_unit, const char *noun, uint64_t strings_max) {
+    return {fn, range_unit, limit_unit, noun, F::PAIR_ITEMS, F::SPAN_ITEMS, F::ITEM_FIXED_MAX, F::ITEM_CHRS, F::PAIR_LIMIT, strings_max};
+}
+// One output file of a call: its kernels, what they read, the caller's buffer.  File m of a call uses ctx->rows.file[m].
+template <class Src>
+struct RowsFile {
+    void (*k_len)(Src, cmrt::ChrTab, uint64_t, uint32_t, uint32_t *);
+    void (*k_rows)(Src, cmrt::ChrTab, uint64_t, uint32_t, const uint32_t *, uint8_t *, uint8_t *);
+    Src src;
+    void *out;
+    uint64_t cap;
+};
+// What all four entry points check first: the arguments nothing can be said without, the outputs zeroed, a resident batch.
+static int rows_enter(cm_ctx *ctx, const char *fn, const cm_chr_info *chrs, uint32_t n_chr, uint64_t *out_bytes, int n_files, uint64_t *n_records, uint64_t stats[4]) {
+    if (!ctx || !out_bytes || (n_chr && !chrs)) return CM_EINVAL;
+    for (int m = 0; m < n_files; ++m) out_bytes[m] = 0;
+    if (n_records) *n_records = 0;
     if (stats) stats[0] = stats[1] = stats[2] = stats[3] = 0;
     HIPCHK(ctx, hipSetDevice(ctx->P.device));
-    if (ctx->n_pairs == 0) return fail(ctx, CM_ESTATE, "%s: no resident batch", c.fn);
-    if (c.missing) return fail(ctx, CM_ESTATE, "%s: the resident batch was not staged with cm_reads_stage_text, flag %s", c.fn, c.missing);
-    if (first > ctx->n_pairs || count > ctx->n_pairs - first)
-        return fail(ctx, CM_EINVAL, "%s: pairs [%llu, +%llu) of %llu", c.fn, (unsigned long long)first, (unsigned long long)count, (unsigned long long)ctx->n_pairs);
-    if (!out && cap) return fail(ctx, CM_EINVAL, "%s: null out", c.fn);
-    if (count == 0) return CM_OK;
-    if (count >= F::PAIR_LIMIT) return fail(ctx, CM_ELIMIT, "%s: %llu %s in one call", c.fn, (unsigned long long)count, c.limit_unit);
+    if (ctx->n_pairs == 0) return fail(ctx, CM_ESTATE, "%s: no resident batch", fn);
+    return CM_OK;
+}
+// The items (PAM rows, SAM records, the remain records of either mate file) of a call, formatted on the device (the plan:
+// cm_rows_text.h) for the files of the call -- one or two -- on the mapping stream, behind everything queued for the batch.  The
+// steps, in the order a caller takes them: check, prepare, lengths, spans_out, finish.  Every file's length pass runs before any
+// file's span pass: lengths() leaves every file's total in out_bytes before it refuses a file for its size, and a call that refuses
+// either file writes neither.  Two waits: in lengths() for the totals (they size the device buffers, and a caller's may be too small), in finish() for the bytes
+// (format_remain has one in front, for the active set's size, sort_remain one for the tie groups); between spans_out() and finish() a caller may queue copies of its own.
+template <class Src>
+struct RowsRun {
+    cm_ctx *ctx;
+    const RowsCall &c;
+    RowsFile<Src> *file;
+    int n_files;
+    uint64_t first = 0, total[2] = {0, 0};
+    uint32_t items = 0, spans = 0, chr_max = 1;
+    cmrt::ChrTab ct{};
     RowsBufs &R = ctx->rows;
     hipStream_t st = ctx->st.B;
-    uint32_t chr_max = 1;
+
+    // what the batch keeps, pairs or records [first, first + count) of `of`, the callers' buffers, the format's limit
+    int check(std::initializer_list<StagedBit> need, uint64_t first_, uint64_t count, uint64_t of) {
+        if (int rc = not_staged(ctx, c.fn, need)) return rc;
+        if (first_ > of || count > of - first_)
+            return fail(ctx, CM_EINVAL, "%s: %s [%llu, +%llu) of %llu", c.fn, c.range_unit, (unsigned long long)first_, (unsigned long long)count, (unsigned long long)of);
+        for (int m = 0; m < n_files; ++m)
+            if (!file[m].out && file[m].cap) return fail(ctx, CM_EINVAL, "%s: null out", c.fn);
+        if (count >= c.pair_limit) return fail(ctx, CM_ELIMIT, "%s: %llu %s in one call", c.fn, (unsigned long long)count, c.limit_unit);
+        first = first_;
+        items = c.pair_items * (uint32_t)count;
+        spans = (items + c.span_items - 1) / c.span_items;
+        return CM_OK;
+    }
+    // the chromosome table in columns -- the names' text and offsets and, where the format prints positions of its own (`shifts`),
+    // the chromosomes' starts --, and the buffers
+    int prepare(const cm_chr_info *chrs, uint32_t n_chr, bool shifts) {
+        std::vector<uint32_t> o((size_t)n_chr + 1, 0u), sh;
+        std::vector<uint8_t> text;
+        for (uint32_t k = 0; k < n_chr; ++k) {
+            if (chrs[k].name) text.insert(text.end(), chrs[k].name, chrs[k].name + strlen(chrs[k].name));
+            o[k + 1] = (uint32_t)text.size();
+            chr_max = std::max(chr_max, o[k + 1] - o[k]);
+            if (shifts) sh.push_back(chrs[k].start_pos);
+        }
+        if (!(R.chr_text.holds(text) && R.chr_off.holds(o) && (!shifts || R.chr_shift.holds(sh)))) {
+            int rc;
+            HIPCHK(ctx, hipStreamSynchronize(st));              // (rows of an earlier call are out, but be sure nothing reads the old table)
+            if ((rc = upload_chr_column(ctx, st, R.chr_text, text, 4)) || (rc = upload_chr_column(ctx, st, R.chr_off, o, 0)) || (shifts && (rc = upload_chr_column(ctx, st, R.chr_shift, sh, 1))))
+                return rc;
+            HIPCHK(ctx, hipStreamSynchronize(st));
+            R.chr_text.valid = R.chr_off.valid = true;
+            if (shifts) R.chr_shift.valid = true;
+        }
+        ct = cmrt::ChrTab{R.chr_text.dev, R.chr_off.dev, n_chr};
+        for (int m = 0; m < n_files; ++m) {
+            HIPCHK(ctx, ensure(ctx, R.file[m].off, ((size_t)items + 1) * sizeof(uint32_t)));
+            HIPCHK(ctx, ensure(ctx, R.file[m].path, spans));
+        }
+        HIPCHK(ctx, ensure(ctx, R.tmp, (size_t)(((uint64_t)items + 1) / S32_B + 2) * sizeof(uint32_t)));
+        HIPCHK(ctx, ensure(ctx, R.total, (size_t)n_files * sizeof(unsigned long long)));
+        return CM_OK;
+    }
+    int lengths(uint64_t *out_bytes) {
+        int rc;
+        // offsets are uint32: where the items of a file could come to 2^32 bytes (the names and strings at their most, every number
+        // at its widest, the longest chromosome name wherever one is printed) the lengths are summed in 64 bits first
+        const bool wide = c.strings_max + (uint64_t)items * (c.item_fixed_max + c.item_chrs * chr_max) >= (1ull << 32);
+        unsigned long long *land = ctx->h_pin + PIN_ROWS;
+        {
+            Timer t(ctx, PC_ROWS, st);
+            for (int m = 0; m < n_files; ++m) {
+                uint32_t *off = R.file[m].off;
+                hipLaunchKernelGGL(file[m].k_len, dim3(items / BLK + 1), dim3(BLK), 0, st, file[m].src, ct, first, items, off);
+                if (wide) hipLaunchKernelGGL(k_rows_total, dim3(1), dim3(BLK), 0, st, (const uint32_t *)off, items, (unsigned long long *)R.total + m);
+                if ((rc = scan32_on(ctx, st, off, (uint64_t)items + 1, off, R.tmp, 0u, 0))) return rc;
+            }
+        }
+        for (int m = 0; m < n_files; ++m) {
+            land[m] = 0;
+            if (wide) HIPCHK(ctx, hipMemcpyAsync(land + m, R.total + m, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+            else HIPCHK(ctx, hipMemcpyAsync(land + m, R.file[m].off + items, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        }
+        HIPCHK(ctx, hipStreamSynchronize(st));
+        for (int m = 0; m < n_files; ++m) out_bytes[m] = total[m] = land[m];
+        const auto noun = [&](int m) { return n_files > 1 ? std::string(c.noun) + " of file " + std::to_string(m + 1) : std::string(c.noun); };
+        for (int m = 0; m < n_files; ++m)
+            if (total[m] >= (1ull << 32))
+                return fail(ctx, CM_ELIMIT, "%s: %llu bytes of %s in one call (offsets are 32 bits: format in ranges)", c.fn, (unsigned long long)total[m], noun(m).c_str());
+        for (int m = 0; m < n_files; ++m)
+            if (total[m] > file[m].cap)
+                return fail(ctx, CM_ELIMIT, "%s: %llu bytes of %s > cap %llu", c.fn, (unsigned long long)total[m], noun(m).c_str(), (unsigned long long)file[m].cap);
+        return CM_OK;
+    }
+    int spans_out() {
+        for (int m = 0; m < n_files; ++m) HIPCHK(ctx, ensure(ctx, R.file[m].out, (size_t)total[m] + 4));
+        {
+            Timer t(ctx, PC_ROWS, st);
+            for (int m = 0; m < n_files; ++m)
+                hipLaunchKernelGGL(file[m].k_rows, dim3(spans), dim3(cmrt::WAVE), 0, st, file[m].src, ct, first, items, (const uint32_t *)R.file[m].off, (uint8_t *)R.file[m].out,
+                                   (uint8_t *)R.file[m].path);
+        }
+        HIPCHK(ctx, hipGetLastError());
+        for (int m = 0; m < n_files; ++m) HIPCHK(ctx, hipMemcpyAsync(file[m].out, R.file[m].out, (size_t)total[m], hipMemcpyDeviceToHost, st));
+        return CM_OK;
+    }
+    int finish(uint64_t stats[4]) {
+        if (stats) {
+            R.h_path.resize((size_t)n_files * spans);
+            for (int m = 0; m < n_files; ++m) HIPCHK(ctx, hipMemcpyAsync(R.h_path.data() + (size_t)m * spans, R.file[m].path, spans, hipMemcpyDeviceToHost, st));
+        }
+        HIPCHK(ctx, hipStreamSynchronize(st));
+        if (stats) {
+            stats[0] = (uint64_t)n_files * items;
+            stats[1] = total[0] + total[1];
+            for (uint8_t p : R.h_path) ++stats[p ? 2 : 3];
+        }
+        return CM_OK;
+    }
+};
+// cm_format_pam, cm_format_sam: pairs [first, first + count) of the resident batch into one file
+template <class Src>
+static int format_rows(cm_ctx *ctx, const RowsCall &c, RowsFile<Src> file, std::initializer_list<StagedBit> need, const cm_chr_info *chrs, uint32_t n_chr, uint64_t first,
+                       uint64_t count, uint64_t *out_bytes, uint64_t stats[4]) {
+    RowsRun<Src> run{ctx, c, &file, 1};
     int rc;
-    if ((rc = upload_chr_table(ctx, R, chrs, n_chr, st, &chr_max))) return rc;
-    const cmrt::ChrTab ct{R.chr_text, R.chr_off, n_chr};
-    const uint32_t items = F::PAIR_ITEMS * (uint32_t)count, spans = (items + F::SPAN_ITEMS - 1) / F::SPAN_ITEMS;
-    HIPCHK(ctx, ensure(ctx, R.off, ((size_t)items + 1) * sizeof(uint32_t)));
-    HIPCHK(ctx, ensure(ctx, R.tmp, (size_t)(((uint64_t)items + 1) / S32_B + 2) * sizeof(uint32_t)));
-    HIPCHK(ctx, ensure(ctx, R.path, spans));
-    HIPCHK(ctx, ensure(ctx, R.total, sizeof(unsigned long long)));
-    // offsets are uint32: where the items could come to 2^32 bytes (the names and strings at their most, every number at its
-    // widest) the lengths are summed in 64 bits first
-    const bool wide = c.strings_max + (uint64_t)items * (F::ITEM_FIXED_MAX + F::ITEM_CHRS * chr_max) >= (1ull << 32);
-    unsigned long long *land = ctx->h_pin + PIN_ROWS;
-    {
-        Timer t(ctx, PC_ROWS, st);
-        hipLaunchKernelGGL(c.k_len, dim3(items / BLK + 1), dim3(BLK), 0, st, c.src, ct, first, items, (uint32_t *)R.off);
-        if (wide) hipLaunchKernelGGL(k_rows_total, dim3(1), dim3(BLK), 0, st, (const uint32_t *)R.off, items, (unsigned long long *)R.total);
-        if ((rc = scan32_on(ctx, st, R.off, (uint64_t)items + 1, R.off, R.tmp, 0u, 0))) return rc;
-    }
-    *land = 0;
-    if (wide) HIPCHK(ctx, hipMemcpyAsync(land, R.total, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    else HIPCHK(ctx, hipMemcpyAsync(land, R.off + items, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipStreamSynchronize(st));
-    const uint64_t total = *land;
-    *out_bytes = total;
-    if (total >= (1ull << 32))
-        return fail(ctx, CM_ELIMIT, "%s: %llu bytes of %s in one call (offsets are 32 bits: format in ranges)", c.fn, (unsigned long long)total, c.noun);
-    if (total > cap) return fail(ctx, CM_ELIMIT, "%s: %llu bytes of %s > cap %llu", c.fn, (unsigned long long)total, c.noun, (unsigned long long)cap);
-    HIPCHK(ctx, ensure(ctx, R.out, (size_t)total + 4));
-    {
-        Timer t(ctx, PC_ROWS, st);
-        hipLaunchKernelGGL(c.k_rows, dim3(spans), dim3(cmrt::WAVE), 0, st, c.src, ct, first, items, (const uint32_t *)R.off, (uint8_t *)R.out, (uint8_t *)R.path);
-    }
-    HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipMemcpyAsync(out, R.out, (size_t)total, hipMemcpyDeviceToHost, st));
-    if (stats) {
-        R.h_path.resize(spans);
-        HIPCHK(ctx, hipMemcpyAsync(R.h_path.data(), R.path, spans, hipMemcpyDeviceToHost, st));
-    }
-    HIPCHK(ctx, hipStreamSynchronize(st));
-    if (stats) {
-        stats[0] = items;
-        stats[1] = total;
-        for (uint32_t i = 0; i < spans; ++i) ++stats[R.h_path[i] ? 2 : 3];
-    }
-    return CM_OK;
+    if ((rc = run.check(need, first, count, ctx->n_pairs)) || count == 0) return rc;
+    if ((rc = run.prepare(chrs, n_chr, false)) || (rc = run.lengths(out_bytes)) || (rc = run.spans_out())) return rc;
+    return run.finish(stats);
 }
 }  // extern "C++"
 
 // PAM rows: one per pair; needs the kept names.  At most: every name once.
 int cm_format_pam(cm_ctx *ctx, const cm_chr_info *chrs, uint32_t n_chr, uint64_t first, uint64_t count, void *out, uint64_t cap, uint64_t *out_bytes,
                   uint64_t stats[4]) {
-    if (!ctx) return CM_EINVAL;
+    const char *fn = "cm_format_pam";
+    if (int rc = rows_enter(ctx, fn, chrs, n_chr, out_bytes, 1, nullptr, stats)) return rc;
     const ReadBufs &rd = ctx->rd;
-    const RowsCall<cmpt::Format> c{"cm_format_pam", "rows", "rows", rd.has_names ? nullptr : "bit 2 (no names)",
-                                   {ctx->d_state, rd.names, rd.name_off}, rd.name_bytes_max, k_pam_len, k_pam_rows};
-    return format_rows(ctx, c, chrs, n_chr, first, count, out, cap, out_bytes, stats);
+    return format_rows<cmpt::Format::Src>(ctx, rows_call<cmpt::Format>(fn, "pairs", "rows", "rows", rd.name_bytes_max),
+                                          {k_pam_len, k_pam_rows, {ctx->d_state, rd.names, rd.name_off}, out, cap}, {{rd.has_names, "2", "names"}}, chrs, n_chr, first, count,
+                                          out_bytes, stats);
 }
 
 // SAM records: two per pair; needs the kept names and qualities.  At most: every name twice, every read as SEQ and as QUAL.
 int cm_format_sam(cm_ctx *ctx, const cm_chr_info *chrs, uint32_t n_chr, uint64_t first, uint64_t count, void *out, uint64_t cap, uint64_t *out_bytes,
                   uint64_t stats[4]) {
-    if (!ctx) return CM_EINVAL;
+    const char *fn = "cm_format_sam";
+    if (int rc = rows_enter(ctx, fn, chrs, n_chr, out_bytes, 1, nullptr, stats)) return rc;
     const ReadBufs &rd = ctx->rd;
-    const char *missing = rd.has_names && rd.has_quals ? nullptr : rd.has_quals ? "bit 2 (no names)" : rd.has_names ? "bit 3 (no qualities)" : "bits 2 and 3 (no names, no qualities)";
-    const RowsCall<cmst::Format> c{"cm_format_sam", "pairs", "records", missing,
-                                   {ctx->d_state, rd.names, rd.name_off, {rd.seq1_base + cmc::CM_STAGE_PAD, rd.seq2_base + cmc::CM_STAGE_PAD}, {rd.qual1, rd.qual2}, {rd.off1, rd.off2}},
-                                   2 * (rd.name_bytes_max + rd.bases), k_sam_len, k_sam_rows};
-    return format_rows(ctx, c, chrs, n_chr, first, count, out, cap, out_bytes, stats);
+    return format_rows<cmst::Format::Src>(
+        ctx, rows_call<cmst::Format>(fn, "pairs", "pairs", "records", 2 * (rd.name_bytes_max + rd.bases)),
+        {k_sam_len, k_sam_rows, {ctx->d_state, rd.names, rd.name_off, {rd.seq1_base + cmc::CM_STAGE_PAD, rd.seq2_base + cmc::CM_STAGE_PAD}, {rd.qual1, rd.qual2}, {rd.off1, rd.off2}}, out, cap},
+        {{rd.has_names, "2", "names"}, {rd.has_quals, "3", "qualities"}}, chrs, n_chr, first, count, out_bytes, stats);
 }
 
 // Either mate file's order of the n entries of the active set (S.sel = compact_active's list) into rows.list1 / list2: the plan of
@@ -4784,130 +4872,41 @@ static int sort_remain(cm_ctx *ctx, const char *fn, const cmrm::Src &S, const cm
     return CM_OK;
 }
 
-// Remain records: one per mate file of every record [first, first + count) of the active set, the set and order of
-// cm_collect_records (compact_active's list is the formats' selection).  The plan runs once per mate: both length passes first --
-// either file may be refused for its size, and then neither is written --, then both span passes.  Needs the kept names of both
-// files and the kept qualities.  Three waits: for the size of the active set, for the two totals, for the bytes.
-// sorted: the order of cm_remain_order.h in place of the active set's (cm_format_remain_sorted, below); out_off (nullable): the
-// records' offsets in either file, count + 1 words each.
+// Remain records: one per mate file of every record [first, first + count) of the active set, the set and order of cm_collect_records
+// (compact_active's list is the formats' selection), through the driver with two files.  Three waits: the set's size, the driver's two.
+// sorted: the order of cm_remain_order.h in place of the active set's (cm_format_remain_sorted, below), one more wait -- a batch
+// refused for a tie group has n_records set, out_bytes and stats zero; out_off (nullable): the records' offsets in either file,
+// count + 1 words each.
 static int format_remain(cm_ctx *ctx, const char *fn, bool sorted, const cm_chr_info *chrs, uint32_t n_chr, uint64_t first, uint64_t count, void *out1, uint64_t cap1,
                          void *out2, uint64_t cap2, uint64_t out_bytes[2], int64_t *out_keys, uint32_t *const out_off[2], uint64_t *n_records, uint64_t stats[4]) {
-    if (!ctx || !out_bytes || (n_chr && !chrs)) return CM_EINVAL;
-    out_bytes[0] = out_bytes[1] = 0;
-    if (n_records) *n_records = 0;
-    if (stats) stats[0] = stats[1] = stats[2] = stats[3] = 0;
-    HIPCHK(ctx, hipSetDevice(ctx->P.device));
-    if (ctx->n_pairs == 0) return fail(ctx, CM_ESTATE, "%s: no resident batch", fn);
     int rc;
     unsigned int active = 0;
-    if ((rc = compact_active(ctx)) || (rc = read_count(ctx, ~0ull, &active, fn))) return rc;
+    if ((rc = rows_enter(ctx, fn, chrs, n_chr, out_bytes, 2, n_records, stats)) || (rc = compact_active(ctx)) || (rc = read_count(ctx, ~0ull, &active, fn))) return rc;
     if (n_records) *n_records = active;
     const ReadBufs &rd = ctx->rd;
-    if (!rd.has_names || !rd.has_quals || !rd.has_names2) {
-        std::string bits, what;
-        const struct { bool has; const char *bit, *what; } need[3] = {{rd.has_names, "2", "R1 names"}, {rd.has_quals, "3", "qualities"}, {rd.has_names2, "4", "R2 names"}};
-        int missing = 0;
-        for (const auto &b : need)
-            if (!b.has) {
-                bits += (missing ? ", " : "") + std::string(b.bit);
-                what += (missing++ ? ", no " : "no ") + std::string(b.what);
-            }
-        return fail(ctx, CM_ESTATE, "%s: the resident batch was not staged with cm_reads_stage_text, flag bit%s %s (%s)", fn, missing > 1 ? "s" : "", bits.c_str(), what.c_str());
-    }
+    const RowsCall c = rows_call<cmrm::Format<0>>(fn, "records", "records", "records", std::max(rd.name_bytes_max, rd.name2_bytes_max) + 2 * rd.bases);
+    RowsFile<cmrm::Src> file[2] = {{k_remain_len<0>, k_remain_rows<0>, {}, out1, cap1}, {k_remain_len<1>, k_remain_rows<1>, {}, out2, cap2}};
+    RowsRun<cmrm::Src> run{ctx, c, file, 2};
     if (count == ~0ull && first <= active) count = active - first;
-    if (first > active || count > active - first)
-        return fail(ctx, CM_EINVAL, "%s: records [%llu, +%llu) of %u", fn, (unsigned long long)first, (unsigned long long)count, active);
-    if ((!out1 && cap1) || (!out2 && cap2)) return fail(ctx, CM_EINVAL, "%s: null out", fn);
-    if (count == 0) return CM_OK;
+    if ((rc = run.check({{rd.has_names, "2", "R1 names"}, {rd.has_quals, "3", "qualities"}, {rd.has_names2, "4", "R2 names"}}, first, count, active)) || count == 0) return rc;
+    if ((rc = run.prepare(chrs, n_chr, true))) return rc;
     RowsBufs &R = ctx->rows;
     hipStream_t st = ctx->st.B;
-    uint32_t chr_max = 1;
-    if ((rc = upload_chr_table(ctx, R, chrs, n_chr, st, &chr_max))) return rc;
-    {   // the shifts, beside the names and by their rule: uploaded when they differ from the table on the device
-        std::vector<uint32_t> sh(n_chr);
-        for (uint32_t c = 0; c < n_chr; ++c) sh[c] = chrs[c].start_pos;
-        if (!R.shift_valid || sh != R.h_chr_shift) {
-            R.shift_valid = false;
-            HIPCHK(ctx, hipStreamSynchronize(st));
-            R.h_chr_shift.swap(sh);
-            HIPCHK(ctx, ensure(ctx, R.chr_shift, (R.h_chr_shift.size() + 1) * sizeof(uint32_t)));
-            if (n_chr) HIPCHK(ctx, hipMemcpyAsync(R.chr_shift, R.h_chr_shift.data(), (size_t)n_chr * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-            HIPCHK(ctx, hipStreamSynchronize(st));
-            R.shift_valid = true;
-        }
-    }
-    const cmrt::ChrTab ct{R.chr_text, R.chr_off, n_chr};
-    const uint32_t items = (uint32_t)count, spans = (items + cmrm::SPAN_RECS - 1) / cmrm::SPAN_RECS;
-    HIPCHK(ctx, ensure(ctx, R.off, ((size_t)items + 1) * sizeof(uint32_t)));
-    HIPCHK(ctx, ensure(ctx, R.off2, ((size_t)items + 1) * sizeof(uint32_t)));
-    HIPCHK(ctx, ensure(ctx, R.tmp, (size_t)(((uint64_t)items + 1) / S32_B + 2) * sizeof(uint32_t)));
-    HIPCHK(ctx, ensure(ctx, R.path, spans));
-    HIPCHK(ctx, ensure(ctx, R.path2, spans));
-    HIPCHK(ctx, ensure(ctx, R.total, 2 * sizeof(unsigned long long)));
-    if (out_keys) HIPCHK(ctx, ensure(ctx, R.keys, (size_t)items * sizeof(int64_t)));
-    const cmrm::Src S{ctx->col.perm, ctx->d_state, {rd.names, rd.names2}, {rd.name_off, rd.name_off2},
-                      {rd.seq1_base + cmc::CM_STAGE_PAD, rd.seq2_base + cmc::CM_STAGE_PAD}, {rd.qual1, rd.qual2}, {rd.off1, rd.off2},
-                      R.chr_shift, out_keys ? (int64_t *)R.keys : nullptr};
+    if (out_keys) HIPCHK(ctx, ensure(ctx, R.keys, (size_t)run.items * sizeof(int64_t)));
     // either file's selection list: the active set, or the file's own order of it
-    cmrm::Src Sm[2] = {S, S};
+    file[0].src = file[1].src = cmrm::Src{ctx->col.perm, ctx->d_state, {rd.names, rd.names2}, {rd.name_off, rd.name_off2},
+                                          {rd.seq1_base + cmc::CM_STAGE_PAD, rd.seq2_base + cmc::CM_STAGE_PAD}, {rd.qual1, rd.qual2}, {rd.off1, rd.off2},
+                                          R.chr_shift.dev, out_keys ? (int64_t *)R.keys : nullptr};
     if (sorted) {
-        if ((rc = sort_remain(ctx, fn, S, ct, active))) return rc;
-        Sm[0].sel = R.list1;
-        Sm[1].sel = R.list2;
+        if ((rc = sort_remain(ctx, fn, file[0].src, run.ct, active))) return rc;
+        file[0].src.sel = R.list1;
+        file[1].src.sel = R.list2;
     }
-    uint32_t *const off[2] = {R.off, R.off2};
-    uint8_t *const path[2] = {R.path, R.path2};
-    // offsets are uint32: where a file's records could come to 2^32 bytes the lengths are summed in 64 bits first (format_rows)
-    const bool wide = std::max(rd.name_bytes_max, rd.name2_bytes_max) + 2 * rd.bases + (uint64_t)items * (cmrm::REC_FIXED_MAX + 2 * chr_max) >= (1ull << 32);
-    unsigned long long *land = ctx->h_pin + PIN_ROWS;
-    {
-        Timer t(ctx, PC_ROWS, st);
-        for (int m = 0; m < 2; ++m) {
-            hipLaunchKernelGGL((m ? k_remain_len<1> : k_remain_len<0>), dim3(items / BLK + 1), dim3(BLK), 0, st, Sm[m], ct, first, items, off[m]);
-            if (wide) hipLaunchKernelGGL(k_rows_total, dim3(1), dim3(BLK), 0, st, (const uint32_t *)off[m], items, (unsigned long long *)R.total + m);
-            if ((rc = scan32_on(ctx, st, off[m], (uint64_t)items + 1, off[m], R.tmp, 0u, 0))) return rc;
-        }
-    }
-    land[0] = land[1] = 0;
-    for (int m = 0; m < 2; ++m) {
-        if (wide) HIPCHK(ctx, hipMemcpyAsync(land + m, R.total + m, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-        else HIPCHK(ctx, hipMemcpyAsync(land + m, off[m] + items, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    }
-    HIPCHK(ctx, hipStreamSynchronize(st));
-    const uint64_t total[2] = {land[0], land[1]}, cap[2] = {cap1, cap2};
-    out_bytes[0] = total[0];
-    out_bytes[1] = total[1];
+    if ((rc = run.lengths(out_bytes)) || (rc = run.spans_out())) return rc;
+    if (out_keys) HIPCHK(ctx, hipMemcpyAsync(out_keys, R.keys, (size_t)run.items * sizeof(int64_t), hipMemcpyDeviceToHost, st));
     for (int m = 0; m < 2; ++m)
-        if (total[m] >= (1ull << 32))
-            return fail(ctx, CM_ELIMIT, "%s: %llu bytes of records of file %d in one call (offsets are 32 bits: format in ranges)", fn, (unsigned long long)total[m], m + 1);
-    for (int m = 0; m < 2; ++m)
-        if (total[m] > cap[m])
-            return fail(ctx, CM_ELIMIT, "%s: %llu bytes of records of file %d > cap %llu", fn, (unsigned long long)total[m], m + 1, (unsigned long long)cap[m]);
-    HIPCHK(ctx, ensure(ctx, R.out, (size_t)total[0] + 4));
-    HIPCHK(ctx, ensure(ctx, R.out2, (size_t)total[1] + 4));
-    uint8_t *const d_out[2] = {R.out, R.out2};
-    void *const h_out[2] = {out1, out2};
-    {
-        Timer t(ctx, PC_ROWS, st);
-        for (int m = 0; m < 2; ++m)
-            hipLaunchKernelGGL((m ? k_remain_rows<1> : k_remain_rows<0>), dim3(spans), dim3(cmrt::WAVE), 0, st, Sm[m], ct, first, items, (const uint32_t *)off[m], d_out[m], path[m]);
-    }
-    HIPCHK(ctx, hipGetLastError());
-    for (int m = 0; m < 2; ++m) HIPCHK(ctx, hipMemcpyAsync(h_out[m], d_out[m], (size_t)total[m], hipMemcpyDeviceToHost, st));
-    if (out_keys) HIPCHK(ctx, hipMemcpyAsync(out_keys, R.keys, (size_t)items * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-    for (int m = 0; m < 2; ++m)
-        if (out_off && out_off[m]) HIPCHK(ctx, hipMemcpyAsync(out_off[m], off[m], ((size_t)items + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    if (stats) {
-        R.h_path.resize(2 * (size_t)spans);
-        for (int m = 0; m < 2; ++m) HIPCHK(ctx, hipMemcpyAsync(R.h_path.data() + (size_t)m * spans, path[m], spans, hipMemcpyDeviceToHost, st));
-    }
-    HIPCHK(ctx, hipStreamSynchronize(st));
-    if (stats) {
-        stats[0] = 2ull * items;
-        stats[1] = total[0] + total[1];
-        for (size_t i = 0; i < 2 * (size_t)spans; ++i) ++stats[R.h_path[i] ? 2 : 3];
-    }
-    return CM_OK;
+        if (out_off && out_off[m]) HIPCHK(ctx, hipMemcpyAsync(out_off[m], R.file[m].off, ((size_t)run.items + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    return run.finish(stats);
 }
 
 int cm_format_remain(cm_ctx *ctx, const cm_chr_info *chrs, uint32_t n_chr, uint64_t first, uint64_t count, void *out1, uint64_t cap1, void *out2, uint64_t cap2,
@@ -4927,7 +4926,7 @@ int cm_quals_peek(cm_ctx *ctx, uint8_t *qual1, uint64_t cap1, uint8_t *qual2, ui
     if (!ctx) return CM_EINVAL;
     HIPCHK(ctx, hipSetDevice(ctx->P.device));
     if (ctx->n_pairs == 0) return fail(ctx, CM_ESTATE, "cm_quals_peek: no resident batch");
-    if (!ctx->rd.has_quals) return fail(ctx, CM_ESTATE, "cm_quals_peek: the resident batch was not staged with cm_reads_stage_text, flag bit 3 (no qualities)");
+    if (int rc = not_staged(ctx, "cm_quals_peek", {{ctx->rd.has_quals, "3", "qualities"}})) return rc;
     const uint64_t n = ctx->n_pairs;
     uint64_t total[2] = {0, 0};
     HIPCHK(ctx, hipMemcpyAsync(&total[0], ctx->rd.off1 + n, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->st.B));

@@ -1,9 +1,12 @@
-// cm_rows_text.h — what the device-side row formatters (cm_format_pam, cm_format_sam, cm_format_remain) share: everything that is
-// not a row format.
+// cm_rows_text.h — what the device-side row formatters (cm_format_pam, cm_format_sam, cm_format_remain, cm_format_remain_sorted)
+// share on the device: everything that is not a row format.
 //
 // Shared by the HIP kernels (cm_hot.hip: k_pam_len / k_sam_len / k_remain_len, k_pam_rows / k_sam_rows / k_remain_rows) and by the
 // host emulation (tests/hostemu_rows.h) that g++ compiles, the way cm_fastq_text.h is shared.  The formats are cm_pam_text.h,
-// cm_sam_text.h and cm_remain_text.h; each plugs into the plan below as a policy type.
+// cm_sam_text.h and cm_remain_text.h; each plugs into the plan below as a policy type.  The host side is written once as well:
+// one driver in cm_hot.hip (RowsRun) runs the plan for the one or two files of a call -- a file is a length kernel, a span kernel,
+// their Src and its buffers --, with a format's constants (PAIR_ITEMS .. ITEM_CHRS below) handed to it as values, and one loop
+// (cm_row_ranges.h) takes a batch through any of the entry points in ranges.
 // The plan of a call: one lane per item (a PAM row, a SAM record) computes the item's length (item_length) -> exclusive scan = the
 // item's offset in the output -> a wave takes F::SPAN_ITEMS consecutive items, which are one contiguous span [s, e) of the output
 // (format_span).  A span of at most WINDOW bytes is put together in the wave's LDS window, every byte at window_at() of its place

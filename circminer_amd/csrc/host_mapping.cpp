@@ -44,6 +44,7 @@
 
 #include "circminer_hot.h"
 #include "cm_pinned_ranges.h"
+#include "cm_row_ranges.h"
 
 namespace {
 
@@ -57,11 +58,6 @@ struct Result {
     std::vector<cm_record> recs;
     uint64_t n_rec = 0;
     cm_fastq_batch batch;
-};
-// CM_PAM_DEVICE=1: the PAM rows of batch k as the device formatted them, in page-locked set k & 1 (cm_host_alloc)
-struct RowBuf {
-    void *p = nullptr;
-    uint64_t cap = 0, n = 0;
 };
 // CM_FASTQ_DEVICE=1: block k in tq[k & 3]: its text is the reader's for three more reads
 struct TextBlock {
@@ -108,7 +104,7 @@ struct Run {
     std::vector<cm_index_view> views;
     std::vector<cm_annot_view> annots, annots_early;             // _early: the GTF thread's, until load_annotation() takes or frees them
     Result res[2];
-    RowBuf rows[2];
+    RowBuf rows[2];                                // CM_PAM_DEVICE=1 / CM_SAM_DEVICE=1: the rows of batch k as the device formatted them, in set k & 1
     RowBuf rem_rows[2][2];                         // CM_REMAIN_DEVICE=1: the remain records of batch k, file 1 and file 2, in set k & 1
     // CM_REMAIN_SORTED=1 beside it: the same records in cm_sort_remain's order (cm_format_remain_sorted), their offsets and keys; the
     // batches' sorted runs, merged into the .srt files after the last batch
@@ -519,65 +515,29 @@ struct Run {
         RB.cap = cap;
         return CM_OK;
     }
-    // The PAM rows or SAM records of the resident batch's n pairs, in ranges: a range whose rows would not fit 32-bit offsets is
-    // halved, a buffer that is too small is replaced by one that holds what is there plus what the device asks for.  A SAM pair is
-    // its name and its reads twice over (~ 800 bytes for 2 x 150 bp, eight PAM rows): its ranges are 2^17 pairs, which keeps the
-    // formatter's device buffer near 100 MB; the page-locked buffer holds the batch's records.
+    std::function<int(RowBuf &, uint64_t)> grower() { return [this](RowBuf &RB, uint64_t cap) { return grow_rows(RB, cap); }; }
+    // Three users of format_ranges (cm_row_ranges.h: halved ranges, grown buffers).  First the PAM rows or SAM records of the resident batch's n pairs, appended to RB.
+    // A SAM pair is its name and its reads twice over (~ 800 bytes for 2 x 150 bp, eight PAM rows): ranges of 2^17 pairs keep the formatter's device buffer near 100 MB.
     int format_rows(RowBuf &RB, uint64_t n) {
         const auto format = sam_device ? cm_format_sam : cm_format_pam;
         const char *const name = sam_device ? "cm_format_sam" : "cm_format_pam";
-        uint64_t done = 0, step = std::min<uint64_t>(n, sam_device ? 1ull << 17 : 1ull << 22);
-        while (done < n) {
-            const uint64_t c = std::min(step, n - done);
-            uint64_t got = 0;
-            int r = format(cm, chrs, n_chr, done, c, RB.p ? (char *)RB.p + RB.n : nullptr, RB.cap - RB.n, &got, nullptr);
-            if (r == CM_ELIMIT && got >= (1ull << 32) && c > 1) {
-                step = c / 2;
-                continue;
-            }
-            if (r == CM_ELIMIT && got > RB.cap - RB.n) {
-                if ((r = grow_rows(RB, RB.n + got + got / c * (n - done - c) + (1u << 16))) != CM_OK) return r;
-                continue;
-            }
-            if (r != CM_OK) return failed(r, name);
-            RB.n += got;
-            done += c;
-        }
-        return CM_OK;
+        return format_ranges(&RB, 1, &n, sam_device ? 1ull << 17 : 1ull << 22,
+                             {[&](uint64_t first, uint64_t count, uint64_t got[2], uint64_t *) { return format(cm, chrs, n_chr, first, count, RB.tail(), RB.room(), got, nullptr); },
+                              grower(), nullptr, [&](int r, bool) { return failed(r, name); }});
     }
-    // CM_REMAIN_DEVICE=1: the remain records of the resident batch's active set, formatted on the device into the two page-locked
-    // buffers of a set (file 1, file 2) -- to the end of the set in one call; where a file's records would not fit 32-bit offsets,
-    // in ranges that are halved until they do.  *n_rec: the size of the set (the run's bsj_pairs).
+    // CM_REMAIN_DEVICE=1: the remain records of the resident batch's active set, appended to the two page-locked buffers of a set
+    // (file 1, file 2) -- to the end of the set in one call, whose size the first call tells.  *n_rec: that size (the run's bsj_pairs).
     int format_remain(RowBuf RM[2], uint64_t *n_rec) {
-        uint64_t done = 0, total = 0, step = ~0ull;
         RM[0].n = RM[1].n = 0;
-        for (;;) {
-            const uint64_t count = step == ~0ull ? ~0ull : std::min(step, total - done);
-            uint64_t got[2] = {0, 0};
-            int r = cm_format_remain(cm, chrs, n_chr, done, count, RM[0].p ? (char *)RM[0].p + RM[0].n : nullptr, RM[0].cap - RM[0].n,
-                                     RM[1].p ? (char *)RM[1].p + RM[1].n : nullptr, RM[1].cap - RM[1].n, got, nullptr, &total, nullptr);
-            const uint64_t c = count == ~0ull ? total - done : count;
-            if (r == CM_ELIMIT && std::max(got[0], got[1]) >= (1ull << 32) && c > 1) {
-                step = c / 2;
-                continue;
-            }
-            if (r == CM_ELIMIT && c && (got[0] > RM[0].cap - RM[0].n || got[1] > RM[1].cap - RM[1].n)) {
-                for (int m = 0; m < 2; ++m)
-                    if (got[m] > RM[m].cap - RM[m].n && (r = grow_rows(RM[m], RM[m].n + got[m] + got[m] / c * (total - done - c) + (1u << 16))) != CM_OK) return r;
-                continue;
-            }
-            if (r != CM_OK) return failed(r, "cm_format_remain");
-            RM[0].n += got[0];
-            RM[1].n += got[1];
-            done += c;
-            if (done >= total) break;
-        }
-        *n_rec = total;
-        return CM_OK;
+        *n_rec = ~0ull;
+        return format_ranges(RM, 2, n_rec, ~0ull,
+                             {[&](uint64_t first, uint64_t count, uint64_t got[2], uint64_t *total) {
+                                  return cm_format_remain(cm, chrs, n_chr, first, count, RM[0].tail(), RM[0].room(), RM[1].tail(), RM[1].room(), got, nullptr, total, nullptr);
+                              },
+                              grower(), nullptr, [&](int r, bool) { return failed(r, "cm_format_remain"); }});
     }
-    // CM_REMAIN_SORTED=1: the batch's records once more, in cm_sort_remain's order, as a run of srt_runs -- in ranges where a file's
-    // records would not fit 32-bit offsets (consecutive ranges of one order are runs like any other).  A batch the device refuses
-    // for a tie group is ordered here, from the unsorted records RM holds.
+    // CM_REMAIN_SORTED=1: the batch's records once more, in cm_sort_remain's order, every range from the start of srt_rows into a run of srt_runs
+    // (consecutive ranges of one order are runs like any other).  A batch the device refuses for a tie group is ordered here, from the unsorted records RM holds.
     int sorted_run(RowBuf RM[2], uint64_t n_rec) {
         int r;
         ++srt_batches;
@@ -587,30 +547,25 @@ struct Run {
             srt_rows[m].n = 0;
             if (srt_rows[m].cap < RM[m].n && (r = grow_rows(srt_rows[m], RM[m].n + (1u << 16))) != CM_OK) return r;
         }
-        uint64_t done = 0, step = n_rec;
-        while (done < n_rec) {
-            const uint64_t c = std::min(step, n_rec - done);
-            uint64_t got[2] = {0, 0}, total = 0;
-            srt_off[0].resize(c + 1);
-            srt_off[1].resize(c + 1);
-            srt_keys.resize(c);
-            r = cm_format_remain_sorted(cm, chrs, n_chr, done, c, srt_rows[0].p, srt_rows[0].cap, srt_rows[1].p, srt_rows[1].cap, got, srt_keys.data(), srt_off[0].data(),
-                                        srt_off[1].data(), &total, nullptr);
-            if (r == CM_ELIMIT && std::max(got[0], got[1]) >= (1ull << 32) && c > 1) {
-                step = c / 2;
-                continue;
-            }
-            if (r == CM_ELIMIT && got[0] == 0 && got[1] == 0 && done == 0) {          // a tie group above the cap
-                ++srt_host_batches;
-                if ((r = cm_remain_runs_add_unsorted(srt_runs, RM[0].p, RM[0].n, RM[1].p, RM[1].n)) != CM_OK) return failed(r, "cm_remain_runs_add_unsorted");
-                return CM_OK;
-            }
-            if (r != CM_OK) return failed(r, "cm_format_remain_sorted");
-            if ((r = cm_remain_runs_add(srt_runs, srt_rows[0].p, srt_off[0].data(), srt_rows[1].p, srt_off[1].data(), srt_keys.data(), c)) != CM_OK)
-                return failed(r, "cm_remain_runs_add");
-            done += c;
-        }
-        return CM_OK;
+        return format_ranges(srt_rows, 2, &n_rec, ~0ull,
+                             {[&](uint64_t first, uint64_t count, uint64_t got[2], uint64_t *) {
+                                  for (auto &o : srt_off) o.resize(count + 1);
+                                  srt_keys.resize(count);
+                                  return cm_format_remain_sorted(cm, chrs, n_chr, first, count, srt_rows[0].p, srt_rows[0].cap, srt_rows[1].p, srt_rows[1].cap, got,
+                                                                 srt_keys.data(), srt_off[0].data(), srt_off[1].data(), nullptr, nullptr);
+                              },
+                              grower(),
+                              [&](uint64_t c) {
+                                  const int a = cm_remain_runs_add(srt_runs, srt_rows[0].p, srt_off[0].data(), srt_rows[1].p, srt_off[1].data(), srt_keys.data(), c);
+                                  srt_rows[0].n = srt_rows[1].n = 0;            // (the run keeps its own copy: the next range starts at byte 0 again)
+                                  return a != CM_OK ? failed(a, "cm_remain_runs_add") : a;
+                              },
+                              [&](int r, bool tie_group) {
+                                  if (!tie_group) return failed(r, "cm_format_remain_sorted");
+                                  ++srt_host_batches;
+                                  const int a = cm_remain_runs_add_unsorted(srt_runs, RM[0].p, RM[0].n, RM[1].p, RM[1].n);
+                                  return a != CM_OK ? failed(a, "cm_remain_runs_add_unsorted") : a;
+                              }});
     }
     // ... and the type histogram, which collect_records delivers on the other path
     int remain_records(Result &R, RowBuf RM[2]) {

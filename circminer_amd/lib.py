@@ -842,55 +842,44 @@ class HotPath:
         keep_names, keep_quals and keep_names2.  chrs: chromosome table rows (name, contig id, start, length).  Returns
         (bytes of file 1, bytes of file 2, keys or None, size of the active set, stats); caps: the sizes (cap1, cap2) of the
         buffers offered (default: what the records need, asked for first); keys: also the int64 sort key of every record."""
-        table = chr_array(list(chrs))
-        cnt = (1 << 64) - 1 if count is None else int(count)
-        got, n_rec, stats = (C.c_uint64 * 2)(), C.c_uint64(0), (C.c_uint64 * 4)()
-
-        def call(b1, c1, b2, c2, kp, sp):
-            return self.L.cm_format_remain(self.h, table, len(chrs), int(first), cnt, b1, c1, b2, c2, got, kp, C.byref(n_rec), sp)
-        if caps is None:
-            rc = call(None, 0, None, 0, None, None)
-            if rc not in (0, -6) or (rc == -6 and max(got) >= 1 << 32):         # CM_ELIMIT with the needed sizes is the answer here
-                self._chk(rc, "cm_format_remain")
-            caps = (got[0], got[1])
-        elif count is None and keys:                                            # (the size of the set, for the keys' array)
-            self._chk(self.L.cm_format_remain(self.h, table, len(chrs), 0, 0, None, 0, None, 0, got, None, C.byref(n_rec), None), "cm_format_remain")
-        n = max(int(n_rec.value) - int(first), 0) if count is None else int(count)
-        bufs = [np.full(int(c) + 64, 0xA5, np.uint8) for c in caps]             # (the bytes behind a cap show a write past it)
-        kk = np.full(n + 1, -0x5A5A5A5A5A5A5A5A, np.int64) if keys else None
-        self._chk(call(bufs[0].ctypes.data, int(caps[0]), bufs[1].ctypes.data, int(caps[1]), kk.ctypes.data if keys else None, stats), "cm_format_remain")
-        assert all(got[m] <= caps[m] and bool((bufs[m][int(caps[m]):] == 0xA5).all()) for m in (0, 1))
-        assert kk is None or kk[-1] == -0x5A5A5A5A5A5A5A5A
-        return bufs[0][:got[0]].tobytes(), bufs[1][:got[1]].tobytes(), (kk[:-1] if keys else None), int(n_rec.value), list(stats)
+        b1, b2, kk, _, n_rec, stats = self._format_remain("cm_format_remain", chrs, first, count, caps, keys, False)
+        return b1, b2, kk, n_rec, stats
 
     def format_remain_sorted(self, chrs=(), first=0, count=None, caps=None):
         """cm_format_remain_sorted: format_remain with the records in cm_sort_remain's order (by key, ties per file by the pasted
         line).  Returns (bytes of file 1, bytes of file 2, keys, (offsets of file 1, offsets of file 2), size of the active set,
         stats); a refusal (a tie group above the cap among them) raises with the library's message."""
+        return self._format_remain("cm_format_remain_sorted", chrs, first, count, caps, True, True)
+
+    def _format_remain(self, fn, chrs, first, count, caps, keys, offsets):
+        """(bytes of file 1, bytes of file 2, keys or None, offsets of both files or None, size of the active set, stats) of the
+        entry point fn, which takes the pointers for the offsets only where `offsets` is set; every array ends in guard words"""
         table = chr_array(list(chrs))
         cnt = (1 << 64) - 1 if count is None else int(count)
         got, n_rec, stats = (C.c_uint64 * 2)(), C.c_uint64(0), (C.c_uint64 * 4)()
 
-        def call(b1, c1, b2, c2, kp, o1, o2, sp):
-            return self.L.cm_format_remain_sorted(self.h, table, len(chrs), int(first), cnt, b1, c1, b2, c2, got, kp, o1, o2, C.byref(n_rec), sp)
+        def call(b1, c1, b2, c2, kp, oo, sp):
+            return getattr(self.L, fn)(self.h, table, len(chrs), int(first), cnt, b1, c1, b2, c2, got, kp, *(oo if offsets else ()), C.byref(n_rec), sp)
         if caps is None:
-            rc = call(None, 0, None, 0, None, None, None, None)
+            rc = call(None, 0, None, 0, None, (None, None), None)
             if rc not in (0, -6) or (rc == -6 and (max(got) >= 1 << 32 or max(got) == 0)):   # CM_ELIMIT with the needed sizes is the answer here
-                self._chk(rc, "cm_format_remain_sorted")
+                self._chk(rc, fn)
             caps = (got[0], got[1])
-        elif count is None:                                                     # (the size of the set, for the arrays)
+        elif count is None and (keys or offsets):                               # (the size of the set, for the arrays)
             self._chk(self.L.cm_format_remain(self.h, table, len(chrs), 0, 0, None, 0, None, 0, got, None, C.byref(n_rec), None), "cm_format_remain")
         n = max(int(n_rec.value) - int(first), 0) if count is None else int(count)
         bufs = [np.full(int(c) + 64, 0xA5, np.uint8) for c in caps]             # (the bytes behind a cap show a write past it)
-        kk = np.full(n + 1, -0x5A5A5A5A5A5A5A5A, np.int64)
-        oo = [np.full(n + 2, 0xA5A5A5A5, np.uint32) for _ in (0, 1)]
-        self._chk(call(bufs[0].ctypes.data, int(caps[0]), bufs[1].ctypes.data, int(caps[1]), kk.ctypes.data, oo[0].ctypes.data, oo[1].ctypes.data, stats),
-                  "cm_format_remain_sorted")
+        kk = np.full(n + 1, -0x5A5A5A5A5A5A5A5A, np.int64) if keys else None
+        oo = [np.full(n + 2, 0xA5A5A5A5, np.uint32) for _ in (0, 1)] if offsets else None
+        self._chk(call(bufs[0].ctypes.data, int(caps[0]), bufs[1].ctypes.data, int(caps[1]), kk.ctypes.data if keys else None,
+                       [o.ctypes.data for o in oo] if offsets else None, stats), fn)
         assert all(got[m] <= caps[m] and bool((bufs[m][int(caps[m]):] == 0xA5).all()) for m in (0, 1))
-        assert kk[-1] == -0x5A5A5A5A5A5A5A5A and all(o[-1] == 0xA5A5A5A5 for o in oo)
-        if n == 0:
+        assert kk is None or kk[-1] == -0x5A5A5A5A5A5A5A5A
+        assert oo is None or all(o[-1] == 0xA5A5A5A5 for o in oo)
+        if offsets and n == 0:
             oo = [np.zeros(2, np.uint32) for _ in (0, 1)]                       # (count == 0 writes nothing: no offsets either)
-        return bufs[0][:got[0]].tobytes(), bufs[1][:got[1]].tobytes(), kk[:-1], (oo[0][:-1], oo[1][:-1]), int(n_rec.value), list(stats)
+        return (bufs[0][:got[0]].tobytes(), bufs[1][:got[1]].tobytes(), (kk[:-1] if keys else None), ((oo[0][:-1], oo[1][:-1]) if offsets else None),
+                int(n_rec.value), list(stats))
 
     def peek_quals(self):
         """cm_quals_peek (test hook): (qual1, qual2) of the resident batch as cm_reads_stage_text kept them (keep_quals), in the

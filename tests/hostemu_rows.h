@@ -91,7 +91,7 @@ struct Shadow {
         return true;
     }
 };
-// the chromosome names as upload_chr_table lays them out
+// the chromosome names as RowsRun::prepare (cm_hot.hip) lays them out
 struct ChrTable {
     std::vector<uint32_t> off;
     std::vector<uint8_t> text;
