@@ -17,6 +17,7 @@
 #define CM_FASTQ_TEXT_H
 
 #include <stdint.h>
+#include "circminer_hot.h"
 
 #if defined(__HIPCC__)
 #define CMFT_HD __host__ __device__ inline
@@ -136,6 +137,51 @@ CMFT_HD void copy_bases(uint8_t *dst, uint64_t d, const uint8_t *text, uint32_t 
     for (uint32_t j = (uint32_t)lane; j < tail; j += (uint32_t)lanes) dst[4 * w1 + j] = text[s + (uint32_t)(4 * w1 - d) + j];
     uint32_t *dw = (uint32_t *)dst;
     for (uint64_t w = w0 + (uint64_t)lane; w < w1; w += (uint64_t)lanes) dw[w] = load_unaligned32(text, (uint64_t)s + (4 * w - d));
+}
+
+// ---- the host's share, called by cm_reads_stage_text and by the emulation: the sizes a stage is planned by, its verdict ------------
+// What the host knows before it has seen a line (bases <= bytes, a record >= 4 bytes).  trail[f]: the block's last line has no '\n'
+// and counts (flag bit f: end of input); max_pairs: the caller's, capped at 2^30 (a block below 2^32 bytes holds fewer records); nb: no
+// more pairs than this (off, rec and the lengths hold nb + 1 words per file); n_chunks[f] newline counts (+ 1: the total), ls_cap[f]
+// line starts (what 4 max_pairs lines need); scan_items: the longest array the tokeniser's scans run over.
+struct Sizes { uint32_t trail[2], nb, n_chunks[2], ls_cap[2]; uint64_t max_pairs, scan_items; };
+// CM_EINVAL: text[*file] is null with a length; CM_ELIMIT: it is too long for 32-bit line starts (the sentinel behind a last line
+// without '\n' is len + 1, a uint32 like every line start).  The files are looked at in order.
+inline int plan_sizes(const uint8_t *const text[2], const uint64_t len[2], uint64_t max_pairs, uint32_t flags, Sizes *S, int *file) {
+    S->max_pairs = max_pairs < (1ull << 30) ? max_pairs : 1ull << 30;
+    const uint64_t shorter = (len[0] < len[1] ? len[0] : len[1]) / 4, ls_max = 4 * S->max_pairs + 1;
+    S->nb = (uint32_t)(S->max_pairs < shorter ? S->max_pairs : shorter);
+    S->scan_items = (uint64_t)S->nb + 1;
+    for (int f = 0; f < 2; ++f) {
+        *file = f;
+        if (len[f] && !text[f]) return CM_EINVAL;
+        S->trail[f] = ((flags >> f) & 1u) && len[f] && text[f][len[f] - 1] != '\n';
+        if (len[f] > 0xffffffffull - S->trail[f]) return CM_ELIMIT;
+        S->n_chunks[f] = (uint32_t)((len[f] + NL_CHUNK - 1) / NL_CHUNK);
+        S->ls_cap[f] = (uint32_t)(len[f] + 2 < ls_max ? len[f] + 2 : ls_max);
+        if ((uint64_t)S->n_chunks[f] + 1 > S->scan_items) S->scan_items = (uint64_t)S->n_chunks[f] + 1;
+    }
+    return CM_OK;
+}
+// floor(longest read / k) seeds are more than a build of the kernels takes: the one line every way a batch comes in refuses by
+inline bool too_many_seeds(int max_len, int kmer, int max_seeds) { return max_len / kmer > max_seeds; }
+// What the result block says about the batch: the verdicts of next_plain / build_side / check_reads, the first that applies.
+// LINES_LEFT: file `file` ends (its flag bit) `count` lines behind its last whole record, within max_pairs; FILE2_SHORT: file 2
+// ends (flag bit 1) before file 1; MALFORMED: record `record` of file `file` is `count` (a Bad; BAD_CARRIED in file 1 only, behind
+// the other three of either file); READ_TOO_LONG, TOO_MANY_SEEDS: the longest read has `count` bases.
+enum Case { ACCEPTED = 0, LINES_LEFT, FILE2_SHORT, MALFORMED, READ_TOO_LONG, TOO_MANY_SEEDS };
+struct Verdict { int code; Case what; int file; unsigned long long record, count; };      // code: CM_OK, CM_EINVAL, CM_ELIMIT (TOO_MANY_SEEDS)
+inline Verdict verdict(const unsigned long long *R, uint32_t flags, uint64_t max_pairs, int32_t max_read_len, int32_t kmer, int max_seeds) {
+    const unsigned long long lines[2] = {R[RES_LINES1], R[RES_LINES2]}, max_len = R[RES_MAX_LEN];
+    for (int f = 0; f < 2; ++f)
+        if (((flags >> f) & 1u) && lines[f] % 4 != 0 && lines[f] / 4 < max_pairs) return {CM_EINVAL, LINES_LEFT, f, 0, lines[f] % 4};
+    if ((flags & 2u) && lines[1] / 4 < (lines[0] / 4 < max_pairs ? lines[0] / 4 : max_pairs)) return {CM_EINVAL, FILE2_SHORT, 1, 0, 0};
+    for (int f = 0; f < 2; ++f)
+        if (R[RES_BAD1 + f] != NO_BAD && (R[RES_BAD1 + f] & 7u) != BAD_CARRIED) return {CM_EINVAL, MALFORMED, f, R[RES_BAD1 + f] >> 3, R[RES_BAD1 + f] & 7u};
+    if (R[RES_BAD1] != NO_BAD) return {CM_EINVAL, MALFORMED, 0, R[RES_BAD1] >> 3, BAD_CARRIED};
+    if (max_len > (unsigned long long)max_read_len) return {CM_EINVAL, READ_TOO_LONG, 0, 0, max_len};
+    if (too_many_seeds((int)max_len, kmer, max_seeds)) return {CM_ELIMIT, TOO_MANY_SEEDS, 0, 0, max_len};
+    return {CM_OK, ACCEPTED, 0, 0, 0};
 }
 
 }  // namespace cmft

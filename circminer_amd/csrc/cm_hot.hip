@@ -2304,44 +2304,41 @@ struct DevBuf : DevMem {
 template <class T> using BatchBuf = DevBuf<T, BATCH>;
 template <class T> using CtxBuf = DevBuf<T, CONTEXT>;
 
-// The read buffers of one batch; a context has two (resident, staged) and cm_reads_swap exchanges them.
-struct ReadBufs {
-    BatchBuf<uint8_t> seq1_base, seq2_base;      // CM_STAGE_PAD readable bytes in front of and behind the reads
-    BatchBuf<uint64_t> off1, off2;
-    // cm_reads_stage_text with flag bit 2: the R1 names of the batch, name i = names[name_off[i] .. name_off[i + 1]) (cm_format_pam)
+// One mate file's share of a batch's read buffers (file 0: R1, file 1: R2).
+struct ReadFile {
+    BatchBuf<uint8_t> seq_base;                  // CM_STAGE_PAD readable bytes in front of and behind the reads
+    BatchBuf<uint64_t> off;
+    // cm_reads_stage_text, flag bit 2 (R1) / 4 (R2): the file's names, name i = names[name_off[i] .. name_off[i + 1]); allocated with the bit
     BatchBuf<uint8_t> names;
     BatchBuf<uint32_t> name_off;
     bool has_names = false;
     uint64_t name_bytes_max = 0;                 // no more name bytes than this (the host never learns the exact number)
-    // cm_reads_stage_text with flag bit 3: the quality lines of the batch in the layout of the bases, quality of read i =
-    // qual[off[i] .. off[i + 1]) (cm_format_sam); allocated only when the bit is given
-    BatchBuf<uint8_t> qual1, qual2;
-    bool has_quals = false;
-    uint64_t bases = 0;                          // with has_quals: off1[n] + off2[n]
-    // cm_reads_stage_text with flag bit 4: the R2 names of the batch, laid out as the R1 names are (cm_format_remain); allocated
-    // only when the bit is given
-    BatchBuf<uint8_t> names2;
-    BatchBuf<uint32_t> name_off2;
-    bool has_names2 = false;
-    uint64_t name2_bytes_max = 0;
+    // cm_reads_stage_text, flag bit 3: the file's quality lines, quality of read i = qual[off[i] .. off[i + 1]); allocated with the bit
+    BatchBuf<uint8_t> qual;
+    uint8_t *seq() const { return seq_base + cmc::CM_STAGE_PAD; }
 };
+// The read buffers of one batch, by mate file; a context has two (resident, staged) and cm_reads_swap exchanges them.
+struct ReadBufs {
+    ReadFile file[2];
+    bool has_quals = false;                      // flag bit 3 was given: both files' qualities are kept
+    uint64_t bases = 0;                          // with has_quals: off[n] of both files
+    void keep_nothing() { file[0].has_names = file[1].has_names = has_quals = false; }
+};
+// Buffer by buffer over the files, in the order the buffers came to be: one that has never allocated joins the other's lifetime
+// list here, and a batch's memory is freed in the order of that list.
 inline void swap(ReadBufs &a, ReadBufs &b) {
-    swap(a.seq1_base, b.seq1_base);
-    swap(a.seq2_base, b.seq2_base);
-    swap(a.off1, b.off1);
-    swap(a.off2, b.off2);
-    swap(a.names, b.names);
-    swap(a.name_off, b.name_off);
-    std::swap(a.has_names, b.has_names);
-    std::swap(a.name_bytes_max, b.name_bytes_max);
-    swap(a.qual1, b.qual1);
-    swap(a.qual2, b.qual2);
+    [[maybe_unused]] auto &[m1, m2, m3, m4, m5, m6, m7] = a.file[0];      // an eighth member does not compile until it changes places below
+    for (int f = 0; f < 2; ++f) swap(a.file[f].seq_base, b.file[f].seq_base);
+    for (int f = 0; f < 2; ++f) swap(a.file[f].off, b.file[f].off);
+    swap(a.file[0].names, b.file[0].names);
+    swap(a.file[0].name_off, b.file[0].name_off);
+    for (int f = 0; f < 2; ++f) swap(a.file[f].qual, b.file[f].qual);
+    swap(a.file[1].names, b.file[1].names);
+    swap(a.file[1].name_off, b.file[1].name_off);
+    for (int f = 0; f < 2; ++f) std::swap(a.file[f].has_names, b.file[f].has_names);
+    for (int f = 0; f < 2; ++f) std::swap(a.file[f].name_bytes_max, b.file[f].name_bytes_max);
     std::swap(a.has_quals, b.has_quals);
     std::swap(a.bases, b.bases);
-    swap(a.names2, b.names2);
-    swap(a.name_off2, b.name_off2);
-    std::swap(a.has_names2, b.has_names2);
-    std::swap(a.name2_bytes_max, b.name2_bytes_max);
 }
 
 // What the seeding of a tile leaves for its chain stage: the seed ranges of every probe, the DP-cell offsets of every chaining
@@ -2564,13 +2561,17 @@ struct cm_ctx {
     BatchBuf<uint8_t> d_active_b;             // the other parity: a round reads one array and writes the other
     BatchBuf<int32_t> d_cat;
     int n_seeds = 0, max_len = 0;
-    // staged batch (cm_reads_stage): a second set of read buffers filled on the copy stream while the resident batch is mapped
-    bool staged = false;
-    uint64_t st_n_pairs = 0;
-    ReadBufs st_rd;
-    BatchBuf<cm_mapped_read> st_prior;
-    bool st_has_prior = false;
-    int st_max_len = 0;
+    // The staged batch (cm_reads_stage, cm_reads_stage_text): a second set of read buffers filled on the copy stream while the
+    // resident batch is mapped.  stage_open and commit() write the record, cm_reads_swap and the prefetch of cm_map_rounds read it.
+    struct Staged {
+        bool ready = false, has_prior = false;    // a batch is staged and not yet swapped in; its carried states are in `prior`
+        uint64_t n_pairs = 0;
+        int max_len = 0;
+        ReadBufs rd;
+        BatchBuf<cm_mapped_read> prior;
+        void reset() { commit(0, 0, false, false), rd.keep_nothing(); }
+        void commit(uint64_t n, int len, bool carried, bool is_ready = true) { n_pairs = n, max_len = len, has_prior = carried, ready = is_ready; }
+    } staged;
     TextStage ft;                             // cm_reads_stage_text
     RowsBufs rows;                            // cm_format_pam, cm_format_sam
     // workspace of one tile
@@ -2679,8 +2680,7 @@ void free_reads(cm_ctx *c) {
     c->pset[0] = c->pset[1] = PairSet{};
     c->ones_cap = 0;
     c->pre_launched = c->pre_ready = false;
-    c->staged = false;
-    c->st_n_pairs = 0;
+    c->staged.reset();
     c->n_pairs = 0;
     c->tile = 0;
 }
@@ -2766,7 +2766,7 @@ int check_slot(cm_ctx *ctx, int slot, bool need_annot) {
     return CM_OK;
 }
 
-ReadsDev reads_dev(const ReadBufs &r) { return ReadsDev{r.seq1_base + cmc::CM_STAGE_PAD, r.seq2_base + cmc::CM_STAGE_PAD, r.off1, r.off2}; }
+ReadsDev reads_dev(const ReadBufs &r) { return ReadsDev{r.file[0].seq(), r.file[1].seq(), r.file[0].off, r.file[1].off}; }
 ReadsDev current_reads(const cm_ctx *ctx) { return reads_dev(ctx->rd); }
 
 constexpr unsigned HP_PLAN_GRID = 2048;      // workgroups of k_hp_plan (each with its own task-list scratch)
@@ -3540,12 +3540,16 @@ int cm_unload_contig(cm_ctx *ctx, int slot) {
     return CM_OK;
 }
 
+static int check_seeds(cm_ctx *ctx, int max_len) {
+    if (!cmft::too_many_seeds(max_len, ctx->P.kmer, cmc::MAX_SEEDS)) return CM_OK;
+    return fail(ctx, CM_ELIMIT, "%d seeds per read > %d supported", max_len / ctx->P.kmer, cmc::MAX_SEEDS);
+}
+
 // Validation shared by cm_reads_upload / cm_reads_stage; returns the longest read through *max_len_out.
 static int check_reads(cm_ctx *ctx, const cm_reads *rd, int *max_len_out) {
     const uint64_t n = rd->n_pairs;
     if (n > 0x3fffffffull) return fail(ctx, CM_ELIMIT, "more than 2^30 pairs in one batch");
     if (!rd->seq1 || !rd->seq2 || !rd->off1 || !rd->off2) return fail(ctx, CM_EINVAL, "null read arrays");
-    int max_len = 0;
     const uint64_t lim = (uint64_t)ctx->P.max_read_len;
     uint64_t bad = 0, longest = 0;
     // (2^21 pairs: 1.4 ms on one core, with the GPU idle when the call sits between two batches -- cm_reads_stage; ranges on a few threads)
@@ -3562,33 +3566,27 @@ static int check_reads(cm_ctx *ctx, const cm_reads *rd, int *max_len_out) {
     };
     const unsigned hw = std::thread::hardware_concurrency();
     const unsigned n_thr = n < (1u << 18) ? 1u : std::min(8u, hw ? hw : 1u);
-    if (n_thr <= 1) {
-        scan(0, n, &bad, &longest);
-    } else {
-        uint64_t bd[8] = {0}, lg[8] = {0};
-        std::thread th[8];
-        unsigned started = 1;
-        try {
-            for (; started < n_thr; ++started) th[started] = std::thread(scan, n * started / n_thr, n * (started + 1) / n_thr, &bd[started], &lg[started]);
-        } catch (...) {                                   // no more threads to be had: the rest of the ranges on this one
-        }
-        scan(0, n / n_thr, &bd[0], &lg[0]);
-        for (unsigned k = started; k < n_thr; ++k) scan(n * k / n_thr, n * (k + 1) / n_thr, &bd[k], &lg[k]);
-        for (unsigned k = 1; k < started; ++k) th[k].join();
-        for (unsigned k = 0; k < n_thr; ++k) {
-            if (bd[k] && !bad) bad = bd[k];                   // the first offending pair
-            if (lg[k] > longest) longest = lg[k];
-        }
+    uint64_t bd[8] = {0}, lg[8] = {0};
+    std::thread th[8];
+    unsigned started = 1;
+    try {
+        for (; started < n_thr; ++started) th[started] = std::thread(scan, n * started / n_thr, n * (started + 1) / n_thr, &bd[started], &lg[started]);
+    } catch (...) {                                       // no more threads to be had: the rest of the ranges on this one
+    }
+    scan(0, n / n_thr, &bd[0], &lg[0]);
+    for (unsigned k = started; k < n_thr; ++k) scan(n * k / n_thr, n * (k + 1) / n_thr, &bd[k], &lg[k]);
+    for (unsigned k = 1; k < started; ++k) th[k].join();
+    for (unsigned k = 0; k < n_thr; ++k) {
+        if (bd[k] && !bad) bad = bd[k];                       // the first offending pair
+        if (lg[k] > longest) longest = lg[k];
     }
     if (bad) {
         const uint64_t i = bad - 1;
         if (rd->off1[i + 1] < rd->off1[i] || rd->off2[i + 1] < rd->off2[i]) return fail(ctx, CM_EINVAL, "read offsets not monotone at pair %llu", (unsigned long long)i);
         return fail(ctx, CM_EINVAL, "pair %llu longer than max_read_len %d", (unsigned long long)i, ctx->P.max_read_len);
     }
-    max_len = (int)longest;
-    if (max_len / ctx->P.kmer > cmc::MAX_SEEDS) return fail(ctx, CM_ELIMIT, "%d seeds per read > %d supported", max_len / ctx->P.kmer, cmc::MAX_SEEDS);
-    *max_len_out = max_len;
-    return CM_OK;
+    *max_len_out = (int)longest;
+    return check_seeds(ctx, (int)longest);
 }
 
 // Pairs per tile (launch group) of a batch of n pairs.
@@ -3728,21 +3726,34 @@ static int prepare_resident(cm_ctx *ctx, uint64_t n, int max_len) {
 // cleared (cmc::stage over-reads into it), the reads themselves are overwritten by the copy.
 static int copy_reads(cm_ctx *ctx, const cm_reads *rd, hipStream_t st, ReadBufs &to) {
     const uint64_t n = rd->n_pairs;
-    const size_t b1 = (size_t)rd->off1[n] - (size_t)rd->off1[0], b2 = (size_t)rd->off2[n] - (size_t)rd->off2[0];
-    if (rd->off1[0] != 0 || rd->off2[0] != 0) return fail(ctx, CM_EINVAL, "read offsets must start at 0");
+    const uint8_t *const seq[2] = {rd->seq1, rd->seq2};
+    const uint64_t *const off[2] = {rd->off1, rd->off2};
+    const size_t bytes[2] = {(size_t)off[0][n] - (size_t)off[0][0], (size_t)off[1][n] - (size_t)off[1][0]};
+    if (off[0][0] != 0 || off[1][0] != 0) return fail(ctx, CM_EINVAL, "read offsets must start at 0");
     const size_t pad = cmc::CM_STAGE_PAD;                  // readable slack around the reads (see cmc::stage)
-    HIPCHK(ctx, ensure(ctx, to.seq1_base, b1 + 2 * pad));
-    HIPCHK(ctx, ensure(ctx, to.seq2_base, b2 + 2 * pad));
-    HIPCHK(ctx, ensure(ctx, to.off1, (n + 1) * sizeof(uint64_t)));
-    HIPCHK(ctx, ensure(ctx, to.off2, (n + 1) * sizeof(uint64_t)));
-    HIPCHK(ctx, hipMemsetAsync(to.seq1_base, 0, pad, st));
-    HIPCHK(ctx, hipMemsetAsync(to.seq1_base + pad + b1, 0, pad, st));
-    HIPCHK(ctx, hipMemsetAsync(to.seq2_base, 0, pad, st));
-    HIPCHK(ctx, hipMemsetAsync(to.seq2_base + pad + b2, 0, pad, st));
-    if (b1) HIPCHK(ctx, hipMemcpyAsync(to.seq1_base + pad, rd->seq1, b1, hipMemcpyHostToDevice, st));
-    if (b2) HIPCHK(ctx, hipMemcpyAsync(to.seq2_base + pad, rd->seq2, b2, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemcpyAsync(to.off1, rd->off1, (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemcpyAsync(to.off2, rd->off2, (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    for (int f = 0; f < 2; ++f) HIPCHK(ctx, ensure(ctx, to.file[f].seq_base, bytes[f] + 2 * pad));
+    for (int f = 0; f < 2; ++f) HIPCHK(ctx, ensure(ctx, to.file[f].off, (n + 1) * sizeof(uint64_t)));
+    for (int f = 0; f < 2; ++f) {
+        HIPCHK(ctx, hipMemsetAsync(to.file[f].seq_base, 0, pad, st));
+        HIPCHK(ctx, hipMemsetAsync(to.file[f].seq_base + pad + bytes[f], 0, pad, st));
+    }
+    for (int f = 0; f < 2; ++f)
+        if (bytes[f]) HIPCHK(ctx, hipMemcpyAsync(to.file[f].seq(), seq[f], bytes[f], hipMemcpyHostToDevice, st));
+    for (int f = 0; f < 2; ++f) HIPCHK(ctx, hipMemcpyAsync(to.file[f].off, off[f], (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    return CM_OK;
+}
+
+// A batch of n pairs becomes resident (cm_reads_upload, cm_reads_swap; n_pairs is 0 here and stays 0 on failure).  `after`: what the
+// main stream waits for first; `prior`: the carried states, the caller's on the host or the staged record's on the device (`kind`).
+static int make_resident(cm_ctx *ctx, uint64_t n, int max_len, hipEvent_t after, const cm_mapped_read *prior, hipMemcpyKind kind) {
+    if (int rc = prepare_resident(ctx, n, max_len)) return rc;
+    ctx->n_pairs = n;
+    if (after) HIPCHK(ctx, hipStreamWaitEvent(ctx->st.B, after, 0));
+    KCore k{};
+    k.P = ctx->P;
+    hipLaunchKernelGGL(k_init_state, dim3((unsigned)((n + BLK - 1) / BLK)), dim3(BLK), 0, ctx->st.B, k, ctx->d_state, ctx->d_active, ctx->d_cat, n);
+    // carried states: a pair is active unless the caller marks it retired by type < 0 (never produced by this library)
+    if (prior) HIPCHK(ctx, hipMemcpyAsync(ctx->d_state, prior, n * sizeof(cm_mapped_read), kind, ctx->st.B));
     return CM_OK;
 }
 
@@ -3758,22 +3769,19 @@ int cm_reads_upload(cm_ctx *ctx, const cm_reads *rd, const cm_mapped_read *prior
         free_reads(ctx);
         return CM_OK;
     }
-    int max_len = 0;
-    int rc = check_reads(ctx, rd, &max_len);
+    int max_len = 0, rc = check_reads(ctx, rd, &max_len);
     if (rc) return rc;
-    ctx->rd.has_names = ctx->rd.has_quals = ctx->rd.has_names2 = false;
-    if ((rc = copy_reads(ctx, rd, ctx->st.B, ctx->rd))) return rc;
-    if ((rc = prepare_resident(ctx, n, max_len))) return rc;
-    ctx->n_pairs = n;
-    KCore k{};
-    k.P = ctx->P;
-    hipLaunchKernelGGL(k_init_state, dim3((unsigned)((n + BLK - 1) / BLK)), dim3(BLK), 0, ctx->st.B, k, ctx->d_state, ctx->d_active, ctx->d_cat, n);
-    if (prior) {
-        // carried state of an earlier round: a pair is active unless the caller marks it retired
-        // by type < 0 (never produced by this library); active flags are otherwise all 1.
-        HIPCHK(ctx, hipMemcpyAsync(ctx->d_state, prior, n * sizeof(cm_mapped_read), hipMemcpyHostToDevice, ctx->st.B));
-    }
+    ctx->rd.keep_nothing();
+    if ((rc = copy_reads(ctx, rd, ctx->st.B, ctx->rd)) || (rc = make_resident(ctx, n, max_len, nullptr, prior, hipMemcpyHostToDevice))) return rc;
     HIPCHK(ctx, hipStreamSynchronize(ctx->st.B));
+    return CM_OK;
+}
+
+// A stage opens behind the copy stream: an earlier staged batch that was never swapped in is dropped (refusals for the arguments come first)
+static int stage_open(cm_ctx *ctx) {
+    HIPCHK(ctx, hipStreamSynchronize(ctx->st.C));
+    ctx->staged.reset();
+    ctx->pre_launched = false;
     return CM_OK;
 }
 
@@ -3781,107 +3789,148 @@ int cm_reads_stage(cm_ctx *ctx, const cm_reads *rd, const cm_mapped_read *prior)
     if (!ctx || !rd) return CM_EINVAL;
     HIPCHK(ctx, hipSetDevice(ctx->P.device));
     if (rd->n_pairs == 0) return fail(ctx, CM_EINVAL, "cm_reads_stage: empty batch");
-    int max_len = 0;
-    int rc = check_reads(ctx, rd, &max_len);
-    if (rc) return rc;
-    HIPCHK(ctx, hipStreamSynchronize(ctx->st.C));          // an earlier staged batch that was never swapped in is dropped
-    ctx->staged = false;
-    ctx->pre_launched = false;
-    ctx->st_rd.has_names = ctx->st_rd.has_quals = ctx->st_rd.has_names2 = false;
-    if ((rc = copy_reads(ctx, rd, ctx->st.C, ctx->st_rd))) return rc;
-    ctx->st_has_prior = prior != nullptr;
+    int max_len = 0, rc = check_reads(ctx, rd, &max_len);
+    if (rc || (rc = stage_open(ctx)) || (rc = copy_reads(ctx, rd, ctx->st.C, ctx->staged.rd))) return rc;
     if (prior) {
-        HIPCHK(ctx, ensure(ctx, ctx->st_prior, rd->n_pairs * sizeof(cm_mapped_read)));
-        HIPCHK(ctx, hipMemcpyAsync(ctx->st_prior, prior, rd->n_pairs * sizeof(cm_mapped_read), hipMemcpyHostToDevice, ctx->st.C));
+        HIPCHK(ctx, ensure(ctx, ctx->staged.prior, rd->n_pairs * sizeof(cm_mapped_read)));
+        HIPCHK(ctx, hipMemcpyAsync(ctx->staged.prior, prior, rd->n_pairs * sizeof(cm_mapped_read), hipMemcpyHostToDevice, ctx->st.C));
     }
     HIPCHK(ctx, hipEventRecord(ctx->ev.staged, ctx->st.C));
-    ctx->st_n_pairs = rd->n_pairs;
-    ctx->st_max_len = max_len;
-    ctx->staged = true;
+    ctx->staged.commit(rd->n_pairs, max_len, prior != nullptr);
+    return CM_OK;
+}
+
+// The steps of cm_reads_stage_text (below), in its order.  First the staged read buffers and the tokeniser's own, sized by the plan; the
+// result block cleared, the two blocks on their way.
+static int ft_begin(cm_ctx *ctx, const cmft::Sizes &S, const uint8_t *const text[2], const uint64_t len[2]) {
+    TextStage &T = ctx->ft;
+    const size_t words = (size_t)S.nb + 1;
+    for (int f = 0; f < 2; ++f) HIPCHK(ctx, ensure(ctx, ctx->staged.rd.file[f].seq_base, len[f] + 2 * cmc::CM_STAGE_PAD));
+    for (int f = 0; f < 2; ++f) HIPCHK(ctx, ensure(ctx, ctx->staged.rd.file[f].off, words * sizeof(uint64_t)));
+    HIPCHK(ctx, ensure(ctx, T.res, cmft::RES_WORDS * sizeof(unsigned long long)));
+    for (int f = 0; f < 2; ++f) {
+        HIPCHK(ctx, ensure(ctx, T.text[f], (len[f] + 15) / 16 * 16 + cmft::TEXT_SLACK));
+        HIPCHK(ctx, ensure(ctx, T.cnt[f], ((size_t)S.n_chunks[f] + 1) * sizeof(uint32_t)));
+        HIPCHK(ctx, ensure(ctx, T.ls[f], (size_t)S.ls_cap[f] * sizeof(uint32_t)));
+        HIPCHK(ctx, ensure(ctx, T.slen[f], words * sizeof(uint32_t)));
+        HIPCHK(ctx, ensure(ctx, T.rec[f], words * sizeof(uint64_t)));
+    }
+    HIPCHK(ctx, ensure(ctx, T.tmp, (size_t)(S.scan_items / S32_B + 2) * sizeof(uint32_t)));
+    HIPCHK(ctx, hipMemsetAsync(T.res, 0xff, 2 * sizeof(unsigned long long), ctx->st.C));                   // RES_BAD1, RES_BAD2: none
+    HIPCHK(ctx, hipMemsetAsync(T.res + cmft::RES_MAX_LEN, 0, sizeof(unsigned long long), ctx->st.C));
+    for (int f = 0; f < 2; ++f)
+        if (len[f]) HIPCHK(ctx, hipMemcpyAsync(T.text[f], text[f], len[f], hipMemcpyHostToDevice, ctx->st.C));
+    return CM_OK;
+}
+// lines of both files (counts, scan, line starts), then their records (verdicts + lengths, scan, offsets, the bases), the result block
+static int ft_tokenise(cm_ctx *ctx, const cmft::Sizes &S, const FtShape &sh, const uint64_t len[2]) {
+    TextStage &T = ctx->ft;
+    const ReadFile *to = ctx->staged.rd.file;
+    hipStream_t st = ctx->st.C;
+    for (int f = 0; f < 2; ++f) {
+        const uint32_t nc = S.n_chunks[f];
+        hipLaunchKernelGGL(k_ft_count, dim3(nc / FT_WAVES + 1), dim3(FT_T), 0, st, (const uint8_t *)T.text[f], len[f], nc, (uint32_t *)T.cnt[f]);
+        if (int rc = scan32_on(ctx, st, T.cnt[f], (uint64_t)nc + 1, T.cnt[f], T.tmp, 0u, 0)) return rc;
+        hipLaunchKernelGGL(k_ft_lines, dim3((nc + FT_WAVES - 1) / FT_WAVES + 1), dim3(FT_T), 0, st, (const uint8_t *)T.text[f], len[f], nc, (const uint32_t *)T.cnt[f],
+                           S.trail[f], (uint32_t *)T.ls[f], S.ls_cap[f]);
+    }
+    for (int f = 0; f < 2; ++f) {
+        const unsigned gb = S.nb / FT_T + 1;                  // covers i = 0 .. S.nb
+        hipLaunchKernelGGL(k_ft_records, dim3(gb), dim3(FT_T), 0, st, (const uint8_t *)T.text[f], (const uint32_t *)T.ls[f], sh, f, S.nb, (uint32_t *)T.slen[f],
+                           (unsigned long long *)T.res);
+        if (int rc = scan32_on(ctx, st, T.slen[f], (uint64_t)S.nb + 1, T.slen[f], T.tmp, 0u, 0)) return rc;
+        hipLaunchKernelGGL(k_ft_offsets, dim3(gb), dim3(FT_T), 0, st, (const uint32_t *)T.ls[f], (const uint32_t *)T.slen[f], sh, len[f], (uint64_t *)to[f].off,
+                           (uint64_t *)T.rec[f]);
+        const unsigned gc = (unsigned)std::min<uint64_t>(((uint64_t)S.nb * cmft::COPY_LANES + FT_T - 1) / FT_T + 1, 1u << 16);
+        hipLaunchKernelGGL(k_ft_copy, dim3(gc), dim3(FT_T), 0, st, (const uint8_t *)T.text[f], (const uint32_t *)T.ls[f], (const uint64_t *)to[f].off, sh,
+                           (uint8_t *)to[f].seq_base);
+    }
+    hipLaunchKernelGGL(k_ft_finish, dim3(1), dim3(1), 0, st, sh, (const uint64_t *)to[0].off, (const uint64_t *)to[1].off, (const uint64_t *)T.rec[0],
+                       (const uint64_t *)T.rec[1], (unsigned long long *)T.res);
+    HIPCHK(ctx, hipGetLastError());
+    return CM_OK;
+}
+// the refusal a verdict stands for, in the words of next_plain / build_side / check_reads
+static int ft_refusal(cm_ctx *ctx, const cmft::Verdict &v) {
+    static const char *const bad[] = {"", "the header line is empty or does not start with '@'", "the third line is empty or does not start with '+'",
+                                      "the quality line is not as long as the sequence line", "a 23-token header (carried state: take cm_fastq_next)"};
+    switch (v.what) {
+    case cmft::LINES_LEFT: return fail(ctx, v.code, "FASTQ file %d: %llu lines behind its last whole record", v.file + 1, v.count);
+    case cmft::FILE2_SHORT: return fail(ctx, v.code, "FASTQ file 2 ends before file 1");
+    case cmft::MALFORMED: return fail(ctx, v.code, "FASTQ file %d, record %llu of the block: %s", v.file + 1, v.record, bad[v.count]);
+    case cmft::READ_TOO_LONG: return fail(ctx, v.code, "a read of %llu bases is longer than max_read_len %d", v.count, ctx->P.max_read_len);
+    case cmft::TOO_MANY_SEEDS: return check_seeds(ctx, (int)v.count);
+    default: return CM_OK;                                  // ACCEPTED
+    }
+}
+// Flag bit 2 (f = 0) / 4 (f = 1): file f's names stay with the staged batch.  Sized by the read-back: no longer than the
+// header lines, which are what the consumed text holds besides bases and qualities.  ev.staged moves behind them; nobody waits here.
+static int ft_keep_names(cm_ctx *ctx, int f, uint64_t n, uint64_t used, uint64_t bases) {
+    TextStage &T = ctx->ft;
+    ReadFile &to = ctx->staged.rd.file[f];
+    hipStream_t st = ctx->st.C;
+    const uint64_t name_max = used - std::min<uint64_t>(used, 2 * bases);
+    HIPCHK(ctx, ensure(ctx, to.names, (size_t)name_max + 4));
+    HIPCHK(ctx, ensure(ctx, to.name_off, ((size_t)n + 1) * sizeof(uint32_t)));
+    HIPCHK(ctx, ensure(ctx, T.nstart, ((size_t)n + 1) * sizeof(uint32_t)));
+    const unsigned gn = (unsigned)(n / FT_T + 1);            // covers i = 0 .. n
+    hipLaunchKernelGGL(k_ft_name_len, dim3(gn), dim3(FT_T), 0, st, (const uint8_t *)T.text[f], (const uint32_t *)T.ls[f], (uint32_t)n, (uint32_t *)T.nstart,
+                       (uint32_t *)to.name_off);
+    if (int rc = scan32_on(ctx, st, to.name_off, n + 1, to.name_off, T.tmp, 0u, 0)) return rc;
+    const unsigned gc = (unsigned)std::min<uint64_t>((n * cmft::COPY_LANES + FT_T - 1) / FT_T, 1u << 16);
+    hipLaunchKernelGGL(k_ft_name_copy, dim3(gc), dim3(FT_T), 0, st, (const uint8_t *)T.text[f], (const uint32_t *)T.nstart, (const uint32_t *)to.name_off, (uint32_t)n,
+                       (uint8_t *)to.names);
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipEventRecord(ctx->ev.staged, st));
+    to.has_names = true;
+    to.name_bytes_max = name_max;
+    return CM_OK;
+}
+// Flag bit 3: both files' quality lines into arrays that share the offsets with the bases; a word of slack: the formatter reads whole words
+static int ft_keep_quals(cm_ctx *ctx, uint64_t n, const uint64_t bases[2]) {
+    TextStage &T = ctx->ft;
+    ReadBufs &to = ctx->staged.rd;
+    for (int f = 0; f < 2; ++f) HIPCHK(ctx, ensure(ctx, to.file[f].qual, (size_t)bases[f] + 8));
+    const unsigned gc = (unsigned)std::min<uint64_t>((n * cmft::COPY_LANES + FT_T - 1) / FT_T, 1u << 16);
+    for (int f = 0; f < 2; ++f)
+        hipLaunchKernelGGL(k_ft_qual_copy, dim3(gc), dim3(FT_T), 0, ctx->st.C, (const uint8_t *)T.text[f], (const uint32_t *)T.ls[f], (const uint64_t *)to.file[f].off,
+                           (uint32_t)n, (uint8_t *)to.file[f].qual);
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipEventRecord(ctx->ev.staged, ctx->st.C));
+    to.has_quals = true;
+    to.bases = bases[0] + bases[1];
     return CM_OK;
 }
 
 // cm_reads_stage for FASTQ text: the two blocks go over PCIe as they are and the kernels k_ft_* (bodies: cm_fastq_text.h) find the
 // lines, check every record and fill the staged read buffers, all on the staging stream.  The batch's shape is known on the device
-// only; the host sizes everything from the text lengths (bases <= bytes, a record has at least four bytes) and learns the shape and
-// the verdicts from one small read-back.
+// only; the host sizes everything from the text lengths (cmft::plan_sizes) and learns the shape and the verdicts from one small
+// read-back (cmft::verdict).
 int cm_reads_stage_text(cm_ctx *ctx, const uint8_t *text1, uint64_t len1, const uint8_t *text2, uint64_t len2, uint64_t max_pairs, uint32_t flags,
                         uint64_t *rec1, uint64_t *rec2, cm_text_batch *out) {
     if (!ctx || !out) return CM_EINVAL;
     memset(out, 0, sizeof *out);
     HIPCHK(ctx, hipSetDevice(ctx->P.device));
-    const uint8_t *text[2] = {text1, text2};
+    const uint8_t *const text[2] = {text1, text2};
     const uint64_t len[2] = {len1, len2};
-    uint32_t trail[2];
-    for (int f = 0; f < 2; ++f) {
-        if (len[f] && !text[f]) return fail(ctx, CM_EINVAL, "cm_reads_stage_text: null text");
-        trail[f] = ((flags >> f) & 1u) && len[f] && text[f][len[f] - 1] != '\n';
-        // (the sentinel behind a last line without '\n' is len + 1, a uint32 like every line start)
-        if (len[f] > 0xffffffffull - trail[f]) return fail(ctx, CM_ELIMIT, "cm_reads_stage_text: a block of %llu bytes", (unsigned long long)len[f]);
-    }
-    const uint64_t mp = std::min<uint64_t>(max_pairs, 1ull << 30);           // (a block below 2^32 bytes holds fewer records than that)
-    const uint32_t nb = (uint32_t)std::min<uint64_t>(mp, std::min(len1, len2) / 4);      // no more pairs than this: four bytes per record at least
-    HIPCHK(ctx, hipStreamSynchronize(ctx->st.C));          // an earlier staged batch that was never swapped in is dropped
-    ctx->staged = false;
-    ctx->pre_launched = false;
+    cmft::Sizes S;
+    int rc, file = 0;
+    if ((rc = cmft::plan_sizes(text, len, max_pairs, flags, &S, &file)))      // refused for its arguments: an earlier staged batch stays
+        return rc == CM_EINVAL ? fail(ctx, rc, "cm_reads_stage_text: null text") : fail(ctx, rc, "cm_reads_stage_text: a block of %llu bytes", (unsigned long long)len[file]);
+    if ((rc = stage_open(ctx)) || (rc = ft_begin(ctx, S, text, len))) return rc;
     TextStage &T = ctx->ft;
     hipStream_t st = ctx->st.C;
-    const size_t pad = cmc::CM_STAGE_PAD;
-    uint32_t n_chunks[2], ls_cap[2];
-    ReadBufs &to = ctx->st_rd;
-    to.has_names = to.has_quals = to.has_names2 = false;
-    HIPCHK(ctx, ensure(ctx, to.seq1_base, len1 + 2 * pad));
-    HIPCHK(ctx, ensure(ctx, to.seq2_base, len2 + 2 * pad));
-    HIPCHK(ctx, ensure(ctx, to.off1, ((size_t)nb + 1) * sizeof(uint64_t)));
-    HIPCHK(ctx, ensure(ctx, to.off2, ((size_t)nb + 1) * sizeof(uint64_t)));
-    HIPCHK(ctx, ensure(ctx, T.res, cmft::RES_WORDS * sizeof(unsigned long long)));
-    uint64_t scan_items = (uint64_t)nb + 1;
-    for (int f = 0; f < 2; ++f) {
-        n_chunks[f] = (uint32_t)((len[f] + cmft::NL_CHUNK - 1) / cmft::NL_CHUNK);
-        ls_cap[f] = (uint32_t)std::min<uint64_t>(len[f] + 2, 4 * mp + 1);
-        scan_items = std::max<uint64_t>(scan_items, (uint64_t)n_chunks[f] + 1);
-        HIPCHK(ctx, ensure(ctx, T.text[f], (len[f] + 15) / 16 * 16 + cmft::TEXT_SLACK));
-        HIPCHK(ctx, ensure(ctx, T.cnt[f], ((size_t)n_chunks[f] + 1) * sizeof(uint32_t)));
-        HIPCHK(ctx, ensure(ctx, T.ls[f], (size_t)ls_cap[f] * sizeof(uint32_t)));
-        HIPCHK(ctx, ensure(ctx, T.slen[f], ((size_t)nb + 1) * sizeof(uint32_t)));
-        HIPCHK(ctx, ensure(ctx, T.rec[f], ((size_t)nb + 1) * sizeof(uint64_t)));
-    }
-    HIPCHK(ctx, ensure(ctx, T.tmp, (size_t)(scan_items / S32_B + 2) * sizeof(uint32_t)));
-    HIPCHK(ctx, hipMemsetAsync(T.res, 0xff, 2 * sizeof(unsigned long long), st));                          // RES_BAD1, RES_BAD2: none
-    HIPCHK(ctx, hipMemsetAsync(T.res + cmft::RES_MAX_LEN, 0, sizeof(unsigned long long), st));
-    int rc;
-    for (int f = 0; f < 2; ++f)
-        if (len[f]) HIPCHK(ctx, hipMemcpyAsync(T.text[f], text[f], len[f], hipMemcpyHostToDevice, st));
     hipEvent_t t_a = nullptr, t_b = nullptr;                // cm_prof_enable: the kernels' time, copies excluded (cm_text_batch.reserved)
     if (ctx->prof) {
         t_a = take_event(ctx);
         t_b = take_event(ctx);
         if (t_a) HIPCHK(ctx, hipEventRecord(t_a, st));
     }
-    for (int f = 0; f < 2; ++f) {                           // lines of both files
-        hipLaunchKernelGGL(k_ft_count, dim3(n_chunks[f] / FT_WAVES + 1), dim3(FT_T), 0, st, (const uint8_t *)T.text[f], len[f], n_chunks[f], (uint32_t *)T.cnt[f]);
-        if ((rc = scan32_on(ctx, st, T.cnt[f], (uint64_t)n_chunks[f] + 1, T.cnt[f], T.tmp, 0u, 0))) return rc;
-        hipLaunchKernelGGL(k_ft_lines, dim3((n_chunks[f] + FT_WAVES - 1) / FT_WAVES + 1), dim3(FT_T), 0, st, (const uint8_t *)T.text[f], len[f], n_chunks[f],
-                           (const uint32_t *)T.cnt[f], trail[f], (uint32_t *)T.ls[f], ls_cap[f]);
-    }
-    const FtShape sh{T.cnt[0] + n_chunks[0], T.cnt[1] + n_chunks[1], trail[0], trail[1], mp};
-    for (int f = 0; f < 2; ++f) {                           // records of both files: the batch is the shorter file's
-        uint8_t *seq_base = f ? to.seq2_base : to.seq1_base;
-        uint64_t *off = f ? to.off2 : to.off1;
-        const unsigned gb = nb / FT_T + 1;                  // covers i = 0 .. nb
-        hipLaunchKernelGGL(k_ft_records, dim3(gb), dim3(FT_T), 0, st, (const uint8_t *)T.text[f], (const uint32_t *)T.ls[f], sh, f, nb, (uint32_t *)T.slen[f],
-                           (unsigned long long *)T.res);
-        if ((rc = scan32_on(ctx, st, T.slen[f], (uint64_t)nb + 1, T.slen[f], T.tmp, 0u, 0))) return rc;
-        hipLaunchKernelGGL(k_ft_offsets, dim3(gb), dim3(FT_T), 0, st, (const uint32_t *)T.ls[f], (const uint32_t *)T.slen[f], sh, len[f], off, (uint64_t *)T.rec[f]);
-        const unsigned gc = (unsigned)std::min<uint64_t>(((uint64_t)nb * cmft::COPY_LANES + FT_T - 1) / FT_T + 1, 1u << 16);
-        hipLaunchKernelGGL(k_ft_copy, dim3(gc), dim3(FT_T), 0, st, (const uint8_t *)T.text[f], (const uint32_t *)T.ls[f], (const uint64_t *)off, sh, seq_base);
-    }
-    hipLaunchKernelGGL(k_ft_finish, dim3(1), dim3(1), 0, st, sh, (const uint64_t *)to.off1, (const uint64_t *)to.off2, (const uint64_t *)T.rec[0],
-                       (const uint64_t *)T.rec[1], (unsigned long long *)T.res);
-    HIPCHK(ctx, hipGetLastError());
+    const FtShape sh{T.cnt[0] + S.n_chunks[0], T.cnt[1] + S.n_chunks[1], S.trail[0], S.trail[1], S.max_pairs};
+    if ((rc = ft_tokenise(ctx, S, sh, len))) return rc;
     HIPCHK(ctx, hipEventRecord(ctx->ev.staged, st));       // behind the last tokeniser kernel: the cross-batch prefetch reads the buffers behind it
     if (t_a && t_b) HIPCHK(ctx, hipEventRecord(t_b, st));
-    unsigned long long *R = ctx->h_pin + PIN_TEXT;
+    unsigned long long *R = ctx->h_pin + PIN_TEXT;          // the read-back
     HIPCHK(ctx, hipMemcpyAsync(R, T.res, cmft::RES_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipStreamSynchronize(st));
     if (t_a && t_b) {
@@ -3890,92 +3939,35 @@ int cm_reads_stage_text(cm_ctx *ctx, const uint8_t *text1, uint64_t len1, const 
     }
     for (hipEvent_t e : {t_a, t_b})
         if (e) ctx->ev_free.push_back(e);
-    const uint64_t n = R[cmft::RES_PAIRS], lines[2] = {R[cmft::RES_LINES1], R[cmft::RES_LINES2]};
-    // the verdicts of next_plain / build_side / check_reads
-    for (int f = 0; f < 2; ++f)
-        if (((flags >> f) & 1u) && lines[f] % 4 != 0 && lines[f] / 4 < max_pairs)
-            return fail(ctx, CM_EINVAL, "FASTQ file %d: %llu lines behind its last whole record", f + 1, (unsigned long long)(lines[f] % 4));
-    if ((flags & 2u) && lines[1] / 4 < std::min<uint64_t>(lines[0] / 4, max_pairs)) return fail(ctx, CM_EINVAL, "FASTQ file 2 ends before file 1");
-    for (int f = 0; f < 2; ++f) {
-        const unsigned long long key = R[cmft::RES_BAD1 + f];
-        if (key == cmft::NO_BAD || (key & 7u) == cmft::BAD_CARRIED) continue;
-        static const char *const what[] = {"", "the header line is empty or does not start with '@'", "the third line is empty or does not start with '+'",
-                                           "the quality line is not as long as the sequence line"};
-        return fail(ctx, CM_EINVAL, "FASTQ file %d, record %llu of the block: %s", f + 1, key >> 3, what[key & 3u]);
-    }
-    if (R[cmft::RES_BAD1] != cmft::NO_BAD)
-        return fail(ctx, CM_EINVAL, "FASTQ file 1, record %llu of the block: a 23-token header (carried state: take cm_fastq_next)", R[cmft::RES_BAD1] >> 3);
-    const uint64_t max_len = R[cmft::RES_MAX_LEN];
-    if (max_len > (uint64_t)ctx->P.max_read_len) return fail(ctx, CM_EINVAL, "a read of %llu bases is longer than max_read_len %d", (unsigned long long)max_len, ctx->P.max_read_len);
-    if ((int)max_len / ctx->P.kmer > cmc::MAX_SEEDS) return fail(ctx, CM_ELIMIT, "%d seeds per read > %d supported", (int)max_len / ctx->P.kmer, cmc::MAX_SEEDS);
-    out->n_pairs = n;
-    out->used1 = R[cmft::RES_USED1];
-    out->used2 = R[cmft::RES_USED2];
-    out->max_len = (int32_t)max_len;
+    if ((rc = ft_refusal(ctx, cmft::verdict(R, flags, max_pairs, ctx->P.max_read_len, ctx->P.kmer, cmc::MAX_SEEDS)))) return rc;
+    *out = cm_text_batch{R[cmft::RES_PAIRS], R[cmft::RES_USED1], R[cmft::RES_USED2], (int32_t)R[cmft::RES_MAX_LEN], out->reserved};
+    const uint64_t n = out->n_pairs, used[2] = {R[cmft::RES_USED1], R[cmft::RES_USED2]}, bases[2] = {R[cmft::RES_BASES1], R[cmft::RES_BASES2]};
     if (n == 0) return CM_OK;                               // nothing staged: the caller supplies more bytes
     if (rec1) HIPCHK(ctx, hipMemcpyAsync(rec1, T.rec[0], (n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
     if (rec2) HIPCHK(ctx, hipMemcpyAsync(rec2, T.rec[1], (n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
     if (rec1 || rec2) HIPCHK(ctx, hipStreamSynchronize(st));
-    if (flags & 4u) {
-        // Keep the R1 names: their lengths (a lane per record), a scan, a word-wise copy into a compact array.  Queued here, behind
-        // the read-back, because only now the host can size the array: the names are no longer than the header lines, which are
-        // what the consumed text holds besides bases and qualities.  ev.staged moves behind them: the formatter reads the names on
-        // the mapping stream, which waits for that event in cm_reads_swap.  Nobody waits here.
-        const uint64_t name_max = R[cmft::RES_USED1] - std::min<uint64_t>(R[cmft::RES_USED1], 2 * R[cmft::RES_BASES1]);
-        HIPCHK(ctx, ensure(ctx, to.names, (size_t)name_max + 4));
-        HIPCHK(ctx, ensure(ctx, to.name_off, ((size_t)n + 1) * sizeof(uint32_t)));
-        HIPCHK(ctx, ensure(ctx, T.nstart, ((size_t)n + 1) * sizeof(uint32_t)));
-        const unsigned gn = (unsigned)(n / FT_T + 1);            // covers i = 0 .. n
-        hipLaunchKernelGGL(k_ft_name_len, dim3(gn), dim3(FT_T), 0, st, (const uint8_t *)T.text[0], (const uint32_t *)T.ls[0], (uint32_t)n, (uint32_t *)T.nstart,
-                           (uint32_t *)to.name_off);
-        if ((rc = scan32_on(ctx, st, to.name_off, n + 1, to.name_off, T.tmp, 0u, 0))) return rc;
-        const unsigned gc = (unsigned)std::min<uint64_t>((n * cmft::COPY_LANES + FT_T - 1) / FT_T, 1u << 16);
-        hipLaunchKernelGGL(k_ft_name_copy, dim3(gc), dim3(FT_T), 0, st, (const uint8_t *)T.text[0], (const uint32_t *)T.nstart, (const uint32_t *)to.name_off,
-                           (uint32_t)n, (uint8_t *)to.names);
-        HIPCHK(ctx, hipGetLastError());
-        HIPCHK(ctx, hipEventRecord(ctx->ev.staged, st));
-        to.has_names = true;
-        to.name_bytes_max = name_max;
-    }
-    if (flags & 8u) {
-        // Keep the qualities: the quality line of every staged record of both files, copied word-wise into arrays that share off1 /
-        // off2 with the bases (the stage has verified that the lines are as long).  Behind the read-back, which gives the sizes, like
-        // the names; ev.staged moves behind the copies.  A word of slack: the formatter reads whole words.
-        const uint64_t bases[2] = {R[cmft::RES_BASES1], R[cmft::RES_BASES2]};
-        HIPCHK(ctx, ensure(ctx, to.qual1, (size_t)bases[0] + 8));
-        HIPCHK(ctx, ensure(ctx, to.qual2, (size_t)bases[1] + 8));
-        const unsigned gc = (unsigned)std::min<uint64_t>((n * cmft::COPY_LANES + FT_T - 1) / FT_T, 1u << 16);
-        for (int f = 0; f < 2; ++f)
-            hipLaunchKernelGGL(k_ft_qual_copy, dim3(gc), dim3(FT_T), 0, st, (const uint8_t *)T.text[f], (const uint32_t *)T.ls[f],
-                               (const uint64_t *)(f ? to.off2 : to.off1), (uint32_t)n, (uint8_t *)(f ? to.qual2 : to.qual1));
-        HIPCHK(ctx, hipGetLastError());
-        HIPCHK(ctx, hipEventRecord(ctx->ev.staged, st));
-        to.has_quals = true;
-        to.bases = bases[0] + bases[1];
-    }
-    if (flags & 16u) {
-        // Keep the R2 names: what bit 2 does for file 1, for file 2, into arrays of their own.  The name starts share T.nstart with
-        // bit 2 (n + 1 words either way, so the buffer does not move): the staging stream runs the two one after the other.
-        const uint64_t name_max = R[cmft::RES_USED2] - std::min<uint64_t>(R[cmft::RES_USED2], 2 * R[cmft::RES_BASES2]);
-        HIPCHK(ctx, ensure(ctx, to.names2, (size_t)name_max + 4));
-        HIPCHK(ctx, ensure(ctx, to.name_off2, ((size_t)n + 1) * sizeof(uint32_t)));
-        HIPCHK(ctx, ensure(ctx, T.nstart, ((size_t)n + 1) * sizeof(uint32_t)));
-        const unsigned gn = (unsigned)(n / FT_T + 1);            // covers i = 0 .. n
-        hipLaunchKernelGGL(k_ft_name_len, dim3(gn), dim3(FT_T), 0, st, (const uint8_t *)T.text[1], (const uint32_t *)T.ls[1], (uint32_t)n, (uint32_t *)T.nstart,
-                           (uint32_t *)to.name_off2);
-        if ((rc = scan32_on(ctx, st, to.name_off2, n + 1, to.name_off2, T.tmp, 0u, 0))) return rc;
-        const unsigned gc = (unsigned)std::min<uint64_t>((n * cmft::COPY_LANES + FT_T - 1) / FT_T, 1u << 16);
-        hipLaunchKernelGGL(k_ft_name_copy, dim3(gc), dim3(FT_T), 0, st, (const uint8_t *)T.text[1], (const uint32_t *)T.nstart, (const uint32_t *)to.name_off2,
-                           (uint32_t)n, (uint8_t *)to.names2);
-        HIPCHK(ctx, hipGetLastError());
-        HIPCHK(ctx, hipEventRecord(ctx->ev.staged, st));
-        to.has_names2 = true;
-        to.name2_bytes_max = name_max;
-    }
-    ctx->st_has_prior = false;
-    ctx->st_n_pairs = n;
-    ctx->st_max_len = (int)max_len;
-    ctx->staged = true;
+    // kept data, on the staging stream in this order: R1 names, qualities, R2 names
+    if ((flags & 4u) && (rc = ft_keep_names(ctx, 0, n, used[0], bases[0]))) return rc;
+    if ((flags & 8u) && (rc = ft_keep_quals(ctx, n, bases))) return rc;
+    if ((flags & 16u) && (rc = ft_keep_names(ctx, 1, n, used[1], bases[1]))) return rc;
+    ctx->staged.commit(n, out->max_len, false);
+    return CM_OK;
+}
+
+// The peeks: per file of the resident batch src[0 .. off[n]) into dst (nullable; cap bytes of room) and, where asked for, the n + 1 offsets
+struct Peek { uint8_t *dst; uint64_t cap; const uint8_t *src; uint64_t *off_out; };
+static int peek_files(cm_ctx *ctx, const char *fn, const char *noun, const Peek (&p)[2]) {
+    const uint64_t n = ctx->n_pairs;
+    hipStream_t st = ctx->st.B;
+    uint64_t total[2] = {0, 0};
+    for (int f = 0; f < 2; ++f) HIPCHK(ctx, hipMemcpyAsync(&total[f], ctx->rd.file[f].off + n, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    for (int f = 0; f < 2; ++f)
+        if (p[f].off_out) HIPCHK(ctx, hipMemcpyAsync(p[f].off_out, ctx->rd.file[f].off, (n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    if ((p[0].dst && p[0].cap < total[0]) || (p[1].dst && p[1].cap < total[1])) return fail(ctx, CM_ELIMIT, "%s: %llu / %llu %s bytes", fn, (unsigned long long)total[0], (unsigned long long)total[1], noun);
+    for (int f = 0; f < 2; ++f)
+        if (p[f].dst && total[f]) HIPCHK(ctx, hipMemcpyAsync(p[f].dst, p[f].src, total[f], hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
     return CM_OK;
 }
 
@@ -3983,44 +3975,26 @@ int cm_reads_stage_text(cm_ctx *ctx, const uint8_t *text1, uint64_t len1, const 
 int cm_reads_peek(cm_ctx *ctx, uint8_t *seq1, uint64_t cap1, uint64_t *off1, uint8_t *seq2, uint64_t cap2, uint64_t *off2, uint64_t *n_pairs) {
     if (!ctx || !n_pairs) return CM_EINVAL;
     HIPCHK(ctx, hipSetDevice(ctx->P.device));
-    const uint64_t n = ctx->n_pairs;
-    *n_pairs = n;
-    if (n == 0 || (!seq1 && !seq2 && !off1 && !off2)) return CM_OK;
-    uint64_t total[2] = {0, 0};
-    HIPCHK(ctx, hipMemcpyAsync(&total[0], ctx->rd.off1 + n, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->st.B));
-    HIPCHK(ctx, hipMemcpyAsync(&total[1], ctx->rd.off2 + n, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->st.B));
-    if (off1) HIPCHK(ctx, hipMemcpyAsync(off1, ctx->rd.off1, (n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->st.B));
-    if (off2) HIPCHK(ctx, hipMemcpyAsync(off2, ctx->rd.off2, (n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->st.B));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->st.B));
-    if ((seq1 && cap1 < total[0]) || (seq2 && cap2 < total[1])) return fail(ctx, CM_ELIMIT, "cm_reads_peek: %llu / %llu read bytes", (unsigned long long)total[0], (unsigned long long)total[1]);
-    if (seq1 && total[0]) HIPCHK(ctx, hipMemcpyAsync(seq1, ctx->rd.seq1_base + cmc::CM_STAGE_PAD, total[0], hipMemcpyDeviceToHost, ctx->st.B));
-    if (seq2 && total[1]) HIPCHK(ctx, hipMemcpyAsync(seq2, ctx->rd.seq2_base + cmc::CM_STAGE_PAD, total[1], hipMemcpyDeviceToHost, ctx->st.B));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->st.B));
-    return CM_OK;
+    *n_pairs = ctx->n_pairs;
+    if (ctx->n_pairs == 0 || (!seq1 && !seq2 && !off1 && !off2)) return CM_OK;
+    const ReadFile *F = ctx->rd.file;
+    return peek_files(ctx, "cm_reads_peek", "read", {{seq1, cap1, F[0].seq(), off1}, {seq2, cap2, F[1].seq(), off2}});
 }
 
 int cm_reads_swap(cm_ctx *ctx) {
     if (!ctx) return CM_EINVAL;
     HIPCHK(ctx, hipSetDevice(ctx->P.device));
-    if (!ctx->staged) return fail(ctx, CM_ESTATE, "cm_reads_swap: no staged batch");
+    cm_ctx::Staged &sb = ctx->staged;
+    if (!sb.ready) return fail(ctx, CM_ESTATE, "cm_reads_swap: no staged batch");
     // work already queued on the mapping stream still reads the old buffers: order the swap behind it on the device
     // (no host wait), and the new batch's first kernel behind the staged copies
-    swap(ctx->rd, ctx->st_rd);
-    ctx->staged = false;
-    const uint64_t n = ctx->st_n_pairs;
+    swap(ctx->rd, sb.rd);
+    sb.ready = false;
     ctx->pre_ready = ctx->pre_launched;                            // cm_map_rounds prepared this batch's first round already
     ctx->pre_launched = false;
-    ctx->pre_n = n;
+    ctx->pre_n = sb.n_pairs;
     ctx->n_pairs = 0;
-    int rc = prepare_resident(ctx, n, ctx->st_max_len);
-    if (rc) return rc;
-    ctx->n_pairs = n;
-    HIPCHK(ctx, hipStreamWaitEvent(ctx->st.B, ctx->ev.staged, 0));
-    KCore k{};
-    k.P = ctx->P;
-    hipLaunchKernelGGL(k_init_state, dim3((unsigned)((n + BLK - 1) / BLK)), dim3(BLK), 0, ctx->st.B, k, ctx->d_state, ctx->d_active, ctx->d_cat, n);
-    if (ctx->st_has_prior)
-        HIPCHK(ctx, hipMemcpyAsync(ctx->d_state, ctx->st_prior, n * sizeof(cm_mapped_read), hipMemcpyDeviceToDevice, ctx->st.B));
+    if (int rc = make_resident(ctx, sb.n_pairs, sb.max_len, ctx->ev.staged, sb.has_prior ? (const cm_mapped_read *)sb.prior : nullptr, hipMemcpyDeviceToDevice)) return rc;
     // the next cm_reads_stage overwrites the buffers this swap retired: it must wait for the mapping stream's work on them
     HIPCHK(ctx, hipEventRecord(ctx->ev.retired, ctx->st.B));
     HIPCHK(ctx, hipStreamWaitEvent(ctx->st.C, ctx->ev.retired, 0));
@@ -4274,8 +4248,8 @@ static int map_rounds_issue(cm_ctx *ctx, const int *slots, int n_rounds, int las
     int rc;
     // Cross-batch prefetch (see the end of this function): possible when this call ends the batch and the next one is staged and fits
     // the workspace as it is sized now (nothing may be reallocated under the kernels in flight).
-    const bool prefetch = last_is_final && ctx->staged && ctx->st_n_pairs <= ctx->n_pairs && ctx->st_max_len <= ctx->max_len;
-    if (prefetch && ctx->ones_cap < ctx->st_n_pairs) {          // flags of a fresh batch: every pair active
+    const bool prefetch = last_is_final && ctx->staged.ready && ctx->staged.n_pairs <= ctx->n_pairs && ctx->staged.max_len <= ctx->max_len;
+    if (prefetch && ctx->ones_cap < ctx->staged.n_pairs) {          // flags of a fresh batch: every pair active
         HIPCHK(ctx, ensure(ctx, ctx->d_ones, ctx->n_pairs));
         HIPCHK(ctx, hipMemsetAsync(ctx->d_ones, 1, ctx->n_pairs, ctx->st.B));
         ctx->ones_cap = ctx->n_pairs;
@@ -4387,8 +4361,8 @@ static int map_rounds_issue(cm_ctx *ctx, const int *slots, int n_rounds, int las
         // held up the hand-over).  Seeds only: the chain records they will be chained into are still being read.
         if (i == n_items - 1 && prefetch && !pre_seeded) {
             const Slot &sl0 = ctx->slots[slots[0]];
-            const uint32_t nt0 = tile_for(ctx->st_n_pairs);                     // = that batch's first tile (<= this batch's: it has no more pairs)
-            const ReadsDev rd_next = reads_dev(ctx->st_rd);
+            const uint32_t nt0 = tile_for(ctx->staged.n_pairs);                     // = that batch's first tile (<= this batch's: it has no more pairs)
+            const ReadsDev rd_next = reads_dev(ctx->staged.rd);
             HIPCHK(ctx, hipStreamWaitEvent(ctx->st.S, ctx->ev.staged, 0));
             if ((rc = run_seed_tile(ctx, make_core(ctx, sl0), rd_next, 0, nt0, ctx->d_ones, n_items & 1, ctx->st.S, nullptr, skip_dead_chains(ctx)))) return rc;
             pre_seeded = true;
@@ -4427,7 +4401,7 @@ static int map_rounds_issue(cm_ctx *ctx, const int *slots, int n_rounds, int las
         const int b = ctx->item_base;
         const Slot &sl = ctx->slots[slots[0]];
         const KCore core = make_core(ctx, sl);
-        const uint32_t nt = tile_for(ctx->st_n_pairs);     // = that batch's first tile (prepare_resident)
+        const uint32_t nt = tile_for(ctx->staged.n_pairs);     // = that batch's first tile (prepare_resident)
         HIPCHK(ctx, hipStreamWaitEvent(ctx->st.B, ctx->ev.staged, 0));
         if ((rc = settle_pair(ctx, b))) return rc;
         if (ctx->pair_pending[b]) {
@@ -4435,7 +4409,7 @@ static int map_rounds_issue(cm_ctx *ctx, const int *slots, int n_rounds, int las
             ctx->pair_pending[b] = false;
         }
         const ChainRecs &rbn = ctx->rec[b];
-        const ReadsDev rd_next = reads_dev(ctx->st_rd);
+        const ReadsDev rd_next = reads_dev(ctx->staged.rd);
         if (pre_seeded) {                                      // seeds are there (or on their way): the classes, into the records now free
             HIPCHK(ctx, hipStreamWaitEvent(ctx->st.B, ctx->ev.seed[n_items & 1], 0));
             if ((rc = seed_classes(ctx, 0, nt, ctx->d_ones, n_items & 1, ctx->st.B, &rbn, skip_dead_chains(ctx)))) return rc;
@@ -4802,9 +4776,9 @@ int cm_format_pam(cm_ctx *ctx, const cm_chr_info *chrs, uint32_t n_chr, uint64_t
                   uint64_t stats[4]) {
     const char *fn = "cm_format_pam";
     if (int rc = rows_enter(ctx, fn, chrs, n_chr, out_bytes, 1, nullptr, stats)) return rc;
-    const ReadBufs &rd = ctx->rd;
-    return format_rows<cmpt::Format::Src>(ctx, rows_call<cmpt::Format>(fn, "pairs", "rows", "rows", rd.name_bytes_max),
-                                          {k_pam_len, k_pam_rows, {ctx->d_state, rd.names, rd.name_off}, out, cap}, {{rd.has_names, "2", "names"}}, chrs, n_chr, first, count,
+    const ReadFile &r1 = ctx->rd.file[0];
+    return format_rows<cmpt::Format::Src>(ctx, rows_call<cmpt::Format>(fn, "pairs", "rows", "rows", r1.name_bytes_max),
+                                          {k_pam_len, k_pam_rows, {ctx->d_state, r1.names, r1.name_off}, out, cap}, {{r1.has_names, "2", "names"}}, chrs, n_chr, first, count,
                                           out_bytes, stats);
 }
 
@@ -4813,11 +4787,11 @@ int cm_format_sam(cm_ctx *ctx, const cm_chr_info *chrs, uint32_t n_chr, uint64_t
                   uint64_t stats[4]) {
     const char *fn = "cm_format_sam";
     if (int rc = rows_enter(ctx, fn, chrs, n_chr, out_bytes, 1, nullptr, stats)) return rc;
-    const ReadBufs &rd = ctx->rd;
+    const ReadFile *F = ctx->rd.file;
     return format_rows<cmst::Format::Src>(
-        ctx, rows_call<cmst::Format>(fn, "pairs", "pairs", "records", 2 * (rd.name_bytes_max + rd.bases)),
-        {k_sam_len, k_sam_rows, {ctx->d_state, rd.names, rd.name_off, {rd.seq1_base + cmc::CM_STAGE_PAD, rd.seq2_base + cmc::CM_STAGE_PAD}, {rd.qual1, rd.qual2}, {rd.off1, rd.off2}}, out, cap},
-        {{rd.has_names, "2", "names"}, {rd.has_quals, "3", "qualities"}}, chrs, n_chr, first, count, out_bytes, stats);
+        ctx, rows_call<cmst::Format>(fn, "pairs", "pairs", "records", 2 * (F[0].name_bytes_max + ctx->rd.bases)),
+        {k_sam_len, k_sam_rows, {ctx->d_state, F[0].names, F[0].name_off, {F[0].seq(), F[1].seq()}, {F[0].qual, F[1].qual}, {F[0].off, F[1].off}}, out, cap},
+        {{F[0].has_names, "2", "names"}, {ctx->rd.has_quals, "3", "qualities"}}, chrs, n_chr, first, count, out_bytes, stats);
 }
 
 // Either mate file's order of the n entries of the active set (S.sel = compact_active's list) into rows.list1 / list2: the plan of
@@ -4883,20 +4857,19 @@ static int format_remain(cm_ctx *ctx, const char *fn, bool sorted, const cm_chr_
     unsigned int active = 0;
     if ((rc = rows_enter(ctx, fn, chrs, n_chr, out_bytes, 2, n_records, stats)) || (rc = compact_active(ctx)) || (rc = read_count(ctx, ~0ull, &active, fn))) return rc;
     if (n_records) *n_records = active;
-    const ReadBufs &rd = ctx->rd;
-    const RowsCall c = rows_call<cmrm::Format<0>>(fn, "records", "records", "records", std::max(rd.name_bytes_max, rd.name2_bytes_max) + 2 * rd.bases);
+    const ReadFile *F = ctx->rd.file;
+    const RowsCall c = rows_call<cmrm::Format<0>>(fn, "records", "records", "records", std::max(F[0].name_bytes_max, F[1].name_bytes_max) + 2 * ctx->rd.bases);
     RowsFile<cmrm::Src> file[2] = {{k_remain_len<0>, k_remain_rows<0>, {}, out1, cap1}, {k_remain_len<1>, k_remain_rows<1>, {}, out2, cap2}};
     RowsRun<cmrm::Src> run{ctx, c, file, 2};
     if (count == ~0ull && first <= active) count = active - first;
-    if ((rc = run.check({{rd.has_names, "2", "R1 names"}, {rd.has_quals, "3", "qualities"}, {rd.has_names2, "4", "R2 names"}}, first, count, active)) || count == 0) return rc;
+    if ((rc = run.check({{F[0].has_names, "2", "R1 names"}, {ctx->rd.has_quals, "3", "qualities"}, {F[1].has_names, "4", "R2 names"}}, first, count, active)) || count == 0) return rc;
     if ((rc = run.prepare(chrs, n_chr, true))) return rc;
     RowsBufs &R = ctx->rows;
     hipStream_t st = ctx->st.B;
     if (out_keys) HIPCHK(ctx, ensure(ctx, R.keys, (size_t)run.items * sizeof(int64_t)));
     // either file's selection list: the active set, or the file's own order of it
-    file[0].src = file[1].src = cmrm::Src{ctx->col.perm, ctx->d_state, {rd.names, rd.names2}, {rd.name_off, rd.name_off2},
-                                          {rd.seq1_base + cmc::CM_STAGE_PAD, rd.seq2_base + cmc::CM_STAGE_PAD}, {rd.qual1, rd.qual2}, {rd.off1, rd.off2},
-                                          R.chr_shift.dev, out_keys ? (int64_t *)R.keys : nullptr};
+    file[0].src = file[1].src = cmrm::Src{ctx->col.perm, ctx->d_state, {F[0].names, F[1].names}, {F[0].name_off, F[1].name_off}, {F[0].seq(), F[1].seq()},
+                                          {F[0].qual, F[1].qual}, {F[0].off, F[1].off}, R.chr_shift.dev, out_keys ? (int64_t *)R.keys : nullptr};
     if (sorted) {
         if ((rc = sort_remain(ctx, fn, file[0].src, run.ct, active))) return rc;
         file[0].src.sel = R.list1;
@@ -4927,16 +4900,8 @@ int cm_quals_peek(cm_ctx *ctx, uint8_t *qual1, uint64_t cap1, uint8_t *qual2, ui
     HIPCHK(ctx, hipSetDevice(ctx->P.device));
     if (ctx->n_pairs == 0) return fail(ctx, CM_ESTATE, "cm_quals_peek: no resident batch");
     if (int rc = not_staged(ctx, "cm_quals_peek", {{ctx->rd.has_quals, "3", "qualities"}})) return rc;
-    const uint64_t n = ctx->n_pairs;
-    uint64_t total[2] = {0, 0};
-    HIPCHK(ctx, hipMemcpyAsync(&total[0], ctx->rd.off1 + n, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->st.B));
-    HIPCHK(ctx, hipMemcpyAsync(&total[1], ctx->rd.off2 + n, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->st.B));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->st.B));
-    if ((qual1 && cap1 < total[0]) || (qual2 && cap2 < total[1])) return fail(ctx, CM_ELIMIT, "cm_quals_peek: %llu / %llu quality bytes", (unsigned long long)total[0], (unsigned long long)total[1]);
-    if (qual1 && total[0]) HIPCHK(ctx, hipMemcpyAsync(qual1, ctx->rd.qual1, total[0], hipMemcpyDeviceToHost, ctx->st.B));
-    if (qual2 && total[1]) HIPCHK(ctx, hipMemcpyAsync(qual2, ctx->rd.qual2, total[1], hipMemcpyDeviceToHost, ctx->st.B));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->st.B));
-    return CM_OK;
+    const ReadFile *F = ctx->rd.file;
+    return peek_files(ctx, "cm_quals_peek", "quality", {{qual1, cap1, F[0].qual, nullptr}, {qual2, cap2, F[1].qual, nullptr}});
 }
 
 // test hook: the carried states of the resident batch overwritten, behind everything queued for it

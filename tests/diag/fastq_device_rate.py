@@ -4,7 +4,7 @@ different boxes do not compare, see ab_multi.py).  Not run by the suite.
   (2) cm_reads_stage_text alone: blocks from cm_fastq_next_text, wall time from pageable blocks and from page-locked copies of
       them (copy over PCIe included), and the kernels' own time by HIP events (cm_text_batch.reserved under cm_prof_enable);
   (3) cm_mapping_run (report 0) from the FASTQ files to the remain files with and without CM_FASTQ_DEVICE=1, alternating, REPS
-      times each; the remain files of both must be the same bytes.
+      times each; the remain files of both must be the same bytes.  REPS=0 ends the script behind leg (2).
 The contigs come from the packed FASTA (tables built on the device: no index file to write); that time is seconds_load, outside
 the rates.  Writes OUT after every leg.
 env: WORKLOAD (hg38like), PAIRS (8388608), BATCH (1048576), REPS (2), THREADS (16), TMPFS (/dev/shm), OUT (profiles/fastq_device.json)"""
@@ -147,13 +147,14 @@ try:
             res["file_to_file"] = runs
             save()
     os.environ.pop("CM_FASTQ_DEVICE", None)
-    res["remain_files_identical"] = files[0] == files[1]
-    for dev, key in ((0, "host"), (1, "device")):
-        v = [r["pairs_per_s"] for r in runs if r["device_tokeniser"] == dev]
-        res[f"file_to_file_{key}_best_pairs_per_s"] = max(v)
-    res["device_path_wins"] = res["file_to_file_device_best_pairs_per_s"] > res["file_to_file_host_best_pairs_per_s"]
-    save()
-    assert res["remain_files_identical"]
+    if runs:                                 # (REPS=0: legs (1) and (2) only)
+        res["remain_files_identical"] = files[0] == files[1]
+        for dev, key in ((0, "host"), (1, "device")):
+            v = [r["pairs_per_s"] for r in runs if r["device_tokeniser"] == dev]
+            res[f"file_to_file_{key}_best_pairs_per_s"] = max(v)
+        res["device_path_wins"] = res["file_to_file_device_best_pairs_per_s"] > res["file_to_file_host_best_pairs_per_s"]
+        save()
+        assert res["remain_files_identical"]
 finally:
     shutil.rmtree(base, ignore_errors=True)
 print("written:", out_path)

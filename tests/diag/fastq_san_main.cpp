@@ -1,5 +1,6 @@
 // Stand-alone sanitizer pass over the bodies of circminer_amd/csrc/cm_fastq_text.h through the host emulation (tests/hostemu_fastq.cpp):
-// random file pairs, some malformed, some cut, every argument array an exact-size heap block.  From the repository root:
+// random file pairs, some malformed, some cut, every argument array an exact-size heap block; then cmft::verdict itself, which the
+// library and the emulation share, on result blocks at its boundaries.  From the repository root:
 //   g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=all -I include -I circminer_amd/csrc \
 //       tests/diag/fastq_san_main.cpp tests/hostemu_fastq.cpp -o /tmp/fastq_san && /tmp/fastq_san
 #include <cstdio>
@@ -9,6 +10,7 @@
 #include <string>
 #include <vector>
 #include "circminer_hot.h"
+#include "cm_fastq_text.h"
 extern "C" int emu_stage_text(const uint8_t *, uint64_t, const uint8_t *, uint64_t, uint64_t, uint32_t, int32_t, int32_t, uint64_t, uint8_t *, uint64_t *, uint64_t *,
                               uint8_t *, uint64_t *, uint64_t *, cm_text_batch *, unsigned long long *);
 static std::string make(std::mt19937_64 &rng, int n, int mate, bool junk) {
@@ -26,7 +28,39 @@ static std::string make(std::mt19937_64 &rng, int n, int mate, bool junk) {
     if (rng() % 2 && !t.empty()) t.pop_back();
     return t;
 }
+// the verdict of a result block with the given lines and longest read, no malformed record: (case, code)
+static bool is(unsigned long long lines1, unsigned long long lines2, unsigned long long max_len, uint32_t flags, uint64_t max_pairs, cmft::Case what, int code,
+               unsigned long long count = 0) {
+    unsigned long long R[cmft::RES_WORDS] = {cmft::NO_BAD, cmft::NO_BAD, max_len, lines1, lines2};
+    const cmft::Verdict v = cmft::verdict(R, flags, max_pairs, 300, 20, CM_MAX_SEEDS_PER_READ);
+    if (v.what == what && v.code == code && v.count == count) return true;
+    printf("verdict(lines %llu / %llu, max_len %llu, flags %u, max_pairs %llu): case %d code %d count %llu\n", lines1, lines2, max_len, flags, (unsigned long long)max_pairs,
+           (int)v.what, v.code, v.count);
+    return false;
+}
+static bool boundaries() {
+    using namespace cmft;
+    bool ok = true;
+    // lines % 4 against max_pairs: 10 whole records + 1 .. 3 lines are refused while the batch may reach them, not when it ends before
+    for (unsigned long long k = 1; k < 4; ++k) {
+        ok &= is(40 + k, 44, 100, 3, 11, LINES_LEFT, CM_EINVAL, k) && is(40 + k, 44, 100, 3, 10, ACCEPTED, CM_OK) && is(40 + k, 44, 100, 2, 11, ACCEPTED, CM_OK);
+        ok &= is(44, 40 + k, 100, 3, 11, LINES_LEFT, CM_EINVAL, k) && is(44, 40 + k, 100, 1, 10, ACCEPTED, CM_OK);
+    }
+    // file 2 one record short: of file 1, of max_pairs
+    ok &= is(40, 36, 100, 3, 10, FILE2_SHORT, CM_EINVAL) && is(40, 36, 100, 3, 9, ACCEPTED, CM_OK) && is(40, 36, 100, 1, 10, ACCEPTED, CM_OK) && is(36, 40, 100, 3, 10, ACCEPTED, CM_OK);
+    // max_len == max_read_len and one more (k = 20: 15 seeds, within any build)
+    ok &= is(40, 40, 300, 3, 10, ACCEPTED, CM_OK) && is(40, 40, 301, 3, 10, READ_TOO_LONG, CM_EINVAL, 301);
+    // a seed count at and one above the limit: floor(max_len / k)
+    for (int kmer : {1, 7, 12}) {
+        const unsigned long long at = (unsigned long long)kmer * CM_MAX_SEEDS_PER_READ + kmer - 1, R[RES_WORDS] = {NO_BAD, NO_BAD, at, 40, 40}, R1[RES_WORDS] = {NO_BAD, NO_BAD, at + 1, 40, 40};
+        const Verdict v = verdict(R, 3, 10, 300, kmer, CM_MAX_SEEDS_PER_READ), v1 = verdict(R1, 3, 10, 300, kmer, CM_MAX_SEEDS_PER_READ);
+        ok &= v.what == ACCEPTED && v.code == CM_OK && v1.what == TOO_MANY_SEEDS && v1.code == CM_ELIMIT && v1.count == at + 1;
+        ok &= !too_many_seeds((int)at, kmer, CM_MAX_SEEDS_PER_READ) && too_many_seeds((int)at + 1, kmer, CM_MAX_SEEDS_PER_READ);
+    }
+    return ok;
+}
 int main() {
+    if (!boundaries()) { printf("verdict boundaries: FAILED\n"); return 1; }
     std::mt19937_64 rng(7);
     int ok = 0, bad = 0;
     for (int it = 0; it < 600; ++it) {

@@ -1,7 +1,8 @@
 """The schedule of cm_map_rounds as text, one file per scenario: every wait, record, host wait, memset, copy and kernel launch the
 library issues, in issue order (tests/diag/sched_trace.h, force-included into a build of the library).  Two builds that write the
 same files queue the same work on the same streams behind the same events, in the same allocations, with the same kernel
-arguments (NOTES 58: made to compare a rewrite of the round scheduler with its parent).
+arguments (NOTES 58: made to compare a rewrite of the round scheduler with its parent; NOTES 71: the producer side of a batch --
+cm_reads_stage_text with every kept array, cm_reads_upload / cm_reads_stage with carried states, the readers of kept data).
     python tests/diag/sched_trace.py OUT_DIR             one trace file per scenario into OUT_DIR (+ line count and digest of each)
     python tests/diag/sched_trace.py --compare DIR DIR   file by file: identical or not
 env CM_LIB: the trace build of another tree (default: this tree's, built here: CM_EXTRA_FLAGS="-include .../sched_trace.h",
@@ -32,6 +33,8 @@ SCENARIOS = {
     "h_no_pipeline": ("rounds", dict(TWO, CM_HEAVY_PIPELINE="0")),
     "i_one_attempt": ("rounds", dict(TWO, CM_HP_ATTEMPTS="1")),
     "j_mapping_run": ("run", {}),                         # cm_mapping_run's calls for 3 000 pairs in batches of 1 024 (1 024, 1 024, 952)
+    "k_stage_text": ("text", {}),                         # the calls of test_staged_text_maps_like_staged_reads with bits 2 | 3 | 4, the readers of kept data
+    "l_prior": ("prior", {}),                             # the tail of test_staged_batches_overlap_and_match: upload / stage + swap with carried states
 }
 KNOBS = ["CM_TILE_PAIRS", "CM_HEAVY_COST", "CM_HP_TASKS_CAP", "CM_HP_UNP_CAP", "CM_POOL_BYTES", "CM_POOL_MAX", "CM_HEAVY_PIPELINE", "CM_HP_ATTEMPTS",
          "CM_HP_TASK_ORDER", "CM_LANE_CLK", "CM_CHAIN_LIGHT_W", "CM_CHAIN_LIGHT_CELLS"]
@@ -64,6 +67,35 @@ def child(what):
             hp.map_rounds(slots); done()
             if k + 1 < len(bs):
                 hp.swap()
+        hp.sync()
+    elif what == "text":                                  # two half batches of FASTQ text: swap, prefetch, take-over
+        n = d.seq1.shape[0]
+        h = n // 2
+
+        def text(arr, mate, lo, hi):
+            return b"".join(b"@pair%d%s/%d\n%s\n+\n%s\n" % (i, b"n" * (i % 9), mate, arr[i].tobytes(), b"I" * arr.shape[1]) for i in range(lo, hi))
+        a, b = (text(d.seq1, 1, 0, h), text(d.seq2, 2, 0, h)), (text(d.seq1, 1, h, n), text(d.seq2, 2, h, n))
+        bits = dict(keep_names=True, keep_quals=True, keep_names2=True)
+        hp.stage_text(*a, h, **bits); hp.swap(); hp.stage_text(*b, n, **bits)
+        hp.map_rounds(slots); done()                                     # prefetches B's first round
+        hp.swap(); hp.stage_text(*a, h, **bits)
+        hp.map_rounds(slots); done()                                     # takes it over; prefetches A's
+        hp.swap()
+        hp.map_rounds(slots); done()
+        chrs = list(d.chr_table)
+        for rows in (hp.format_pam(chrs)[0], hp.format_sam(chrs)[0], *hp.format_remain(chrs)[:2], *hp.peek_reads(), *hp.peek_quals()):
+            digests.append(hashlib.sha1(bytes(rows)).hexdigest()[:12])
+        hp.sync()
+    elif what == "prior":                                 # carried states from the host (upload) and from the staged record (swap)
+        import numpy as np
+        batch = cl.ReadBatch(d.seq1, d.seq2)
+        hp.upload(batch); hp.map_round(0, False)
+        st1, _, act1 = hp.download()
+        idx = np.nonzero(act1)[0]
+        sub, prior = cl.ReadBatch(d.seq1[idx], d.seq2[idx]), np.ascontiguousarray(st1[idx])
+        hp.upload(sub, prior); hp.map_round(1, True); done()
+        hp.upload(batch); hp.map_round(0, False)
+        hp.stage(sub, prior); hp.swap(); hp.map_round(1, True); done()
         hp.sync()
     elif what == "rounds":                                # both slots in one call
         hp.upload(cl.ReadBatch(d.seq1, d.seq2))

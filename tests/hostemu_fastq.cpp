@@ -4,8 +4,8 @@
 // NL_CHUNK bytes (64 lanes x 16 bytes), an exclusive scan, the line-start table, one lane per record for the checks, a scan of
 // the sequence lengths, COPY_LANES lanes per record for the copy into a buffer with CM_STAGE_PAD bytes of slack on both sides.
 // Chunks, records and the lanes of a copy run in a SHUFFLED order (seed): nothing may depend on the order the device happens to
-// run them in.  The read buffers start out filled with 0xA5, so a byte nobody wrote shows.  The verdicts are those the entry point
-// derives from the result block.
+// run them in.  The read buffers start out filled with 0xA5, so a byte nobody wrote shows.  The sizes every array is made by and
+// the verdicts drawn from the result block are the entry point's own: cmft::plan_sizes and cmft::verdict, which both call.
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -24,7 +24,6 @@ struct File {
     std::vector<uint32_t> store;      // the block in an aligned array with TEXT_SLACK readable bytes behind it
     const uint8_t *text = nullptr;
     uint64_t len = 0;
-    uint32_t trail = 0, n_chunks = 0, ls_cap = 0;
     std::vector<uint32_t> cnt, ls, slen;
     std::vector<uint64_t> off, rec;
     std::vector<uint8_t> seq;
@@ -54,53 +53,50 @@ extern "C" int emu_stage_text(const uint8_t *text1, uint64_t len1, const uint8_t
     memset(out, 0, sizeof *out);
     std::mt19937_64 rng(seed);
     File F[2];
-    const uint8_t *text[2] = {text1, text2};
+    const uint8_t *const text[2] = {text1, text2};
     const uint64_t len[2] = {len1, len2};
+    cmft::Sizes S;
+    if (int file = 0; const int rc = cmft::plan_sizes(text, len, max_pairs, flags, &S, &file)) return rc;
     for (int f = 0; f < 2; ++f) {
         File &X = F[f];
         X.len = len[f];
-        X.trail = ((flags >> f) & 1u) && len[f] && text[f][len[f] - 1] != '\n';
-        if (len[f] > 0xffffffffull - X.trail) return CM_ELIMIT;
         X.store.assign((size_t)((len[f] + 15) / 16 * 16 + cmft::TEXT_SLACK) / 4, 0xa5a5a5a5u);
         if (len[f]) memcpy(X.store.data(), text[f], len[f]);
         X.text = (const uint8_t *)X.store.data();
     }
-    const uint64_t mp = std::min<uint64_t>(max_pairs, 1ull << 30);
-    const uint32_t nb = (uint32_t)std::min<uint64_t>(mp, std::min(len1, len2) / 4);
     for (int f = 0; f < 2; ++f) {                            // k_ft_count, scan, k_ft_lines
         File &X = F[f];
-        X.n_chunks = (uint32_t)((X.len + cmft::NL_CHUNK - 1) / cmft::NL_CHUNK);
-        X.ls_cap = (uint32_t)std::min<uint64_t>(X.len + 2, 4 * mp + 1);
-        X.cnt.assign(X.n_chunks + 1, 0xffffffffu);
-        X.ls.assign(X.ls_cap, 0xffffffffu);
-        for (uint32_t c : shuffled(X.n_chunks + 1, rng)) {
+        const uint32_t n_chunks = S.n_chunks[f], ls_cap = S.ls_cap[f];
+        X.cnt.assign(n_chunks + 1, 0xffffffffu);
+        X.ls.assign(ls_cap, 0xffffffffu);
+        for (uint32_t c : shuffled(n_chunks + 1, rng)) {
             uint32_t k = 0;
-            for (uint32_t lane = 0; lane < 64 && c < X.n_chunks; ++lane)
+            for (uint32_t lane = 0; lane < 64 && c < n_chunks; ++lane)
                 k += cmft::popcount16(cmft::nl_mask16(X.text, (uint64_t)c * cmft::NL_CHUNK + lane * cmft::LANE_BYTES, X.len));
             X.cnt[c] = k;
         }
         exclusive_scan(X.cnt);
         X.ls[0] = 0;
-        if (X.trail && X.cnt[X.n_chunks] + 1 < X.ls_cap) X.ls[X.cnt[X.n_chunks] + 1] = (uint32_t)X.len + 1u;
-        for (uint32_t c : shuffled(X.n_chunks, rng)) {
+        if (S.trail[f] && X.cnt[n_chunks] + 1 < ls_cap) X.ls[X.cnt[n_chunks] + 1] = (uint32_t)X.len + 1u;
+        for (uint32_t c : shuffled(n_chunks, rng)) {
             uint32_t before = X.cnt[c];                      // the wave's exclusive scan over its lanes
             for (uint32_t lane = 0; lane < 64; ++lane) {
                 const uint64_t at = (uint64_t)c * cmft::NL_CHUNK + lane * cmft::LANE_BYTES;
                 const uint32_t mask = cmft::nl_mask16(X.text, at, X.len);
-                cmft::put_line_starts(mask, at, before, X.ls.data(), X.ls_cap);
+                cmft::put_line_starts(mask, at, before, X.ls.data(), ls_cap);
                 before += cmft::popcount16(mask);
             }
         }
     }
-    const uint32_t lines[2] = {cmft::line_count(F[0].cnt[F[0].n_chunks], F[0].trail != 0), cmft::line_count(F[1].cnt[F[1].n_chunks], F[1].trail != 0)};
-    const uint32_t n = cmft::pair_count(lines[0], lines[1], mp);
-    if (n > nb) return CM_EHIP;                              // (the sizing rule of the entry point would be wrong)
+    const uint32_t lines[2] = {cmft::line_count(F[0].cnt[S.n_chunks[0]], S.trail[0] != 0), cmft::line_count(F[1].cnt[S.n_chunks[1]], S.trail[1] != 0)};
+    const uint32_t n = cmft::pair_count(lines[0], lines[1], S.max_pairs);
+    if (n > S.nb) return CM_EHIP;                              // (the sizing rule would be wrong)
     for (int w = 0; w < cmft::RES_WORDS; ++w) res[w] = 0;
     res[cmft::RES_BAD1] = res[cmft::RES_BAD2] = cmft::NO_BAD;
     for (int f = 0; f < 2; ++f) {                            // k_ft_records, scan, k_ft_offsets, k_ft_copy
         File &X = F[f];
-        X.slen.assign((size_t)nb + 1, 0xffffffffu);
-        for (uint32_t tile : shuffled(nb / REC_TILE + 1, rng))
+        X.slen.assign((size_t)S.nb + 1, 0xffffffffu);
+        for (uint32_t tile : shuffled(S.nb / REC_TILE + 1, rng))
             for (uint32_t t = 0; t < REC_TILE; ++t) {
                 const uint32_t i = tile * REC_TILE + (REC_TILE - 1 - t);
                 uint32_t sl = 0;
@@ -108,12 +104,12 @@ extern "C" int emu_stage_text(const uint8_t *text1, uint64_t len1, const uint8_t
                     const uint32_t bad = cmft::check_record(X.text, X.ls.data(), i, f == 0, &sl);
                     if (bad) res[cmft::RES_BAD1 + f] = std::min(res[cmft::RES_BAD1 + f], cmft::bad_key(i, bad));
                 }
-                if (i <= nb) X.slen[i] = sl;
+                if (i <= S.nb) X.slen[i] = sl;
                 res[cmft::RES_MAX_LEN] = std::max<unsigned long long>(res[cmft::RES_MAX_LEN], sl);
             }
         exclusive_scan(X.slen);
-        X.off.assign((size_t)nb + 1, ~0ull);
-        X.rec.assign((size_t)nb + 1, ~0ull);
+        X.off.assign((size_t)S.nb + 1, ~0ull);
+        X.rec.assign((size_t)S.nb + 1, ~0ull);
         for (uint32_t i : shuffled(n + 1, rng)) {
             X.off[i] = X.slen[i];
             const uint32_t r = X.ls[4 * (uint64_t)i];
@@ -144,16 +140,7 @@ extern "C" int emu_stage_text(const uint8_t *text1, uint64_t len1, const uint8_t
     res[cmft::RES_BASES2] = F[1].off[n];
     res[cmft::RES_USED1] = F[0].rec[n];
     res[cmft::RES_USED2] = F[1].rec[n];
-    // the verdicts, as cm_reads_stage_text derives them from the result block
-    for (int f = 0; f < 2; ++f)
-        if (((flags >> f) & 1u) && lines[f] % 4 != 0 && lines[f] / 4 < max_pairs) return CM_EINVAL;
-    if ((flags & 2u) && lines[1] / 4 < std::min<uint64_t>(lines[0] / 4, max_pairs)) return CM_EINVAL;
-    if (res[cmft::RES_BAD1] != cmft::NO_BAD || res[cmft::RES_BAD2] != cmft::NO_BAD) return CM_EINVAL;
-    if (res[cmft::RES_MAX_LEN] > (unsigned long long)max_read_len) return CM_EINVAL;
-    if ((int)res[cmft::RES_MAX_LEN] / kmer > CM_MAX_SEEDS_PER_READ) return CM_ELIMIT;
-    out->n_pairs = n;
-    out->used1 = res[cmft::RES_USED1];
-    out->used2 = res[cmft::RES_USED2];
-    out->max_len = (int32_t)res[cmft::RES_MAX_LEN];
-    return CM_OK;
+    const cmft::Verdict v = cmft::verdict(res, flags, max_pairs, max_read_len, kmer, CM_MAX_SEEDS_PER_READ);
+    if (v.code == CM_OK) *out = cm_text_batch{res[cmft::RES_PAIRS], res[cmft::RES_USED1], res[cmft::RES_USED2], (int32_t)res[cmft::RES_MAX_LEN], 0};
+    return v.code;
 }
