@@ -12,6 +12,16 @@
 // batch goes to cm_reads_upload without another copy; with cm_host_alloc'ed staging the copy is one DMA.
 // Deliberately defined where the reference has undefined behaviour: names shorter than 2 characters are not
 // inspected for the "/x" suffix, header lines with more than 23 tokens are treated like fresh reads.
+//
+// The reader (first half of the file, down to cm_fastq_close): whatever exists once per mate file is one type indexed [x] --
+// MateFile (the stream, its newline index, its text blocks) in the reader, Side (the arrays of one mate) in a storage generation.
+//   cm_fastq_next      = rotate the generation, then next_plain (two regular plain-text files: blocks, tokenised on several
+//                        threads) or next_records (gzip, pipes, CM_FASTQ_SERIAL: record by record), then publish;
+//   cm_fastq_next_text = next_text_block per file: the text itself, for cm_reads_stage_text.
+// Both files are always worked on side by side through both_files(); loops over records go through par_for().  Either reports
+// a worker's std::bad_alloc to its caller as its return value; the reader has no state outside its cm_fastq.  Stated once each:
+// thread_count() (how many workers), count_lines() (lines of a text, a last line without a newline counts), Lap (the
+// CM_FASTQ_TRACE timing), record_lines() (the four lines of record i of an indexed block).
 #include <fcntl.h>
 #include <sys/mman.h>
 #include <unistd.h>
@@ -196,7 +206,6 @@ struct ReleaseHook {
     void (*fn)(void *user, const void *ptr, uint64_t bytes) = nullptr;
     void *user = nullptr;
 };
-std::atomic<int> g_raw_oom{0};       // a RawVec could not grow inside a worker thread (reported by the cm_fastq_* call as CM_ENOMEM)
 template <class T> struct RawVec {
     T *p = nullptr;
     size_t n = 0, cap = 0;
@@ -253,14 +262,68 @@ template <class T> struct RawVec {
         for (size_t i = 0; i < k; ++i) p[i] = v;
     }
 };
-// body of a worker thread: an allocation failure inside it must not terminate the process
-template <class F> void guarded(F &&f) {
-    try {
-        f();
-    } catch (const std::bad_alloc &) {
-        g_raw_oom = 1;
-    }
+
+// The two ways work goes to other threads.  An allocation failure inside a worker must not terminate the process: std::bad_alloc
+// on any of the threads, the calling one included, is the helper's return value (false), and the C entry point's CM_ENOMEM.
+
+// the two mate files side by side: f(1) on a second thread, f(0) on this one
+template <class F> bool both_files(F &&f) {
+    bool ok[2] = {true, true};
+    auto run = [&](int x) {
+        try {
+            f(x);
+        } catch (const std::bad_alloc &) {
+            ok[x] = false;
+        }
+    };
+    std::thread second([&]() { run(1); });
+    run(0);
+    second.join();
+    return ok[0] && ok[1];
 }
+// f(piece, begin, end) over [0, n) in nt contiguous pieces, piece 0 on this thread
+template <class F> bool par_for(int nt, size_t n, F f) {
+    if (nt <= 1 || n < 4096) nt = 1;
+    std::atomic<bool> ok{true};
+    auto piece = [&](int t) {
+        try {
+            f(t, n * (size_t)t / (size_t)nt, n * (size_t)(t + 1) / (size_t)nt);
+        } catch (const std::bad_alloc &) {
+            ok = false;
+        }
+    };
+    std::vector<std::thread> th;
+    th.reserve((size_t)nt);                     // (no allocation between the first thread's start and the joins)
+    for (int t = 1; t < nt; ++t) th.emplace_back(piece, t);
+    piece(0);
+    for (auto &x : th) x.join();
+    return ok;
+}
+// How many worker threads: the reader's n_threads (0: the hardware's), at most `most`; the environment variable, where one is
+// named and set, decides instead, up to `env_most`; never fewer than `least`.
+int thread_count(int n_threads, const char *env, int least, int most, int env_most) {
+    int nt = std::min(n_threads > 0 ? n_threads : (int)std::thread::hardware_concurrency(), most);
+    const char *e = env ? getenv(env) : nullptr;
+    if (e) nt = std::min(atoi(e), env_most);
+    return std::max(nt, least);
+}
+// Lines of a text with `newlines` line feeds and `last` as its last byte ('\n' for an empty text): a last line without a
+// newline still is a line.  Four lines are a record; lines % 4 are what follows the last whole record.
+inline uint64_t count_lines(uint64_t newlines, char last) { return newlines + (last != '\n'); }
+// CM_FASTQ_TRACE: ms() is the time since the call before it (or since the timer was made)
+inline bool tracing() {
+    static const bool on = getenv("CM_FASTQ_TRACE") != nullptr;
+    return on;
+}
+struct Lap {
+    std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
+    double ms() {
+        const auto now = std::chrono::steady_clock::now();
+        const double d = std::chrono::duration<double, std::milli>(now - t).count();
+        t = now;
+        return d;
+    }
+};
 
 struct Side {
     RawVec<uint8_t> seq, qual;
@@ -274,47 +337,57 @@ struct Side {
         names.clear();
         name_off.assign(1, 0);
     }
+    void keep(size_t n) {                    // the first n records
+        off.resize(n + 1);
+        seq.resize(off[n]);
+        qual.resize(off[n]);
+        name_off.resize(n + 1);
+        names.resize(name_off[n]);
+    }
+};
+
+// What the reader has once per mate file.
+struct MateFile {
+    Stream s;
+    std::vector<size_t> nl;                  // newline index of s.buf (plain-text path)
+    // raw-block mode (cm_fastq_next_text): four generations of text buffers, used in turn like the batches.  A block is the
+    // unconsumed tail of the block before it followed by freshly read bytes: the bytes are read behind head room at the front of
+    // the generation's buffer and the tail is copied into that room, so the block itself is never moved.
+    RawVec<uint8_t> text[4];
+    const uint8_t *block = nullptr;          // the block handed out last ...
+    uint64_t block_len = 0;
+    uint64_t block_used = 0;                 // ... and what cm_fastq_text_consumed said of it (0: nothing yet)
 };
 
 }  // namespace
 
 struct cm_fastq {
-    ReleaseHook hook;                        // cm_fastq_set_release_hook (declared first: the batch arrays below call it when they go)
-    Stream s1, s2;
+    ReleaseHook hook;                        // cm_fastq_set_release_hook (declared first: the arrays below call it when they go)
+    MateFile file[2];
     // four generations of batch storage, used in turn: the batch a call returns stays valid over the next three calls, so a
     // caller can have batch k-1 with its writer thread, batch k on the GPU, batch k+1 staged (its H2D copy in flight) and
     // batch k+2 in the parser at the same time
     struct Gen {
-        Side a, b;
+        Side side[2];
         RawVec<cm_mapped_read> prior;
     } gen[4];
-    int cur = 3;
+    int cur = 3, text_cur = 3;               // the generation of the last batch / the last text block
     int n_threads = 0;                       // tokeniser threads of the plain-text path (0 = hardware concurrency, at most 16; CM_FASTQ_THREADS overrides, at most 32)
-    std::vector<size_t> nl1, nl2;            // newline index of the two block buffers (plain-text path)
     std::vector<std::string> chr_names;
     int max_ed = 4;
-    bool any_prior = false;
-    std::string err;
     // cm_fastq_open_shard on input that cannot be cut at a byte offset (gzip, pipes): this reader inflates the stream from its start,
     // steps over the first skip_left records and hands out take_left (~0: to the end of the input)
     uint64_t skip_left = 0, take_left = ~0ull;
-    // raw-block mode (cm_fastq_next_text): four generations of text buffers per file, used in turn like the batches.  A block is
-    // the unconsumed tail of the block before it followed by freshly read bytes: the bytes are read behind head room at the
-    // front of the generation's buffer and the tail is copied into that room, so the block itself is never moved.
-    struct TextGen {
-        RawVec<uint8_t> buf[2];
-    } tgen[4];
-    int tcur = 3;
-    const uint8_t *block[2] = {nullptr, nullptr};    // the block handed out last ...
-    uint64_t block_len[2] = {0, 0};
-    uint64_t block_used[2] = {0, 0};                 // ... and what cm_fastq_text_consumed said of it (0: nothing yet)
-    cm_fastq() {
-        for (Gen &g : gen) {                 // the arrays cm_fastq_batch::reads / prior point into
-            g.a.seq.hook = g.a.off.hook = g.b.seq.hook = g.b.off.hook = &hook;
+    cm_fastq() {                             // the arrays a caller may have page-locked: what cm_fastq_batch::reads / prior and the text blocks point into
+        for (Gen &g : gen) {
+            for (Side &s : g.side) s.seq.hook = s.off.hook = &hook;
             g.prior.hook = &hook;
         }
-        for (TextGen &g : tgen) g.buf[0].hook = g.buf[1].hook = &hook;
+        for (MateFile &m : file)
+            for (RawVec<uint8_t> &b : m.text) b.hook = &hook;
     }
+    bool plain() const { return file[0].s.plain && file[1].s.plain; }          // two regular plain-text files
+    bool io_error() const { return file[0].s.io_error || file[1].s.io_error; }
 };
 
 namespace {
@@ -414,10 +487,6 @@ int parse_record(cm_fastq *f, Stream &s, Side &side, bool want_state, cm_mapped_
     return 1;
 }
 
-}  // namespace
-
-namespace {
-
 // ---------------------------------------------------------------------------------------------------------------------
 // Plain-text fast path of cm_fastq_next: the reference tokenises FASTQ inside one lock-protected serial section
 // (src/circminer.cpp:373-379); here both files are read in large blocks and everything after the read() is data parallel:
@@ -425,6 +494,7 @@ namespace {
 //   2. four lines = one record; per record the lengths of name / sequence and the header checks (pass A);
 //   3. prefix sums give every record its place in the batch arrays; bytes are copied in parallel (pass B).
 // Records that do not fit the block stay in the buffer for the next call.  Same results as parse_record().
+
 // offsets (from base) of the line feeds in base[lo, hi), appended to v.  One memchr call per line costs more than the scan itself
 // on 150-byte lines (2 GB/s per thread); with AVX2 the block is compared 64 bytes at a time and the set bits are read off the mask.
 #if defined(__x86_64__)
@@ -466,20 +536,12 @@ void scan_newlines(const char *base, size_t lo, size_t hi, RawVec<size_t> &v) {
     }
 }
 
-template <class F> void par_for(int nt, size_t n, F f) {       // f(thread, begin, end) over [0, n) in nt contiguous pieces
-    if (nt <= 1 || n < 4096) {
-        f(0, (size_t)0, n);
-        return;
-    }
-    std::vector<std::thread> th;
-    for (int t = 0; t < nt; ++t)
-        th.emplace_back([&f, t, n, nt]() { guarded([&]() { f(t, n * (size_t)t / (size_t)nt, n * (size_t)(t + 1) / (size_t)nt); }); });
-    for (auto &x : th) x.join();
-}
-
-// makes sure s.buf[s.pos .. s.end) holds at least `want` complete records (or everything up to end of input); nl = offsets
-// (relative to s.pos) of the line ends of those bytes.  Returns the number of complete records available.
-size_t fill_and_index(Stream &s, std::vector<size_t> &nl, size_t want, size_t bytes_hint, int nt, size_t *tail_lines) {
+// makes sure m.s.buf[0 .. m.s.end) holds at least `want` complete records (or everything up to end of input); m.nl = offsets of
+// the line ends of those bytes.  Returns the number of complete records available; *tail_lines = the lines behind the last
+// whole record of the input (0 while the input goes on).
+size_t fill_and_index(MateFile &m, size_t want, size_t bytes_hint, int nt, size_t *tail_lines) {
+    Stream &s = m.s;
+    std::vector<size_t> &nl = m.nl;
     s.read_threads = nt;
     if (s.pos > 0) {                                              // drop what the previous batch consumed
         memmove(s.buf.data(), s.buf.data() + s.pos, s.end - s.pos);
@@ -488,19 +550,15 @@ size_t fill_and_index(Stream &s, std::vector<size_t> &nl, size_t want, size_t by
     }
     nl.clear();
     size_t scanned = 0;
-    static const bool trace = getenv("CM_FASTQ_TRACE") != nullptr;
-    double t_idx = 0, t_cat = 0, t_read = 0;
-    auto now = []() { return std::chrono::steady_clock::now(); };
-    auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
-    const auto t_in = now();
+    Lap lap;
+    double t_move = 0, t_read = 0, t_idx = 0, t_cat = 0;
     for (;;) {
-        // index the bytes not scanned yet
-        const size_t a = scanned, b = s.end;
-        if (b > a) {
-            const auto t0 = now();
+        if (s.end > scanned) {                                    // index the bytes not scanned yet
+            const size_t a = scanned, b = s.end;
+            t_move += lap.ms();
             std::vector<RawVec<size_t>> part((size_t)std::max(nt, 1));
-            par_for(nt, b - a, [&](int t, size_t lo, size_t hi) { scan_newlines(s.buf.data(), a + lo, a + hi, part[(size_t)t]); });
-            const auto t1 = now();
+            if (!par_for(nt, b - a, [&](int t, size_t lo, size_t hi) { scan_newlines(s.buf.data(), a + lo, a + hi, part[(size_t)t]); })) throw std::bad_alloc();
+            t_idx += lap.ms();
             {   // the slices' lists one behind the other, copied side by side
                 std::vector<size_t> at(part.size() + 1, nl.size());
                 for (size_t t = 0; t < part.size(); ++t) at[t + 1] = at[t] + part[t].size();
@@ -516,14 +574,12 @@ size_t fill_and_index(Stream &s, std::vector<size_t> &nl, size_t want, size_t by
                     for (size_t t = 0; t < part.size(); ++t) put(t);
             }
             scanned = b;
-            t_idx += ms(t0, t1);
-            t_cat += ms(t1, now());
+            t_cat += lap.ms();
         }
-        size_t lines = nl.size();
-        if (s.eof && s.end > 0 && (nl.empty() || nl.back() != s.end - 1)) ++lines;     // last line without a newline
-        if (tail_lines) *tail_lines = s.eof ? lines % 4 : 0;                           // lines behind the last whole record of the input
+        const size_t lines = s.eof ? (size_t)count_lines(nl.size(), s.end ? s.buf[s.end - 1] : '\n') : nl.size();
+        *tail_lines = s.eof ? lines % 4 : 0;
         if (lines / 4 >= want || s.eof) {
-            if (trace) fprintf(stderr, "[fastq]   fill: move %.1f read %.1f index %.1f concat %.1f ms\n", ms(t_in, now()) - t_idx - t_cat - t_read, t_read, t_idx, t_cat);
+            if (tracing()) fprintf(stderr, "[fastq]   fill: move %.1f read %.1f index %.1f concat %.1f ms\n", t_move + lap.ms(), t_read, t_idx, t_cat);
             return lines / 4;
         }
         // more input: room for the rest of the estimate (at least one block)
@@ -532,7 +588,7 @@ size_t fill_and_index(Stream &s, std::vector<size_t> &nl, size_t want, size_t by
             s.buf.resize(s.end + need);
             advise_huge(s.buf.data(), s.buf.size());
         }
-        const auto t_r = now();
+        t_move += lap.ms();
         while (need > 0) {
             const int got = s.read_some(s.buf.data() + s.end, need);
             if (got <= 0) {
@@ -542,54 +598,60 @@ size_t fill_and_index(Stream &s, std::vector<size_t> &nl, size_t want, size_t by
             s.end += (size_t)got;
             need -= (size_t)got;
         }
-        t_read += ms(t_r, now());
+        t_read += lap.ms();
     }
 }
 
-// one side of a batch from the indexed block; returns false on a malformed record
-bool build_side(cm_fastq *f, Stream &s, const std::vector<size_t> &nl, size_t n, Side &side, RawVec<cm_mapped_read> *prior, bool *any_prior,
-                int nt) {
-    const char *base = s.buf.data();
-    auto line_of = [&](size_t k, const char *&p, size_t &len) {      // k-th line of the block
-        const size_t b = k ? nl[k - 1] + 1 : 0;
-        const size_t e = k < nl.size() ? nl[k] : s.end;               // the last line may have no newline
-        p = base + b;
-        len = e - b;
-    };
-    static const bool trace = getenv("CM_FASTQ_TRACE") != nullptr;
-    const auto tb0 = std::chrono::steady_clock::now();
+// the four lines of record i of an indexed block (the last line of the input may have no newline)
+struct RecordLines {
+    const char *p[4];
+    size_t len[4];
+};
+inline RecordLines record_lines(const MateFile &m, size_t i) {
+    RecordLines r;
+    size_t b = i ? m.nl[4 * i - 1] + 1 : 0;
+    for (size_t k = 0; k < 4; ++k) {
+        const size_t e = 4 * i + k < m.nl.size() ? m.nl[4 * i + k] : m.s.end;
+        r.p[k] = m.s.buf.data() + b;
+        r.len[k] = e - b;
+        b = e + 1;
+    }
+    return r;
+}
+
+// one side of a batch from the first n records of the indexed block, which are consumed; with `prior`, the state each header
+// carries and *carried = one of them has 23 tokens.  Returns false on a malformed record.
+bool build_side(cm_fastq *f, MateFile &m, size_t n, Side &side, RawVec<cm_mapped_read> *prior, bool *carried, int nt) {
+    Lap lap;
     RawVec<uint32_t> nlen, slen;
     nlen.resize(n);
     slen.resize(n);
-    std::vector<uint8_t> bad((size_t)std::max(nt, 1), 0), carried((size_t)std::max(nt, 1), 0);
+    std::vector<uint8_t> bad((size_t)std::max(nt, 1), 0), has23((size_t)std::max(nt, 1), 0);
     if (prior) prior->resize(n);
-    par_for(nt, n, [&](int t, size_t lo, size_t hi) {                 // pass A
+    auto pass_a = [&](int t, size_t lo, size_t hi) {                  // the checks, the lengths, the carried state
         const char *tok[FQCOMMENTCNT + 1];
         size_t tl[FQCOMMENTCNT + 1];
         for (size_t i = lo; i < hi; ++i) {
-            const char *p;
-            size_t len, l2, l3, l4;
-            const char *p2, *p3, *p4;
-            line_of(4 * i, p, len);
-            line_of(4 * i + 1, p2, l2);
-            line_of(4 * i + 2, p3, l3);
-            line_of(4 * i + 3, p4, l4);
-            if (len == 0 || p[0] != '@' || l3 == 0 || p3[0] != '+' || l4 != l2) {
+            const RecordLines r = record_lines(m, i);
+            if (r.len[0] == 0 || r.p[0][0] != '@' || r.len[2] == 0 || r.p[2][0] != '+' || r.len[3] != r.len[1]) {
                 bad[(size_t)t] = 1;
                 return;
             }
-            const int ntok = split_header(p, len, tok, tl);
+            const int ntok = split_header(r.p[0], r.len[0], tok, tl);
             nlen[i] = (uint32_t)name_len(ntok, tok, tl);
-            slen[i] = (uint32_t)l2;
+            slen[i] = (uint32_t)r.len[1];
             if (prior) {
-                if (ntok == FQCOMMENTCNT) carried[(size_t)t] = 1;
+                if (ntok == FQCOMMENTCNT) has23[(size_t)t] = 1;
                 state_from_header(f, ntok, tok, tl, (*prior)[i]);
             }
         }
-    });
-    const auto tb1 = std::chrono::steady_clock::now();
-    for (uint8_t b : bad) if (b) return false;
-    if (any_prior) for (uint8_t c : carried) *any_prior = *any_prior || c;
+    };
+    if (!par_for(nt, n, pass_a)) throw std::bad_alloc();
+    const double t_a = lap.ms();
+    for (uint8_t b : bad)
+        if (b) return false;
+    if (prior)
+        for (uint8_t c : has23) *carried = *carried || c;
     side.off.resize(n + 1);
     side.name_off.resize(n + 1);
     side.off[0] = 0;
@@ -601,101 +663,391 @@ bool build_side(cm_fastq *f, Stream &s, const std::vector<size_t> &nl, size_t n,
     side.seq.resize(side.off[n]);
     side.qual.resize(side.off[n]);
     side.names.resize(side.name_off[n]);
-    const auto tb2 = std::chrono::steady_clock::now();
-    par_for(nt, n, [&](int, size_t lo, size_t hi) {                   // pass B
+    const double t_sizes = lap.ms();
+    auto pass_b = [&](int, size_t lo, size_t hi) {                    // the copies (the header is split again: the measured shape)
         const char *tok[FQCOMMENTCNT + 1];
         size_t tl[FQCOMMENTCNT + 1];
         for (size_t i = lo; i < hi; ++i) {
-            const char *p;
-            size_t len;
-            line_of(4 * i, p, len);
-            const int ntok = split_header(p, len, tok, tl);
+            const RecordLines r = record_lines(m, i);
+            const int ntok = split_header(r.p[0], r.len[0], tok, tl);
             char *nm = side.names.data() + side.name_off[i];
             if (ntok) memcpy(nm, tok[0], nlen[i]);
             nm[nlen[i]] = '\0';
-            line_of(4 * i + 1, p, len);
-            memcpy(side.seq.data() + side.off[i], p, len);
-            line_of(4 * i + 3, p, len);
-            memcpy(side.qual.data() + side.off[i], p, len);
+            memcpy(side.seq.data() + side.off[i], r.p[1], r.len[1]);
+            memcpy(side.qual.data() + side.off[i], r.p[3], r.len[3]);
         }
-    });
-    if (trace) {
-        const auto tb3 = std::chrono::steady_clock::now();
-        auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
-        fprintf(stderr, "[fastq]   build: pass A %.1f, offsets + sizing %.1f, pass B %.1f ms\n", ms(tb0, tb1), ms(tb1, tb2), ms(tb2, tb3));
-    }
-    // consumed: everything up to the end of record n - 1
-    const size_t last = 4 * n - 1;
-    s.pos = last < nl.size() ? nl[last] + 1 : s.end;
+    };
+    if (!par_for(nt, n, pass_b)) throw std::bad_alloc();
+    if (tracing()) fprintf(stderr, "[fastq]   build: pass A %.1f, offsets + sizing %.1f, pass B %.1f ms\n", t_a, t_sizes, lap.ms());
+    const size_t last = 4 * n - 1;                                    // consumed: everything up to the end of record n - 1
+    m.s.pos = last < m.nl.size() ? m.nl[last] + 1 : m.s.end;
     return true;
 }
 
-// cm_fastq_next for two plain-text files; *n_out pairs
-int next_plain(cm_fastq *f, uint64_t max_pairs, cm_fastq::Gen &G, uint64_t *n_out, uint64_t *n2_out) {
-    int nt = f->n_threads > 0 ? f->n_threads : (int)std::thread::hardware_concurrency();
-    // more threads than this only fight over the page-cache copies and the writer's bandwidth: file to file on a 256-CPU box,
+// The two bodies of cm_fastq_next.  Either leaves the next *n_out pairs (at most max_pairs) in the two sides of G and their
+// states in G.prior, *carried = one of R1's headers has 23 tokens, and gives the same verdict in the same call:
+//   * CM_EIO (a read failed) before CM_EINVAL;
+//   * R2 ends before R1: CM_EINVAL;
+//   * what follows the last whole record -- a partial record, blank lines -- is malformed input (the reference asserts the '@',
+//     fastq_parser.h:64-65) and is reported by the call that would have parsed it, i.e. unless this batch is full without it;
+//   * R1 decides where the input ends: R2 records beyond R1's last are parsed too (a malformed one among them is an error) and cut.
+
+// ... for two regular plain-text files
+int next_plain(cm_fastq *f, uint64_t max_pairs, cm_fastq::Gen &G, uint64_t *n_out, bool *carried) {
+    // more threads than 16 only fight over the page-cache copies and the writer's bandwidth: file to file on a 256-CPU box,
     // 32 M chr21-like pairs: 10.1 / 14.4 / 13.1 / 11.7 / 9.0 M pairs/s with 8 / 16 / 24 / 32 / 64 threads (tests/diag/e2e_reports.py)
-    if (nt > 16) nt = 16;
-    if (const char *e = getenv("CM_FASTQ_THREADS")) nt = atoi(e);
-    nt = nt < 1 ? 1 : (nt > 32 ? 32 : nt);
-    const int half = nt > 1 ? nt / 2 : 1;
-    // ~ 2 x (read length + name) + 8 per record; the estimate only sizes the first read(), more is read on demand
+    const int nt = thread_count(f->n_threads, "CM_FASTQ_THREADS", 1, 16, 32), half = nt > 1 ? nt / 2 : 1;
+    // ~ 2 x (read length + name) + 8 per record; the estimate only sizes the first read(), more is read on demand ...
     size_t hint = (size_t)std::min<uint64_t>(max_pairs, 1ull << 22) * 360 + (1u << 20);
-    {   // never more than what is left of the larger file (a caller asking for "everything" must not cost a 1.5-GB buffer)
-        struct stat sa, sb;
-        if (f->s1.plain && f->s2.plain && fstat(fileno(f->s1.plain), &sa) == 0 && fstat(fileno(f->s2.plain), &sb) == 0) {
-            const uint64_t left1 = (uint64_t)sa.st_size > f->s1.file_pos ? (uint64_t)sa.st_size - f->s1.file_pos : 0;
-            const uint64_t left2 = (uint64_t)sb.st_size > f->s2.file_pos ? (uint64_t)sb.st_size - f->s2.file_pos : 0;
-            const uint64_t left = std::max(left1, left2) + (1u << 16);
-            if (left < hint) hint = (size_t)left;
+    {   // ... and never more than what is left of the larger file (a caller asking for "everything" must not cost a 1.5-GB buffer)
+        uint64_t left = 0;
+        bool known = true;
+        for (const MateFile &m : f->file) {
+            struct stat sb;
+            known = known && fstat(fileno(m.s.plain), &sb) == 0;
+            if (known && (uint64_t)sb.st_size > m.s.file_pos) left = std::max(left, (uint64_t)sb.st_size - m.s.file_pos);
         }
+        if (known && left + (1u << 16) < hint) hint = (size_t)(left + (1u << 16));
     }
-    size_t a1 = 0, a2 = 0, tail1 = 0, tail2 = 0;
-    const bool trace = getenv("CM_FASTQ_TRACE") != nullptr;
-    const auto t0 = std::chrono::steady_clock::now();
-    {   // the two files are filled and indexed side by side
-        std::thread t2([&]() { guarded([&]() { a2 = fill_and_index(f->s2, f->nl2, (size_t)max_pairs, hint, half, &tail2); }); });
-        try {
-            a1 = fill_and_index(f->s1, f->nl1, (size_t)max_pairs, hint, half, &tail1);
-        } catch (const std::bad_alloc &) {
-            g_raw_oom = 1;
-        }
-        t2.join();
-    }
-    if (g_raw_oom.exchange(0)) return CM_ENOMEM;
-    if (f->s1.io_error || f->s2.io_error) return CM_EIO;
-    if (a2 < a1 && a2 < max_pairs) return CM_EINVAL;                  // R2 ends before R1
-    const size_t n = (size_t)std::min<uint64_t>(a1, max_pairs);      // R1 decides; surplus R2 records at the end of input are ignored
-    // R2 records beyond R1's last (only at the end of the input) are parsed too, as the record-by-record parser does, and cut
-    // off by the caller: a malformed one among them is an error there, so it is one here
-    const size_t n2 = (size_t)std::min<uint64_t>(a2, max_pairs);
-    *n_out = n;
-    *n2_out = n2;
-    // The same verdicts, in the same call, as the record-by-record parser (gzip / pipe input): what follows the last whole
-    // record -- a partial record, blank lines -- is malformed input (the reference asserts the '@', fastq_parser.h:64-65), and it
-    // is reported by the call that would have parsed it, i.e. unless this batch is full without it.
-    if ((tail1 != 0 && a1 < max_pairs) || (tail2 != 0 && a2 < max_pairs)) return CM_EINVAL;
-    if (n == 0 && n2 == 0) return CM_OK;
-    bool ok1 = true, ok2 = true, any = false;
-    const auto t_mid = std::chrono::steady_clock::now();
-    {
-        std::thread t2([&]() { guarded([&]() { ok2 = n2 == 0 || build_side(f, f->s2, f->nl2, n2, G.b, nullptr, nullptr, half); }); });
-        try {
-            ok1 = n == 0 || build_side(f, f->s1, f->nl1, n, G.a, &G.prior, &any, half);
-        } catch (const std::bad_alloc &) {
-            g_raw_oom = 1;
-        }
-        t2.join();
-    }
-    if (g_raw_oom.exchange(0)) return CM_ENOMEM;
-    if (!ok1 || !ok2) return CM_EINVAL;
-    f->any_prior = any;
-    if (trace) fprintf(stderr, "[fastq] %zu pairs: fill+index %.1f ms, build %.1f ms\n", n, std::chrono::duration<double, std::milli>(t_mid - t0).count(),
-                       std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_mid).count());
+    Lap lap;
+    size_t avail[2] = {0, 0}, tail[2] = {0, 0};
+    if (!both_files([&](int x) { avail[x] = fill_and_index(f->file[x], (size_t)max_pairs, hint, half, &tail[x]); })) return CM_ENOMEM;
+    if (f->io_error()) return CM_EIO;
+    if (avail[1] < avail[0] && avail[1] < max_pairs) return CM_EINVAL;
+    if ((tail[0] != 0 && avail[0] < max_pairs) || (tail[1] != 0 && avail[1] < max_pairs)) return CM_EINVAL;
+    const size_t n[2] = {(size_t)std::min<uint64_t>(avail[0], max_pairs), (size_t)std::min<uint64_t>(avail[1], max_pairs)};
+    *n_out = n[0];
+    if (n[0] == 0 && n[1] == 0) return CM_OK;
+    const double t_fill = lap.ms();
+    bool ok[2] = {true, true};
+    if (!both_files([&](int x) { ok[x] = n[x] == 0 || build_side(f, f->file[x], n[x], G.side[x], x ? nullptr : &G.prior, carried, half); })) return CM_ENOMEM;
+    if (!ok[0] || !ok[1]) return CM_EINVAL;
+    if (n[1] > n[0]) G.side[1].keep(n[0]);
+    if (tracing()) fprintf(stderr, "[fastq] %zu pairs: fill+index %.1f ms, build %.1f ms\n", n[0], t_fill, lap.ms());
     return CM_OK;
 }
 
+// ... record by record, for any input: gzip, pipes, CM_FASTQ_SERIAL.  The two files are independent streams until the records
+// are paired up: R2 is parsed (and inflated) on a second thread while this one does R1 and its carried state.  The reference does
+// both inside one lock-protected serial section (src/circminer.cpp:373-379), which is its ingest ceiling.
+int next_records(cm_fastq *f, uint64_t max_pairs, cm_fastq::Gen &G, uint64_t *n_out, bool *carried) {
+    for (; f->skip_left; --f->skip_left)                   // a shard of gzip input: the records of the ranks before this one
+        for (int k = 0; k < 4; ++k)
+            for (MateFile &m : f->file) {
+                const char *p;
+                size_t len;
+                if (!m.s.line(p, len)) return f->io_error() ? CM_EIO : CM_EINVAL;
+            }
+    if (f->take_left < max_pairs) max_pairs = f->take_left;
+    uint64_t n[2] = {0, 0};
+    bool bad[2] = {false, false};
+    if (!both_files([&](int x) {
+            for (; n[x] < max_pairs; ++n[x]) {
+                cm_mapped_read st;
+                bool has23 = false;
+                const int r = parse_record(f, f->file[x].s, G.side[x], x == 0, &st, &has23);
+                if (r <= 0) {
+                    bad[x] = r < 0;
+                    break;
+                }
+                if (x == 0) {
+                    G.prior.push_back(st);
+                    *carried = *carried || has23;
+                }
+            }
+        }))
+        return CM_ENOMEM;
+    if (f->io_error()) return CM_EIO;
+    if (bad[0] || bad[1] || n[1] < n[0]) return CM_EINVAL;
+    if (f->take_left != ~0ull) f->take_left -= n[0];
+    if (n[1] > n[0]) G.side[1].keep((size_t)n[0]);
+    *n_out = n[0];
+    return CM_OK;
+}
+
+// the one place a cm_fastq_batch is filled: n pairs of the generation's two sides
+void publish(const cm_fastq::Gen &G, uint64_t n, bool carried, cm_fastq_batch *out) {
+    const Side &a = G.side[0], &b = G.side[1];
+    memset(out, 0, sizeof *out);
+    out->reads.n_pairs = n;
+    out->reads.seq1 = a.seq.data();
+    out->reads.off1 = a.off.data();
+    out->reads.seq2 = b.seq.data();
+    out->reads.off2 = b.off.data();
+    out->qual1 = a.qual.data();
+    out->qual2 = b.qual.data();
+    out->names1 = a.names.data();
+    out->name_off1 = a.name_off.data();
+    out->names2 = b.names.data();
+    out->name_off2 = b.name_off.data();
+    out->prior = carried ? G.prior.data() : nullptr;
+}
+
+// ---- raw-block mode: the text itself, for cm_reads_stage_text --------------------------------------------------------
+struct TextBlock {
+    const uint8_t *text = nullptr;
+    uint64_t len = 0;
+    int eof = 0;
+};
+// The next block of one file in generation g of its buffers: what the caller left of the block before it, then fresh bytes.
+// `again`: nothing was consumed of that block, which is of this generation: it grows in place.  False when a read failed.
+bool next_text_block(MateFile &m, int g, bool again, uint64_t want, int read_threads, TextBlock &out) {
+    constexpr size_t HEAD_MIN = 64u << 10;                 // head room in front of the fresh bytes: a tail is a few records as a rule
+    RawVec<uint8_t> &B = m.text[g];
+    const uint64_t tl = m.block_len - m.block_used;
+    const uint8_t *tail = m.block + m.block_used;
+    // a block of `want` bytes, tail included (files whose records differ in length then keep a steady tail); a tail that is
+    // most of that -- nothing was consumed: a record larger than the block -- still gets half a block of fresh bytes
+    const uint64_t fresh = tl < want / 2 ? want - tl : (want + 1) / 2;
+    uint8_t *data;
+    if (again) {
+        const size_t at = (size_t)(tail - B.data());
+        B.n = at + (size_t)tl;                              // (kept if the buffer has to grow)
+        B.resize(at + (size_t)tl + (size_t)fresh);
+        data = B.data() + at + tl;
+    } else {
+        const size_t head = std::max<size_t>(HEAD_MIN, ((size_t)tl + 4095) / 4096 * 4096);
+        B.clear();                                          // (nothing of the old block is kept when the buffer has to grow)
+        B.resize(head + (size_t)fresh);
+        data = B.data() + head;
+        if (tl) memcpy(data - tl, tail, (size_t)tl);
+    }
+    Stream &s = m.s;
+    s.read_threads = read_threads;
+    uint64_t got = 0;
+    while (got < fresh) {
+        const int r = s.read_some((char *)data + got, (size_t)(fresh - got));
+        if (r < 0) return false;
+        if (r == 0) break;
+        got += (uint64_t)r;
+    }
+    struct stat sb;
+    const uint64_t size = fstat(fileno(s.plain), &sb) == 0 ? (uint64_t)sb.st_size : ~0ull;
+    out.eof = got < fresh || s.file_pos >= std::min(size, s.file_end);
+    out.text = data - tl;
+    out.len = tl + got;
+    return true;
+}
+
+// ---- cm_fastq_open_shard: where a rank's block of pairs begins and ends ------------------------------------------------
+// Byte offsets at which the records `rec[0..n)` (4 lines each) of a plain-text FASTQ file start: the newlines of the file are
+// counted in blocks on several threads, then the block holding the wanted newline is looked at again.  A record index equal to
+// the number of records maps to the end of the file.  Returns the number of records, or -1 on a read error.
+long long record_offsets(int fd, uint64_t size, const uint64_t *rec, int n, uint64_t *off, int nt) {
+    constexpr uint64_t BLK = 32ull << 20;
+    const uint64_t nblk = (size + BLK - 1) / BLK;
+    std::vector<uint64_t> cnt(nblk + 1, 0);
+    std::atomic<uint64_t> next{0};
+    std::atomic<int> bad{0};
+    auto read_blk = [&](uint64_t b, std::vector<char> &buf) -> size_t {
+        const uint64_t a = b * BLK, e = std::min(size, a + BLK);
+        buf.resize((size_t)(e - a));
+        size_t done = 0;
+        while (done < buf.size()) {
+            const ssize_t r = pread(fd, buf.data() + done, buf.size() - done, (off_t)(a + done));
+            if (r < 0 && errno == EINTR) continue;
+            if (r <= 0) {
+                bad = 1;
+                return 0;
+            }
+            done += (size_t)r;
+        }
+        return done;
+    };
+    std::vector<std::thread> th;
+    for (int t = 0; t < nt; ++t)
+        th.emplace_back([&]() {
+            std::vector<char> buf;
+            for (uint64_t b; (b = next.fetch_add(1)) < nblk;) {
+                const size_t got = read_blk(b, buf);
+                cnt[b + 1] = (uint64_t)std::count(buf.data(), buf.data() + got, '\n');
+            }
+        });
+    for (auto &x : th) x.join();
+    if (bad) return -1;
+    for (uint64_t b = 0; b < nblk; ++b) cnt[b + 1] += cnt[b];
+    char last = '\n';
+    if (size > 0 && pread(fd, &last, 1, (off_t)(size - 1)) != 1) return -1;
+    const uint64_t n_rec = count_lines(cnt[nblk], last) / 4;
+    std::vector<char> buf;
+    for (int i = 0; i < n; ++i) {
+        const uint64_t want = rec[i] * 4;             // the record starts behind the want-th newline
+        if (rec[i] >= n_rec) {
+            off[i] = size;
+            continue;
+        }
+        if (want == 0) {
+            off[i] = 0;
+            continue;
+        }
+        const uint64_t b = (uint64_t)(std::lower_bound(cnt.begin(), cnt.end(), want) - cnt.begin()) - 1;     // cnt[b] < want <= cnt[b + 1]
+        const size_t got = read_blk(b, buf);
+        if (bad) return -1;
+        uint64_t seen = cnt[b];
+        size_t k = 0;
+        for (; k < got; ++k)
+            if (buf[k] == '\n' && ++seen == want) break;
+        off[i] = b * BLK + k + 1;
+    }
+    return (long long)n_rec;
+}
+// the number of records of a gzip file, by one inflate pass; -1 when it cannot be read
+long long gzip_records(const char *path) {
+    gzFile g = gzopen(path, "rb");
+    if (!g) return -1;
+    gzbuffer(g, 1u << 20);
+    std::vector<char> buf(4u << 20);
+    uint64_t newlines = 0;
+    char last = '\n';
+    int got;
+    while ((got = gzread(g, buf.data(), (unsigned)buf.size())) > 0) {
+        newlines += (uint64_t)std::count(buf.data(), buf.data() + got, '\n');
+        last = buf[(size_t)got - 1];
+    }
+    gzclose(g);
+    return got < 0 ? -1 : (long long)(count_lines(newlines, last) / 4);
+}
+
 }  // namespace
+extern "C" {
+
+int cm_fastq_open(const char *r1_path, const char *r2_path, const cm_chr_info *chrs, uint32_t n_chr, int32_t max_ed, cm_fastq **out) {
+    if (!r1_path || !r2_path || !out || (n_chr && !chrs)) return CM_EINVAL;
+    *out = nullptr;
+    cm_fastq *f = new cm_fastq();
+    if (!f->file[0].s.open(r1_path) || !f->file[1].s.open(r2_path)) {
+        cm_fastq_close(f);
+        return CM_EINVAL;
+    }
+    for (uint32_t i = 0; i < n_chr; ++i) f->chr_names.emplace_back(chrs[i].name ? chrs[i].name : "");
+    f->max_ed = max_ed;
+    *out = f;
+    return CM_OK;
+}
+
+int cm_fastq_open_shard(const char *r1_path, const char *r2_path, const cm_chr_info *chrs, uint32_t n_chr, int32_t max_ed, int32_t rank,
+                        int32_t world, int n_threads, cm_fastq **out, uint64_t *first_pair, uint64_t *n_pairs) {
+    if (world < 1 || rank < 0 || rank >= world) return CM_EINVAL;
+    const int rc = cm_fastq_open(r1_path, r2_path, chrs, n_chr, max_ed, out);
+    if (rc != CM_OK) return rc;
+    cm_fastq *f = *out;
+    if (first_pair) *first_pair = 0;
+    if (n_pairs) *n_pairs = ~0ull;
+    if (world == 1 && !n_pairs) return CM_OK;
+    auto fail = [&](int e) {
+        cm_fastq_close(f);
+        *out = nullptr;
+        return e;
+    };
+    // The number of records first: R1 decides, as everywhere.  Contiguous blocks of pairs need both files cut at the same RECORD,
+    // which seekable plain text allows.  gzip members cannot be entered in the middle: the records are counted with one inflate
+    // pass over R1, every rank then inflates from the start and steps over what belongs to the ranks before it.  Slow by nature
+    // (one zlib stream per file: ~ 0.4 M pairs/s) -- but the same contiguous blocks, hence the same output bytes after
+    // cm_merge_parts, as plain-text input.  A pipe cannot be read twice: refused.
+    const bool last_rank = rank == world - 1;
+    const int nt = thread_count(n_threads, nullptr, 1, 32, 32);
+    struct stat sb[2];
+    long long n1;
+    if (f->plain()) {
+        for (int x = 0; x < 2; ++x)
+            if (fstat(fileno(f->file[x].s.plain), &sb[x]) != 0) return fail(CM_EIO);
+        uint64_t none = 0, dummy = 0;
+        n1 = record_offsets(fileno(f->file[0].s.plain), (uint64_t)sb[0].st_size, &none, 0, &dummy, nt);
+    } else {
+        if (stat(r1_path, &sb[0]) != 0 || !S_ISREG(sb[0].st_mode)) return world == 1 ? CM_OK : fail(CM_EINVAL);
+        n1 = gzip_records(r1_path);
+    }
+    if (n1 < 0) return fail(CM_EIO);
+    const uint64_t lo = (uint64_t)n1 * (uint64_t)rank / (uint64_t)world, hi = (uint64_t)n1 * (uint64_t)(rank + 1) / (uint64_t)world;
+    // This rank's [lo, hi) in both files.  The last rank reads to the end of both, so that what follows the last whole record is
+    // seen (and refused) as in an unsharded run; R2's surplus records, if any, stay with it too.
+    if (f->plain()) {
+        const uint64_t want[2] = {lo, hi};
+        for (int x = 0; x < 2; ++x) {
+            Stream &s = f->file[x].s;
+            uint64_t cut[2];
+            const long long nx = record_offsets(fileno(s.plain), (uint64_t)sb[x].st_size, want, 2, cut, nt);
+            if (nx < 0) return fail(CM_EIO);
+            if ((uint64_t)nx < hi) return fail(CM_EINVAL);                                  // R2 ends before R1
+            s.file_pos = cut[0];
+            s.file_end = last_rank ? ~0ull : cut[1];
+        }
+    } else {
+        f->skip_left = lo;
+        f->take_left = last_rank ? ~0ull : hi - lo;
+    }
+    if (first_pair) *first_pair = lo;
+    if (n_pairs) *n_pairs = hi - lo;
+    return CM_OK;
+}
+
+void cm_fastq_set_release_hook(cm_fastq *f, void (*fn)(void *user, const void *ptr, uint64_t bytes), void *user) {
+    if (!f) return;
+    f->hook.fn = fn;
+    f->hook.user = user;
+}
+
+int cm_fastq_next(cm_fastq *f, uint64_t max_pairs, cm_fastq_batch *out) {
+    if (!f || !out) return CM_EINVAL;
+    try {
+        f->cur = (f->cur + 1) % 4;
+        cm_fastq::Gen &G = f->gen[f->cur];
+        for (Side &s : G.side) s.clear();
+        G.prior.clear();
+        uint64_t n = 0;
+        bool carried = false;
+        const bool plain = f->plain() && !getenv("CM_FASTQ_SERIAL");
+        const int rc = plain ? next_plain(f, max_pairs, G, &n, &carried) : next_records(f, max_pairs, G, &n, &carried);
+        if (rc == CM_OK) publish(G, n, carried, out);
+        return rc;
+    } catch (const std::bad_alloc &) {
+        return CM_ENOMEM;
+    }
+}
+
+int cm_fastq_next_text(cm_fastq *f, uint64_t want_bytes, const uint8_t **text1, uint64_t *len1, int *eof1, const uint8_t **text2, uint64_t *len2,
+                       int *eof2) {
+    if (!f || !text1 || !len1 || !eof1 || !text2 || !len2 || !eof2) return CM_EINVAL;
+    // regular plain-text files only, and not behind cm_fastq_next calls that have buffered text of their own
+    if (!f->plain()) return CM_EINVAL;
+    for (const MateFile &m : f->file)
+        if (m.s.end != m.s.pos) return CM_EINVAL;
+    const uint64_t want = std::min<uint64_t>(std::max<uint64_t>(want_bytes, 1), 1ull << 31);      // (a block stays below cm_reads_stage_text's 2^32 - 1 bytes)
+    // Nothing consumed of the last block (it held no whole pair): the same generation again, fresh bytes appended in place, so that
+    // the blocks a caller still holds keep their three calls of life.
+    const MateFile *m = f->file;
+    const bool again = m[0].block && m[0].block_used == 0 && m[1].block_used == 0 && (m[0].block_len || m[1].block_len);
+    if (!again) f->text_cur = (f->text_cur + 1) % 4;
+    const int read_threads = thread_count(f->n_threads, nullptr, 2, 16, 16) / 2;
+    TextBlock b[2];
+    bool ok[2] = {true, true};
+    if (!both_files([&](int x) { ok[x] = next_text_block(f->file[x], f->text_cur, again, want, read_threads, b[x]); })) return CM_ENOMEM;
+    if (!ok[0] || !ok[1]) return CM_EIO;
+    for (int x = 0; x < 2; ++x) {
+        f->file[x].block = b[x].text;
+        f->file[x].block_len = b[x].len;
+        f->file[x].block_used = 0;
+    }
+    *text1 = b[0].text, *len1 = b[0].len, *eof1 = b[0].eof;
+    *text2 = b[1].text, *len2 = b[1].len, *eof2 = b[1].eof;
+    return CM_OK;
+}
+int cm_fastq_text_consumed(cm_fastq *f, uint64_t used1, uint64_t used2) {
+    if (!f || used1 > f->file[0].block_len || used2 > f->file[1].block_len) return CM_EINVAL;
+    f->file[0].block_used = used1;
+    f->file[1].block_used = used2;
+    return CM_OK;
+}
+
+void cm_fastq_close(cm_fastq *f) {
+    if (!f) return;
+    for (MateFile &m : f->file) m.s.close();
+    delete f;
+}
+
+}  // extern "C"
+
+// ======================================================= writers =======================================================
 // Append-only text buffer in front of a FILE: the writers format integers themselves (a PAM row is 20 of them), which is
 // several times faster than one fprintf per record.
 struct Out {
@@ -760,364 +1112,6 @@ struct cm_writer {
 };
 
 extern "C" {
-
-int cm_fastq_open(const char *r1_path, const char *r2_path, const cm_chr_info *chrs, uint32_t n_chr, int32_t max_ed, cm_fastq **out) {
-    if (!r1_path || !r2_path || !out || (n_chr && !chrs)) return CM_EINVAL;
-    *out = nullptr;
-    cm_fastq *f = new cm_fastq();
-    if (!f->s1.open(r1_path) || !f->s2.open(r2_path)) {
-        f->s1.close();
-        f->s2.close();
-        delete f;
-        return CM_EINVAL;
-    }
-    for (uint32_t i = 0; i < n_chr; ++i) f->chr_names.emplace_back(chrs[i].name ? chrs[i].name : "");
-    f->max_ed = max_ed;
-    *out = f;
-    return CM_OK;
-}
-
-// Byte offsets at which the records `rec[0..n)` (4 lines each) of a plain-text FASTQ file start: the newlines of the file are
-// counted in blocks on several threads, then the block holding the wanted newline is looked at again.  A record index equal to
-// the number of records maps to the end of the file.  Returns the number of records, or -1 on a read error.
-static long long record_offsets(int fd, uint64_t size, const uint64_t *rec, int n, uint64_t *off, int nt) {
-    constexpr uint64_t BLK = 32ull << 20;
-    const uint64_t nblk = (size + BLK - 1) / BLK;
-    std::vector<uint64_t> cnt(nblk + 1, 0);
-    std::atomic<uint64_t> next{0};
-    std::atomic<int> bad{0};
-    auto read_blk = [&](uint64_t b, std::vector<char> &buf) -> size_t {
-        const uint64_t a = b * BLK, e = std::min(size, a + BLK);
-        buf.resize((size_t)(e - a));
-        size_t done = 0;
-        while (done < buf.size()) {
-            const ssize_t r = pread(fd, buf.data() + done, buf.size() - done, (off_t)(a + done));
-            if (r < 0 && errno == EINTR) continue;
-            if (r <= 0) {
-                bad = 1;
-                return 0;
-            }
-            done += (size_t)r;
-        }
-        return done;
-    };
-    std::vector<std::thread> th;
-    for (int t = 0; t < std::max(1, nt); ++t)
-        th.emplace_back([&]() {
-            std::vector<char> buf;
-            for (uint64_t b; (b = next.fetch_add(1)) < nblk;) {
-                const size_t got = read_blk(b, buf);
-                cnt[b + 1] = (uint64_t)std::count(buf.data(), buf.data() + got, '\n');
-            }
-        });
-    for (auto &x : th) x.join();
-    if (bad) return -1;
-    for (uint64_t b = 0; b < nblk; ++b) cnt[b + 1] += cnt[b];
-    uint64_t lines = cnt[nblk];
-    if (size > 0) {                                   // a last line without a newline still is a line
-        char last = 0;
-        if (pread(fd, &last, 1, (off_t)(size - 1)) != 1) return -1;
-        if (last != '\n') ++lines;
-    }
-    const uint64_t n_rec = lines / 4;
-    std::vector<char> buf;
-    for (int i = 0; i < n; ++i) {
-        const uint64_t want = rec[i] * 4;             // the record starts behind the want-th newline
-        if (rec[i] >= n_rec) {
-            off[i] = size;
-            continue;
-        }
-        if (want == 0) {
-            off[i] = 0;
-            continue;
-        }
-        const uint64_t b = (uint64_t)(std::lower_bound(cnt.begin(), cnt.end(), want) - cnt.begin()) - 1;     // cnt[b] < want <= cnt[b + 1]
-        const size_t got = read_blk(b, buf);
-        if (bad) return -1;
-        uint64_t seen = cnt[b];
-        size_t k = 0;
-        for (; k < got; ++k)
-            if (buf[k] == '\n' && ++seen == want) break;
-        off[i] = b * BLK + k + 1;
-    }
-    return (long long)n_rec;
-}
-
-int cm_fastq_open_shard(const char *r1_path, const char *r2_path, const cm_chr_info *chrs, uint32_t n_chr, int32_t max_ed, int32_t rank,
-                        int32_t world, int n_threads, cm_fastq **out, uint64_t *first_pair, uint64_t *n_pairs) {
-    if (world < 1 || rank < 0 || rank >= world) return CM_EINVAL;
-    const int rc = cm_fastq_open(r1_path, r2_path, chrs, n_chr, max_ed, out);
-    if (rc != CM_OK) return rc;
-    cm_fastq *f = *out;
-    if (first_pair) *first_pair = 0;
-    if (n_pairs) *n_pairs = ~0ull;
-    if (world == 1 && !n_pairs) return CM_OK;
-    auto fail = [&](int e) {
-        cm_fastq_close(f);
-        *out = nullptr;
-        return e;
-    };
-    // contiguous blocks of pairs need both files cut at the same RECORD: seekable plain text only (gzip members cannot be entered
-    // in the middle, a pipe cannot be read twice)
-    if (!f->s1.plain || !f->s2.plain) {
-        if (world == 1 && !n_pairs) return CM_OK;
-        // gzip members cannot be entered in the middle: the records are counted with one inflate pass over R1 (R1 decides, as
-        // everywhere), every rank then inflates from the start and steps over what belongs to the ranks before it.  Slow by
-        // nature (one zlib stream per file: ~ 0.4 M pairs/s) -- but the same contiguous blocks, hence the same output bytes after
-        // cm_merge_parts, as plain-text input.  A pipe cannot be read twice: refused.
-        struct stat sa;
-        if (stat(r1_path, &sa) != 0 || !S_ISREG(sa.st_mode)) return world == 1 ? CM_OK : fail(CM_EINVAL);
-        gzFile g = gzopen(r1_path, "rb");
-        if (!g) return fail(CM_EIO);
-        gzbuffer(g, 1u << 20);
-        std::vector<char> buf(4u << 20);
-        uint64_t lines = 0;
-        char last = '\n';
-        for (;;) {
-            const int got = gzread(g, buf.data(), (unsigned)buf.size());
-            if (got < 0) {
-                gzclose(g);
-                return fail(CM_EIO);
-            }
-            if (got == 0) break;
-            lines += (uint64_t)std::count(buf.data(), buf.data() + got, '\n');
-            last = buf[(size_t)got - 1];
-        }
-        gzclose(g);
-        if (last != '\n') ++lines;                    // a last line without a newline still is a line
-        const uint64_t n1 = lines / 4;
-        const uint64_t lo = n1 * (uint64_t)rank / (uint64_t)world, hi = n1 * (uint64_t)(rank + 1) / (uint64_t)world;
-        f->skip_left = lo;
-        f->take_left = rank == world - 1 ? ~0ull : hi - lo;      // the last rank reads on: what follows the last whole record is seen (and refused) as in one process
-        if (first_pair) *first_pair = lo;
-        if (n_pairs) *n_pairs = hi - lo;
-        return CM_OK;
-    }
-    struct stat sa, sb;
-    if (fstat(fileno(f->s1.plain), &sa) != 0 || fstat(fileno(f->s2.plain), &sb) != 0) return fail(CM_EIO);
-    int nt = n_threads > 0 ? n_threads : (int)std::thread::hardware_concurrency();
-    nt = nt < 1 ? 1 : (nt > 32 ? 32 : nt);
-    // number of records first (R1 decides, as everywhere), then this rank's [lo, hi) in both files
-    uint64_t none = 0, dummy = 0;
-    const long long n1 = record_offsets(fileno(f->s1.plain), (uint64_t)sa.st_size, &none, 0, &dummy, nt);
-    if (n1 < 0) return fail(CM_EIO);
-    const uint64_t lo = (uint64_t)n1 * (uint64_t)rank / (uint64_t)world, hi = (uint64_t)n1 * (uint64_t)(rank + 1) / (uint64_t)world;
-    const uint64_t want[2] = {lo, hi};
-    uint64_t o1[2], o2[2];
-    if (record_offsets(fileno(f->s1.plain), (uint64_t)sa.st_size, want, 2, o1, nt) < 0) return fail(CM_EIO);
-    const long long n2 = record_offsets(fileno(f->s2.plain), (uint64_t)sb.st_size, want, 2, o2, nt);
-    if (n2 < 0) return fail(CM_EIO);
-    if ((uint64_t)n2 < hi) return fail(CM_EINVAL);                                      // R2 ends before R1
-    f->s1.file_pos = o1[0];
-    f->s2.file_pos = o2[0];
-    // the last rank reads to the end of both files, so that what follows the last whole record is seen (and refused) as in an
-    // unsharded run; R2's surplus records, if any, stay with it too
-    f->s1.file_end = rank == world - 1 ? ~0ull : o1[1];
-    f->s2.file_end = rank == world - 1 ? ~0ull : o2[1];
-    if (first_pair) *first_pair = lo;
-    if (n_pairs) *n_pairs = hi - lo;
-    return CM_OK;
-}
-
-static int fastq_next(cm_fastq *f, uint64_t max_pairs, cm_fastq_batch *out);
-int cm_fastq_next(cm_fastq *f, uint64_t max_pairs, cm_fastq_batch *out) {
-    if (!f || !out) return CM_EINVAL;
-    try {
-        return fastq_next(f, max_pairs, out);
-    } catch (const std::bad_alloc &) {
-        return CM_ENOMEM;
-    }
-}
-void cm_fastq_set_release_hook(cm_fastq *f, void (*fn)(void *user, const void *ptr, uint64_t bytes), void *user) {
-    if (!f) return;
-    f->hook.fn = fn;
-    f->hook.user = user;
-}
-static int fastq_next(cm_fastq *f, uint64_t max_pairs, cm_fastq_batch *out) {
-    f->cur = (f->cur + 1) % 4;
-    cm_fastq::Gen &G = f->gen[f->cur];
-    G.a.clear();
-    G.b.clear();
-    G.prior.clear();
-    f->any_prior = false;
-    uint64_t n_fast = 0, n2_fast = 0;
-    const bool fast = f->s1.plain && f->s2.plain && !getenv("CM_FASTQ_SERIAL");
-    if (fast) {
-        const int rc = next_plain(f, max_pairs, G, &n_fast, &n2_fast);
-        if (rc != CM_OK) return rc;
-    }
-    // The two files are independent streams until the records are paired up: R2 is parsed (and, for .gz input, inflated)
-    // on a second thread while this one does R1 and its carried state.  The reference does both inside one lock-protected
-    // serial section (src/circminer.cpp:373-379), which is its ingest ceiling.
-    uint64_t n = fast ? n_fast : 0, n2 = fast ? n2_fast : 0;
-    int bad2 = 0;
-    if (!fast && f->skip_left) {                       // a shard of gzip input: the records of the ranks before this one
-        const char *lp;
-        size_t ll;
-        for (; f->skip_left; --f->skip_left)
-            for (int k = 0; k < 4; ++k)
-                if (!f->s1.line(lp, ll) || !f->s2.line(lp, ll)) return (f->s1.io_error || f->s2.io_error) ? CM_EIO : CM_EINVAL;
-    }
-    if (!fast && f->take_left < max_pairs) max_pairs = f->take_left;
-    std::thread side_b([&]() {
-        guarded([&]() {
-            while (!fast && n2 < max_pairs) {
-                const int r2 = parse_record(f, f->s2, G.b, false, nullptr, nullptr);
-                if (r2 == 0) break;
-                if (r2 < 0) {
-                    bad2 = 1;
-                    break;
-                }
-                ++n2;
-            }
-        });
-    });
-    int bad1 = 0;
-    try {
-        while (!fast && n < max_pairs) {
-            cm_mapped_read st;
-            bool carried = false;
-            const int r1 = parse_record(f, f->s1, G.a, true, &st, &carried);
-            if (r1 == 0) break;
-            if (r1 < 0) {
-                bad1 = 1;
-                break;
-            }
-            G.prior.push_back(st);
-            f->any_prior = f->any_prior || carried;
-            ++n;
-        }
-    } catch (const std::bad_alloc &) {
-        g_raw_oom = 1;
-    }
-    side_b.join();
-    if (g_raw_oom.exchange(0)) return CM_ENOMEM;
-    if (f->s1.io_error || f->s2.io_error) return CM_EIO;
-    if (bad1 || bad2 || n2 < n) return CM_EINVAL;                   // malformed record, or R2 ends before R1
-    if (!fast && f->take_left != ~0ull) f->take_left -= n;
-    if (n2 > n) {        // R1 ended first: like the reference, which stops at R1's end, the surplus R2 records are not paired
-        G.b.off.resize(n + 1);
-        G.b.seq.resize(G.b.off[n]);
-        G.b.qual.resize(G.b.off[n]);
-        G.b.name_off.resize(n + 1);
-        G.b.names.resize(G.b.name_off[n]);
-    }
-    memset(out, 0, sizeof *out);
-    out->reads.n_pairs = n;
-    out->reads.seq1 = G.a.seq.data();
-    out->reads.off1 = G.a.off.data();
-    out->reads.seq2 = G.b.seq.data();
-    out->reads.off2 = G.b.off.data();
-    out->qual1 = G.a.qual.data();
-    out->qual2 = G.b.qual.data();
-    out->names1 = G.a.names.data();
-    out->name_off1 = G.a.name_off.data();
-    out->names2 = G.b.names.data();
-    out->name_off2 = G.b.name_off.data();
-    out->prior = f->any_prior ? G.prior.data() : nullptr;
-    return CM_OK;
-}
-
-// ---- raw-block mode: the text itself, for cm_reads_stage_text --------------------------------------------------------
-static int fastq_next_text(cm_fastq *f, uint64_t want, const uint8_t **text, uint64_t *len, int *eof) {
-    constexpr size_t HEAD_MIN = 64u << 10;                 // head room in front of the fresh bytes: a tail is a few records as a rule
-    if (want == 0) want = 1;
-    if (want > (1ull << 31)) want = 1ull << 31;            // (a block stays below cm_reads_stage_text's 2^32 - 1 bytes)
-    // Nothing consumed of the last block (it held no whole pair): the same generation again, fresh bytes appended in place, so that
-    // the blocks a caller still holds keep their three calls of life.
-    const bool again = f->block[0] && f->block_used[0] == 0 && f->block_used[1] == 0 && (f->block_len[0] || f->block_len[1]);
-    if (!again) f->tcur = (f->tcur + 1) % 4;
-    Stream *ss[2] = {&f->s1, &f->s2};
-    int nt = f->n_threads > 0 ? f->n_threads : (int)std::thread::hardware_concurrency();
-    nt = nt > 16 ? 16 : (nt < 2 ? 2 : nt);
-    int rc[2] = {CM_OK, CM_OK};
-    auto side = [&](int x) {
-        RawVec<uint8_t> &B = f->tgen[f->tcur].buf[x];
-        const uint64_t tl = f->block_len[x] - f->block_used[x];
-        const uint8_t *tail = f->block[x] + f->block_used[x];
-        // a block of `want` bytes, tail included (files whose records differ in length then keep a steady tail); a tail that is
-        // most of that -- nothing was consumed: a record larger than the block -- still gets half a block of fresh bytes
-        const uint64_t fresh = tl < want / 2 ? want - tl : (want + 1) / 2;
-        uint8_t *data;
-        if (again) {
-            const size_t at = (size_t)(tail - B.data());
-            B.n = at + (size_t)tl;                          // (kept if the buffer has to grow)
-            B.resize(at + (size_t)tl + (size_t)fresh);
-            data = B.data() + at + tl;
-        } else {
-            const size_t head = std::max<size_t>(HEAD_MIN, ((size_t)tl + 4095) / 4096 * 4096);
-            B.clear();                                      // (nothing of the old block is kept when the buffer has to grow)
-            B.resize(head + (size_t)fresh);
-            data = B.data() + head;
-            if (tl) memcpy(data - tl, tail, (size_t)tl);
-        }
-        Stream &s = *ss[x];
-        s.read_threads = nt / 2;
-        uint64_t got = 0;
-        while (got < fresh) {
-            const int r = s.read_some((char *)data + got, (size_t)(fresh - got));
-            if (r < 0) {
-                rc[x] = CM_EIO;
-                return;
-            }
-            if (r == 0) break;
-            got += (uint64_t)r;
-        }
-        struct stat sb;
-        const uint64_t size = fstat(fileno(s.plain), &sb) == 0 ? (uint64_t)sb.st_size : ~0ull;
-        eof[x] = got < fresh || s.file_pos >= std::min(size, s.file_end);
-        text[x] = data - tl;
-        len[x] = tl + got;
-    };
-    {
-        std::thread t2([&]() { guarded([&]() { side(1); }); });
-        try {
-            side(0);
-        } catch (const std::bad_alloc &) {
-            g_raw_oom = 1;
-        }
-        t2.join();
-    }
-    if (g_raw_oom.exchange(0)) return CM_ENOMEM;
-    if (rc[0] != CM_OK || rc[1] != CM_OK) return CM_EIO;
-    for (int x = 0; x < 2; ++x) {
-        f->block[x] = text[x];
-        f->block_len[x] = len[x];
-        f->block_used[x] = 0;
-    }
-    return CM_OK;
-}
-int cm_fastq_next_text(cm_fastq *f, uint64_t want_bytes, const uint8_t **text1, uint64_t *len1, int *eof1, const uint8_t **text2, uint64_t *len2,
-                       int *eof2) {
-    if (!f || !text1 || !len1 || !eof1 || !text2 || !len2 || !eof2) return CM_EINVAL;
-    // regular plain-text files only, and not behind cm_fastq_next calls that have buffered text of their own
-    if (!f->s1.plain || !f->s2.plain || f->s1.end != f->s1.pos || f->s2.end != f->s2.pos) return CM_EINVAL;
-    const uint8_t *text[2] = {nullptr, nullptr};
-    uint64_t len[2] = {0, 0};
-    int eof[2] = {0, 0};
-    const int rc = fastq_next_text(f, want_bytes, text, len, eof);
-    if (rc != CM_OK) return rc;
-    *text1 = text[0];
-    *len1 = len[0];
-    *eof1 = eof[0];
-    *text2 = text[1];
-    *len2 = len[1];
-    *eof2 = eof[1];
-    return CM_OK;
-}
-int cm_fastq_text_consumed(cm_fastq *f, uint64_t used1, uint64_t used2) {
-    if (!f || used1 > f->block_len[0] || used2 > f->block_len[1]) return CM_EINVAL;
-    f->block_used[0] = used1;
-    f->block_used[1] = used2;
-    return CM_OK;
-}
-
-void cm_fastq_close(cm_fastq *f) {
-    if (!f) return;
-    f->s1.close();
-    f->s2.close();
-    delete f;
-}
 
 int cm_writer_open(const char *path1, const char *path2, const cm_chr_info *chrs, uint32_t n_chr, cm_writer **out) {
     if (!path1 || !out || (n_chr && !chrs)) return CM_EINVAL;
@@ -1298,9 +1292,7 @@ int cm_write_pam(cm_writer *w, const cm_fastq_batch *b, const cm_mapped_read *st
         for (uint64_t k = 0; k < n; ++k)
             if (sel[k] >= b->reads.n_pairs) return CM_EINVAL;
     // large batches: rows formatted on several threads into private buffers, written out in order
-    int nt = (int)std::thread::hardware_concurrency();
-    if (const char *e = getenv("CM_WRITER_THREADS")) nt = atoi(e);
-    nt = nt < 1 ? 1 : (nt > 16 ? 16 : nt);
+    const int nt = thread_count(0, "CM_WRITER_THREADS", 1, 16, 16);
     if (n < 65536 || nt == 1) {
         for (uint64_t k = 0; k < n; ++k) {
             const uint64_t i = sel ? sel[k] : k;
@@ -1310,7 +1302,7 @@ int cm_write_pam(cm_writer *w, const cm_fastq_batch *b, const cm_mapped_read *st
     }
     w->o1.flush();
     std::vector<Out> part((size_t)nt);
-    par_for(nt, (size_t)n, [&](int t, size_t lo, size_t hi) {
+    const bool formatted = par_for(nt, (size_t)n, [&](int t, size_t lo, size_t hi) {
         Out &o = part[(size_t)t];
         o.buf.resize((hi - lo) * 160 + 4096);          // grows on demand (room()); never flushed: f == nullptr
         for (size_t k = lo; k < hi; ++k) {
@@ -1318,6 +1310,7 @@ int cm_write_pam(cm_writer *w, const cm_fastq_batch *b, const cm_mapped_read *st
             pam_row(w, b, states[i], i, o);
         }
     });
+    if (!formatted) return CM_ENOMEM;                  // a thread could not grow its buffer: nothing of this call's rows is written
     for (Out &o : part)
         if (o.n && fwrite(o.buf.data(), 1, o.n, w->f1) != o.n) {
             w->o1.failed = true;

@@ -1,6 +1,7 @@
 """FASTQ ingest, the 23-token carry-over header, PAM and remain-FASTQ writers
 (circminer_amd/csrc/host_fastq.cpp) against Python restatements of the reference's formats
 (src/fastq_parser.cpp:178-269, src/filter.cpp:413-455, src/output.cpp:118-333)."""
+import ctypes as C
 import gzip
 import os
 
@@ -554,3 +555,160 @@ def test_batch_arrays_that_grow_are_announced_before_they_go(tmp_path, monkeypat
     n_before = len(gone)
     rd.close()
     assert len(gone) > n_before and not live                 # closing announces what is left
+
+
+def _batch_bytes(b):
+    """every array of a parsed batch, both mates, as bytes"""
+    n, fb = b.n, b.fb
+    out = [n, None if b.prior is None else b.prior.tobytes()]
+    for seq, off, qual, names, name_off in ((b.c.seq1, b.c.off1, fb.qual1, fb.names1, fb.name_off1), (b.c.seq2, b.c.off2, fb.qual2, fb.names2, fb.name_off2)):
+        o = np.ctypeslib.as_array(off, (n + 1,)).copy()
+        no = np.ctypeslib.as_array(name_off, (n + 1,)).copy()
+        out += [o.tobytes(), no.tobytes(), bytes(np.ctypeslib.as_array(seq, (int(o[n]),))), bytes(np.ctypeslib.as_array(qual, (int(o[n]),))),
+                C.string_at(names, int(no[n]))]
+    return out
+
+
+@pytest.mark.parametrize("config", ["plain", "serial", "gzip"])
+def test_two_readers_in_one_process_do_not_see_each_other(built, tmp_path, monkeypatch, config):
+    """Two readers over file pairs of different content, read from two threads at once (every cm_fastq_next of one overlaps one
+    of the other): each returns exactly the batches it returns alone.  The plain path with 4 tokeniser threads, the
+    record-by-record parser, gzip input."""
+    import threading
+    monkeypatch.delenv("CM_FASTQ_SERIAL", raising=False)
+    monkeypatch.delenv("CM_FASTQ_THREADS", raising=False)
+    if config == "plain":
+        monkeypatch.setenv("CM_FASTQ_THREADS", "4")
+    if config == "serial":
+        monkeypatch.setenv("CM_FASTQ_SERIAL", "1")
+    op, ext = (gzip.open, ".gz") if config == "gzip" else (open, "")
+    n, batch = 3000, 700
+    pairs = []
+    for k in range(2):
+        rng = np.random.default_rng(40 + k)
+        s1, q1 = _rand_reads(rng, n, 20, 301)
+        s2, q2 = _rand_reads(rng, n, 20, 301)
+        st = _rand_states(rng, n)
+        names = [py_remain_header(f"p{k}_{i}", st[i], CHRS)[1:] if i % 5 == k else f"p{k}_{i}/1" for i in range(n)]
+        p1, p2 = str(tmp_path / f"t{k}_1.fq{ext}"), str(tmp_path / f"t{k}_2.fq{ext}")
+        _fastq(p1, names, s1, q1, op)
+        _fastq(p2, [f"p{k}_{i}/2" for i in range(n)], s2, q2, op)
+        pairs.append((p1, p2))
+
+    def read_all(p, gate, out):
+        rd = cl.FastqReader(p[0], p[1], CHRS, 4)
+        while True:
+            if gate:
+                gate.wait()
+            b = rd.next_batch(batch)
+            if b is None:
+                break
+            out.append(_batch_bytes(b))
+        rd.close()
+
+    alone = [[], []]
+    for k in range(2):
+        read_all(pairs[k], None, alone[k])
+    assert [sum(x[0] for x in a) for a in alone] == [n, n] and alone[0] != alone[1]
+    gate = threading.Barrier(2, timeout=60)                  # both files have as many batches: the calls go in lockstep
+    both = [[], []]
+    th = [threading.Thread(target=read_all, args=(pairs[k], gate, both[k])) for k in range(2)]
+    [t.start() for t in th]
+    [t.join() for t in th]
+    assert both[0] == alone[0] and both[1] == alone[1]
+
+
+def _whole_records(block):
+    """bytes of the whole records (four lines each) at the front of a text block"""
+    nl = np.flatnonzero(np.asarray(block) == 10)
+    k = len(nl) // 4
+    return int(nl[4 * k - 1]) + 1 if k else 0
+
+
+def test_text_blocks_grow_in_place_when_nothing_is_consumed(built, tmp_path):
+    """cm_fastq_next_text with want_bytes smaller than a record: while the caller consumes nothing (cm_fastq_text_consumed(0, 0))
+    the same block grows until it holds a pair, and the blocks handed out by the three calls before it keep their bytes however
+    many calls that takes.  In the consuming sequence a block stays intact over the next three calls.  Always: a block is the
+    file's bytes from the consumed position on, and eof is set by the call whose block ends at the end of the file."""
+    rng = np.random.default_rng(17)
+    n = 60
+    s1, q1 = _rand_reads(rng, n, 300, 301)
+    s2, q2 = _rand_reads(rng, n, 250, 301)
+    p = [str(tmp_path / "x_1.fq"), str(tmp_path / "x_2.fq")]
+    _fastq(p[0], [f"pair{i}/1" for i in range(n)], s1, q1)
+    _fastq(p[1], [f"pair{i}/2 some comment" for i in range(n)], s2, q2)
+    data = [open(x, "rb").read() for x in p]
+    rd = cl.FastqReader(p[0], p[1], CHRS, 4)
+    pos = [0, 0]
+    held = []                                                # (views, copies) of the blocks of the consuming sequence
+
+    def call(want):
+        t1, e1, t2, e2 = rd.next_text(want)
+        for x, (t, e) in enumerate(((t1, e1), (t2, e2))):
+            assert bytes(t) == data[x][pos[x]:pos[x] + len(t)]
+            assert e == (pos[x] + len(t) == len(data[x]))
+        return (t1, t2)
+
+    def starve(want):
+        """asks with nothing consumed until the block holds a pair; returns the number of calls and the last block"""
+        calls, blk, last = 0, call(want), -1
+        while min(_whole_records(t) for t in blk) == 0:
+            assert len(blk[0]) + len(blk[1]) > last           # it grows
+            last = len(blk[0]) + len(blk[1])
+            rd.consumed(0, 0)
+            blk = call(want)
+            calls += 1
+        return calls, blk
+
+    def consume(blk):
+        used = [_whole_records(t) for t in blk]
+        rd.consumed(*used)
+        pos[0] += used[0]
+        pos[1] += used[1]
+
+    calls, blk = starve(64)                                  # at the start of the files: 64 bytes, then half a block more per call
+    assert calls >= 8 and len(blk[0]) < 2 * len(data[0]) // n
+    consume(blk)
+    for step in range(200):
+        if step == 6:                                        # in the middle: the three blocks before it outlive the starved one's calls
+            calls, blk = starve(64)
+            for views, copies in held[-3:]:
+                assert [bytes(v) for v in views] == copies
+        else:
+            blk = call(1500)
+        for views, copies in held[-3:]:                      # a block stays valid over the next three calls
+            assert [bytes(v) for v in views] == copies
+        held.append((blk, [bytes(v) for v in blk]))
+        consume(blk)
+        if pos == [len(data[0]), len(data[1])]:
+            break
+    assert pos == [len(data[0]), len(data[1])] and step > 10
+    t1, e1, t2, e2 = rd.next_text(1500)
+    assert len(t1) == 0 and len(t2) == 0 and e1 and e2
+    rd.close()
+
+
+def test_text_blocks_are_refused_where_they_cannot_be_served(built, tmp_path):
+    """cm_fastq_next_text is CM_EINVAL behind a cm_fastq_next that left buffered text, and on gzip input; the reader goes on as if
+    it had not been asked, and closes."""
+    rng = np.random.default_rng(19)
+    n = 100
+    s, q = _rand_reads(rng, n)
+    names = [f"m{i}" for i in range(n)]
+    p1, p2 = str(tmp_path / "m_1.fq"), str(tmp_path / "m_2.fq")
+    g1, g2 = p1 + ".gz", p2 + ".gz"
+    for a, b, op in ((p1, p2, open), (g1, g2, gzip.open)):
+        _fastq(a, names, s, q, op)
+        _fastq(b, names, s, q, op)
+    rd = cl.FastqReader(p1, p2, CHRS, 4)
+    assert rd.next_batch(10).n == 10                         # the rest of the files is in the reader's buffers now
+    with pytest.raises(RuntimeError, match=r"cm_fastq_next_text failed \(-1\)"):
+        rd.next_text(1 << 16)
+    b = rd.next_batch(1000)
+    assert b.n == n - 10 and b.name(0) == "m10" and b.seq(n - 11, 2).decode() == s[n - 1]
+    rd.close()
+    rd = cl.FastqReader(g1, g2, CHRS, 4)
+    with pytest.raises(RuntimeError, match=r"cm_fastq_next_text failed \(-1\)"):
+        rd.next_text(1 << 16)
+    assert rd.next_batch(1000).n == n
+    rd.close()
