@@ -15,7 +15,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 INC = os.path.join(HERE, "..", "include")
 OUT = os.path.join(CSRC, "libcmhot.so")
-SOURCES = ["cm_hot.hip", "cm_dp_probe.hip", "cm_annot_probe.hip", "cm_dispatch.cpp", "host_index.cpp", "host_annot.cpp", "host_index_io.cpp", "host_fastq.cpp", "host_mapping.cpp", "host_circ.cpp",
+SOURCES = ["cm_hot.hip", "cm_dp_probe.hip", "cm_annot_probe.hip", "cm_circ_chain.hip", "cm_dispatch.cpp", "host_index.cpp", "host_annot.cpp", "host_index_io.cpp", "host_fastq.cpp", "host_mapping.cpp", "host_circ.cpp",
            "host_circ_call.cpp"]
 ABI_DEF = "cm_device_abi.def"
 DEPS = SOURCES + sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + [ABI_DEF, os.path.join("..", "..", "include", "circminer_hot.h")]
@@ -39,7 +39,7 @@ def device_abi(path: str = os.path.join(CSRC, ABI_DEF)):
 
 
 VARIANTS = (("k16", []), ("k24", ["-DCM_MAX_CHAIN_FRAGS=24"]))
-HIP_ONCE = ["cm_dp_probe.hip", "cm_annot_probe.hip"]      # device code that does not depend on CM_MAX_CHAIN_FRAGS: one build, its own names (the test hooks behind cm_dp_batch / cm_annot_batch)
+HIP_ONCE = ["cm_dp_probe.hip", "cm_annot_probe.hip", "cm_circ_chain.hip"]      # device code that does not depend on CM_MAX_CHAIN_FRAGS: one build, its own names (the test hooks behind cm_dp_batch / cm_annot_batch, stage 2's seeds and chains behind cm_circ_chain_batch)
 
 
 def needs_build(out: str = OUT) -> bool:

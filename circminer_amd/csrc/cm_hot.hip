@@ -5047,6 +5047,29 @@ int cm_annot_batch(cm_ctx *ctx, int slot, const cm_params *P, const cm_annot_req
     return rc == CM_OK ? CM_OK : fail(ctx, rc, "cm_annot_batch: %s", msg);
 }
 
+// stage 2's seeds and chains (kernels, validation and launch in cm_circ_chain.hip); here only what needs the context: the slot's
+// annotation and, for genome == NULL, its resident sequence
+extern "C" int cm_circ_chain_run(hipStream_t so, const cm_params *P, const void *annot, size_t annot_bytes, const uint8_t *d_contig, uint32_t contig_len,
+                                 int32_t window_size, const uint8_t *genome, uint32_t ref_len, const uint8_t *seqs, uint64_t seqs_len,
+                                 const cm_circ_chain_req *req, uint32_t n_req, cm_circ_chain_res *res, float *chain_score, uint32_t *chain_len,
+                                 uint64_t *chain_frag_off, uint64_t cap_chains, uint32_t *rpos, int32_t *qpos, uint64_t cap_frags, uint64_t *n_chains_out,
+                                 uint64_t *n_frags_out, uint64_t stats[8], char *err, size_t err_cap);
+int cm_circ_chain_batch(cm_ctx *ctx, int slot, int32_t window_size, const uint8_t *genome, uint32_t ref_len, const uint8_t *seqs, uint64_t seqs_len,
+                        const cm_circ_chain_req *req, uint32_t n_req, cm_circ_chain_res *res, float *chain_score, uint32_t *chain_len,
+                        uint64_t *chain_frag_off, uint64_t cap_chains, uint32_t *rpos, int32_t *qpos, uint64_t cap_frags, uint64_t *n_chains_out,
+                        uint64_t *n_frags_out, uint64_t stats[8]) {
+    if (!ctx) return CM_EINVAL;
+    if (slot < 0 || slot >= MAX_SLOTS) return fail(ctx, CM_EINVAL, "slot %d out of range", slot);
+    const Slot &s = ctx->slots[slot];
+    if (!s.has_annot) return fail(ctx, CM_ESTATE, "annotation of slot %d not loaded", slot);
+    HIPCHK(ctx, hipSetDevice(ctx->P.device));
+    char msg[256] = "";
+    const int rc = cm_circ_chain_run(ctx->st.B, &ctx->P, &s.A, sizeof(cmc::AnnotDev), s.loaded ? s.X.genome : nullptr, s.loaded ? s.X.ref_len : 0, window_size,
+                                     genome, ref_len, seqs, seqs_len, req, n_req, res, chain_score, chain_len, chain_frag_off, cap_chains, rpos, qpos,
+                                     cap_frags, n_chains_out, n_frags_out, stats, msg, sizeof msg);
+    return rc == CM_OK ? CM_OK : fail(ctx, rc, "cm_circ_chain_batch: %s", msg);
+}
+
 /* diagnostic: per-pair k_pair lane time in 100 MHz ticks (only when CM_LANE_CLK was set at upload) */
 // diagnostic builds (-DCM_CHAIN_DIAG ...): the CN_WORDS raw counter words, [8 ..] = whatever the build accumulates there (enum Counter)
 int cm_debug_counters(cm_ctx *ctx, unsigned long long *out) {

@@ -95,6 +95,7 @@ struct Call {                 // one entry of circ_res
 };
 
 struct TidOff { uint32_t tid; int off; };
+struct ChainInfo { uint32_t listed = 0; uint64_t cells = 0, log = 0; };      // what cm_circ_chain_host reports beside the chains of a problem
 
 class Caller {
 public:
@@ -181,19 +182,20 @@ private:
         uint32_t *off = nullptr, *loc = nullptr;
         uint32_t gene_end = 0;
     };
-    std::map<uint32_t, Table> tables_;
-    const Table &table_for(uint32_t gene) {
-        auto it = tables_.find(gene);
+    std::map<uint64_t, Table> tables_;                                      // by (gene start, gene end)
+    const Table &table_for(uint32_t gene) { return table_at(av_.gene_start[gene], av_.gene_end[gene]); }
+    const Table &table_at(uint32_t gs, uint32_t ge) {
+        const uint64_t key = (uint64_t)gs << 32 | ge;
+        auto it = tables_.find(key);
         if (it != tables_.end()) return it->second;
         S2_TIME(0);
         Table t;
-        const uint32_t gs = av_.gene_start[gene], ge = av_.gene_end[gene];
         std::string g;
         const int glen = (int)(ge - gs + 1);
         if (!genome_at(gs, glen, g)) g.assign((size_t)std::max(glen, 0), '\0');
         t.gene_end = ge;
         if (cm_regional_table_build((const uint8_t *)g.data(), 0, glen, ws_, &t.off, &t.loc) != CM_OK) t.off = t.loc = nullptr;
-        return tables_.emplace(gene, t).first->second;
+        return tables_.emplace(key, t).first->second;
     }
     void drop_tables_before(uint32_t pos) {                                 // check_removables: genes that end before this pair
         for (auto it = tables_.begin(); it != tables_.end();) {
@@ -229,9 +231,10 @@ private:
     // gene start is added only when a chain is emitted, and the annotation queries of the scoring run on the bare offsets
     // (as the reference does).  Improvements are logged in order and replayed best score first, at most max_chain_len per score.
     struct Seed { const uint32_t *hit; uint32_t n; int32_t qpos; };
-    void chains_of(uint32_t qs, uint32_t qe, const Table &tab, const Seq &seq, uint32_t gene_start, std::vector<WideChain> &out) {
+    void chains_of(uint32_t qs, uint32_t qe, const Table &tab, const Seq &seq, uint32_t gene_start, std::vector<WideChain> &out, ChainInfo *info = nullptr) {
         S2_TIME(1);
         out.clear();
+        if (info) *info = ChainInfo{};
         const int span = (int)qe - (int)qs + 1;
         if (span < ws_ || !tab.off) return;
         std::vector<Seed> seeds;
@@ -243,6 +246,7 @@ private:
             seeds.push_back(Seed{tab.loc + tab.off[hv], n, (int32_t)i});
         }
         const int listed = (int)seeds.size();
+        if (info) info->listed = (uint32_t)listed;
         int kc = listed;
         while (kc >= 1 && seeds[kc - 1].n == 0) --kc;
         if (kc <= 0) return;
@@ -293,6 +297,10 @@ private:
                 }
             }
         }
+        if (info) {
+            info->log = log.size();
+            for (int a = 0; a < kc; ++a) info->cells += seeds[a].n;
+        }
         // replay: scores descending, insertion order inside a score, only the first max_best entries of a score count
         std::stable_sort(log.begin(), log.end(), [](const Ev &x, const Ev &y) { return x.score > y.score; });
         const double top = log.empty() ? (double)kmer : log[0].score;
@@ -337,6 +345,56 @@ private:
             }
             least = missing;
         }
+    }
+
+public:
+    // Chains computed ahead (cm_circ_chain_batch / cm_circ_chain_host) for the problems cm_circ_chain_list names: the requests of
+    // pair `rec` are first[rec] .. first[rec] + count[rec]), one per gene of the interval for a CHIBSJ pair, two (piece 0, 1) for a
+    // CHI2BSJ pair.  An answer is taken only if its request is the problem asked for; anything else is computed here.
+    struct Answers {
+        const cm_circ_chain_req *req = nullptr;
+        const cm_circ_chain_res *res = nullptr;
+        const float *score = nullptr;
+        const uint32_t *len = nullptr;
+        const uint64_t *frag_off = nullptr;
+        const uint32_t *rpos = nullptr;
+        const int32_t *qpos = nullptr;
+        const uint64_t *first = nullptr;      // per pair of the batch; ~0: none
+        const uint32_t *count = nullptr, *per_gene = nullptr;
+    };
+    const Answers *answers = nullptr;
+    uint64_t taken = 0, recomputed = 0;
+    void answer(const cm_circ_chain_req &q, const uint8_t *seqs, std::vector<WideChain> &out, ChainInfo &info) {      // cm_circ_chain_host
+        if (tables_.size() > 256) drop_tables_before(~0u);
+        chains_of(q.qs, q.qe, table_at(q.gene_start, q.gene_end), Seq{seqs + q.seq_off, q.seq_len}, q.gene_start, out, &info);
+    }
+private:
+    void chains_for(uint32_t gene_ord, int piece, uint32_t qs, uint32_t qe, uint32_t gene, const Seq &seq, std::vector<WideChain> &out) {
+        if (answers && answers->first[rec_] != ~0ull) {
+            const uint32_t per = answers->per_gene[rec_], at = gene_ord * per + (per == 2 ? (uint32_t)piece : 0u);
+            if (at < answers->count[rec_]) {
+                const uint64_t x = answers->first[rec_] + at;
+                const cm_circ_chain_req &q = answers->req[x];
+                const cm_circ_chain_res &v = answers->res[x];
+                if (!(v.flags & CM_CIRC_CHAIN_REFUSED) && q.gene_start == av_.gene_start[gene] && q.gene_end == av_.gene_end[gene] && q.qs == qs && q.qe == qe &&
+                    q.tag == (uint32_t)piece && q.seq_len == seq.n) {
+                    out.clear();
+                    for (uint32_t c = 0; c < v.n_stored; ++c) {
+                        WideChain w;
+                        w.kmer = ws_;
+                        w.score = answers->score[v.chain_off + c];
+                        const uint64_t f = answers->frag_off[v.chain_off + c];
+                        w.r.assign(answers->rpos + f, answers->rpos + f + answers->len[v.chain_off + c]);
+                        w.q.assign(answers->qpos + f, answers->qpos + f + answers->len[v.chain_off + c]);
+                        out.push_back(std::move(w));
+                    }
+                    ++taken;
+                    return;
+                }
+            }
+            ++recomputed;
+        }
+        chains_of(qs, qe, table_for(gene), seq, av_.gene_start[gene], out);
     }
 
     // ---------------------------------------------------------------- mates
@@ -787,7 +845,7 @@ private:
         Best best;
         for (uint32_t g = av_.giv_gene_off[gi]; g < av_.giv_gene_off[gi + 1]; ++g) {
             const uint32_t gene = av_.giv_gene[g];
-            chains_of(qs, qe, table_for(gene), rem_, av_.gene_start[gene], ch1_);
+            chains_for(g - av_.giv_gene_off[gi], r1_split ? 0 : 1, qs, qe, gene, rem_, ch1_);
             for (size_t j = 0; j < ch1_.size() && j < (size_t)TOPCHAIN; ++j) {
                 k::MM piece = k::mm_init(core_);
                 if (!place_piece(m1, m2, piece, dir, qs, todo, (int)rlen, ch1_[j])) continue;
@@ -865,9 +923,8 @@ private:
         Best best;
         for (uint32_t g = av_.giv_gene_off[gi]; g < av_.giv_gene_off[gi + 1]; ++g) {
             const uint32_t gene = av_.giv_gene[g];
-            const Table &tab = table_for(gene);
-            chains_of(qs1, qe1, tab, o1, av_.gene_start[gene], ch1_);
-            chains_of(qs2, qe2, tab, o2, av_.gene_start[gene], ch2_);
+            chains_for(g - av_.giv_gene_off[gi], 0, qs1, qe1, gene, o1, ch1_);
+            chains_for(g - av_.giv_gene_off[gi], 1, qs2, qe2, gene, o2, ch2_);
             if (ch1_.empty() && ch2_.empty()) continue;
             if (ch1_.empty() || ch2_.empty()) {
                 one_split(fwd, rc, st, shift);
@@ -936,14 +993,179 @@ struct Fail {
     }
 };
 
+// ---- the problems of a batch, listed ahead (cm_circ_chain_list, cm_circ_call_device)
+struct Problems {
+    std::vector<cm_circ_chain_req> req;
+    std::vector<uint64_t> pair_of;
+    std::vector<uint8_t> seqs;
+};
+void side_of(uint32_t qspos, uint32_t qepos, uint32_t rlen, uint32_t &qs, uint32_t &qe) {      // Caller::unmapped_side
+    const bool right_matched = (qspos - 1) > (rlen - qepos);
+    qs = right_matched ? 1 : qepos + 1;
+    qe = right_matched ? qspos - 1 : rlen;
+}
+int gene_interval_at(const cm_annot_view &av, uint32_t pos) {                                  // Caller::genes_at
+    if (av.n_giv == 0 || pos < av.giv_spos[0]) return -1;
+    const uint32_t *e = std::upper_bound(av.giv_spos, av.giv_spos + av.n_giv, pos);
+    const int i = (int)(e - av.giv_spos) - 1;
+    if (i < 0 || av.giv_epos[i] < pos || av.giv_gene_off[i + 1] == av.giv_gene_off[i]) return -1;
+    return i;
+}
+// the requests of pair i: every chains_of call one_split / two_splits can make for it (the same problem asked twice is listed once).
+// per_gene: requests per gene of the interval (1: the split mate's side, 2: both sides)
+void list_pair(int ws, const cm_annot_view &av, const cm_chr_info *chrs, const cm_fastq_batch *b, uint64_t i, Problems &out, uint32_t &per_gene) {
+    per_gene = 0;
+    const cm_mapped_read &st = b->prior[i];
+    const uint32_t len[2] = {(uint32_t)(b->reads.off1[i + 1] - b->reads.off1[i]), (uint32_t)(b->reads.off2[i + 1] - b->reads.off2[i])};
+    const uint8_t *fwd[2] = {b->reads.seq1 + b->reads.off1[i], b->reads.seq2 + b->reads.off2[i]};
+    const bool forward[2] = {st.r1_forward != 0, st.r2_forward != 0};
+    uint32_t qs[2] = {0, 0}, qe[2] = {0, 0};
+    bool use[2] = {false, false};
+    if (st.type == CM_CHIBSJ) {
+        const int k = st.mlen_r1 < st.mlen_r2 ? 0 : 1;
+        side_of(k == 0 ? st.qspos_r1 : st.qspos_r2, k == 0 ? st.qepos_r1 : st.qepos_r2, len[k], qs[k], qe[k]);
+        if (qe[k] < qs[k] || (int)(qe[k] - qs[k] + 1) < ws) return;
+        use[k] = true;
+        per_gene = 1;
+    } else if (st.type == CM_CHI2BSJ) {
+        side_of(st.qspos_r1, st.qepos_r1, len[0], qs[0], qe[0]);
+        side_of(st.qspos_r2, st.qepos_r2, len[1], qs[1], qe[1]);
+        if ((int)(qe[0] - qs[0] + 1) < ws && (int)(qe[1] - qs[1] + 1) < ws) return;
+        use[0] = use[1] = true;
+        per_gene = 2;
+    } else return;
+    const int gi = gene_interval_at(av, st.spos_r1 + chrs[st.chr_id].start_pos);
+    if (gi < 0) {
+        per_gene = 0;
+        return;
+    }
+    uint64_t off[2] = {0, 0};
+    std::vector<uint8_t> rc;
+    for (int k = 0; k < 2; ++k) {
+        if (!use[k]) continue;
+        off[k] = out.seqs.size();
+        if (forward[k]) out.seqs.insert(out.seqs.end(), fwd[k], fwd[k] + len[k]);
+        else {
+            reverse_complement(fwd[k], len[k], rc);
+            out.seqs.insert(out.seqs.end(), rc.begin(), rc.begin() + len[k]);
+        }
+    }
+    for (uint32_t g = av.giv_gene_off[gi]; g < av.giv_gene_off[gi + 1]; ++g)
+        for (int k = 0; k < 2; ++k) {
+            if (!use[k]) continue;
+            const uint32_t gene = av.giv_gene[g];
+            out.req.push_back(cm_circ_chain_req{av.gene_start[gene], av.gene_end[gene], off[k], len[k], qs[k], qe[k], (uint32_t)k});
+            out.pair_of.push_back(i);
+        }
+}
+bool pair_eligible(const cm_mapped_read &st, uint32_t n_contigs, uint32_t n_chr) {
+    if (st.type != CM_CHIBSJ && st.type != CM_CHI2BSJ) return false;
+    return !(st.contig_num < 0 || (uint32_t)st.contig_num >= n_contigs || st.chr_id < 0 || (uint32_t)st.chr_id >= n_chr);
+}
+int chain_req_check(int32_t window_size, const uint8_t *seqs, uint64_t seqs_len, const cm_circ_chain_req *req, uint32_t n_req, int &ws) {
+    ws = window_size == 0 ? 8 : window_size;
+    if (ws < 6 || ws > 10) return CM_ELIMIT;
+    if (n_req && (!req || !seqs)) return CM_EINVAL;
+    for (uint32_t i = 0; i < n_req; ++i) {
+        const cm_circ_chain_req &q = req[i];
+        if (q.qs == 0 || q.qe > q.seq_len || q.seq_off > seqs_len || q.seq_len > seqs_len - q.seq_off || q.gene_end < q.gene_start) return CM_EINVAL;
+    }
+    return CM_OK;
+}
+
 }  // namespace
+
+extern "C" int cm_circ_chain_abi_sizes(uint32_t *out, uint32_t cap) {
+    if (!out || cap < 2) return CM_EINVAL;
+    out[0] = (uint32_t)sizeof(cm_circ_chain_req);
+    out[1] = (uint32_t)sizeof(cm_circ_chain_res);
+    return 2;
+}
+
+extern "C" int cm_circ_chain_host(const cm_params *P, const cm_annot_view *av, int32_t window_size, const uint8_t *genome, uint32_t ref_len, const uint8_t *seqs,
+                                  uint64_t seqs_len, const cm_circ_chain_req *req, uint32_t n_req, cm_circ_chain_res *res, float *chain_score,
+                                  uint32_t *chain_len, uint64_t *chain_frag_off, uint64_t cap_chains, uint32_t *rpos, int32_t *qpos, uint64_t cap_frags,
+                                  uint64_t *n_chains_out, uint64_t *n_frags_out, uint64_t stats[8]) {
+    if (stats) memset(stats, 0, 8 * sizeof(uint64_t));
+    if (n_chains_out) *n_chains_out = 0;
+    if (n_frags_out) *n_frags_out = 0;
+    if (!P || !av || !genome || (n_req && !res)) return CM_EINVAL;
+    int ws;
+    const int chk = chain_req_check(window_size, seqs, seqs_len, req, n_req, ws);
+    if (chk != CM_OK) return chk;
+    if ((cap_chains && (!chain_score || !chain_len || !chain_frag_off)) || (cap_frags && (!rpos || !qpos))) return CM_EINVAL;
+    cm_index_view X{};
+    X.genome = genome;
+    X.ref_len = ref_len;
+    Caller cur(*P, X, *av, ws, nullptr);
+    std::vector<WideChain> out;
+    std::map<uint64_t, int> distinct;
+    uint64_t c_at = 0, f_at = 0, cells = 0, events = 0, longest = 0;
+    for (uint32_t i = 0; i < n_req; ++i) {
+        ChainInfo info;
+        cur.answer(req[i], seqs, out, info);
+        distinct[(uint64_t)req[i].gene_start << 32 | req[i].gene_end] = 1;
+        cells += info.cells;
+        events += info.log;
+        longest = std::max(longest, info.log);
+        const uint32_t stored = (uint32_t)std::min<size_t>(out.size(), (size_t)TOPCHAIN);
+        res[i] = cm_circ_chain_res{(uint32_t)out.size(), stored, info.listed, 0, c_at};
+        for (uint32_t c = 0; c < stored; ++c) {
+            const uint32_t len = out[c].len();
+            if (c_at < cap_chains) {
+                chain_score[c_at] = out[c].score;
+                chain_len[c_at] = len;
+                chain_frag_off[c_at] = f_at;
+            }
+            for (uint32_t f = 0; f < len; ++f)
+                if (f_at + f < cap_frags) {
+                    rpos[f_at + f] = out[c].r[f];
+                    qpos[f_at + f] = out[c].q[f];
+                }
+            f_at += len;
+            ++c_at;
+        }
+    }
+    if (n_chains_out) *n_chains_out = c_at;
+    if (n_frags_out) *n_frags_out = f_at;
+    if (stats) {
+        stats[0] = distinct.size();
+        stats[3] = cells;
+        stats[4] = events;
+        stats[7] = longest;
+    }
+    return (c_at > cap_chains || f_at > cap_frags) ? CM_ELIMIT : CM_OK;
+}
+
+extern "C" int cm_circ_chain_list(const cm_params *P, int32_t window_size, const cm_annot_view *av, const cm_chr_info *chrs, uint32_t n_chr,
+                                  const cm_fastq_batch *sorted, int32_t contig, cm_circ_chain_req *req, uint64_t *pair_of, uint64_t cap_req, uint8_t *seqs,
+                                  uint64_t cap_seqs, uint64_t *n_req, uint64_t *seqs_len) {
+    if (!P || !av || !chrs || !sorted || !n_req || !seqs_len || contig < 0) return CM_EINVAL;
+    const int ws = window_size > 0 ? window_size : 8;
+    Problems pr;
+    for (uint64_t i = 0; i < sorted->reads.n_pairs && sorted->prior; ++i) {
+        const cm_mapped_read &st = sorted->prior[i];
+        if (!pair_eligible(st, (uint32_t)contig + 1, n_chr) || st.contig_num != contig) continue;
+        uint32_t per;
+        list_pair(ws, *av, chrs, sorted, i, pr, per);
+    }
+    *n_req = pr.req.size();
+    *seqs_len = pr.seqs.size();
+    if (pr.req.size() > cap_req || pr.seqs.size() > cap_seqs) return CM_ELIMIT;
+    if (!pr.req.empty() && (!req || !pair_of)) return CM_EINVAL;
+    if (!pr.seqs.empty() && !seqs) return CM_EINVAL;
+    std::copy(pr.req.begin(), pr.req.end(), req);
+    std::copy(pr.pair_of.begin(), pr.pair_of.end(), pair_of);
+    std::copy(pr.seqs.begin(), pr.seqs.end(), seqs);
+    return CM_OK;
+}
 
 // ProcessCirc::do_process over the sorted remain pairs.  Pairs are independent of one another (the per-gene regional tables are a
 // cache, dropped once the sorted input has moved past the gene), so runs of pairs on one contig are cut into chunks that
 // worker threads take in turn, each with a Caller of its own; rows and calls are put together in chunk order, i.e. input order.
 static int circ_call_mt(const cm_params *P, int32_t window_size, uint32_t n_contigs, const cm_index_view *contigs, const cm_annot_view *annots,
                         const cm_chr_info *chrs, uint32_t n_chr, const cm_fastq_batch *sorted, const char *candidates_path,
-                        const char *report_path, cm_circ_stats *stats, int n_threads) {
+                        const char *report_path, cm_circ_stats *stats, int n_threads, bool ahead = false, cm_ctx *ctx = nullptr, int slot = 0) {
     if (!P || !contigs || !annots || !chrs || !sorted || !candidates_path || !report_path) return CM_EINVAL;
     const int ws = window_size > 0 ? window_size : 8;
     if (ws > 12) return CM_EINVAL;
@@ -961,17 +1183,110 @@ static int circ_call_mt(const cm_params *P, int32_t window_size, uint32_t n_cont
         if (st.contig_num < 0 || (uint32_t)st.contig_num >= n_contigs || st.chr_id < 0 || (uint32_t)st.chr_id >= n_chr) continue;
         todo.push_back(i);
     }
+    // `ahead` (cm_circ_call_device): the seeds and chains of every eligible pair are computed before any pair is judged, contig by
+    // contig, in groups of bounded size -- on the device (ctx) or by the serial statement (no ctx)
+    struct Ahead {
+        Problems pr;
+        std::vector<cm_circ_chain_res> res;
+        std::vector<float> score;
+        std::vector<uint32_t> len, rpos;
+        std::vector<uint64_t> frag_off;
+        std::vector<int32_t> qpos;
+        Caller::Answers view;
+    };
+    std::vector<Ahead> ahead_of(ahead ? n_contigs : 0);
+    std::vector<uint64_t> first_req;
+    std::vector<uint32_t> count_req, per_gene_req;
+    if (ahead) {
+        first_req.assign(n, ~0ull);
+        count_req.assign(n, 0);
+        per_gene_req.assign(n, 0);
+        uint64_t tot[8] = {0, 0, 0, 0, 0, 0, 0, 0}, n_problems = 0;
+        for (uint64_t i : todo) {
+            Ahead &A = ahead_of[states[i].contig_num];
+            const uint64_t before = A.pr.req.size();
+            uint32_t per = 0;
+            list_pair(ws, annots[states[i].contig_num], chrs, sorted, i, A.pr, per);
+            if (A.pr.req.size() > before) {
+                first_req[i] = before;
+                count_req[i] = (uint32_t)(A.pr.req.size() - before);
+                per_gene_req[i] = per;
+            }
+        }
+        constexpr size_t GROUP = 16384;          // requests per cm_circ_chain_batch call: bounds the device memory of one call
+        for (uint32_t con = 0; con < n_contigs; ++con) {
+            Ahead &A = ahead_of[con];
+            const size_t nr = A.pr.req.size();
+            if (nr == 0) continue;
+            n_problems += nr;
+            if (ctx) {
+                const int lrc = cm_load_annotation(ctx, slot, &annots[con]);
+                if (lrc != CM_OK) {
+                    fclose(fc);
+                    remove(candidates_path);          // no partial file beside an error
+                    return lrc;
+                }
+            }
+            A.res.resize(nr);
+            for (size_t a = 0; a < nr; a += GROUP) {
+                const size_t b = std::min(nr, a + GROUP);
+                std::vector<cm_circ_chain_req> rq(A.pr.req.begin() + a, A.pr.req.begin() + b);
+                uint64_t lo = rq[0].seq_off, hi = 0, fr = 0;
+                for (auto &q : rq) {
+                    lo = std::min(lo, q.seq_off);
+                    hi = std::max(hi, q.seq_off + q.seq_len);
+                    const uint32_t span = q.qe >= q.qs ? q.qe - q.qs + 1 : 0;
+                    fr += 10ull * (span / 3 + 1);
+                }
+                for (auto &q : rq) q.seq_off -= lo;
+                const uint64_t c0 = A.score.size(), f0 = A.rpos.size(), cc = 10ull * (b - a);
+                A.score.resize(c0 + cc);
+                A.len.resize(c0 + cc);
+                A.frag_off.resize(c0 + cc);
+                A.rpos.resize(f0 + fr);
+                A.qpos.resize(f0 + fr);
+                uint64_t nc = 0, nf = 0, st8[8];
+                const int brc = ctx ? cm_circ_chain_batch(ctx, slot, ws, contigs[con].genome, contigs[con].ref_len, A.pr.seqs.data() + lo, hi - lo, rq.data(),
+                                                          (uint32_t)rq.size(), A.res.data() + a, A.score.data() + c0, A.len.data() + c0, A.frag_off.data() + c0,
+                                                          cc, A.rpos.data() + f0, A.qpos.data() + f0, fr, &nc, &nf, st8)
+                                    : cm_circ_chain_host(P, &annots[con], ws, contigs[con].genome, contigs[con].ref_len, A.pr.seqs.data() + lo, hi - lo, rq.data(),
+                                                         (uint32_t)rq.size(), A.res.data() + a, A.score.data() + c0, A.len.data() + c0, A.frag_off.data() + c0,
+                                                         cc, A.rpos.data() + f0, A.qpos.data() + f0, fr, &nc, &nf, st8);
+                if (brc != CM_OK) {
+                    fclose(fc);
+                    remove(candidates_path);
+                    return brc;
+                }
+                for (size_t x = a; x < b; ++x) A.res[x].chain_off += c0;
+                for (uint64_t x = c0; x < c0 + nc; ++x) A.frag_off[x] += f0;
+                A.score.resize(c0 + nc);
+                A.len.resize(c0 + nc);
+                A.frag_off.resize(c0 + nc);
+                A.rpos.resize(f0 + nf);
+                A.qpos.resize(f0 + nf);
+                tot[0] += st8[0];
+                tot[1] = std::max(tot[1], st8[1]);
+                for (int k = 2; k < 8; ++k) tot[k] += st8[k];
+            }
+            A.view = Caller::Answers{A.pr.req.data(), A.res.data(), A.score.data(), A.len.data(), A.frag_off.data(), A.rpos.data(), A.qpos.data(),
+                                     first_req.data(), count_req.data(), per_gene_req.data()};
+        }
+        if (getenv("CM_CIRC_TRACE"))
+            fprintf(stderr, "[circ] chains ahead (%s): %llu problems, %llu genes, %llu table bytes, %llu gene groups, %llu cells, %llu log events, %llu refused, tables %.3f ms, chaining %.3f ms\n",
+                    ctx ? "device" : "host", (unsigned long long)n_problems, (unsigned long long)tot[0], (unsigned long long)tot[1], (unsigned long long)tot[2],
+                    (unsigned long long)tot[3], (unsigned long long)tot[4], (unsigned long long)tot[5], ctx ? tot[6] / 1e3 : 0.0, ctx ? tot[7] / 1e3 : 0.0);
+    }
     int T = n_threads > 0 ? n_threads : (int)std::thread::hardware_concurrency();
     if (const char *e = getenv("CM_CIRC_THREADS")) T = atoi(e);
     T = T < 1 ? 1 : (T > 64 ? 64 : T);
     const size_t chunk_len = std::max<size_t>(256, todo.size() / (size_t)(T * 8) + 1);
-    struct Chunk { size_t a, b; std::string rows; std::vector<Call> calls; int err = 0; };
+    struct Chunk { size_t a, b; std::string rows; std::vector<Call> calls; int err = 0; uint64_t taken = 0, recomputed = 0; };
     std::vector<Chunk> chunks;
     for (size_t a = 0; a < todo.size();) {
         size_t b = a;
         const int con = states[todo[a]].contig_num;
         while (b < todo.size() && b - a < chunk_len && states[todo[b]].contig_num == con) ++b;
-        chunks.push_back(Chunk{a, b, {}, {}, 0});
+        chunks.push_back(Chunk{a, b, {}, {}, 0, 0, 0});
         a = b;
     }
     std::atomic<size_t> next{0};
@@ -981,6 +1296,7 @@ static int circ_call_mt(const cm_params *P, int32_t window_size, uint32_t n_cont
             Chunk &ck = chunks[c];
             const int con = states[todo[ck.a]].contig_num;
             Caller cur(*P, contigs[con], annots[con], ws, chrs);
+            if (ahead && !ahead_of[con].pr.req.empty()) cur.answers = &ahead_of[con].view;
             for (size_t x = ck.a; x < ck.b; ++x) {
                 const uint64_t i = todo[x];
                 const cm_mapped_read &st = states[i];
@@ -994,6 +1310,8 @@ static int circ_call_mt(const cm_params *P, int32_t window_size, uint32_t n_cont
             ck.rows.swap(cur.candidates);
             ck.calls.swap(cur.calls);
             ck.err = cur.err_;
+            ck.taken = cur.taken;
+            ck.recomputed = cur.recomputed;
         }
     };
     {
@@ -1002,6 +1320,14 @@ static int circ_call_mt(const cm_params *P, int32_t window_size, uint32_t n_cont
         for (int t = 1; t < nt; ++t) th.emplace_back(work);
         work();
         for (auto &t : th) t.join();
+    }
+    if (ahead && getenv("CM_CIRC_TRACE")) {
+        uint64_t taken = 0, recomputed = 0;
+        for (const Chunk &ck : chunks) {
+            taken += ck.taken;
+            recomputed += ck.recomputed;
+        }
+        fprintf(stderr, "[circ] chains ahead: %llu answers taken, %llu problems recomputed on the host\n", (unsigned long long)taken, (unsigned long long)recomputed);
     }
     std::vector<Call> calls;
     uint64_t n_rows = 0;
@@ -1042,6 +1368,14 @@ extern "C" int cm_circ_call(const cm_params *P, int32_t window_size, uint32_t n_
     return circ_call_mt(P, window_size, n_contigs, contigs, annots, chrs, n_chr, sorted, candidates_path, report_path, stats, 0);
 }
 
+extern "C" int cm_circ_call_device(cm_ctx *ctx, int slot, const cm_params *P, int32_t window_size, uint32_t n_contigs, const cm_index_view *contigs,
+                                   const cm_annot_view *annots, const cm_chr_info *chrs, uint32_t n_chr, const cm_fastq_batch *sorted,
+                                   const char *candidates_path, const char *report_path, cm_circ_stats *stats) {
+    const int ws = window_size > 0 ? window_size : 8;
+    if (ws < 6 || ws > 10) return CM_ELIMIT;            // the windows cm_circ_chain_batch takes
+    return circ_call_mt(P, window_size, n_contigs, contigs, annots, chrs, n_chr, sorted, candidates_path, report_path, stats, 0, true, ctx, slot);
+}
+
 extern "C" int cm_circ_run(const cm_circ_args *a, cm_circ_stats *stats, char *err, uint64_t err_cap) {
     Fail fail{err, (size_t)err_cap};
     if (err && err_cap) err[0] = 0;
@@ -1053,7 +1387,10 @@ extern "C" int cm_circ_run(const cm_circ_args *a, cm_circ_stats *stats, char *er
     cm_fastq *fq = nullptr;
     std::vector<cm_index_view> views;
     std::vector<cm_annot_view> annots;
+    cm_ctx *dev_ctx = nullptr;
     auto cleanup = [&]() {
+        if (dev_ctx) cm_destroy(dev_ctx);
+        dev_ctx = nullptr;
         if (fq) cm_fastq_close(fq);
         if (!annots.empty()) cm_host_free_annotation(annots.data(), (uint32_t)annots.size());
         for (auto &v : views) cm_host_free_loaded_contig(&v);
@@ -1107,6 +1444,21 @@ extern "C" int cm_circ_run(const cm_circ_args *a, cm_circ_stats *stats, char *er
     S2_TRY(cm_host_open_index(a->index_path, &idx, &kmer, &full, &n_rec), "cm_host_open_index");
     cm_params P = a->params;
     if (P.kmer == 0) P.kmer = kmer;
+    // CM_CIRC_DEVICE=1: seeds and chains on the device (cm_circ_call_device) with a context of this run's own; no device is an
+    // error, not a reason to take the host path
+    const char *dev_env = getenv("CM_CIRC_DEVICE");
+    const bool on_device = dev_env && atoi(dev_env) != 0;
+    cm_ctx *ctx = nullptr;
+    if (on_device) {
+        rc = cm_create(&P, &ctx);
+        if (rc != CM_OK) {
+            rc = fail(rc, rc == CM_ENODEV ? "cm_circ_run: CM_CIRC_DEVICE=1 and no HIP device (CM_ENODEV); the host path is taken only without the variable"
+                                          : "cm_circ_run: CM_CIRC_DEVICE=1 and cm_create failed (%d)", rc);
+            cleanup();
+            return rc;
+        }
+        dev_ctx = ctx;
+    }
     // the GTF model needs the contig lengths: those of the .index.info rows first (checked against the index file's below)
     std::vector<uint32_t> clen_guess;
     for (uint32_t i = 0; i < n_chr; ++i) {
@@ -1161,8 +1513,8 @@ extern "C" int cm_circ_run(const cm_circ_args *a, cm_circ_stats *stats, char *er
     lap("parse sorted remain files");
     const std::string cand = out + ".candidates.pam", rep = out + ".circ_report";
     rc = circ_call_mt(&P, a->window_size, (uint32_t)views.size(), views.data(), annots.data(), chrs, n_chr, &b, cand.c_str(), rep.c_str(), stats,
-                      a->n_threads);
-    if (rc != CM_OK) rc = fail(rc, "cm_circ_call failed (%d)", rc);
+                      a->n_threads, on_device, dev_ctx, 0);
+    if (rc != CM_OK) rc = on_device ? fail(rc, "cm_circ_call_device failed (%d): %s", rc, cm_last_error(dev_ctx)) : fail(rc, "cm_circ_call failed (%d)", rc);
     lap("calling + report");
     cleanup();
     lap("cleanup");

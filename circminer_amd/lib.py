@@ -103,6 +103,21 @@ class AnnotRes(C.Structure):           # cm_annot_res
 ANNOT_REQ_DTYPE = np.dtype([("kind", "<i4")] + [(n, "<u4") for n in ("p0", "p1", "p2", "p3")] + [(n, "<i4") for n in ("i0", "i1", "i2")])
 ANNOT_RES_DTYPE = np.dtype([("ret", "<i4"), ("aux", "<i4"), ("u0", "<u4"), ("u1", "<u4")])
 assert ANNOT_REQ_DTYPE.itemsize == C.sizeof(AnnotReq) == 32 and ANNOT_RES_DTYPE.itemsize == C.sizeof(AnnotRes) == 16
+
+
+class CircChainReq(C.Structure):       # cm_circ_chain_req (cm_circ_chain_batch / cm_circ_chain_host)
+    _fields_ = [("gene_start", C.c_uint32), ("gene_end", C.c_uint32), ("seq_off", C.c_uint64), ("seq_len", C.c_uint32), ("qs", C.c_uint32),
+                ("qe", C.c_uint32), ("tag", C.c_uint32)]
+
+
+class CircChainRes(C.Structure):       # cm_circ_chain_res
+    _fields_ = [("n_chains", C.c_uint32), ("n_stored", C.c_uint32), ("listed", C.c_uint32), ("flags", C.c_uint32), ("chain_off", C.c_uint64)]
+
+
+CIRC_CHAIN_REQ_DTYPE = np.dtype([("gene_start", "<u4"), ("gene_end", "<u4"), ("seq_off", "<u8"), ("seq_len", "<u4"), ("qs", "<u4"), ("qe", "<u4"), ("tag", "<u4")])
+CIRC_CHAIN_RES_DTYPE = np.dtype([("n_chains", "<u4"), ("n_stored", "<u4"), ("listed", "<u4"), ("flags", "<u4"), ("chain_off", "<u8")])
+assert CIRC_CHAIN_REQ_DTYPE.itemsize == C.sizeof(CircChainReq) == 32 and CIRC_CHAIN_RES_DTYPE.itemsize == C.sizeof(CircChainRes) == 24
+CIRC_CHAIN_REFUSED = 1
 ANNOT_TIDS = 64                        # words of out_tids per request (cmc::MAX_TID)
 
 
@@ -292,6 +307,13 @@ SIGNATURES = {
     "cm_circ_call": (C.c_int, [pp(Params), C.c_int32, C.c_uint32, pp(IndexView), pp(AnnotView), pp(ChrInfo), C.c_uint32, pp(FastqBatch),
                                C.c_char_p, C.c_char_p, pp(CircStats)]),
     "cm_circ_run": (C.c_int, [pp(CircArgs), pp(CircStats), C.c_char_p, C.c_uint64]),
+    "cm_circ_chain_batch": (C.c_int, [vp, C.c_int, C.c_int32, vp, C.c_uint32, vp, C.c_uint64, vp, C.c_uint32, vp, vp, vp, vp, C.c_uint64, vp, vp, C.c_uint64, pp(C.c_uint64), pp(C.c_uint64), pp(C.c_uint64)]),
+    "cm_circ_chain_host": (C.c_int, [pp(Params), pp(AnnotView), C.c_int32, vp, C.c_uint32, vp, C.c_uint64, vp, C.c_uint32, vp, vp, vp, vp, C.c_uint64, vp, vp, C.c_uint64, pp(C.c_uint64), pp(C.c_uint64), pp(C.c_uint64)]),
+    "cm_circ_chain_list": (C.c_int, [pp(Params), C.c_int32, pp(AnnotView), pp(ChrInfo), C.c_uint32, pp(FastqBatch), C.c_int32, vp, vp, C.c_uint64, vp,
+                                     C.c_uint64, pp(C.c_uint64), pp(C.c_uint64)]),
+    "cm_circ_call_device": (C.c_int, [vp, C.c_int, pp(Params), C.c_int32, C.c_uint32, pp(IndexView), pp(AnnotView), pp(ChrInfo), C.c_uint32, pp(FastqBatch),
+                                      C.c_char_p, C.c_char_p, pp(CircStats)]),
+    "cm_circ_chain_abi_sizes": (C.c_int, [pp(C.c_uint32), C.c_uint32]),
     "cm_write_sam_header": (C.c_int, [vp]),
     "cm_write_sam": (C.c_int, [vp, pp(FastqBatch), vp, vp, C.c_uint64]),
     "cm_writer_flush": (C.c_int, [vp]),
@@ -323,6 +345,9 @@ def load(path: str = LIB_PATH) -> C.CDLL:
                                   MappingStats, CircRes, CircArgs, CircStats, IndexRaw, BuildStats, DpReq, DpRes, AnnotReq, AnnotRes)]
     if n != len(mine) or list(got[:n]) != mine:
         raise RuntimeError(f"circminer_amd.lib: struct sizes differ from {path}: library {list(got[:max(n, 0)])}, ctypes {mine}")
+    two = (C.c_uint32 * 2)()
+    if L.cm_circ_chain_abi_sizes(two, 2) != 2 or list(two) != [C.sizeof(CircChainReq), C.sizeof(CircChainRes)]:
+        raise RuntimeError(f"circminer_amd.lib: cm_circ_chain_req / cm_circ_chain_res differ from {path}: library {list(two)}")
     _lib = L
     return L
 
@@ -580,6 +605,95 @@ def circ_call(params, host_index, chr_table, sorted_batch, candidates_path, repo
                         candidates_path.encode(), report_path.encode(), C.byref(st))
     if rc != 0:
         raise RuntimeError(f"cm_circ_call failed ({rc})")
+    return st
+
+
+class CircChains:
+    """The answers of cm_circ_chain_batch / cm_circ_chain_host: res (CIRC_CHAIN_RES_DTYPE, one per request), score / len / frag_off
+    per stored chain, rpos / qpos per fragment, stats (8 words).  bytes() is what two equal answers have in common."""
+
+    def __init__(self, res, score, length, frag_off, rpos, qpos, stats):
+        self.res, self.score, self.len, self.frag_off, self.rpos, self.qpos, self.stats = res, score, length, frag_off, rpos, qpos, stats
+
+    def bytes(self):
+        return b"".join(a.tobytes() for a in (self.res, self.score, self.len, self.frag_off, self.rpos, self.qpos))
+
+    def chains(self, i):
+        """request i's stored chains as [(score, [(rpos, qpos), ...]), ...]"""
+        v = self.res[i]
+        out = []
+        for c in range(int(v["chain_off"]), int(v["chain_off"]) + int(v["n_stored"])):
+            f, n = int(self.frag_off[c]), int(self.len[c])
+            out.append((float(self.score[c]), list(zip(self.rpos[f:f + n].tolist(), self.qpos[f:f + n].tolist()))))
+        return out
+
+
+def _circ_chain_call(fn, head, what, err, genome, ref_len, seqs, req, window, cap_chains, cap_frags):
+    req = np.ascontiguousarray(req, dtype=CIRC_CHAIN_REQ_DTYPE)
+    seqs = np.ascontiguousarray(seqs, dtype=np.uint8)
+    n = len(req)
+    if cap_chains is None:
+        cap_chains = 10 * n
+    if cap_frags is None:
+        span = np.maximum(req["qe"].astype(np.int64) - req["qs"].astype(np.int64) + 1, 0)
+        cap_frags = int((10 * (span // 3 + 1)).sum())
+    res = np.zeros(n, CIRC_CHAIN_RES_DTYPE)
+    score = np.zeros(max(cap_chains, 1), np.float32)
+    length = np.zeros(max(cap_chains, 1), np.uint32)
+    frag_off = np.zeros(max(cap_chains, 1), np.uint64)
+    rpos = np.zeros(max(cap_frags, 1), np.uint32)
+    qpos = np.zeros(max(cap_frags, 1), np.int32)
+    nc, nf = C.c_uint64(0), C.c_uint64(0)
+    stats = (C.c_uint64 * 8)()
+    g = None if genome is None else np.ascontiguousarray(genome, dtype=np.uint8)
+    rc = fn(*head, window, g.ctypes.data if g is not None else None, ref_len if g is None else (len(g) if ref_len is None else ref_len),
+            seqs.ctypes.data if seqs.size else None, seqs.size, req.ctypes.data if n else None, n, res.ctypes.data if n else None, score.ctypes.data,
+            length.ctypes.data, frag_off.ctypes.data, cap_chains, rpos.ctypes.data, qpos.ctypes.data, cap_frags, C.byref(nc), C.byref(nf), stats)
+    if rc != 0:
+        raise RuntimeError(f"{what} failed ({rc}): {err()} [needs {nc.value} chains, {nf.value} fragments]")
+    return CircChains(res, score[:nc.value].copy(), length[:nc.value].copy(), frag_off[:nc.value].copy(), rpos[:nf.value].copy(), qpos[:nf.value].copy(),
+                      [int(x) for x in stats])
+
+
+def circ_chain_host(params, av, genome, seqs, req, window=0, ref_len=None, cap_chains=None, cap_frags=None) -> CircChains:
+    """cm_circ_chain_host: the requests (CIRC_CHAIN_REQ_DTYPE) answered by the serial statement of stage 2's chaining"""
+    L = load()
+    return _circ_chain_call(L.cm_circ_chain_host, (C.byref(params), C.byref(av)), "cm_circ_chain_host", lambda: "", genome, ref_len, seqs, req, window,
+                            cap_chains, cap_frags)
+
+
+def circ_chain_list(params, av, chr_table, sorted_batch, contig=0, window=0):
+    """cm_circ_chain_list: the problems cm_circ_call_device lists for one contig -> (req, pair_of, seqs)"""
+    L = load()
+    chrs = chr_array(list(chr_table))
+    nr, ns = C.c_uint64(0), C.c_uint64(0)
+    rc = L.cm_circ_chain_list(C.byref(params), window, C.byref(av), chrs, len(chr_table), C.byref(sorted_batch.fb), contig, None, None, 0, None, 0,
+                              C.byref(nr), C.byref(ns))
+    if rc not in (0, -6):
+        raise RuntimeError(f"cm_circ_chain_list failed ({rc})")
+    req = np.zeros(nr.value, CIRC_CHAIN_REQ_DTYPE)
+    pair_of = np.zeros(nr.value, np.uint64)
+    seqs = np.zeros(ns.value, np.uint8)
+    if nr.value:
+        rc = L.cm_circ_chain_list(C.byref(params), window, C.byref(av), chrs, len(chr_table), C.byref(sorted_batch.fb), contig, req.ctypes.data,
+                                  pair_of.ctypes.data, len(req), seqs.ctypes.data if ns.value else None, len(seqs), C.byref(nr), C.byref(ns))
+        if rc != 0:
+            raise RuntimeError(f"cm_circ_chain_list failed ({rc})")
+    return req, pair_of, seqs
+
+
+def circ_call_device(hot, params, host_index, chr_table, sorted_batch, candidates_path, report_path, window=0, slot=0):
+    """cm_circ_call_device: cm_circ_call with the seeds and chains from the device (hot: a HotPath made with `params`), or, with
+    hot=None, from cm_circ_chain_host through the same provider path"""
+    L = load()
+    n_con = host_index.n_contigs
+    views = (IndexView * n_con)(*host_index.views)
+    chrs = chr_array(list(chr_table))
+    st = CircStats()
+    rc = L.cm_circ_call_device(hot.h if hot is not None else None, slot, C.byref(params), window, n_con, views, host_index.annots, chrs, len(chr_table),
+                               C.byref(sorted_batch.fb), candidates_path.encode(), report_path.encode(), C.byref(st))
+    if rc != 0:
+        raise RuntimeError(f"cm_circ_call_device failed ({rc})" + (": " + L.cm_last_error(hot.h).decode() if hot is not None else ""))
     return st
 
 
@@ -1020,6 +1134,12 @@ class HotPath:
     def load_annotation(self, slot, av: AnnotView):
         """the annotation alone: what cm_annot_batch needs (no index in the slot)"""
         self._chk(self.L.cm_load_annotation(self.h, slot, C.byref(av)), "cm_load_annotation")
+
+    def circ_chain_batch(self, slot, genome, seqs, req, window=0, ref_len=0, cap_chains=None, cap_frags=None) -> CircChains:
+        """cm_circ_chain_batch: the requests (CIRC_CHAIN_REQ_DTYPE) on the device against the annotation of `slot`; genome=None takes
+        the contig resident in the slot"""
+        return _circ_chain_call(self.L.cm_circ_chain_batch, (self.h, slot), "cm_circ_chain_batch", lambda: self.L.cm_last_error(self.h).decode(),
+                                genome, ref_len if genome is None else None, seqs, req, window, cap_chains, cap_frags)
 
     def annot_batch(self, slot, P, req):
         """cm_annot_batch: the requests `req` (ANNOT_REQ_DTYPE) against the annotation of `slot` -> (results (ANNOT_RES_DTYPE),

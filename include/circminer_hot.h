@@ -826,6 +826,67 @@ typedef struct cm_circ_args {
 } cm_circ_args;
 int cm_circ_run(const cm_circ_args *args, cm_circ_stats *stats, char *err, uint64_t err_cap);
 
+/* ---------------- stage 2, seeds and chains of many problems at once (opt-in device path) ----------------
+ * One problem = what ProcessCirc::chaining (src/process_circ.cpp:677-737) does for one gene and one unmapped part of an oriented
+ * mate: the 8-mer seeds every 3 bases of [qs, qe] (1-based, inclusive) looked up in the gene's regional table
+ * (RegionalHashTable::create_table, src/hash_table.cpp:58-112) and chained k-best (chain_seeds_sorted_kbest2, src/chain.cpp:310-539).
+ * gene_start / gene_end: contig coordinates, 1-based inclusive; seq_off / seq_len: the oriented mate in the byte arena `seqs`,
+ * as the reference holds it in Record::seq / Record::rcseq (a reverse complement has NUL for a byte outside ACGTN); qe <= seq_len. */
+typedef struct cm_circ_chain_req {
+    uint32_t gene_start, gene_end;
+    uint64_t seq_off;
+    uint32_t seq_len, qs, qe;
+    uint32_t tag;            /* the caller's word, not read by the chaining (cm_circ_chain_list: the piece, 0 or 1) */
+} cm_circ_chain_req;
+/* n_chains: chains the reference keeps (<= max_chain_len); n_stored = min(n_chains, 10), all a consumer reads (TOPCHAIN,
+ * src/process_circ.cpp:19); listed: seeds with a valid code; flags bit 0: the problem was refused (it does not fit the device
+ * workspace) and nothing else of it is written; chain_off: its first chain in the chain arrays.  Chain c has score[c] (the float
+ * of the fp64 score), len[c] fragments and its fragments at rpos / qpos[frag_off[c] ..): contig position of the hit, 0-based
+ * offset of the seed on the mate.  All offsets are running sums in request order, so equal answers are equal bytes. */
+typedef struct cm_circ_chain_res {
+    uint32_t n_chains, n_stored, listed, flags;
+    uint64_t chain_off;
+} cm_circ_chain_res;
+#define CM_CIRC_CHAIN_REFUSED 1u
+/* All problems of a batch on the device, against the annotation loaded in `slot` (cm_load_annotation).  genome: host bytes in the
+ * cm_index_view.genome convention (only the merged spans of the listed genes are uploaded); NULL takes the contig resident in the
+ * slot (CM_EINVAL if there is none; ref_len is then the resident one).  window_size 0 = 8, 6 .. 10 accepted, else CM_ELIMIT.
+ * Capacities are the caller's: cap_chains >= sum of n_stored, cap_frags >= sum of fragments (10 * listed per request always
+ * suffice); too small is CM_ELIMIT and the context stays usable.  *n_chains_out / *n_frags_out: what was used.
+ * Tables are built once per distinct gene; their memory per pass is bounded (CM_CIRC_TABLE_BYTES, default 1 GiB): the genes are
+ * worked through in groups that fit, a gene that alone exceeds the bound refuses its problems.  CM_CIRC_LOG_CAP: improvement-log
+ * entries per resident problem (default 65536).  A refused problem is for the caller to answer with cm_circ_chain_host.
+ * stats: distinct genes, table bytes (largest group), gene groups, DP cells, log events, refused problems, device time of the
+ * tables and of the chaining from HIP events (microseconds: the array holds integers). */
+int cm_circ_chain_batch(cm_ctx *ctx, int slot, int32_t window_size, const uint8_t *genome, uint32_t ref_len, const uint8_t *seqs, uint64_t seqs_len,
+                        const cm_circ_chain_req *req, uint32_t n_req, cm_circ_chain_res *res, float *chain_score, uint32_t *chain_len,
+                        uint64_t *chain_frag_off, uint64_t cap_chains, uint32_t *rpos, int32_t *qpos, uint64_t cap_frags, uint64_t *n_chains_out,
+                        uint64_t *n_frags_out, uint64_t stats[8]);
+/* The same requests answered by the serial statement (Caller::chains_of + cm_regional_table_build) into the same layout: the
+ * checker of the device path and its fall-back.  Never refuses.  stats may be NULL; [0] distinct genes, [3] cells, [4] log events,
+ * [5] 0, [7] the longest log of one problem, the others 0. */
+int cm_circ_chain_host(const cm_params *p, const cm_annot_view *av, int32_t window_size, const uint8_t *genome, uint32_t ref_len, const uint8_t *seqs,
+                       uint64_t seqs_len, const cm_circ_chain_req *req, uint32_t n_req, cm_circ_chain_res *res, float *chain_score, uint32_t *chain_len,
+                       uint64_t *chain_frag_off, uint64_t cap_chains, uint32_t *rpos, int32_t *qpos, uint64_t cap_frags, uint64_t *n_chains_out,
+                       uint64_t *n_frags_out, uint64_t stats[8]);
+/* The problems cm_circ_call_device lists for the eligible pairs of contig `contig` of a sorted batch: pair-major, genes in the
+ * interval's order, piece 0 (mate 1) then 1.  A CHIBSJ pair lists the unmapped side of its split mate, a CHI2BSJ pair both sides
+ * (call_circ_single_split called from call_circ_double_split asks for one of the same two).  The oriented mates go to `seqs` one
+ * after the other (seq_off of the requests).  pair_of[i]: the batch index of request i's pair.  Returns CM_ELIMIT with the needed
+ * sizes in *n_req / *seqs_len when a capacity is too small (call with 0 capacities to size). */
+int cm_circ_chain_list(const cm_params *p, int32_t window_size, const cm_annot_view *av, const cm_chr_info *chrs, uint32_t n_chr,
+                       const cm_fastq_batch *sorted, int32_t contig, cm_circ_chain_req *req, uint64_t *pair_of, uint64_t cap_req, uint8_t *seqs,
+                       uint64_t cap_seqs, uint64_t *n_req, uint64_t *seqs_len);
+/* cm_circ_call with the seeds and chains of every pair taken from cm_circ_chain_batch (ctx, slot: the contig's annotation is
+ * loaded into the slot here, contig by contig) and the rest -- split_realignment, the judges, placement -- on the host threads
+ * as in cm_circ_call.  A refused problem is recomputed on the host.  ctx == NULL answers the problems with cm_circ_chain_host
+ * instead (the same provider path without a device).  The two files are cm_circ_call's byte for byte, for any thread count. */
+int cm_circ_call_device(cm_ctx *ctx, int slot, const cm_params *p, int32_t window_size, uint32_t n_contigs, const cm_index_view *contigs,
+                        const cm_annot_view *annots, const cm_chr_info *chrs, uint32_t n_chr, const cm_fastq_batch *sorted,
+                        const char *candidates_path, const char *report_path, cm_circ_stats *stats);
+/* sizeof(cm_circ_chain_req), sizeof(cm_circ_chain_res): cm_abi_sizes for the two structs above (its own list is closed at 19). */
+int cm_circ_chain_abi_sizes(uint32_t *out, uint32_t cap);
+
 /* sizeof of the structs above, in this order: cm_params, cm_index_view, cm_annot_view, cm_mapped_read, cm_reads, cm_record,
  * cm_chr_info, cm_fastq_batch, cm_mapping_args, cm_mapping_stats, cm_circ_res, cm_circ_args, cm_circ_stats, cm_index_raw, cm_build_stats, cm_dp_req,
  * cm_dp_res, cm_annot_req, cm_annot_res -- for a binding to
