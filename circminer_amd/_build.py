@@ -16,7 +16,7 @@ CSRC = os.path.join(HERE, "csrc")
 INC = os.path.join(HERE, "..", "include")
 OUT = os.path.join(CSRC, "libcmhot.so")
 SOURCES = ["cm_hot.hip", "cm_dp_probe.hip", "cm_annot_probe.hip", "cm_circ_chain.hip", "cm_dispatch.cpp", "host_index.cpp", "host_annot.cpp", "host_index_io.cpp", "host_fastq.cpp", "host_mapping.cpp", "host_circ.cpp",
-           "host_circ_call.cpp"]
+           "host_circ_call.cpp", "host_detect.cpp"]
 ABI_DEF = "cm_device_abi.def"
 DEPS = SOURCES + sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + [ABI_DEF, os.path.join("..", "..", "include", "circminer_hot.h")]
 # cm_hot.hip is compiled twice (reads of <= 16 seeds / <= 24 seeds, see cm_dispatch.cpp): the names it exports get a suffix.  The

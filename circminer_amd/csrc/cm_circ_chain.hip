@@ -27,6 +27,7 @@
 #define cmc cmc_cc                     // the bodies' namespace: every build of them has its own (cm_dispatch.cpp)
 #include "cm_core.h"
 #include "cm_circ_chain.h"
+#include "cm_circ_chain_ws.h"
 
 namespace {
 
@@ -431,17 +432,6 @@ __global__ void __launch_bounds__(64) k_cc_chain(cmc::KCore kcore, CcWork w) {
     }
 }
 
-struct Tmp {                                       // device memory of one call, gone when it returns
-    void *p = nullptr;
-    Tmp() = default;
-    Tmp(const Tmp &) = delete;
-    Tmp &operator=(const Tmp &) = delete;
-    ~Tmp() { if (p) (void)hipFree(p); }
-    void drop() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-    }
-};
 struct Ev2 {
     hipEvent_t a = nullptr, b = nullptr;
     ~Ev2() {
@@ -466,8 +456,9 @@ uint64_t env_u64(const char *name, uint64_t dflt) {
     } while (0)
 
 // annot: the slot's cmc::AnnotDev (device pointers), annot_bytes its sizeof in the caller's build.  d_contig / contig_len: the
-// slot's resident sequence (device memory), used when genome == NULL.
-extern "C" int cm_circ_chain_run(hipStream_t so, const cm_params *P, const void *annot, size_t annot_bytes, const uint8_t *d_contig, uint32_t contig_len,
+// slot's resident sequence (device memory), used when genome == NULL.  wsp: the context's workspace (cm_circ_chain_ws.h): every
+// device buffer of the call lives there and stays there; CM_CIRC_TRACE prints what the call allocated and what is held.
+extern "C" int cm_circ_chain_run(hipStream_t so, cm_circ_chain_ws *wsp, const cm_params *P, const void *annot, size_t annot_bytes, const uint8_t *d_contig, uint32_t contig_len,
                                  int32_t window_size, const uint8_t *genome, uint32_t ref_len, const uint8_t *seqs, uint64_t seqs_len,
                                  const cm_circ_chain_req *req, uint32_t n_req, cm_circ_chain_res *res, float *chain_score, uint32_t *chain_len,
                                  uint64_t *chain_frag_off, uint64_t cap_chains, uint32_t *rpos, int32_t *qpos, uint64_t cap_frags, uint64_t *n_chains_out,
@@ -479,7 +470,7 @@ extern "C" int cm_circ_chain_run(hipStream_t so, const cm_params *P, const void 
     if (stats) memset(stats, 0, 8 * sizeof(uint64_t));
     if (n_chains_out) *n_chains_out = 0;
     if (n_frags_out) *n_frags_out = 0;
-    if (!P || !annot || (n_req && (!req || !res || !seqs))) return fail(CM_EINVAL, "null argument");
+    if (!P || !wsp || !annot || (n_req && (!req || !res || !seqs))) return fail(CM_EINVAL, "null argument");
     if (annot_bytes != sizeof(cmc::AnnotDev)) return fail(CM_EINVAL, "AnnotDev of %zu bytes, %zu here", annot_bytes, sizeof(cmc::AnnotDev));
     const int ws = window_size == 0 ? 8 : window_size;
     if (ws < 6 || ws > 10) return fail(CM_ELIMIT, "window size %d (6 .. 10)", ws);
@@ -539,31 +530,45 @@ extern "C" int cm_circ_chain_run(hipStream_t so, const cm_params *P, const void 
     kc.P = *P;
     kc.A = *(const cmc::AnnotDev *)annot;
 
-    Tmp d_req, d_seqs, d_geneof, d_fragbase, d_res, d_cscore, d_clen, d_rpos, d_qpos, d_cursor, d_counters, d_score, d_prev, d_log, d_seen;
-    // resident waves: as many as a quarter of the free device memory holds workspace slices for, 1024 at the most
+    // resident waves: as many as a quarter of the free device memory holds workspace slices for, 1024 at the most -- decided when
+    // the slices are first sized, and again when CM_CIRC_LOG_CAP has changed the size of a slice
     const uint32_t seen_cap = (uint32_t)P->max_chain_len * cmc::CC_MAX_LISTS;
     const uint64_t slice_bytes = (uint64_t)CELL_CAP * (sizeof(double) + sizeof(int32_t)) + (uint64_t)log_cap * sizeof(cmc::CcEv) + (uint64_t)seen_cap * 4;
-    size_t mem_free = 0, mem_total = 0;
-    HIPCHK(hipMemGetInfo(&mem_free, &mem_total));
-    if (slice_bytes > mem_free / 4)
-        return fail(CM_ELIMIT, "CM_CIRC_LOG_CAP %u: one problem's workspace of %llu bytes against %llu free", log_cap, (unsigned long long)slice_bytes,
-                    (unsigned long long)mem_free);
-    const uint32_t workers = (uint32_t)std::min<uint64_t>(std::min<uint32_t>(n_req, MAX_WORKERS), mem_free / 4 / slice_bytes);
-    HIPCHK(hipMalloc(&d_req.p, (size_t)n_req * sizeof(cm_circ_chain_req)));
-    HIPCHK(hipMalloc(&d_seqs.p, (size_t)std::max<uint64_t>(seqs_len, 1)));
-    HIPCHK(hipMalloc(&d_geneof.p, (size_t)n_req * 4));
-    HIPCHK(hipMalloc(&d_fragbase.p, (size_t)n_req * 8));
-    HIPCHK(hipMalloc(&d_res.p, (size_t)n_req * sizeof(CcRes)));
-    HIPCHK(hipMalloc(&d_cscore.p, (size_t)n_req * cmc::CC_TOPCHAIN * 4));
-    HIPCHK(hipMalloc(&d_clen.p, (size_t)n_req * cmc::CC_TOPCHAIN * 4));
-    HIPCHK(hipMalloc(&d_rpos.p, (size_t)frag_cap * 4));
-    HIPCHK(hipMalloc(&d_qpos.p, (size_t)frag_cap * 4));
-    HIPCHK(hipMalloc(&d_cursor.p, 4));
-    HIPCHK(hipMalloc(&d_counters.p, 8 * 8));
-    HIPCHK(hipMalloc(&d_score.p, (size_t)workers * CELL_CAP * sizeof(double)));
-    HIPCHK(hipMalloc(&d_prev.p, (size_t)workers * CELL_CAP * sizeof(int32_t)));
-    HIPCHK(hipMalloc(&d_log.p, (size_t)workers * log_cap * sizeof(cmc::CcEv)));
-    HIPCHK(hipMalloc(&d_seen.p, (size_t)workers * seen_cap * 4));
+    const uint64_t allocs_before = wsp->allocations;
+    if (wsp->max_workers == 0 || wsp->log_cap != log_cap || wsp->seen_cap != seen_cap) {
+        for (int b : {CCW_SCORE, CCW_PREV, CCW_LOG, CCW_SEEN}) cc_ws_drop(*wsp, b);
+        wsp->max_workers = 0;
+        size_t mem_free = 0, mem_total = 0;
+        HIPCHK(hipMemGetInfo(&mem_free, &mem_total));
+        if (slice_bytes > mem_free / 4)
+            return fail(CM_ELIMIT, "CM_CIRC_LOG_CAP %u: one problem's workspace of %llu bytes against %llu free", log_cap, (unsigned long long)slice_bytes,
+                        (unsigned long long)mem_free);
+        wsp->max_workers = (uint32_t)std::min<uint64_t>(MAX_WORKERS, mem_free / 4 / slice_bytes);
+        wsp->log_cap = log_cap;
+        wsp->seen_cap = seen_cap;
+    }
+    const uint32_t workers = std::min<uint32_t>(n_req, wsp->max_workers);
+    struct Dev { void *p; } d_req, d_seqs, d_geneof, d_fragbase, d_res, d_cscore, d_clen, d_rpos, d_qpos, d_cursor, d_counters, d_score, d_prev, d_log, d_seen;
+#define WS_BUF(dst, which, need)                      \
+    do {                                              \
+        HIPCHK(cc_ws_ensure(*wsp, which, (need)));     \
+        (dst).p = wsp->p[which];                       \
+    } while (0)
+    WS_BUF(d_req, CCW_REQ, (size_t)n_req * sizeof(cm_circ_chain_req));
+    WS_BUF(d_seqs, CCW_SEQS, (size_t)std::max<uint64_t>(seqs_len, 1));
+    WS_BUF(d_geneof, CCW_GENEOF, (size_t)n_req * 4);
+    WS_BUF(d_fragbase, CCW_FRAGBASE, (size_t)n_req * 8);
+    WS_BUF(d_res, CCW_RES, (size_t)n_req * sizeof(CcRes));
+    WS_BUF(d_cscore, CCW_CSCORE, (size_t)n_req * cmc::CC_TOPCHAIN * 4);
+    WS_BUF(d_clen, CCW_CLEN, (size_t)n_req * cmc::CC_TOPCHAIN * 4);
+    WS_BUF(d_rpos, CCW_RPOS, (size_t)frag_cap * 4);
+    WS_BUF(d_qpos, CCW_QPOS, (size_t)frag_cap * 4);
+    WS_BUF(d_cursor, CCW_CURSOR, 4);
+    WS_BUF(d_counters, CCW_COUNTERS, 8 * 8);
+    WS_BUF(d_score, CCW_SCORE, (size_t)workers * CELL_CAP * sizeof(double));
+    WS_BUF(d_prev, CCW_PREV, (size_t)workers * CELL_CAP * sizeof(int32_t));
+    WS_BUF(d_log, CCW_LOG, (size_t)workers * log_cap * sizeof(cmc::CcEv));
+    WS_BUF(d_seen, CCW_SEEN, (size_t)workers * seen_cap * 4);
     HIPCHK(hipMemcpyAsync(d_req.p, req, (size_t)n_req * sizeof(cm_circ_chain_req), hipMemcpyHostToDevice, so));
     if (seqs_len) HIPCHK(hipMemcpyAsync(d_seqs.p, seqs, (size_t)seqs_len, hipMemcpyHostToDevice, so));
     HIPCHK(hipMemcpyAsync(d_fragbase.p, frag_base.data(), (size_t)n_req * 8, hipMemcpyHostToDevice, so));
@@ -638,7 +643,7 @@ extern "C" int cm_circ_chain_run(hipStream_t so, const cm_params *P, const void 
             loc_words += nw;
             max_nw = std::max(max_nw, nw);
         }
-        Tmp d_genes, d_arena, d_off, d_cnt, d_loc, d_order;
+        Dev d_genes, d_arena, d_off, d_cnt, d_loc, d_order;
         CcTab t{};
         t.n_genes = (uint32_t)gd.size();
         t.ws = ws;
@@ -646,13 +651,13 @@ extern "C" int cm_circ_chain_run(hipStream_t so, const cm_params *P, const void 
         t.off_words = (uint64_t)gd.size() * (S + 1);
         t.cnt_words = (uint64_t)gd.size() * S;
         t.loc_words = std::max<uint64_t>(loc_words, 1);
-        HIPCHK(hipMalloc(&d_genes.p, gd.size() * sizeof(CcGene)));
-        HIPCHK(hipMalloc(&d_off.p, (size_t)t.off_words * 4));
-        HIPCHK(hipMalloc(&d_cnt.p, (size_t)t.cnt_words * 4));
-        HIPCHK(hipMalloc(&d_loc.p, (size_t)t.loc_words * 4));
+        WS_BUF(d_genes, CCW_GENES, gd.size() * sizeof(CcGene));
+        WS_BUF(d_off, CCW_OFF, (size_t)t.off_words * 4);
+        WS_BUF(d_cnt, CCW_CNT, (size_t)t.cnt_words * 4);
+        WS_BUF(d_loc, CCW_LOC, (size_t)t.loc_words * 4);
         HIPCHK(hipMemcpyAsync(d_genes.p, gd.data(), gd.size() * sizeof(CcGene), hipMemcpyHostToDevice, so));
         if (genome) {
-            HIPCHK(hipMalloc(&d_arena.p, std::max<size_t>(arena.size(), 1)));
+            WS_BUF(d_arena, CCW_ARENA, std::max<size_t>(arena.size(), 1));
             if (!arena.empty()) HIPCHK(hipMemcpyAsync(d_arena.p, arena.data(), arena.size(), hipMemcpyHostToDevice, so));
             t.seq = (const uint8_t *)d_arena.p;
             t.seq_len = arena.size();
@@ -677,7 +682,7 @@ extern "C" int cm_circ_chain_run(hipStream_t so, const cm_params *P, const void 
 
         const std::vector<uint32_t> &ord = order[gr];
         if (!ord.empty()) {
-            HIPCHK(hipMalloc(&d_order.p, ord.size() * 4));
+            WS_BUF(d_order, CCW_ORDER, ord.size() * 4);
             HIPCHK(hipMemcpyAsync(d_order.p, ord.data(), ord.size() * 4, hipMemcpyHostToDevice, so));
             HIPCHK(hipMemsetAsync(d_cursor.p, 0, 4, so));
             CcWork w{};
@@ -716,7 +721,7 @@ extern "C" int cm_circ_chain_run(hipStream_t so, const cm_params *P, const void 
             HIPCHK(hipGetLastError());
             HIPCHK(hipEventRecord(ev_c.b, so));
         }
-        HIPCHK(hipStreamSynchronize(so));            // the group's tables go out of scope below
+        HIPCHK(hipStreamSynchronize(so));            // the next group takes the group's buffers
         float ms = 0;
         if (hipEventElapsedTime(&ms, ev_t.a, ev_t.b) == hipSuccess) ms_tab += ms;
         if (!ord.empty() && hipEventElapsedTime(&ms, ev_c.a, ev_c.b) == hipSuccess) ms_chain += ms;
@@ -747,6 +752,8 @@ extern "C" int cm_circ_chain_run(hipStream_t so, const cm_params *P, const void 
             need_frags += h_len[(size_t)i * cmc::CC_TOPCHAIN + k];
         }
     }
+    if (getenv("CM_CIRC_TRACE"))
+        fprintf(stderr, "[circ] workspace: %llu allocations, %llu held\n", (unsigned long long)(wsp->allocations - allocs_before), (unsigned long long)wsp->held);
     if (n_chains_out) *n_chains_out = need_chains;
     if (n_frags_out) *n_frags_out = need_frags;
     if (stats) {
@@ -783,3 +790,4 @@ extern "C" int cm_circ_chain_run(hipStream_t so, const cm_params *P, const void 
     }
     return CM_OK;
 }
+#undef WS_BUF

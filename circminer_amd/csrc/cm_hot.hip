@@ -32,6 +32,7 @@
 #include "cm_remain_order.h"
 #include "cm_remain_text.h"
 #include "cm_sam_text.h"
+#include "cm_circ_chain_ws.h"
 
 using cmc::Core;
 using cmc::KCore;
@@ -2553,6 +2554,7 @@ struct cm_ctx {
     uint32_t h_pin_nt = 0;                        // pairs of the tile whose heavy load was last sent to h_pin[PIN_HEAVY_LOAD] (0: none yet)
     std::string err = "";
     Slot slots[MAX_SLOTS];
+    cm_circ_chain_ws circ_ws{};               // cm_circ_chain_batch's device workspace: grow-only, filled by cm_circ_chain_run, released by cm_destroy
     // reads
     uint64_t n_pairs = 0;
     ReadBufs rd;
@@ -3104,6 +3106,7 @@ void cm_destroy(cm_ctx *ctx) {
         drop_entry_near(ctx, s);
     }
     release(ctx, CONTEXT);                 // (the grow-only output staging of cm_collect_* outlives a batch)
+    report_hip(ctx, "hipFree (stage 2 chain workspace)", cc_ws_release(ctx->circ_ws));
     if (ctx->h_pin) report_hip(ctx, "hipHostFree", hipHostFree(ctx->h_pin));
     for (hipEvent_t e : ctx->ev)
         if (e) report_hip(ctx, "hipEventDestroy", hipEventDestroy(e));
@@ -5048,8 +5051,8 @@ int cm_annot_batch(cm_ctx *ctx, int slot, const cm_params *P, const cm_annot_req
 }
 
 // stage 2's seeds and chains (kernels, validation and launch in cm_circ_chain.hip); here only what needs the context: the slot's
-// annotation and, for genome == NULL, its resident sequence
-extern "C" int cm_circ_chain_run(hipStream_t so, const cm_params *P, const void *annot, size_t annot_bytes, const uint8_t *d_contig, uint32_t contig_len,
+// annotation, for genome == NULL its resident sequence, and the workspace the calls of a context share
+extern "C" int cm_circ_chain_run(hipStream_t so, cm_circ_chain_ws *wsp, const cm_params *P, const void *annot, size_t annot_bytes, const uint8_t *d_contig, uint32_t contig_len,
                                  int32_t window_size, const uint8_t *genome, uint32_t ref_len, const uint8_t *seqs, uint64_t seqs_len,
                                  const cm_circ_chain_req *req, uint32_t n_req, cm_circ_chain_res *res, float *chain_score, uint32_t *chain_len,
                                  uint64_t *chain_frag_off, uint64_t cap_chains, uint32_t *rpos, int32_t *qpos, uint64_t cap_frags, uint64_t *n_chains_out,
@@ -5064,7 +5067,7 @@ int cm_circ_chain_batch(cm_ctx *ctx, int slot, int32_t window_size, const uint8_
     if (!s.has_annot) return fail(ctx, CM_ESTATE, "annotation of slot %d not loaded", slot);
     HIPCHK(ctx, hipSetDevice(ctx->P.device));
     char msg[256] = "";
-    const int rc = cm_circ_chain_run(ctx->st.B, &ctx->P, &s.A, sizeof(cmc::AnnotDev), s.loaded ? s.X.genome : nullptr, s.loaded ? s.X.ref_len : 0, window_size,
+    const int rc = cm_circ_chain_run(ctx->st.B, &ctx->circ_ws, &ctx->P, &s.A, sizeof(cmc::AnnotDev), s.loaded ? s.X.genome : nullptr, s.loaded ? s.X.ref_len : 0, window_size,
                                      genome, ref_len, seqs, seqs_len, req, n_req, res, chain_score, chain_len, chain_frag_off, cap_chains, rpos, qpos,
                                      cap_frags, n_chains_out, n_frags_out, stats, msg, sizeof msg);
     return rc == CM_OK ? CM_OK : fail(ctx, rc, "cm_circ_chain_batch: %s", msg);

@@ -369,17 +369,55 @@ int64_t parsed_key(const char *p, size_t n) {
 }  // namespace
 struct cm_remain_runs {
     std::string path[2];
+    bool has_paths = false;           // opened without paths: only the memory finish is allowed
     std::vector<Run> runs[2];
+    std::vector<char> merged[2];      // cm_remain_runs_finish_mem: the two merged files, kept until close
 };
+namespace {
+// The merge of one mate file's runs, written once: records leave in the order of key, pasted line, run number, and `sink` takes
+// each record's bytes as they are.  Two sinks: a buffered file (cm_remain_runs_finish) and a vector (cm_remain_runs_finish_mem).
+template <class Sink> void merge_runs(const std::vector<Run> &runs, Sink sink) {
+    struct Head {
+        uint32_t run;
+        uint64_t rec;
+    };
+    // a > b: a comes out later (std::*_heap keep the largest on top, so the comparator is the order reversed)
+    auto later = [&](const Head &a, const Head &b) {
+        const Run &A = runs[a.run], &B = runs[b.run];
+        if (A.key[a.rec] != B.key[b.rec]) return A.key[a.rec] > B.key[b.rec];
+        const size_t la = (size_t)(A.off[a.rec + 1] - A.off[a.rec]) - 1, lb = (size_t)(B.off[b.rec + 1] - B.off[b.rec]) - 1;
+        const int c = pasted_cmp_bytes(A.bytes.data() + A.off[a.rec], la, la, B.bytes.data() + B.off[b.rec], lb, lb);
+        if (c) return c > 0;
+        return a.run > b.run;
+    };
+    std::vector<Head> heap;
+    for (uint32_t k = 0; k < runs.size(); ++k)
+        if (!runs[k].key.empty()) heap.push_back(Head{k, 0});
+    std::make_heap(heap.begin(), heap.end(), later);
+    while (!heap.empty()) {
+        std::pop_heap(heap.begin(), heap.end(), later);
+        Head h = heap.back();
+        const Run &R = runs[h.run];
+        sink(R.bytes.data() + R.off[h.rec], (size_t)(R.off[h.rec + 1] - R.off[h.rec]));
+        if (++h.rec < R.key.size()) {
+            heap.back() = h;
+            std::push_heap(heap.begin(), heap.end(), later);
+        } else heap.pop_back();
+    }
+}
+}  // namespace
 
 extern "C" int cm_remain_runs_open(const char *srt_path1, const char *srt_path2, cm_remain_runs **out) {
-    if (!srt_path1 || !srt_path2 || !out) return CM_EINVAL;
+    if (!out || (!srt_path1) != (!srt_path2)) return CM_EINVAL;            // both paths, or neither (memory finish only)
     *out = nullptr;
     try {
         cm_remain_runs *r = new cm_remain_runs;
         *out = r;
-        r->path[0] = srt_path1;
-        r->path[1] = srt_path2;
+        if (srt_path1) {
+            r->path[0] = srt_path1;
+            r->path[1] = srt_path2;
+            r->has_paths = true;
+        }
     } catch (const std::bad_alloc &) {
         delete *out;
         *out = nullptr;
@@ -449,27 +487,9 @@ extern "C" int cm_remain_runs_add_unsorted(cm_remain_runs *r, const void *bytes1
     return CM_OK;
 }
 extern "C" int cm_remain_runs_finish(cm_remain_runs *r) {
-    if (!r) return CM_EINVAL;
-    struct Head {
-        uint32_t run;
-        uint64_t rec;
-    };
+    if (!r || !r->has_paths) return CM_EINVAL;
     try {
     for (int m = 0; m < 2; ++m) {
-        const std::vector<Run> &runs = r->runs[m];
-        // a > b: a comes out later (std::*_heap keep the largest on top, so the comparator is the order reversed)
-        auto later = [&](const Head &a, const Head &b) {
-            const Run &A = runs[a.run], &B = runs[b.run];
-            if (A.key[a.rec] != B.key[b.rec]) return A.key[a.rec] > B.key[b.rec];
-            const size_t la = (size_t)(A.off[a.rec + 1] - A.off[a.rec]) - 1, lb = (size_t)(B.off[b.rec + 1] - B.off[b.rec]) - 1;
-            const int c = pasted_cmp_bytes(A.bytes.data() + A.off[a.rec], la, la, B.bytes.data() + B.off[b.rec], lb, lb);
-            if (c) return c > 0;
-            return a.run > b.run;
-        };
-        std::vector<Head> heap;
-        for (uint32_t k = 0; k < runs.size(); ++k)
-            if (!runs[k].key.empty()) heap.push_back(Head{k, 0});
-        std::make_heap(heap.begin(), heap.end(), later);
         FILE *out = fopen(r->path[m].c_str(), "wb");
         if (!out) return CM_EIO;
         std::vector<char> ob;
@@ -479,23 +499,36 @@ extern "C" int cm_remain_runs_finish(cm_remain_runs *r) {
             if (!ob.empty() && fwrite(ob.data(), 1, ob.size(), out) != ob.size()) bad = true;
             ob.clear();
         };
-        while (!heap.empty()) {
-            std::pop_heap(heap.begin(), heap.end(), later);
-            Head h = heap.back();
-            const Run &R = runs[h.run];
-            ob.insert(ob.end(), R.bytes.data() + R.off[h.rec], R.bytes.data() + R.off[h.rec + 1]);
+        merge_runs(r->runs[m], [&](const char *p, size_t n) {
+            ob.insert(ob.end(), p, p + n);
             if (ob.size() > (8u << 20) - 4096) flush();
-            if (++h.rec < R.key.size()) {
-                heap.back() = h;
-                std::push_heap(heap.begin(), heap.end(), later);
-            } else heap.pop_back();
-        }
+        });
         flush();
         if (fclose(out) != 0 || bad) return CM_EIO;
     }
     } catch (const std::bad_alloc &) {
         return CM_ENOMEM;
     }
+    return CM_OK;
+}
+extern "C" int cm_remain_runs_finish_mem(cm_remain_runs *r, const void **bytes1, uint64_t *n1, const void **bytes2, uint64_t *n2) {
+    if (!r || !bytes1 || !n1 || !bytes2 || !n2) return CM_EINVAL;
+    try {
+    for (int m = 0; m < 2; ++m) {
+        std::vector<char> &ob = r->merged[m];
+        ob.clear();
+        size_t total = 0;
+        for (const Run &run : r->runs[m]) total += run.bytes.size();
+        ob.reserve(total);
+        merge_runs(r->runs[m], [&](const char *p, size_t n) { ob.insert(ob.end(), p, p + n); });
+    }
+    } catch (const std::bad_alloc &) {
+        return CM_ENOMEM;
+    }
+    *bytes1 = r->merged[0].data();
+    *n1 = r->merged[0].size();
+    *bytes2 = r->merged[1].data();
+    *n2 = r->merged[1].size();
     return CM_OK;
 }
 extern "C" void cm_remain_runs_close(cm_remain_runs *r) { delete r; }

@@ -36,6 +36,7 @@ struct S2Tm {
 #define S2_TIME(k) ((void)0)
 #endif
 #include "circminer_hot.h"
+#include "cm_run.h"
 
 #define CM_STAGE2_HOST 1
 #define cmc cmc_s2            // the kernel bodies get their own namespace here: this build of them differs (host-only members)
@@ -1163,9 +1164,24 @@ extern "C" int cm_circ_chain_list(const cm_params *P, int32_t window_size, const
 // ProcessCirc::do_process over the sorted remain pairs.  Pairs are independent of one another (the per-gene regional tables are a
 // cache, dropped once the sorted input has moved past the gene), so runs of pairs on one contig are cut into chunks that
 // worker threads take in turn, each with a Caller of its own; rows and calls are put together in chunk order, i.e. input order.
+// `resident` (cm_circ_call_resident): ctx holds contig c and its annotation in slot c, so contig c's problems go to slot c against
+// the sequence in HBM -- no annotation is loaded here and no gene span uploaded.  counts: problems listed, refused by the device,
+// recomputed on the host (what CM_CIRC_TRACE prints).
+struct ChainsAhead {
+    bool on = false;               // the seeds and chains of every eligible pair are computed before any pair is judged
+    cm_ctx *ctx = nullptr;         // ... on the device; null: by the serial statement
+    int slot = 0;                  // the slot each contig's annotation is loaded into (not `resident`)
+    bool resident = false;         // contig c and its annotation are in slot c already
+    uint64_t *counts = nullptr;    // [3]: problems, refused, recomputed
+};
 static int circ_call_mt(const cm_params *P, int32_t window_size, uint32_t n_contigs, const cm_index_view *contigs, const cm_annot_view *annots,
                         const cm_chr_info *chrs, uint32_t n_chr, const cm_fastq_batch *sorted, const char *candidates_path,
-                        const char *report_path, cm_circ_stats *stats, int n_threads, bool ahead = false, cm_ctx *ctx = nullptr, int slot = 0) {
+                        const char *report_path, cm_circ_stats *stats, int n_threads, const ChainsAhead &opt = ChainsAhead{}) {
+    const bool ahead = opt.on, resident = opt.resident;
+    cm_ctx *const ctx = opt.ctx;
+    const int slot = opt.slot;
+    uint64_t *const counts = opt.counts;
+    if (counts) counts[0] = counts[1] = counts[2] = 0;
     if (!P || !contigs || !annots || !chrs || !sorted || !candidates_path || !report_path) return CM_EINVAL;
     const int ws = window_size > 0 ? window_size : 8;
     if (ws > 12) return CM_EINVAL;
@@ -1219,7 +1235,7 @@ static int circ_call_mt(const cm_params *P, int32_t window_size, uint32_t n_cont
             const size_t nr = A.pr.req.size();
             if (nr == 0) continue;
             n_problems += nr;
-            if (ctx) {
+            if (ctx && !resident) {
                 const int lrc = cm_load_annotation(ctx, slot, &annots[con]);
                 if (lrc != CM_OK) {
                     fclose(fc);
@@ -1246,7 +1262,7 @@ static int circ_call_mt(const cm_params *P, int32_t window_size, uint32_t n_cont
                 A.rpos.resize(f0 + fr);
                 A.qpos.resize(f0 + fr);
                 uint64_t nc = 0, nf = 0, st8[8];
-                const int brc = ctx ? cm_circ_chain_batch(ctx, slot, ws, contigs[con].genome, contigs[con].ref_len, A.pr.seqs.data() + lo, hi - lo, rq.data(),
+                const int brc = ctx ? cm_circ_chain_batch(ctx, resident ? (int)con : slot, ws, resident ? nullptr : contigs[con].genome, contigs[con].ref_len, A.pr.seqs.data() + lo, hi - lo, rq.data(),
                                                           (uint32_t)rq.size(), A.res.data() + a, A.score.data() + c0, A.len.data() + c0, A.frag_off.data() + c0,
                                                           cc, A.rpos.data() + f0, A.qpos.data() + f0, fr, &nc, &nf, st8)
                                     : cm_circ_chain_host(P, &annots[con], ws, contigs[con].genome, contigs[con].ref_len, A.pr.seqs.data() + lo, hi - lo, rq.data(),
@@ -1273,8 +1289,9 @@ static int circ_call_mt(const cm_params *P, int32_t window_size, uint32_t n_cont
         }
         if (getenv("CM_CIRC_TRACE"))
             fprintf(stderr, "[circ] chains ahead (%s): %llu problems, %llu genes, %llu table bytes, %llu gene groups, %llu cells, %llu log events, %llu refused, tables %.3f ms, chaining %.3f ms\n",
-                    ctx ? "device" : "host", (unsigned long long)n_problems, (unsigned long long)tot[0], (unsigned long long)tot[1], (unsigned long long)tot[2],
+                    ctx ? (resident ? "device, resident contigs" : "device") : "host", (unsigned long long)n_problems, (unsigned long long)tot[0], (unsigned long long)tot[1], (unsigned long long)tot[2],
                     (unsigned long long)tot[3], (unsigned long long)tot[4], (unsigned long long)tot[5], ctx ? tot[6] / 1e3 : 0.0, ctx ? tot[7] / 1e3 : 0.0);
+        if (counts) counts[0] = n_problems, counts[1] = tot[5];
     }
     int T = n_threads > 0 ? n_threads : (int)std::thread::hardware_concurrency();
     if (const char *e = getenv("CM_CIRC_THREADS")) T = atoi(e);
@@ -1321,13 +1338,14 @@ static int circ_call_mt(const cm_params *P, int32_t window_size, uint32_t n_cont
         work();
         for (auto &t : th) t.join();
     }
-    if (ahead && getenv("CM_CIRC_TRACE")) {
+    if (ahead) {
         uint64_t taken = 0, recomputed = 0;
         for (const Chunk &ck : chunks) {
             taken += ck.taken;
             recomputed += ck.recomputed;
         }
-        fprintf(stderr, "[circ] chains ahead: %llu answers taken, %llu problems recomputed on the host\n", (unsigned long long)taken, (unsigned long long)recomputed);
+        if (counts) counts[2] = recomputed;
+        if (getenv("CM_CIRC_TRACE")) fprintf(stderr, "[circ] chains ahead: %llu answers taken, %llu problems recomputed on the host\n", (unsigned long long)taken, (unsigned long long)recomputed);
     }
     std::vector<Call> calls;
     uint64_t n_rows = 0;
@@ -1373,7 +1391,36 @@ extern "C" int cm_circ_call_device(cm_ctx *ctx, int slot, const cm_params *P, in
                                    const char *candidates_path, const char *report_path, cm_circ_stats *stats) {
     const int ws = window_size > 0 ? window_size : 8;
     if (ws < 6 || ws > 10) return CM_ELIMIT;            // the windows cm_circ_chain_batch takes
-    return circ_call_mt(P, window_size, n_contigs, contigs, annots, chrs, n_chr, sorted, candidates_path, report_path, stats, 0, true, ctx, slot);
+    return circ_call_mt(P, window_size, n_contigs, contigs, annots, chrs, n_chr, sorted, candidates_path, report_path, stats, 0, ChainsAhead{true, ctx, slot});
+}
+
+// The tail both end-to-end entry points share once a sorted batch is parsed: cm_circ_run gets there through its own front (sorts,
+// genome, GTF), cm_detect_run (host_detect.cpp) with what stage 1 left resident.
+int cmrun::circ_call_resident(cm_ctx *ctx, const cm_params *P, int32_t window_size, uint32_t n_contigs, const cm_index_view *contigs, const cm_annot_view *annots,
+                              const cm_chr_info *chrs, uint32_t n_chr, const cm_fastq_batch *sorted, const char *candidates_path, const char *report_path,
+                              cm_circ_stats *stats, int n_threads, uint64_t counts[3]) {
+    if (!ctx || !P || !contigs || !annots || !chrs || !sorted || !candidates_path || !report_path) return CM_EINVAL;
+    const int ws = window_size > 0 ? window_size : 8;
+    if (ws < 6 || ws > 10) return CM_ELIMIT;
+    // the rounds may have left copies and a prefetch in flight: they are through before the first chain call, and the chain calls
+    // touch nothing but the slots' tables and the context's chain workspace
+    int rc = cm_sync(ctx);
+    if (rc != CM_OK) return rc;
+    // An empty call tells what the slot holds: no annotation is CM_ESTATE already, no contig is the call's CM_EINVAL with a text
+    // of its own.  Any other refusal (a slot beyond the context's, a parameter) is passed on as it is, with the context's message.
+    for (uint32_t c = 0; c < n_contigs; ++c) {
+        rc = cm_circ_chain_batch(ctx, (int)c, ws, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0, nullptr,
+                                 nullptr, nullptr);
+        if (rc == CM_EINVAL && strstr(cm_last_error(ctx), "no contig is resident")) return CM_ESTATE;
+        if (rc != CM_OK) return rc;
+    }
+    return circ_call_mt(P, window_size, n_contigs, contigs, annots, chrs, n_chr, sorted, candidates_path, report_path, stats, n_threads,
+                        ChainsAhead{true, ctx, 0, true, counts});
+}
+extern "C" int cm_circ_call_resident(cm_ctx *ctx, const cm_params *P, int32_t window_size, uint32_t n_contigs, const cm_index_view *contigs,
+                                     const cm_annot_view *annots, const cm_chr_info *chrs, uint32_t n_chr, const cm_fastq_batch *sorted,
+                                     const char *candidates_path, const char *report_path, cm_circ_stats *stats) {
+    return cmrun::circ_call_resident(ctx, P, window_size, n_contigs, contigs, annots, chrs, n_chr, sorted, candidates_path, report_path, stats, 0, nullptr);
 }
 
 extern "C" int cm_circ_run(const cm_circ_args *a, cm_circ_stats *stats, char *err, uint64_t err_cap) {
@@ -1513,7 +1560,7 @@ extern "C" int cm_circ_run(const cm_circ_args *a, cm_circ_stats *stats, char *er
     lap("parse sorted remain files");
     const std::string cand = out + ".candidates.pam", rep = out + ".circ_report";
     rc = circ_call_mt(&P, a->window_size, (uint32_t)views.size(), views.data(), annots.data(), chrs, n_chr, &b, cand.c_str(), rep.c_str(), stats,
-                      a->n_threads, on_device, dev_ctx, 0);
+                      a->n_threads, ChainsAhead{on_device, dev_ctx, 0});
     if (rc != CM_OK) rc = on_device ? fail(rc, "cm_circ_call_device failed (%d): %s", rc, cm_last_error(dev_ctx)) : fail(rc, "cm_circ_call failed (%d)", rc);
     lap("calling + report");
     cleanup();

@@ -68,6 +68,9 @@ void unmapped_state(cm_mapped_read &m, int type, int max_ed) {        // fill_ma
 struct Stream {
     gzFile gz = nullptr;
     FILE *plain = nullptr;                   // set for uncompressed input: read in big blocks and tokenised on several threads
+    const char *mem = nullptr;               // cm_fastq_open_mem: the caller's text, read like a stream (record by record, as gzip input is)
+    uint64_t mem_len = 0, mem_pos = 0;
+    bool from_mem = false;
     std::vector<char> buf;
     size_t pos = 0, end = 0;
     bool eof = false;
@@ -99,6 +102,12 @@ struct Stream {
         buf.resize(BLOCK);
         return true;
     }
+    void open_mem(const void *text, uint64_t n) {
+        mem = (const char *)text;
+        mem_len = n;
+        from_mem = true;
+        buf.resize(BLOCK);
+    }
     void close() {
         if (gz) gzclose(gz);
         if (plain) fclose(plain);
@@ -110,6 +119,12 @@ struct Stream {
     int read_threads = 1;
     int read_some(char *dst, size_t cap) {
         if (cap > (1u << 30)) cap = 1u << 30;
+        if (from_mem) {
+            const size_t n = (size_t)std::min<uint64_t>(cap, mem_len - mem_pos);
+            if (n) memcpy(dst, mem + mem_pos, n);
+            mem_pos += n;
+            return (int)n;
+        }
         if (!plain) {
             const int r = gzread(gz, dst, (unsigned)cap);
             if (r < 0) io_error = true;
@@ -919,6 +934,19 @@ int cm_fastq_open(const char *r1_path, const char *r2_path, const cm_chr_info *c
         cm_fastq_close(f);
         return CM_EINVAL;
     }
+    for (uint32_t i = 0; i < n_chr; ++i) f->chr_names.emplace_back(chrs[i].name ? chrs[i].name : "");
+    f->max_ed = max_ed;
+    *out = f;
+    return CM_OK;
+}
+
+int cm_fastq_open_mem(const void *text1, uint64_t n1, const void *text2, uint64_t n2, const cm_chr_info *chrs, uint32_t n_chr, int32_t max_ed,
+                      cm_fastq **out) {
+    if (!out || (n1 && !text1) || (n2 && !text2) || (n_chr && !chrs)) return CM_EINVAL;
+    *out = nullptr;
+    cm_fastq *f = new cm_fastq();
+    f->file[0].s.open_mem(text1, n1);
+    f->file[1].s.open_mem(text2, n2);
     for (uint32_t i = 0; i < n_chr; ++i) f->chr_names.emplace_back(chrs[i].name ? chrs[i].name : "");
     f->max_ed = max_ed;
     *out = f;

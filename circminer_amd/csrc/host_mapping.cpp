@@ -31,6 +31,12 @@
 //
 // The run is one object (Run): cm_mapping_run walks its phases, a phase returns a code, and what the phases acquired -- threads, files,
 // page-locked ranges, the context, host tables -- is released by ~Run, in one order, on every way out.
+//
+// Which feed a run takes is a set of fields (cmrun::Paths, cm_run.h): cm_mapping_run fills them from the environment, cm_detect_run
+// (host_detect.cpp) from its own rule.  cmrun::mapping_phases is the walk both share; cm_detect_run hands it a step that runs after
+// the last batch and before the release, while the context, the annotation tables, the chromosome table, the sorted runs and --
+// kept for it -- each contig's host sequence bytes are still there.  Keeping those bytes costs one byte per base of host memory
+// (3.1 GB at hg38 size) for the length of the run; the k-mer tables' host copies go back after each upload as before.
 #include <algorithm>
 #include <chrono>
 #include <cstdarg>
@@ -45,6 +51,7 @@
 #include "circminer_hot.h"
 #include "cm_pinned_ranges.h"
 #include "cm_row_ranges.h"
+#include "cm_run.h"
 
 namespace {
 
@@ -81,6 +88,7 @@ struct ContigSource {
 
 struct Run {
     const cm_mapping_args *const a;
+    const cmrun::Paths paths;
     char *const err;
     const size_t err_cap;
     const char *what = nullptr;                    // the call that failed, for cm_mapping_run's message; null when the text is set already
@@ -102,6 +110,7 @@ struct Run {
     cm_fastq *fq = nullptr;
     cm_writer *w_map = nullptr, *w_rem = nullptr;
     std::vector<cm_index_view> views;
+    std::vector<cm_index_view> genomes;                          // Paths::keep_genome: contig c's sequence bytes (genome, ref_len), for stage 2's judges
     std::vector<cm_annot_view> annots, annots_early;             // _early: the GTF thread's, until load_annotation() takes or frees them
     Result res[2];
     RowBuf rows[2];                                // CM_PAM_DEVICE=1 / CM_SAM_DEVICE=1: the rows of batch k as the device formatted them, in set k & 1
@@ -124,7 +133,7 @@ struct Run {
     bool text_path = false, pam_device = false, sam_device = false, remain_device = false, remain_sorted = false, want_fixed = false;
     TextBlock tq[4];
     cm_fastq_batch cur{}, nxt{}, nn{};
-    Run(const cm_mapping_args *args, char *e, uint64_t cap) : a(args), err(e), err_cap((size_t)cap) {
+    Run(const cm_mapping_args *args, const cmrun::Paths &pt, char *e, uint64_t cap) : a(args), paths(pt), err(e), err_cap((size_t)cap) {
         if (err && err_cap) err[0] = 0;
         pins.user = this;
         pins.reg = [](void *u, void *p, uint64_t bytes) { return cm_host_register(((Run *)u)->cm, p, bytes); };
@@ -156,6 +165,7 @@ struct Run {
         if (!annots.empty()) cm_host_free_annotation(annots.data(), (uint32_t)annots.size());
         if (early_rc == CM_OK && !annots_early.empty()) cm_host_free_annotation(annots_early.data(), (uint32_t)annots_early.size());
         for (auto &v : views) cm_host_free_loaded_contig(&v);
+        for (auto &v : genomes) cm_host_free_loaded_contig(&v);
         if (idx) cm_host_close_index(idx);
         if (chrs) cm_host_free_index_info(chrs, n_chr);
     }
@@ -268,12 +278,36 @@ struct Run {
             tl = now();
             const int lrc = S.load(*this, (int)views.size() - 1, c);
             lap(S.lap_load, tl);
+            if (paths.keep_genome && lrc == CM_OK && !keep_sequence(S, c)) {
+                ahead.join();
+                if (S.frees_host_copy && nxt_rc == CM_OK && nxt_loaded) cm_host_free_loaded_contig(&nxt.iv);
+                return refuse(CM_ENOMEM, "no memory to keep the sequence of contig %d on the host", c.iv.contig_num + 1);
+            }
             if (S.frees_host_copy) cm_host_free_loaded_contig(&views.back());
             ahead.join();
             if (lrc == CM_OK) continue;
             if (S.frees_host_copy && nxt_rc == CM_OK && nxt_loaded) cm_host_free_loaded_contig(&nxt.iv);
             return failed(lrc, S.load_name);
         }
+    }
+    // Paths::keep_genome: the sequence bytes of the contig just uploaded stay with the run.  A source that hands out arrays of its
+    // own per contig gives its sequence up (the tables still go back); the full-format source's belong to the file handle: copied.
+    bool keep_sequence(const ContigSource &S, const Contig &c) {
+        cm_index_view g{};
+        g.contig_num = c.iv.contig_num;
+        g.ref_len = c.iv.ref_len;
+        if (S.frees_host_copy) {
+            g.genome = views.back().genome;
+            views.back().genome = nullptr;
+        } else {
+            uint8_t *copy = (uint8_t *)malloc((size_t)c.raw.ref_len + 1);
+            if (!copy) return false;
+            memcpy(copy, c.raw.genome, c.raw.ref_len);
+            copy[c.raw.ref_len] = 0;
+            g.genome = copy;
+        }
+        genomes.push_back(g);
+        return true;
     }
     // ---- phase 4: GTF (gtf_parser.init / load_gtf) ----
     int load_annotation() {
@@ -335,11 +369,10 @@ struct Run {
     }
     // The device-side tokeniser's path is opt-in and falls back to the host parser, for the run, where that one is needed.
     int choose_text_path() {
-        const char *e = getenv("CM_FASTQ_DEVICE"), *ep = getenv("CM_PAM_DEVICE"), *es = getenv("CM_SAM_DEVICE"), *er = getenv("CM_REMAIN_DEVICE");
-        pam_device = a->report == 1 && ep && atoi(ep) == 1;      // the rows of report 1 formatted on the device: needs the text path
-        sam_device = a->report == 2 && es && atoi(es) == 1;      // the records of report 2 likewise
-        text_path = e && atoi(e) == 1 && (a->report == 0 || pam_device || sam_device);
-        remain_device = er && atoi(er) == 1;                     // the remain records formatted on the device: on the text path, in any report mode it covers
+        pam_device = a->report == 1 && paths.pam_device;         // the rows of report 1 formatted on the device: needs the text path
+        sam_device = a->report == 2 && paths.sam_device;         // the records of report 2 likewise
+        text_path = paths.fastq_device && (a->report == 0 || pam_device || sam_device);
+        remain_device = paths.remain_device;                     // the remain records formatted on the device: on the text path, in any report mode it covers
         // bytes per file and block: what batch_pairs records take, first by a guess (a 150-bp record with its name and qualities is
         // ~ 350 bytes), then by what the records of the last batch took -- a block that holds much more than a batch only grows the tail
         want = batch_pairs * 400 + (1u << 16);
@@ -352,8 +385,7 @@ struct Run {
         }
         if (!text_path) return CM_OK;
         // the sorted runs beside the remain files: one process only (the ranks' part files are not merged into one order)
-        const char *eo = getenv("CM_REMAIN_SORTED");
-        remain_sorted = remain_device && world <= 1 && eo && atoi(eo) == 1;
+        remain_sorted = remain_device && world <= 1 && paths.remain_sorted;
         const int rc = read_block(tq[0], want);
         if (rc != CM_OK && rc != CM_EINVAL) return failed(rc, "cm_fastq_next_text");
         if (rc == CM_EINVAL) return text_path = false, CM_OK;    // gzip input or a pipe: the host parser's
@@ -585,7 +617,8 @@ struct Run {
         st.seconds_device += now() - td0;
         if (remain_sorted) {
             const std::string base = std::string(a->out_prefix) + "_" + std::to_string(n_con) + "_remain_R";
-            if ((rc = cm_remain_runs_open((base + "1.fastq.srt").c_str(), (base + "2.fastq.srt").c_str(), &srt_runs)) != CM_OK) return failed(rc, "cm_remain_runs_open");
+            rc = paths.srt_files ? cm_remain_runs_open((base + "1.fastq.srt").c_str(), (base + "2.fastq.srt").c_str(), &srt_runs) : cm_remain_runs_open(nullptr, nullptr, &srt_runs);
+            if (rc != CM_OK) return failed(rc, "cm_remain_runs_open");
         }
         if (tq[0].tb.n_pairs) {
             if ((rc = cm_reads_swap(cm)) != CM_OK) return failed(rc, "cm_reads_swap");
@@ -627,7 +660,7 @@ struct Run {
         if ((rc = hand_to_writer(nullptr)) != CM_OK) return rc;
         if (w_map && (rc = cm_writer_flush(w_map)) != CM_OK) return failed(rc, "writing the mapping file");
         if ((rc = cm_writer_flush(w_rem)) != CM_OK) return failed(rc, "writing the remain files");
-        if (srt_runs) {
+        if (srt_runs && paths.srt_files) {
             const double tm = now();
             if ((rc = cm_remain_runs_finish(srt_runs)) != CM_OK) return failed(rc, "cm_remain_runs_finish (the .srt files)");
             if (getenv("CM_REMAIN_TRACE"))
@@ -639,20 +672,50 @@ struct Run {
         if (stats) *stats = st;
         return CM_OK;
     }
+    // ---- phase 8 (cm_detect_run only): the caller's step, with everything stage 2 needs still held ----
+    int hand_over(const cmrun::Then &then) {
+        // finish() has flushed the files; they are closed here because stage 2 may read the remain files
+        if (w_map) cm_writer_close(w_map);
+        if (w_rem) cm_writer_close(w_rem);
+        w_map = w_rem = nullptr;
+        const cmrun::Resident R{cm, &P, n_con, n_chr, chrs, genomes.size() == n_con ? genomes.data() : nullptr, annots.data(), srt_runs,
+                                srt_batches, srt_host_batches, srt_records, n_threads};
+        std::string msg;
+        const int rc = then(R, msg);
+        return rc == CM_OK ? CM_OK : refuse(rc, "%s", msg.c_str());
+    }
 };
 
 }  // namespace
 
-extern "C" int cm_mapping_run(const cm_mapping_args *a, cm_mapping_stats *stats, char *err, uint64_t err_cap) {
-    Run run(a, err, err_cap);
+cmrun::Paths cmrun::paths_from_environment(int32_t report) {
+    auto is_one = [](const char *name) {
+        const char *e = getenv(name);
+        return e && atoi(e) == 1;
+    };
+    Paths p;
+    p.fastq_device = is_one("CM_FASTQ_DEVICE");
+    p.pam_device = report == 1 && is_one("CM_PAM_DEVICE");
+    p.sam_device = report == 2 && is_one("CM_SAM_DEVICE");
+    p.remain_device = is_one("CM_REMAIN_DEVICE");
+    p.remain_sorted = p.srt_files = is_one("CM_REMAIN_SORTED");
+    return p;
+}
+
+int cmrun::mapping_phases(const cm_mapping_args *a, cm_mapping_stats *stats, char *err, uint64_t err_cap, const Paths &paths, const Then *then) {
+    Run run(a, paths, err, err_cap);
     int rc;
     if ((rc = run.check_args()) == CM_OK && (rc = run.open_index()) == CM_OK && (rc = run.load_contigs()) == CM_OK &&
         (rc = run.load_annotation()) == CM_OK && (rc = run.open_outputs_and_reader()) == CM_OK &&
-        (rc = run.text_path ? run.text_batches() : run.host_batches()) == CM_OK)
-        rc = run.finish(stats);
+        (rc = run.text_path ? run.text_batches() : run.host_batches()) == CM_OK && (rc = run.finish(stats)) == CM_OK && then)
+        rc = run.hand_over(*then);
     // a call that failed is named here, with what the context says of it, while there still is a context; ~Run releases the rest
     if (rc != CM_OK && run.what) run.refuse(rc, "%s failed (%d)%s%s", run.what, rc, run.cm ? ": " : "", run.cm ? cm_last_error(run.cm) : "");
     return rc;
+}
+
+extern "C" int cm_mapping_run(const cm_mapping_args *a, cm_mapping_stats *stats, char *err, uint64_t err_cap) {
+    return cmrun::mapping_phases(a, stats, err, err_cap, cmrun::paths_from_environment(a ? a->report : 0), nullptr);
 }
 
 extern "C" int cm_merge_parts(const char *out_prefix, int32_t rounds, int32_t world, int32_t report) {

@@ -51,6 +51,15 @@ class MappingStats(C.Structure):
                 ("seconds_device", C.c_double), ("seconds_write", C.c_double)]
 
 
+class DetectArgs(C.Structure):         # cm_detect_args
+    _fields_ = [("map", MappingArgs), ("window_size", C.c_int32), ("circ_threads", C.c_int32), ("handover", C.c_int32), ("flags", C.c_int32)]
+
+
+class DetectStats(C.Structure):        # cm_detect_stats
+    _fields_ = [("map", MappingStats), ("circ", CircStats), ("handover_used", C.c_int32), ("reserved", C.c_int32), ("problems", C.c_uint64),
+                ("refused", C.c_uint64), ("recomputed", C.c_uint64), ("seconds_handover", C.c_double), ("seconds_total", C.c_double)]
+
+
 def default_params(**kw) -> Params:
     """Defaults of reference src/commandline_parser.cpp:7-33 / src/common.h:39-53."""
     d = dict(kmer=20, seed_lim=500, max_read_len=300, scan_level=0, max_ed=4, max_sc=7, band=3, max_tlen=500,
@@ -283,6 +292,7 @@ SIGNATURES = {
     "cm_host_free_loaded_contig": (None, [pp(IndexView)]),
     "cm_host_close_index": (None, [vp]),
     "cm_fastq_open": (C.c_int, [C.c_char_p, C.c_char_p, pp(ChrInfo), C.c_uint32, C.c_int32, pp(vp)]),
+    "cm_fastq_open_mem": (C.c_int, [vp, C.c_uint64, vp, C.c_uint64, pp(ChrInfo), C.c_uint32, C.c_int32, pp(vp)]),
     "cm_fastq_open_shard": (C.c_int, [C.c_char_p, C.c_char_p, pp(ChrInfo), C.c_uint32, C.c_int32, C.c_int32, C.c_int32, C.c_int, pp(vp),
                                       pp(C.c_uint64), pp(C.c_uint64)]),
     "cm_merge_parts": (C.c_int, [C.c_char_p, C.c_int32, C.c_int32, C.c_int32]),
@@ -299,6 +309,7 @@ SIGNATURES = {
     "cm_remain_runs_add": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_uint64]),
     "cm_remain_runs_add_unsorted": (C.c_int, [vp, vp, C.c_uint64, vp, C.c_uint64]),
     "cm_remain_runs_finish": (C.c_int, [vp]),
+    "cm_remain_runs_finish_mem": (C.c_int, [vp, pp(vp), pp(C.c_uint64), pp(vp), pp(C.c_uint64)]),
     "cm_remain_runs_close": (None, [vp]),
     "cm_regional_table_build": (C.c_int, [vp, C.c_uint32, C.c_int32, C.c_int32, pp(u32p), pp(u32p)]),
     "cm_regional_table_free": (None, [u32p, u32p]),
@@ -314,6 +325,10 @@ SIGNATURES = {
     "cm_circ_call_device": (C.c_int, [vp, C.c_int, pp(Params), C.c_int32, C.c_uint32, pp(IndexView), pp(AnnotView), pp(ChrInfo), C.c_uint32, pp(FastqBatch),
                                       C.c_char_p, C.c_char_p, pp(CircStats)]),
     "cm_circ_chain_abi_sizes": (C.c_int, [pp(C.c_uint32), C.c_uint32]),
+    "cm_circ_call_resident": (C.c_int, [vp, pp(Params), C.c_int32, C.c_uint32, pp(IndexView), pp(AnnotView), pp(ChrInfo), C.c_uint32, pp(FastqBatch),
+                                        C.c_char_p, C.c_char_p, pp(CircStats)]),
+    "cm_detect_run": (C.c_int, [pp(DetectArgs), pp(DetectStats), C.c_char_p, C.c_uint64]),
+    "cm_detect_abi_sizes": (C.c_int, [pp(C.c_uint32), C.c_uint32]),
     "cm_write_sam_header": (C.c_int, [vp]),
     "cm_write_sam": (C.c_int, [vp, pp(FastqBatch), vp, vp, C.c_uint64]),
     "cm_writer_flush": (C.c_int, [vp]),
@@ -348,6 +363,8 @@ def load(path: str = LIB_PATH) -> C.CDLL:
     two = (C.c_uint32 * 2)()
     if L.cm_circ_chain_abi_sizes(two, 2) != 2 or list(two) != [C.sizeof(CircChainReq), C.sizeof(CircChainRes)]:
         raise RuntimeError(f"circminer_amd.lib: cm_circ_chain_req / cm_circ_chain_res differ from {path}: library {list(two)}")
+    if L.cm_detect_abi_sizes(two, 2) != 2 or list(two) != [C.sizeof(DetectArgs), C.sizeof(DetectStats)]:
+        raise RuntimeError(f"circminer_amd.lib: cm_detect_args / cm_detect_stats differ from {path}: library {list(two)}")
     _lib = L
     return L
 
@@ -544,9 +561,10 @@ class ParsedBatch:
 class RemainRuns:
     """cm_remain_runs: sorted runs of remain records, merged into the two .srt files by finish()"""
 
-    def __init__(self, srt1: str, srt2: str):
+    def __init__(self, srt1: str = None, srt2: str = None):
+        """srt1 = srt2 = None: runs without paths, for finish_mem() alone"""
         self.L, self.h = load(), C.c_void_p()
-        rc = self.L.cm_remain_runs_open(srt1.encode(), srt2.encode(), C.byref(self.h))
+        rc = self.L.cm_remain_runs_open(srt1.encode() if srt1 is not None else None, srt2.encode() if srt2 is not None else None, C.byref(self.h))
         if rc != 0:
             raise RuntimeError(f"cm_remain_runs_open failed ({rc})")
 
@@ -566,6 +584,14 @@ class RemainRuns:
 
     def finish(self) -> int:
         return self.L.cm_remain_runs_finish(self.h)
+
+    def finish_mem(self):
+        """cm_remain_runs_finish_mem: the merge of finish() as (bytes of file 1, bytes of file 2), copied out of the runs' buffers"""
+        b1, b2, n1, n2 = C.c_void_p(), C.c_void_p(), C.c_uint64(0), C.c_uint64(0)
+        rc = self.L.cm_remain_runs_finish_mem(self.h, C.byref(b1), C.byref(n1), C.byref(b2), C.byref(n2))
+        if rc != 0:
+            raise RuntimeError(f"cm_remain_runs_finish_mem failed ({rc})")
+        return C.string_at(b1, n1.value) if n1.value else b"", C.string_at(b2, n2.value) if n2.value else b""
 
     def close(self):
         if self.h:
@@ -697,6 +723,39 @@ def circ_call_device(hot, params, host_index, chr_table, sorted_batch, candidate
     return st
 
 
+def circ_call_resident(hot, params, host_index, chr_table, sorted_batch, candidates_path, report_path, window=0):
+    """cm_circ_call_resident: cm_circ_call with the seeds and chains from the device against what `hot` (a HotPath) holds: contig c
+    and its annotation in slot c.  host_index supplies the host sequence of every contig and the annotation tables of the judges.
+    Returns (rc, CircStats): CM_ESTATE (-5) for a slot that lacks its contig or annotation is the caller's to judge."""
+    L = load()
+    n_con = host_index.n_contigs
+    views = (IndexView * n_con)(*host_index.views)
+    chrs = chr_array(list(chr_table))
+    st = CircStats()
+    rc = L.cm_circ_call_resident(hot.h if hot is not None else None, C.byref(params), window, n_con, views, host_index.annots, chrs, len(chr_table),
+                                 C.byref(sorted_batch.fb), candidates_path.encode(), report_path.encode(), C.byref(st))
+    return rc, st
+
+
+def run_detect(index_path, gtf, fastq1, fastq2, out_prefix, params=None, report=0, n_threads=4, batch_pairs=0, index_info=None, window=0, circ_threads=0,
+               handover=0, srt_files=False, world=1):
+    """cm_detect_run: both stages from files to files in one call (the reference's default command, src/circminer.cpp: mapping()
+    then circ_detect()).  handover 0: the remain records go to stage 2 in memory where the input allows it, 1: through the remain /
+    .srt files; srt_files: also write the two .srt files on the memory hand-over.  Returns DetectStats."""
+    L = load()
+    m = MappingArgs(index_path.encode(), (index_info or index_path + ".info").encode(), gtf.encode(), fastq1.encode(), fastq2.encode(),
+                    out_prefix.encode(), params if params is not None else default_params(), report, n_threads, batch_pairs, 0, world)
+    a = DetectArgs(m, window, circ_threads, handover, 1 if srt_files else 0)
+    st = DetectStats()
+    err = C.create_string_buffer(1024)
+    rc = L.cm_detect_run(C.byref(a), C.byref(st), err, len(err))
+    if rc != 0:
+        e = RuntimeError(f"cm_detect_run failed ({rc}): {err.value.decode()}")
+        e.rc = rc
+        raise e
+    return st
+
+
 def run_circ(index_path, gtf, out_prefix, last_round, params=None, n_threads=4, index_info=None, window=0):
     """cm_circ_run: stage 2 from files to files (the reference's circ_detect(), src/circminer.cpp:347-352)."""
     L = load()
@@ -779,6 +838,22 @@ class FastqReader:
         if self.h:
             self.L.cm_fastq_close(self.h)
             self.h = C.c_void_p()
+
+
+def fastq_open_mem(text1: bytes, text2: bytes, chr_table=(), max_ed: int = 4) -> "FastqReader":
+    """cm_fastq_open_mem: a FastqReader over two texts in memory (kept alive by the reader)"""
+    r = FastqReader.__new__(FastqReader)
+    r.L = load()
+    r._chrs = chr_array(list(chr_table))
+    r.h = C.c_void_p()
+    r._text = (np.frombuffer(text1, np.uint8).copy(), np.frombuffer(text2, np.uint8).copy())
+    t1, t2 = r._text
+    rc = r.L.cm_fastq_open_mem(t1.ctypes.data if t1.size else None, t1.size, t2.ctypes.data if t2.size else None, t2.size, r._chrs, len(chr_table), max_ed,
+                               C.byref(r.h))
+    if rc != 0:
+        raise RuntimeError(f"cm_fastq_open_mem failed ({rc})")
+    r.first_pair, r.n_pairs = 0, None
+    return r
 
 
 class RecordWriter:

@@ -552,6 +552,12 @@ int cm_fastq_open(const char *r1_path, const char *r2_path, const cm_chr_info *c
  * counted with one inflate pass over R1 and every rank inflates from the start, stepping over the blocks of the ranks before it --
  * the same blocks and output bytes as plain text, at zlib's speed.  A pipe cannot be read twice: CM_EINVAL when world > 1.
  * first_pair / n_pairs (nullable): the block's position in the whole input.  Every rank of a node can open its share at the same time. */
+/* The same reader over two texts in memory: cm_fastq_next returns the batches it returns for two files that hold these bytes
+ * (reads, qualities, names, `prior`), with the same verdict on malformed text in the same call.  The text stays the caller's and
+ * must outlive the reader; it is read record by record, as gzip input is.  cm_fastq_next_text does not serve it (CM_EINVAL).
+ * n1 / n2 == 0 with a null text is an empty file. */
+int cm_fastq_open_mem(const void *text1, uint64_t n1, const void *text2, uint64_t n2, const cm_chr_info *chrs, uint32_t n_chr,
+                      int32_t max_ed, cm_fastq **out);
 int cm_fastq_open_shard(const char *r1_path, const char *r2_path, const cm_chr_info *chrs, uint32_t n_chr, int32_t max_ed,
                         int32_t rank, int32_t world, int n_threads, cm_fastq **out, uint64_t *first_pair, uint64_t *n_pairs);
 int cm_fastq_next(cm_fastq *f, uint64_t max_pairs, cm_fastq_batch *out);   /* out->reads.n_pairs == 0 at the end; CM_ENOMEM when a batch array cannot grow */
@@ -778,6 +784,10 @@ int cm_remain_runs_open(const char *srt_path1, const char *srt_path2, cm_remain_
 int cm_remain_runs_add(cm_remain_runs *r, const void *bytes1, const uint32_t *off1, const void *bytes2, const uint32_t *off2,
                        const int64_t *keys, uint64_t n_records);
 int cm_remain_runs_finish(cm_remain_runs *r);
+/* The same merge into two buffers in host memory instead of the two files: *bytes1 / *n1 and *bytes2 / *n2 are what `finish`
+ * would have written to srt_path1 / srt_path2.  The buffers belong to `r` until `close` (a second call makes them anew).
+ * cm_remain_runs_open(NULL, NULL, &r) opens runs without paths for this finish alone; `finish` on them is CM_EINVAL. */
+int cm_remain_runs_finish_mem(cm_remain_runs *r, const void **bytes1, uint64_t *n1, const void **bytes2, uint64_t *n2);
 void cm_remain_runs_close(cm_remain_runs *r);
 /* A run made on the host from UNSORTED records (the fall-back for a batch cm_format_remain_sorted refuses): the two files' bytes
  * as cm_format_remain delivers them are ordered by the in-memory body of cm_sort_remain -- the key parsed from the text -- and
@@ -856,6 +866,9 @@ typedef struct cm_circ_chain_res {
  * Tables are built once per distinct gene; their memory per pass is bounded (CM_CIRC_TABLE_BYTES, default 1 GiB): the genes are
  * worked through in groups that fit, a gene that alone exceeds the bound refuses its problems.  CM_CIRC_LOG_CAP: improvement-log
  * entries per resident problem (default 65536).  A refused problem is for the caller to answer with cm_circ_chain_host.
+ * The device memory of a call is the context's: grow-only buffers that a later call of the same or a smaller size reuses without
+ * allocating, that a larger call or a changed CM_CIRC_LOG_CAP re-sizes, and that cm_destroy releases.  With CM_CIRC_TRACE set every
+ * call prints `workspace: <n> allocations, <bytes> held` to stderr.
  * stats: distinct genes, table bytes (largest group), gene groups, DP cells, log events, refused problems, device time of the
  * tables and of the chaining from HIP events (microseconds: the array holds integers). */
 int cm_circ_chain_batch(cm_ctx *ctx, int slot, int32_t window_size, const uint8_t *genome, uint32_t ref_len, const uint8_t *seqs, uint64_t seqs_len,
@@ -886,6 +899,54 @@ int cm_circ_call_device(cm_ctx *ctx, int slot, const cm_params *p, int32_t windo
                         const char *candidates_path, const char *report_path, cm_circ_stats *stats);
 /* sizeof(cm_circ_chain_req), sizeof(cm_circ_chain_res): cm_abi_sizes for the two structs above (its own list is closed at 19). */
 int cm_circ_chain_abi_sizes(uint32_t *out, uint32_t cap);
+/* cm_circ_call_device against what a mapping context already holds: contig c and its annotation are resident in slot c of ctx
+ * (cm_load_contig / cm_load_contig_raw / cm_build_contig + cm_load_annotation, as cm_mapping_run leaves them), so contig c's
+ * problems go to cm_circ_chain_batch(ctx, slot = c, genome = NULL, ...): no annotation is loaded here, no second context is made
+ * and no gene span is uploaded.  contigs: the HOST sequence of every contig (genome and ref_len; the tables are not read), which
+ * the judges on the host threads read.  CM_ESTATE when one of the slots 0 .. n_contigs - 1 lacks its contig or its annotation
+ * (nothing is written then).  The context is synchronised (cm_sync) before the first chain call; a resident batch, a staged batch
+ * or a prefetch the rounds have left is neither read nor written, and cm_map_rounds works on afterwards as before.  The device
+ * memory the chain calls need is the context's (grow-only, released by cm_destroy).  The two files are cm_circ_call's byte for byte. */
+int cm_circ_call_resident(cm_ctx *ctx, const cm_params *p, int32_t window_size, uint32_t n_contigs, const cm_index_view *contigs,
+                          const cm_annot_view *annots, const cm_chr_info *chrs, uint32_t n_chr, const cm_fastq_batch *sorted,
+                          const char *candidates_path, const char *report_path, cm_circ_stats *stats);
+
+/* ---------------- both stages in one call: mapping() then circ_detect() of the reference (src/circminer.cpp) ----------------
+ * One process, one context, one load of genome and GTF.  The files it leaves are those of cm_mapping_run(args->map) followed by
+ * cm_circ_run on its output with the same parameters and no environment opt-in set, byte for byte: the two remain files, the
+ * mapping file of report 1 / 2, <out>.candidates.pam and <out>.circ_report.  The .srt files are the one difference, see below.
+ * It always takes the device paths: no HIP device is CM_ENODEV (err says so), there is no host fall-back, and the variables that
+ * select a path elsewhere (CM_FASTQ_DEVICE, CM_PAM_DEVICE, CM_SAM_DEVICE, CM_REMAIN_DEVICE, CM_REMAIN_SORTED, CM_CIRC_PRESORTED,
+ * CM_CIRC_DEVICE) are not read.  The knobs and traces are: CM_FASTQ_DEVICE_BLOCK, CM_REMAIN_TIE_CAP, CM_CIRC_TABLE_BYTES,
+ * CM_CIRC_LOG_CAP, CM_CIRC_THREADS, CM_REMAIN_TRACE, CM_CIRC_TRACE.
+ * Memory hand-over (handover 0 and two regular plain-text FASTQ files of fresh reads -- no gzip, no pipe, no carried 23-token
+ * headers): the device tokenises, formats the rows of the report mode and the remain records, and sorts every batch's records; the
+ * sorted runs are merged in memory (cm_remain_runs_finish_mem), parsed from there (cm_fastq_open_mem) and called against the
+ * contigs and annotations stage 1 left resident (cm_circ_call_resident).  The .srt files are written only with flags bit 0, and
+ * are then the bytes cm_sort_remain makes of the remain files.
+ * Files hand-over (any other input, or handover 1): the host parser feeds the device, the remain files are sorted by cm_sort_remain
+ * into the .srt files, and those are parsed -- in the same process, against the same resident contigs and annotations.
+ * Stage 2's judges read genome bytes on the host, so a detect run keeps each contig's sequence (not its k-mer tables) in host
+ * memory until it returns: one byte per base (3.1 GB at hg38 size) that cm_mapping_run gives back after each upload.
+ * map.world must be 0 or 1 (CM_EINVAL otherwise). */
+typedef struct cm_detect_args {
+    cm_mapping_args map;        /* as for cm_mapping_run; world must be 0 or 1 (else CM_EINVAL) */
+    int32_t window_size;        /* stage 2, 0 = 8 */
+    int32_t circ_threads;       /* host threads of the judges, 0 = map.n_threads */
+    int32_t handover;           /* 0 = memory where the input allows it, 1 = through the remain / .srt files */
+    int32_t flags;              /* bit 0: also write the two .srt files on the memory hand-over */
+} cm_detect_args;
+typedef struct cm_detect_stats {
+    cm_mapping_stats map;
+    cm_circ_stats circ;
+    int32_t handover_used;      /* 0 memory, 1 files */
+    int32_t reserved;
+    uint64_t problems, refused, recomputed;   /* what CM_CIRC_TRACE prints today, summed over the contigs */
+    double seconds_handover, seconds_total;
+} cm_detect_stats;
+int cm_detect_run(const cm_detect_args *args, cm_detect_stats *stats, char *err, uint64_t err_cap);
+/* sizeof(cm_detect_args), sizeof(cm_detect_stats): cm_abi_sizes for the two structs above (its own list stays closed at 19). */
+int cm_detect_abi_sizes(uint32_t *out, uint32_t cap);
 
 /* sizeof of the structs above, in this order: cm_params, cm_index_view, cm_annot_view, cm_mapped_read, cm_reads, cm_record,
  * cm_chr_info, cm_fastq_batch, cm_mapping_args, cm_mapping_stats, cm_circ_res, cm_circ_args, cm_circ_stats, cm_index_raw, cm_build_stats, cm_dp_req,
